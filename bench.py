@@ -12,6 +12,10 @@ no collective on the data path (weights are replicated once by an RCCL broadcast
 `python bench.py --gpus N` without a torchrun environment starts the N ranks itself (torch.distributed.run as a CHILD
 process, before this process touches the GPU) and relays rank 0's JSON line.
 
+A plain run measures the headline only.  `--full` adds the secondary measurements ("also": BASELINE config 3 / 4 / 5, the
+product loop, the reference's 3-beam default mode, the IEEE-half build) and the CPU oracle baseline.  `--dump-outputs DIR`
+writes the waveforms of the last timed step to DIR as .npy files (float32), so that two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -54,7 +58,11 @@ def parse():
                          "top_p 0.8, temperature 1.0) instead of greedy; decode rows = sentences x beams")
     ap.add_argument("--sample", action="store_true", help="HF sample() (top_k 30, top_p 0.8, temperature 1.0, one beam) instead of greedy")
     ap.add_argument("--no-graph", action="store_true", help="eager decode launches (for rocprofv3 --pmc passes)")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements of the default run (BASELINE config 3 / 4, product loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (BASELINE config 3 / 4 / 5, product loop, 3-beam mode, f16) and the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the secondary measurements (BASELINE config 3 / 4, product loop)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveforms of the last timed step to DIR/*.npy (float32, at most 64 MB: a seeded sample beyond that)")
     ap.add_argument("--eos", action="store_true",
                     help="decode with the product loop of Engine.generate: a status() read-back (stream sync + D2H of the unfinished "
                          "flags) every 16 steps, as with eos enabled; the stop token stays suppressed so the work is the same")
@@ -270,6 +278,9 @@ def measure(eng, cfg, a, BU, steps, warmup, rank, world, product_loop=False):
         samples += step(True)
     sync_all()
     dt = time.perf_counter() - t0
+    # the last timed step's waveforms as a caller receives them: one int16 array per utterance (its sentences in order)
+    per_utt = {u: np.concatenate([last["wav"][j * NS + k].numpy().reshape(-1) for k in range(NS)]) for j, u in enumerate(mine)}
+    utterances = [per_utt[u] for u in mine]
     if world > 1:
         import torch.distributed as dist
 
@@ -282,10 +293,10 @@ def measure(eng, cfg, a, BU, steps, warmup, rank, world, product_loop=False):
         samples = float(tot[1])
         # outside the timed region: the shard results travel to rank 0 once (dp.gather_waveforms), as a user of
         # dp.run_sharded gets them; checks that every utterance of the global list was synthesised exactly once
-        per_utt = {u: np.concatenate([last["wav"][j * NS + k].numpy().reshape(-1) for k in range(NS)]) for j, u in enumerate(mine)}
         full = dp.gather_waveforms(per_utt, n_utt)
         if rank == 0:
             assert len(full) == n_utt and all(w.shape[0] == NS * T * 1024 for w in full)
+            utterances = full
     audio_s = samples / 24000.0
     # ---- roofline of the dominant kernel group: the per-token decode step ----
     D, NL, V = g["model_dim"], g["layers"], g["number_mel_codes"]
@@ -336,7 +347,26 @@ def measure(eng, cfg, a, BU, steps, warmup, rank, world, product_loop=False):
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
                      "algorithmic_bytes_per_launch": int(step_bytes), "avg_launch_ms": round(ms_step, 4),
                      "decode_tokens_per_s": round(B * 1e3 / ms_step, 1)},
+        "utterances": utterances,
     }
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE = 4 * 2 ** 20  # samples kept when the waveforms exceed the budget: 4 B value + 8 B position each = 48 MiB
+
+
+def dump_outputs(path, utterances):
+    """--dump-outputs: the waveforms of the last timed step, all utterances concatenated in order, as float32 (`wav.npy`)
+    with the length of each utterance (`wav_lengths.npy`).  Beyond the budget, a fixed seeded sample of positions is kept
+    (`wav.npy` = the values there, `wav_index.npy` = the positions)."""
+    os.makedirs(path, exist_ok=True)
+    wav = np.concatenate([np.asarray(u).reshape(-1) for u in utterances]).astype(np.float32)
+    np.save(os.path.join(path, "wav_lengths.npy"), np.array([np.asarray(u).size for u in utterances], dtype=np.float64))
+    if wav.nbytes > DUMP_BUDGET_BYTES - 8 * len(utterances):
+        idx = np.sort(np.random.default_rng(0).choice(wav.size, size=DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(path, "wav_index.npy"), idx.astype(np.float64))
+        wav = wav[idx]
+    np.save(os.path.join(path, "wav.npy"), wav)
 
 
 def main():
@@ -376,6 +406,8 @@ def main():
     if a.no_graph:
         eng.debug(no_graph=True)
     m = measure(eng, cfg, a, a.batch, a.steps, a.warmup, rank, world, product_loop=a.eos)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, m["utterances"])
     out = {
         "metric": "audio_sec_per_sec", "value": m["value"], "unit": "audio-s/s", "n_gpus": world,
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": m["ms_per_step"], "higher_is_better": True,
@@ -398,11 +430,12 @@ def main():
                        "ranks_on_persistent_engine": "all" if int(lo[0]) == 1 else "NOT all"}
         if dist.get_backend() == "nccl" and a.dtype in ("bf16", "f16") and not a.micro and os.environ.get("ITTS_ENGINE", "1") != "0":
             assert int(lo[0]) == 1, "a rank fell back from the persistent decode engine to the launch path"
-    # the default run also measures, next to the headline line (the same per-GPU workload at every N, so the driver's
+    # --full also measures, next to the headline line (the same per-GPU workload at every N, so the driver's
     # scaling curve compares like with like): 32 utterances per GPU = 64 decode rows - BASELINE config 3 at one GPU, BASELINE
     # config 4 (N x 32 utterances sharded data-parallel) at N GPUs - and, at one GPU, the product loop of Engine.generate
     # (status() read-back every 16 steps).  Never allowed to break the headline.
-    if a.batch == 1 and not (a.no_also or a.no_graph or a.gpt_fp8 or a.eos) and a.dtype == "bf16" and a.beams == 1 and not a.sample:
+    if (a.full and a.batch == 1 and not (a.no_also or a.no_graph or a.gpt_fp8 or a.eos) and a.dtype == "bf16" and a.beams == 1
+            and not a.sample):
         also = {}
         key = "config3_batch32" if world == 1 else "config4_batch32_per_gpu"
         try:
@@ -460,7 +493,7 @@ def main():
                 also["ieee_half_f16"] = {"error": repr(e)[:200]}
         out["also"] = also
     if rank == 0:
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, a)
         print(json.dumps(out), flush=True)
     if world > 1:

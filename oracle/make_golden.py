@@ -747,6 +747,31 @@ def typical_fixtures():
 
 
 @torch.no_grad()
+def typical_warper_fixtures():
+    """The reference's TypicalLogitsWarper subclass (indextts/utils/typical_sampling.py) on the score vectors of
+    tests/test_sampling_oracle.py::test_typical_filter_matches_reference_class: the tokens it keeps, one bit per token.
+    The kept scores pass through unchanged, so the mask is the whole output."""
+    from indextts.utils.typical_sampling import TypicalLogitsWarper
+
+    out = {}
+    for V in (66, 8194):
+        for mass, min_keep in ((0.9, 1), (0.5, 2), (0.2, 1), (0.97, 2)):
+            warper = TypicalLogitsWarper(mass=mass, min_tokens_to_keep=min_keep)
+            rng = np.random.default_rng(V)
+            keep = []
+            for trial in range(6):
+                s = (rng.standard_normal(V) * (0.5 + trial)).astype(np.float32)
+                if trial == 4:
+                    s[5] = -np.inf
+                want = warper(torch.zeros(1, 1, dtype=torch.long), torch.from_numpy(s)[None].clone())[0].numpy()
+                k = np.isfinite(want)
+                assert np.array_equal(want, np.where(k, s, -np.inf).astype(np.float32))
+                keep.append(np.packbits(k))
+            out[f"keep_V{V}_m{mass}_k{min_keep}"] = np.stack(keep)
+    save("typical_warper_cases", **out)
+
+
+@torch.no_grad()
 def cond_batch_fixtures():
     """A batch of prompts of different lengths (model.py:490-502 with cond_mel_lengths, :599-602 per-row conditioning): two
     prompts padded to 61 frames, lengths 61 and 45, the padding filled with noise (it must not matter); conditioning latents
@@ -831,6 +856,7 @@ if __name__ == "__main__":
     ap.add_argument("--smooth", action="store_true")
     ap.add_argument("--cond-batch", action="store_true")
     ap.add_argument("--typical", action="store_true")
+    ap.add_argument("--typical-warper", action="store_true")
     ap.add_argument("--eos", action="store_true")
     ap.add_argument("--nrs", action="store_true")
     ap.add_argument("--host-beams", action="store_true")
@@ -847,6 +873,8 @@ if __name__ == "__main__":
         cond_batch_fixtures()
     if a.typical:
         typical_fixtures()
+    if a.typical_warper:
+        typical_warper_fixtures()
     if a.eos:
         eos_fixtures()
     if a.nrs:

@@ -138,3 +138,25 @@ def test_mel_front_end_shapes_and_bank():
     m = fe(tone)[0, :, 20]
     f_pts = 700.0 * (10.0 ** (torch.linspace(0, 2595.0 * math.log10(1 + 12000.0 / 700.0), 102) / 2595.0) - 1.0)
     assert abs(float(f_pts[1 + int(m.argmax())]) - 3000.0) < 150.0  # the loudest band sits on the tone
+
+
+def test_bench_dump_outputs_within_and_beyond_the_budget(tmp_path):
+    """bench.py --dump-outputs: every sample while the waveforms fit in 64 MB, a fixed seeded sample (values + positions,
+    the same on every call) beyond it."""
+    import bench
+
+    small = [np.arange(-5, 5, dtype=np.int16), np.full(3, 7, np.int16)]
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert np.load(tmp_path / "a" / "wav.npy").tolist() == list(range(-5, 5)) + [7, 7, 7]
+    assert np.load(tmp_path / "a" / "wav_lengths.npy").tolist() == [10.0, 3.0] and not (tmp_path / "a" / "wav_index.npy").exists()
+    rng = np.random.default_rng(1)
+    big = [rng.integers(-32767, 32768, 9 * 2 ** 20, dtype=np.int16) for _ in range(2)]
+    flat = np.concatenate(big)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = [tmp_path / "b" / f for f in ("wav.npy", "wav_index.npy", "wav_lengths.npy")]
+    assert sum(os.path.getsize(f) for f in files) <= bench.DUMP_BUDGET_BYTES == 64 * 10 ** 6
+    wav, idx = np.load(files[0]), np.load(files[1])
+    assert wav.dtype == np.float32 and idx.dtype == np.float64 and wav.shape == idx.shape == (bench.DUMP_SAMPLE,)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(wav, flat[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "wav_index.npy"))

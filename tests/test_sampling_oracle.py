@@ -193,27 +193,16 @@ def test_beam_sample_generate_matches_reference_fixture(gold, tag):
 
 @pytest.mark.parametrize("V", [66, 8194])
 @pytest.mark.parametrize("mass,min_keep", [(0.9, 1), (0.5, 2), (0.2, 1), (0.97, 2)])
-def test_typical_filter_matches_reference_class(V, mass, min_keep):
-    """hf_beam.typical_filter against the reference's own TypicalLogitsWarper subclass (indextts/utils/typical_sampling.py,
-    imported from /root/reference when present; the installed transformers base class otherwise - same algorithm)."""
-    from oracle import ref_import
-
-    if ref_import.available():
-        import importlib.util
-        import os
-
-        spec = importlib.util.spec_from_file_location("_ref_typical", os.path.join(ref_import.REF_ROOT, "indextts", "utils", "typical_sampling.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        warper = mod.TypicalLogitsWarper(mass=mass, min_tokens_to_keep=min_keep)
-    else:
-        warper = tlp.TypicalLogitsWarper(mass=mass, min_tokens_to_keep=min_keep)
+def test_typical_filter_matches_reference_class(V, mass, min_keep, gold):
+    """hf_beam.typical_filter against the reference's own TypicalLogitsWarper subclass (indextts/utils/typical_sampling.py):
+    the tokens it keeps on these score vectors are stored in typical_warper_cases (oracle/make_golden.py --typical-warper)."""
+    keep = np.unpackbits(gold("typical_warper_cases")[f"keep_V{V}_m{mass}_k{min_keep}"], axis=1, count=V).astype(bool)
     rng = np.random.default_rng(V)
     for trial in range(6):
         s = (rng.standard_normal(V) * (0.5 + trial)).astype(np.float32)
         if trial == 4:
             s[5] = -np.inf
-        want = warper(torch.zeros(1, 1, dtype=torch.long), torch.from_numpy(s)[None].clone())[0].numpy()
+        want = np.where(keep[trial], s, -np.inf).astype(np.float32)  # the warper passes kept scores through unchanged
         got = hf_beam.typical_filter(s, mass, min_keep)
         kg, kw = np.isfinite(got), np.isfinite(want)
         # the cut sits where an fp32 running sum over thousands of terms crosses `mass`: torch.cumsum and a sequential sum

@@ -1,13 +1,14 @@
 #!/bin/bash
-# Round profile: (1) bench with cpu baseline, (2) rocprofv3 --kernel-trace --stats of the same bench command,
+# Round profile: (1) the --full bench line (cpu baseline, secondary measurements), (2) rocprofv3 --kernel-trace --stats of the same bench command,
 # (3) PMC passes (FETCH_SIZE, WRITE_SIZE) on a short decode for the HBM-traffic column.  Run on the GPU box:
 #   tools/round_profile.sh r01
 tag=${1:-rXX}
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 if [ -z "$ONLY_PMC" ]; then
-python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 > $out/bench.json 2> $out/bench.err
+python3 $repo/bench.py --full --steps 5 --warmup 1 > $out/bench.json 2> $out/bench.err
 tail -1 $out/bench.json | cut -c1-300
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-also > $out/bench_profiled.json 2> $out/prof.err
 t=$(find $out/stats -name "*kernel_trace.csv" | head -1)
