@@ -11,10 +11,6 @@
 namespace itts {
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int DH = 64, QT = 64, KT = 64, KROW = 72;  // LDS row stride in bf16 (144 B: conflict-free for ds_read_b128)
 // DQK = query/key width: 64 (GPT, perceiver) or 128 (conformer rel-pos attention as [q+u | q+v] . [k | p]); values are 64 wide
 
@@ -54,13 +50,13 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnArgs a) {
   const int fr = lane & 15, fg = lane >> 4;
   // Q fragments of this wave's 16 rows (A operand: row fr, dims 32*ks + 8*fg .. +8), pre-scaled later in fp32
   const int qrow = min(q0 + wave * 16 + fr, a.Sq - 1);
-  bf16x8 qf[KS];
+  half8_bits qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8*>(q + ((size_t)b * a.Sq + qrow) * a.ldq + h * DQK + ks * 32 + fg * 8);
-  f32x4v oacc[4];
+    qf[ks] = *reinterpret_cast<const half8_bits*>(q + ((size_t)b * a.Sq + qrow) * a.ldq + h * DQK + ks * 32 + fg * 8);
+  f32x4 oacc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) oacc[t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 4; ++t) oacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[4], l[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -93,13 +89,13 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnArgs a) {
     }
     __syncthreads();
     // ---- S = Q K^T : 4 key tiles of 16 x 2 k-steps ----
-    f32x4v s[4];
+    f32x4 s[4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      s[nt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+      s[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(&sK[nt * 16 + fr][ks * 32 + fg * 8]);
+        const half8_bits kf = *reinterpret_cast<const half8_bits*>(&sK[nt * 16 + fr][ks * 32 + fg * 8]);
         s[nt] = half_mfma16(qf[ks], kf, s[nt]);
       }
     }
@@ -140,15 +136,15 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) sP[wave][fg * 4 + r][nt * 16 + fr] = (bf16_t)p[nt][r];
     __builtin_amdgcn_wave_barrier();
-    bf16x8 pf[2];
+    half8_bits pf[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) pf[ks] = *reinterpret_cast<const bf16x8*>(&sP[wave][fr][ks * 32 + fg * 8]);
+    for (int ks = 0; ks < 2; ++ks) pf[ks] = *reinterpret_cast<const half8_bits*>(&sP[wave][fr][ks * 32 + fg * 8]);
     // ---- O += P V : 4 dim tiles of 16 x 2 k-steps (keys) ----
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 vf = *reinterpret_cast<const bf16x8*>(&sVt[t * 16 + fr][ks * 32 + fg * 8]);
+        const half8_bits vf = *reinterpret_cast<const half8_bits*>(&sVt[t * 16 + fr][ks * 32 + fg * 8]);
         oacc[t] = half_mfma16(pf[ks], vf, oacc[t]);
       }
   }

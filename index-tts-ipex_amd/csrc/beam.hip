@@ -14,17 +14,12 @@
 // KV-cache ancestry rows (see decode_attn2_kernel ANC - the cache itself is never copied), and prepare the next
 // step's input embeddings.
 #include "itts_decode.h"
+#include "itts_wave_dev.h"
 
 namespace itts {
 namespace {
 
-constexpr int MAXB = 10;   // beams per batch item (the reference web UI offers 1..10)
-constexpr int MAXC = BEAM_MAX_CAND;  // kept candidates per beam (top_k <= 128; the UI offers 0..100)
-
-__device__ __forceinline__ unsigned okey(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+constexpr int MAXB = 10;   // beams per batch item (the reference web UI offers 1..10); kept candidates per beam: BEAM_MAX_CAND
 
 __device__ __forceinline__ float block_max(float v, float* red, int tid) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -45,14 +40,14 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid) {
   return r;
 }
 
-// bitonic sort of MAXC (value, index) pairs in LDS by ONE wave (lanes 0..63 = the MAXC / 2 comparators of a stage): a
+// bitonic sort of BEAM_MAX_CAND (value, index) pairs in LDS by ONE wave (lanes 0..63 = the BEAM_MAX_CAND / 2 comparators of a stage): a
 // wave's LDS operations execute in program order, so the 28 stages need no workgroup barrier (at 16 waves each barrier
 // costs ~0.4 us and the block form spent 11 us per sort); the fence only pins the compiler's order.
 // BY_SCORE: descending value, ascending index on ties; else ascending index.
 template <bool BY_SCORE>
 __device__ __forceinline__ void sort_cands_wave(float* cv, int* ci, int lane) {
-  static_assert(MAXC == 128, "one comparator per lane");
-  for (int kq = 2; kq <= MAXC; kq <<= 1)
+  static_assert(BEAM_MAX_CAND == 128, "one comparator per lane");
+  for (int kq = 2; kq <= BEAM_MAX_CAND; kq <<= 1)
     for (int j = kq >> 1; j > 0; j >>= 1) {
       const int lo = ((lane & ~(j - 1)) << 1) | (lane & (j - 1)), hi = lo | j;
       const bool up = (lo & kq) == 0;
@@ -69,31 +64,14 @@ __device__ __forceinline__ void sort_cands_wave(float* cv, int* ci, int lane) {
     }
 }
 
-// value of lane l (wave-uniform l) in every lane: v_readlane_b32, no LDS crossbar round trip
-__device__ __forceinline__ float lane_val(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
-// histogram increment aggregated over the wave: the digits of log-probabilities crowd into a handful of bins (the top
-// byte is sign + high exponent bits), and 64 lanes adding to one LDS word serialise; here each distinct digit of the
-// wave costs one atomic.  Every lane of the wave must call it (act = does this lane contribute).
-__device__ __forceinline__ void hist_add_wave(unsigned* hist, unsigned digit, bool act, int lane) {
-  unsigned long long m = __ballot(act);
-  while (m) {  // wave-uniform
-    const int leader = __ffsll((long long)m) - 1;
-    const unsigned dl = (unsigned)__shfl((int)digit, leader, 64);
-    const unsigned long long same = __ballot(act && digit == dl);
-    if (lane == leader) atomicAdd(&hist[dl], (unsigned)__popcll(same));
-    m &= ~same;
-  }
-}
-
 __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   extern __shared__ float ssc[];  // [V] processed scores of this beam
   __shared__ unsigned seenw[512];  // V <= 16384 bits
   __shared__ unsigned hist[256];
   __shared__ float red[16];
   __shared__ int s_bin, s_k, s_cnt;
-  __shared__ float cval[MAXC];
-  __shared__ int cidx[MAXC];
+  __shared__ float cval[BEAM_MAX_CAND];
+  __shared__ int cidx[BEAM_MAX_CAND];
   const int r = blockIdx.x, bi = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
   const int nb = a.nb, V = a.V, Beff = a.B * nb, mg = a.max_gen;
   const int k = a.len[bi * nb];  // tokens generated so far: the same for every beam (they step together)
@@ -145,7 +123,7 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
     __syncthreads();
     for (int i0 = 0; i0 < V; i0 += 1024) {  // every lane takes part in every round (wave-aggregated atomics)
       const int i = i0 + tid;
-      const unsigned key = i < V ? okey(ssc[i]) : 0u;
+      const unsigned key = i < V ? order_key(ssc[i]) : 0u;
       const bool act = i < V && (pass == 3 || (key >> (shift + 8)) == (prefix >> (shift + 8)));
       hist_add_wave(hist, (key >> shift) & 255u, act, lane);
     }
@@ -181,7 +159,7 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
     kk = s_k;
   }
   if (tid == 0) s_cnt = 0;
-  if (tid < MAXC) {
+  if (tid < BEAM_MAX_CAND) {
     cval[tid] = -INFINITY;
     cidx[tid] = 0x7fffffff;
   }
@@ -190,16 +168,16 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
     const float v = ssc[i];
     // (-inf scores - filtered by the typical pre-pass, the suppressed stop - never count: when fewer than top_k finite
     // scores exist the k-th largest is -inf and HF's `scores < kth` removes nothing, i.e. keeps exactly the finite ones)
-    if (okey(v) >= prefix && v > -INFINITY) {
+    if (order_key(v) >= prefix && v > -INFINITY) {
       const int p = atomicAdd(&s_cnt, 1);
-      if (p < MAXC) {
+      if (p < BEAM_MAX_CAND) {
         cval[p] = v;
         cidx[p] = i;
       }
     }
   }
   __syncthreads();
-  const int n = min(s_cnt, MAXC);
+  const int n = min(s_cnt, BEAM_MAX_CAND);
   if (tid < 64) sort_cands_wave<true>(cval, cidx, lane);  // descending score, ascending index on ties
   __syncthreads();
   if (tid < 64) {
@@ -228,7 +206,7 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   }
   __syncthreads();
   const int R = s_cnt;
-  if (tid < MAXC && tid >= R) {  // dropped by top-p (or never filled): out of the token-order sort
+  if (tid < BEAM_MAX_CAND && tid >= R) {  // dropped by top-p (or never filled): out of the token-order sort
     cval[tid] = 0.f;
     cidx[tid] = 0x7fffffff;
   }
@@ -236,19 +214,19 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   // the kept ones in token order (the flat index order of next_token_scores.view(batch, beams * vocab))
   if (tid < 64) sort_cands_wave<false>(cval, cidx, lane);
   __syncthreads();
-  if (tid < MAXC) {
-    a.cand_sc[(size_t)row * MAXC + tid] = cval[tid] + a.beam_scores[row];
-    a.cand_tok[(size_t)row * MAXC + tid] = cidx[tid];
+  if (tid < BEAM_MAX_CAND) {
+    a.cand_sc[(size_t)row * BEAM_MAX_CAND + tid] = cval[tid] + a.beam_scores[row];
+    a.cand_tok[(size_t)row * BEAM_MAX_CAND + tid] = cidx[tid];
     if (tid == 0) a.cand_n[row] = R;
   }
 }
 
 __global__ __launch_bounds__(1024) void beam_select_kernel(BeamArgs a) {
   // the kept candidates of the item's beams in flat (beam-major, token-ascending) order, running beam score included
-  __shared__ float fsc[MAXB * MAXC];
-  __shared__ int ftok[MAXB * MAXC];
-  __shared__ float fe[MAXB * MAXC];  // exp(score - max)
-  __shared__ unsigned char fbeam[MAXB * MAXC], falive[MAXB * MAXC];
+  __shared__ float fsc[MAXB * BEAM_MAX_CAND];
+  __shared__ int ftok[MAXB * BEAM_MAX_CAND];
+  __shared__ float fe[MAXB * BEAM_MAX_CAND];  // exp(score - max)
+  __shared__ unsigned char fbeam[MAXB * BEAM_MAX_CAND], falive[MAXB * BEAM_MAX_CAND];
   __shared__ int cand_n[MAXB], cand_off[MAXB + 1];
   __shared__ float red[16];
   __shared__ float p_sc[2 * MAXB];  // the 2 * nb picks in draw order
@@ -298,13 +276,13 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(BeamArgs a) {
     __syncthreads();
     const int T = cand_off[nb];
     float mloc = -INFINITY;
-    for (int i = tid; i < nb * MAXC; i += 1024) {
-      const int r = i / MAXC, q = i - r * MAXC;
+    for (int i = tid; i < nb * BEAM_MAX_CAND; i += 1024) {
+      const int r = i / BEAM_MAX_CAND, q = i - r * BEAM_MAX_CAND;
       if (q < cand_n[r]) {
         const int f = cand_off[r] + q;
-        const float v = a.cand_sc[(size_t)(bi * nb + r) * MAXC + q];
+        const float v = a.cand_sc[(size_t)(bi * nb + r) * BEAM_MAX_CAND + q];
         fsc[f] = v;
-        ftok[f] = a.cand_tok[(size_t)(bi * nb + r) * MAXC + q];
+        ftok[f] = a.cand_tok[(size_t)(bi * nb + r) * BEAM_MAX_CAND + q];
         fbeam[f] = (unsigned char)r;
         falive[f] = 1;
         mloc = fmaxf(mloc, v);
@@ -708,7 +686,7 @@ int typical_filter(const TypicalArgs& a, int rows, hipStream_t s) {
 
 int beam_sample_step(const BeamArgs& a, hipStream_t s) {
   ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB, "beam_sample: 2 <= num_beams <= 10");
-  ITTS_REQUIRE(!a.do_sample || (a.top_k >= 1 && a.top_k <= MAXC && a.top_p > 0.f && a.temperature > 0.f),
+  ITTS_REQUIRE(!a.do_sample || (a.top_k >= 1 && a.top_k <= BEAM_MAX_CAND && a.top_p > 0.f && a.temperature > 0.f),
                "beam_sample: 1 <= top_k <= 128, top_p > 0, temperature > 0");
   ITTS_REQUIRE(a.V <= 15000, "beam_sample: vocabulary too large for the LDS-resident sampler");
   ITTS_REQUIRE(a.logits && (a.uniforms || !a.do_sample) && a.ids && a.anc && a.len && a.hyp_tok && a.done, "beam_sample: null state");

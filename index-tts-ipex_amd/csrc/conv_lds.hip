@@ -30,10 +30,6 @@
 namespace itts {
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WROW = 32;  // bf16 per staged weight row: 64 bytes = four 16-byte slots, slot q of row r at q ^ ((r >> 1) & 2)
 constexpr int PROWE = 32;  // bf16 per activation-plane row (64 bytes)
 __device__ __forceinline__ int swz4(int row) { return (row >> 1) & 2; }
@@ -156,11 +152,11 @@ __global__ __launch_bounds__(256) void conv_lds_kernel(GemmArgs g, int tiles_per
           *reinterpret_cast<u32x4*>(sW + ((size_t)c * NP + lr + 64 * p) * WROW + ((lq ^ swz4(lr + 64 * p)) << 3)) =
               ((wok >> (c * 8 + p)) & 1u) ? rw[c][p] : u32x4{0u, 0u, 0u, 0u};
   };
-  f32x4v acc[MT][NT];
+  f32x4 acc[MT][NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   load_w();
   store_w();
   __syncthreads();
@@ -176,14 +172,14 @@ __global__ __launch_bounds__(256) void conv_lds_kernel(GemmArgs g, int tiles_per
         const bool cok = fk < C - c0;  // lanes past the last channel of a partial chunk read zero
         const int arow = a_row0 + tap * g.dil;
         const bf16_t* ap = sA + ((size_t)(c0 >> 5) * HR + arow) * PROWE + ((fg ^ swz4(arow)) << 3);
-        bf16x8 af[MT], wf[NT];
+        half8_bits af[MT], wf[NT];
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
-          const bf16x8 v = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * PROWE);
-          af[i] = cok ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+          const half8_bits v = *reinterpret_cast<const half8_bits*>(ap + (size_t)i * 16 * PROWE);
+          af[i] = cok ? v : half8_bits{0, 0, 0, 0, 0, 0, 0, 0};
         }
 #pragma unroll
-        for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const bf16x8*>(w_lane + ((size_t)c * NP + j * 16) * WROW);
+        for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const half8_bits*>(w_lane + ((size_t)c * NP + j * 16) * WROW);
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll

@@ -8,32 +8,11 @@
 
 #include "itts_decode.h"
 #include "itts_sampler_dev.h"
+#include "itts_wave_dev.h"
 #include "decode_pinned.h"
 
 namespace itts {
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// weights are read exactly once per step: non-temporal 16-byte loads (MI355X_MICROARCH "nt-weights")
-template <typename TW> struct V8;
-template <> struct V8<bf16_t> {
-  u32x4 raw;
-  __device__ __forceinline__ void load(const bf16_t* p) { raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-  __device__ __forceinline__ float get(int i) const {
-    const uint32_t w = raw[i >> 1];
-    return (i & 1) ? half_hi(w) : half_lo(w);
-  }
-};
-template <> struct V8<float> {
-  f32x4 a, b;
-  __device__ __forceinline__ void load(const float* p) {
-    a = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    b = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + 4));
-  }
-  __device__ __forceinline__ float get(int i) const { return i < 4 ? a[i] : b[i - 4]; }
-};
 
 // ---------------------------------------------------------------------------------------------
 // gemv2: Y[b, n] (+)= act( prologue(X)[b, :] . W[n, :] + bias[n] )
@@ -230,42 +209,6 @@ __global__ __launch_bounds__(256) void gemv2_kernel(GemvArgs g) {
 //     16-byte weight fragment instead of 8 cvt + 8 fma (the kernels are short enough to be issue-bound);
 //   * the output can be written as bf16 (gelu(fc) feeding proj2) to halve the next kernel's LDS fill.
 // ---------------------------------------------------------------------------------------------
-typedef bf16_t bf16x2_t __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
-  v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
-  v = dpp_add<0x141>(v);  // row_half_mirror
-  v = dpp_add<0x140>(v);  // row_mirror: every lane now holds the sum of its 16-lane row
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-// full-wave sum, result uniform in every lane: DPP inside the 16-lane rows, then one v_readlane per row - no ds_bpermute
-// (an LDS-crossbar round trip with an lgkmcnt wait) on the dependent chain
-__device__ __forceinline__ float wave_sum_rl(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  v = dpp_add<0x140>(v);
-  const int iv = __float_as_int(v);
-  const float a = __int_as_float(__builtin_amdgcn_readlane(iv, 0)), b = __int_as_float(__builtin_amdgcn_readlane(iv, 16));
-  const float c = __int_as_float(__builtin_amdgcn_readlane(iv, 32)), d = __int_as_float(__builtin_amdgcn_readlane(iv, 48));
-  return (a + b) + (c + d);
-}
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  bf16x2_t v = {(bf16_t)a, (bf16_t)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
-  return half_dot2(a, b, c);
-}
-
 // PRO: 0 plain, 1 LayerNorm without affine (gamma/beta are folded into W by the packer), 2 LayerNorm(affine) then
 // LayerNorm without affine (ln_f, then final_norm folded into mel_head).  XBF: X is bf16 [B, K].  YBF: Y is bf16.
 // (A wave-specialised variant - dedicated activation waves - was measured slower.)
@@ -496,12 +439,12 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_bf16_kernel(GemvArgs g) {
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2) {
             const uint32_t q = w8[r][c][h2];  // 4 fp8: bytes 0,1 -> pair 2*h2, bytes 2,3 -> pair 2*h2 + 1
-            acc[r][b] = dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, false)), xq[2 * h2], acc[r][b]);
-            acc[r][b] = dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, true)), xq[2 * h2 + 1], acc[r][b]);
+            acc[r][b] = half_dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, false)), xq[2 * h2], acc[r][b]);
+            acc[r][b] = half_dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, true)), xq[2 * h2 + 1], acc[r][b]);
           }
         } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[r][b] = dot2(w[r][c][e], xq[e], acc[r][b]);
+          for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(w[r][c][e], xq[e], acc[r][b]);
         }
       }
     }
@@ -668,15 +611,15 @@ __global__ __launch_bounds__(256) void gemv_wave_kernel(GemvArgs g) {
           const uint32_t hi = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, true));
 #pragma unroll
           for (int b = 0; b < NB; ++b) {
-            acc[r][b] = dot2(lo, xq[b][c][2 * h2], acc[r][b]);
-            acc[r][b] = dot2(hi, xq[b][c][2 * h2 + 1], acc[r][b]);
+            acc[r][b] = half_dot2(lo, xq[b][c][2 * h2], acc[r][b]);
+            acc[r][b] = half_dot2(hi, xq[b][c][2 * h2 + 1], acc[r][b]);
           }
         }
       } else {
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[r][b] = dot2(w[r][c][e], xq[b][c][e], acc[r][b]);
+          for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(w[r][c][e], xq[b][c][e], acc[r][b]);
       }
     }
   // ---- 4. wave reduction, then one lane per output ----
@@ -717,8 +660,7 @@ template <> struct CacheVec<bf16_t> {
 #else
   // the cache is read once per step and never again before it has left every cache: nontemporal (streaming) loads
   __device__ __forceinline__ void load(const bf16_t* p) {
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
+    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
     raw = make_uint4(t[0], t[1], t[2], t[3]);
   }
 #endif
@@ -1217,12 +1159,12 @@ __device__ __forceinline__ void fused_gemv_part(const GemvArgs& g, int blk, unsi
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2) {
             const uint32_t q = w8[r][c][h2];  // 4 fp8: bytes 0,1 -> pair 2*h2, bytes 2,3 -> pair 2*h2 + 1
-            acc[r][b] = dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, false)), xq[2 * h2], acc[r][b]);
-            acc[r][b] = dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, true)), xq[2 * h2 + 1], acc[r][b]);
+            acc[r][b] = half_dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, false)), xq[2 * h2], acc[r][b]);
+            acc[r][b] = half_dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, true)), xq[2 * h2 + 1], acc[r][b]);
           }
         } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[r][b] = dot2(w[r][c][e], xq[e], acc[r][b]);
+          for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(w[r][c][e], xq[e], acc[r][b]);
         }
       }
     }
@@ -1601,38 +1543,15 @@ __global__ __launch_bounds__(1024) void sampler2_kernel(SamplerArgs a) {
 // sampler_sample: the do_sample=True path of HF 4.36.2 GenerationMixin.sample as infer.py:116-124 configures it
 // (RepetitionPenaltyLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax ->
 // multinomial), one 1024-thread block per row.  Scores live in LDS; the k-th largest score is found by a 4-pass
-// radix select on order-preserving keys (no sort of the vocabulary), the <= 64 survivors are bitonic-sorted by one
+// radix select on order-preserving keys (no sort of the vocabulary), the <= 128 survivors are bitonic-sorted by one
 // wave, top-p and the draw run serially over them in the order torch.cumsum uses.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned order_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-constexpr int SMAXC = 128;  // kept candidates (top_k <= 128: the reference web UI offers 0..100)
-
-// value of lane l (wave-uniform l) in every lane: v_readlane_b32, no LDS crossbar round trip
-__device__ __forceinline__ float lane_val(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
-// histogram increment aggregated over the wave (as beam.hip): the digits of scores crowd into a few bins and 64 lanes
-// adding to one LDS word serialise; each distinct digit of the wave costs one atomic.  Every lane of the wave calls it.
-__device__ __forceinline__ void hist_add_wave(unsigned* hist, unsigned digit, bool act, int lane) {
-  unsigned long long m = __ballot(act);
-  while (m) {  // wave-uniform
-    const int leader = __ffsll((long long)m) - 1;
-    const unsigned dl = (unsigned)__shfl((int)digit, leader, 64);
-    const unsigned long long same = __ballot(act && digit == dl);
-    if (lane == leader) atomicAdd(&hist[dl], (unsigned)__popcll(same));
-    m &= ~same;
-  }
-}
-
 __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
   extern __shared__ float ssc[];  // [V] processed scores
   __shared__ unsigned hist[256];
   __shared__ int s_bin, s_k, s_cnt;
-  __shared__ float cval[SMAXC];
-  __shared__ int cidx[SMAXC];
+  __shared__ float cval[BEAM_MAX_CAND];
+  __shared__ int cidx[BEAM_MAX_CAND];
   __shared__ int si[2];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const float* __restrict__ lg = a.logits + (size_t)b * a.V;
@@ -1691,9 +1610,9 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
     prefix |= (unsigned)s_bin << shift;
     kk = s_k;
   }
-  // ---- gather the survivors (score >= k-th largest; ties kept as HF's `scores < kth` mask keeps them, up to SMAXC) ----
+  // ---- gather the survivors (score >= k-th largest; ties kept as HF's `scores < kth` mask keeps them, up to BEAM_MAX_CAND) ----
   if (tid == 0) s_cnt = 0;
-  if (tid < SMAXC) {
+  if (tid < BEAM_MAX_CAND) {
     cval[tid] = -INFINITY;
     cidx[tid] = 0x7fffffff;
   }
@@ -1703,18 +1622,18 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
     // -inf scores never count: with fewer than top_k finite scores HF's `scores < kth` (kth = -inf) keeps exactly the finite ones
     if (order_key(v) >= prefix && v > -INFINITY) {
       const int pos = atomicAdd(&s_cnt, 1);
-      if (pos < SMAXC) {
+      if (pos < BEAM_MAX_CAND) {
         cval[pos] = v;
         cidx[pos] = i;
       }
     }
   }
   __syncthreads();
-  // bitonic sort in LDS by ONE wave (64 lanes = the SMAXC / 2 comparators of a stage; a wave's LDS operations execute in
+  // bitonic sort in LDS by ONE wave (64 lanes = the BEAM_MAX_CAND / 2 comparators of a stage; a wave's LDS operations execute in
   // program order, so the 28 stages need no workgroup barrier): descending score, ascending index on ties
-  static_assert(SMAXC == 128, "one comparator per lane");
+  static_assert(BEAM_MAX_CAND == 128, "one comparator per lane");
   if (tid < 64) {
-    for (int kq = 2; kq <= SMAXC; kq <<= 1)
+    for (int kq = 2; kq <= BEAM_MAX_CAND; kq <<= 1)
       for (int j = kq >> 1; j > 0; j >>= 1) {
         const int lo = ((lane & ~(j - 1)) << 1) | (lane & (j - 1)), hi = lo | j;
         const bool up = (lo & kq) == 0;
@@ -1734,7 +1653,7 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
   if (tid < 64) {
     // wave 0: the exponentials and quotients in parallel (lane r and r + 64 of the sorted candidates), the running sums
     // sequentially in the restatement's order, every lane carrying them (values broadcast lane by lane)
-    const int n = min(s_cnt, SMAXC);
+    const int n = min(s_cnt, BEAM_MAX_CAND);
     const float m = cval[0];
     const float e0 = lane < n ? expf(cval[lane] - m) : 0.f, e1 = lane + 64 < n ? expf(cval[lane + 64] - m) : 0.f;
     auto ev = [&](int r) { return r < 64 ? lane_val(e0, r) : lane_val(e1, r - 64); };

@@ -24,7 +24,8 @@
 //     rows are requested right after the layer's first gather, one projection ahead of the scores.
 //
 // Arithmetic is the launch path's, operation for operation (same lane <-> k mapping and accumulation order of the GEMV
-// dot products, same LayerNorm reduction tree, same attention window / split / merge): logits and ids are bit-identical
+// dot products, same LayerNorm reduction tree - itts_wave_dev.h, one definition for both paths -, same attention window /
+// split / merge; contraction-sensitive expressions in decode_pinned.h): logits and ids are bit-identical
 // to gemv_bf16_kernel + decode_attn2_kernel at 1 - 4 rows (tests/test_gpu_engine_persistent.py); 5 - 6 rows keep that
 // arithmetic row for row (the launch path runs on the matrix cores there: tolerance + row-independence tests).
 // LDS maps by row count: three weight slots (<= 2 rows), two slots with aliased edge buffers (3 - 4), a half slot B (5 - 6).
@@ -37,6 +38,7 @@
 #include "itts_decode.h"
 #include "itts_engine_kernel.h"
 #include "itts_sampler_dev.h"
+#include "itts_wave_dev.h"
 #include "decode_pinned.h"
 
 #ifndef ITTS_KV_PREFETCH
@@ -52,45 +54,7 @@
 namespace itts {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef bf16_t bf16x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-// full-wave sum, uniform in every lane (decode2.hip wave_sum_rl: same tree, same bits)
-__device__ __forceinline__ float wave_sum_rl(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  v = dpp_add<0x140>(v);
-  const int iv = __float_as_int(v);
-  const float a = __int_as_float(__builtin_amdgcn_readlane(iv, 0)), b = __int_as_float(__builtin_amdgcn_readlane(iv, 16));
-  const float c = __int_as_float(__builtin_amdgcn_readlane(iv, 32)), d = __int_as_float(__builtin_amdgcn_readlane(iv, 48));
-  return (a + b) + (c + d);
-}
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  bf16x2_t v = {(bf16_t)a, (bf16_t)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
-  return half_dot2(a, b, c);
-}
-__device__ __forceinline__ float bf16_lo(uint32_t w) { return half_lo(w); }
-__device__ __forceinline__ float bf16_hi(uint32_t w) { return half_hi(w); }
-
-struct KVec {  // 8 bf16 of one cache row (decode2.hip CacheVec<bf16_t>)
-  u32x4 raw;
-  __device__ __forceinline__ void load(const bf16_t* p) { raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-  __device__ __forceinline__ float get(int i) const {
-    const uint32_t w = raw[i >> 1];
-    return (i & 1) ? bf16_hi(w) : bf16_lo(w);
-  }
-};
 
 // ---- run-time state of one workgroup's hand-offs ----
 struct Rt {
@@ -335,7 +299,7 @@ __device__ __forceinline__ void dots(const unsigned char* __restrict__ wrow, con
 #pragma unroll
         for (int e = 0; e < 4; ++e) xq[e] = kok ? xq[e] : 0u;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[b] = dot2(w[e], xq[e], acc[b]);
+      for (int e = 0; e < 4; ++e) acc[b] = half_dot2(w[e], xq[e], acc[b]);
     }
   }
 }
@@ -352,7 +316,7 @@ __device__ __forceinline__ void dots_part(const unsigned char* __restrict__ wpar
     for (int b = 0; b < NB; ++b) {
       const u32x4 xq = *reinterpret_cast<const u32x4*>(sxb + (b * KTOT + k) / 2);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[b] = dot2(w[e], xq[e], acc[b]);
+      for (int e = 0; e < 4; ++e) acc[b] = half_dot2(w[e], xq[e], acc[b]);
     }
   }
 }
@@ -654,7 +618,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     // for c_attn (vmcnt is in-order: a wait of theirs in front of these requests would hold the sweep / the first barrier for
     // an HBM miss).  Same rows, same registers, same arithmetic as before.
     constexpr int NIT_ = 3, NSPLIT_ = 4, SLOTS_ = 32, LPK_ = 8, VEC_ = 8, UNC_ = 2;
-    KVec kr[2 * NIT_], vr[2 * NIT_];
+    V8<bf16_t> kr[2 * NIT_], vr[2 * NIT_];
     const int a_sp = wave >> 2, a_atid = (wave & 3) * 64 + ll, a_slot = a_atid / LPK_, a_sub = a_atid % LPK_;
     const size_t a_lo = ((size_t)l * a.B * H + (size_t)(acu ? gm : 0) * H + gh) * a.Smax * DH;
     const uint8_t* a_arow = nullptr;
@@ -817,7 +781,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       float m = -INFINITY, lsum = 0.f, acc[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      auto score = [&](const KVec& kk) {
+      auto score = [&](const V8<bf16_t>& kk) {
         float sc = 0.f;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) sc = fmaf(qr[i], kk.get(i), sc);
@@ -865,7 +829,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           m = mw;
         }
       }
-      auto consume = [&](const KVec& kk, const KVec& vv, int j) {
+      auto consume = [&](const V8<bf16_t>& kk, const V8<bf16_t>& vv, int j) {
         const bool ok = j < S && j >= ks && j != pos;
         float sc = score(kk);
         sc = ok ? sc : -INFINITY;
@@ -878,7 +842,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         m = mn;
       };
       for (int cb = 2 * NIT; (cb * NSPLIT + sp) * SLOTS < S; cb += SD) {
-        KVec k2[SD], v2[SD];
+        V8<bf16_t> k2[SD], v2[SD];
 #pragma unroll
         for (int u = 0; u < SD; ++u) {
           const int j = min(((cb + u) * NSPLIT + sp) * SLOTS + slot, a.Smax - 1);
@@ -1160,7 +1124,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
 #pragma unroll
           for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[r][b] = dot2(wh[r][c][e], xq[e], acc[r][b]);
+            for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(wh[r][c][e], xq[e], acc[r][b]);
         }
       }
       float mine = 0.f;

@@ -12,20 +12,14 @@
 namespace itts {
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 constexpr int SW = 8;  // waves per workgroup (K split inside the workgroup)
-
 
 // NT = 16-feature tiles per workgroup (each wave multiplies the same X fragments into NT weight tiles: X is the larger
 // L2->CU stream at B = 64, so two tiles per workgroup halve it per output); gridDim.y = K split across workgroups
 // (ksplit > 1: raw partial sums go to g.partial[split][b][n]; bias / residual are applied by ln_rows_bf16).
 // W8: the weights are OCP fp8 e4m3 bytes with one power-of-two scale per output row (BASELINE config 5: half the weight
-// stream); a lane's 8 bytes become the same bf16x8 MFMA operand through v_cvt_scalef32_pk_bf16_fp8, the row scale
+// stream); a lane's 8 bytes become the same half8_bits MFMA operand through v_cvt_scalef32_pk_bf16_fp8, the row scale
 // multiplies the fp32 sum in the epilogue - bit-identical to running the bf16 dequantisation of the same weights.
-typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 
 // LNP (B <= 16 only, BT = 1): X is the fp32 residual stream [B][K]; LayerNorm without affine (folded into W) runs in the
 // prologue - wave w owns rows 2w and 2w + 1, moments by DPP wave sums, the normalised bf16 rows go to LDS and every wave
@@ -73,7 +67,7 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(GemvArgs g) {
   // LNP: this wave's two rows of the residual stream, requested before the weights (L2 hits: they return while the HBM
   // weight requests behind them are in flight - loads return in issue order)
   constexpr int LNE = 8;  // float4 per lane and row: K <= 2048
-  f32x4v hx[LNP ? 2 : 1][LNP ? LNE : 1];
+  f32x4 hx[LNP ? 2 : 1][LNP ? LNE : 1];
   float hpiv[2] = {0.f, 0.f};
   if constexpr (LNP) {
     const float* Hs = g.X;
@@ -83,14 +77,14 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(GemvArgs g) {
       hpiv[r] = hr[0];
 #pragma unroll
       for (int i = 0; i < LNE; ++i)
-        if (i * 256 < K) hx[r][i] = *reinterpret_cast<const f32x4v*>(hr + min(i * 256 + lane * 4, K - 4));
+        if (i * 256 < K) hx[r][i] = *reinterpret_cast<const f32x4*>(hr + min(i * 256 + lane * 4, K - 4));
     }
   }
-  f32x4v acc[NT][BT];
+  f32x4 acc[NT][BT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int bt = 0; bt < BT; ++bt) acc[t][bt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int bt = 0; bt < BT; ++bt) acc[t][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
   // epilogue operands (bias of the outputs this thread will finish) requested up front: the tail then has no
   // dependent memory latency
   constexpr int EPT = (NT * BT * 256 + 511) / 512;
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(GemvArgs g) {
   // LNP: every wave passes through the body exactly once (nks <= SW * SU, host-checked), also one without a k-step of its
   // own - it still normalises its two rows and joins the barrier
   for (int k0 = wave; k0 < nks || (LNP && k0 == wave); k0 += SW * SU) {
-    bf16x8 wf[SU][NT], xf[SU][BT];
+    half8_bits wf[SU][NT], xf[SU][BT];
 #pragma unroll
     for (int u = 0; u < SU; ++u) {
       const int ks = k0 + u * SW;
@@ -123,17 +117,17 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(GemvArgs g) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         if (HALF && !wlive) {
-          wf[u][t] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+          wf[u][t] = half8_bits{0, 0, 0, 0, 0, 0, 0, 0};
         } else if constexpr (W8) {
-          const u32x2v q = __builtin_nontemporal_load(reinterpret_cast<const u32x2v*>(wq[t] + (size_t)ks * WSTEP));
-          u32x4v w4;  // bytes 0,1 | 2,3 of each dword -> one bf16 pair each (same pairing as gemv_bf16_kernel<W8>)
+          const u32x2 q = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wq[t] + (size_t)ks * WSTEP));
+          u32x4 w4;  // bytes 0,1 | 2,3 of each dword -> one bf16 pair each (same pairing as gemv_bf16_kernel<W8>)
           w4[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[0], 1.0f, false));
           w4[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[0], 1.0f, true));
           w4[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[1], 1.0f, false));
           w4[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[1], 1.0f, true));
-          wf[u][t] = __builtin_bit_cast(bf16x8, w4);
+          wf[u][t] = __builtin_bit_cast(half8_bits, w4);
         } else {
-          wf[u][t] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp[t] + (size_t)ks * WSTEP));
+          wf[u][t] = __builtin_nontemporal_load(reinterpret_cast<const half8_bits*>(wp[t] + (size_t)ks * WSTEP));
         }
       }
     }
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(GemvArgs g) {
       for (int u = 0; u < SU; ++u) {
         const int ks = k0 + u * SW;
         if (ks >= nks) break;
-        xf[u][0] = *reinterpret_cast<const bf16x8*>(xs + (size_t)fr * xld + ((size_t)ks0 + ks) * 32 + fg * 8);
+        xf[u][0] = *reinterpret_cast<const half8_bits*>(xs + (size_t)fr * xld + ((size_t)ks0 + ks) * 32 + fg * 8);
       }
     } else {
 #pragma unroll
@@ -182,9 +176,9 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(GemvArgs g) {
 #pragma unroll
         for (int bt = 0; bt < BT; ++bt) {
           if (HALF && fr >= g.B)  // rows past the batch: nothing to fetch (their outputs are never stored)
-            xf[u][bt] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            xf[u][bt] = half8_bits{0, 0, 0, 0, 0, 0, 0, 0};
           else
-            xf[u][bt] = *reinterpret_cast<const bf16x8*>(xp[bt] + (size_t)ks * xstep);
+            xf[u][bt] = *reinterpret_cast<const half8_bits*>(xp[bt] + (size_t)ks * xstep);
         }
       }
     }
@@ -313,7 +307,7 @@ __global__ __launch_bounds__(256) void ln_rows_bf16_kernel(bf16_t* __restrict__ 
 }
 
 // one thread per 16-byte group of the tiled copy: (tile, k-step, lane) <- W[tile*16 + lane%16][k-step*32 + lane/16*8 .. +8]
-__global__ __launch_bounds__(256) void retile_weights_kernel(u32x4v* __restrict__ dst, const bf16_t* __restrict__ src, int N, int K,
+__global__ __launch_bounds__(256) void retile_weights_kernel(u32x4* __restrict__ dst, const bf16_t* __restrict__ src, int N, int K,
                                                              size_t groups) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= groups) return;
@@ -321,11 +315,11 @@ __global__ __launch_bounds__(256) void retile_weights_kernel(u32x4v* __restrict_
   const size_t tk = i >> 6;
   const int ks = (int)(tk % nks), tile = (int)(tk / nks);
   const int n = tile * 16 + (lane & 15), k = ks * 32 + (lane >> 4) * 8;
-  dst[i] = n < N ? *reinterpret_cast<const u32x4v*>(src + (size_t)n * K + k) : u32x4v{0u, 0u, 0u, 0u};
+  dst[i] = n < N ? *reinterpret_cast<const u32x4*>(src + (size_t)n * K + k) : u32x4{0u, 0u, 0u, 0u};
 }
 
 // fp8: one thread per 8-byte group
-__global__ __launch_bounds__(256) void retile_weights8_kernel(u32x2v* __restrict__ dst, const uint8_t* __restrict__ src, int N, int K,
+__global__ __launch_bounds__(256) void retile_weights8_kernel(u32x2* __restrict__ dst, const uint8_t* __restrict__ src, int N, int K,
                                                               size_t groups) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= groups) return;
@@ -333,7 +327,7 @@ __global__ __launch_bounds__(256) void retile_weights8_kernel(u32x2v* __restrict
   const size_t tk = i >> 6;
   const int ks = (int)(tk % nks), tile = (int)(tk / nks);
   const int n = tile * 16 + (lane & 15), k = ks * 32 + (lane >> 4) * 8;
-  dst[i] = n < N ? *reinterpret_cast<const u32x2v*>(src + (size_t)n * K + k) : u32x2v{0u, 0u};
+  dst[i] = n < N ? *reinterpret_cast<const u32x2*>(src + (size_t)n * K + k) : u32x2{0u, 0u};
 }
 
 }  // namespace
@@ -342,7 +336,7 @@ int retile_weights_fp8(void* dst, const void* src, int N, int K, hipStream_t s) 
   ITTS_REQUIRE(dst && src && N > 0 && K > 0 && K % 32 == 0, "retile_weights_fp8: K must be a multiple of 32");
   ITTS_REQUIRE(!(((uintptr_t)dst | (uintptr_t)src) & 7), "retile_weights_fp8: pointers must be 8-byte aligned");
   const size_t groups = (size_t)((N + 15) / 16) * (K / 32) * 64;
-  hipLaunchKernelGGL(retile_weights8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (u32x2v*)dst, (const uint8_t*)src, N, K,
+  hipLaunchKernelGGL(retile_weights8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (u32x2*)dst, (const uint8_t*)src, N, K,
                      groups);
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;
@@ -352,7 +346,7 @@ int retile_weights_bf16(void* dst, const void* src, int N, int K, hipStream_t s)
   ITTS_REQUIRE(dst && src && N > 0 && K > 0 && K % 32 == 0, "retile_weights_bf16: K must be a multiple of 32");
   ITTS_REQUIRE(!(((uintptr_t)dst | (uintptr_t)src) & 15), "retile_weights_bf16: pointers must be 16-byte aligned");
   const size_t groups = (size_t)((N + 15) / 16) * (K / 32) * 64;
-  hipLaunchKernelGGL(retile_weights_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (u32x4v*)dst, (const bf16_t*)src, N, K,
+  hipLaunchKernelGGL(retile_weights_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (u32x4*)dst, (const bf16_t*)src, N, K,
                      groups);
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;

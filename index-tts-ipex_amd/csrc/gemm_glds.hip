@@ -15,26 +15,13 @@
 //   * workgroup ids are remapped so that the column tiles of one row tile share an XCD (their A rows hit that L2).
 #include <cstdlib>
 
+#include "itts_gemm_dev.h"
 #include "itts_kernels.h"
 
 namespace itts {
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 __device__ uint4 g_zero_page[16];  // 256 bytes of zeros: the source of out-of-range conv rows
-
-__device__ __forceinline__ int reflect_i(int t, int T) {
-  if (t < 0) t = -t;
-  if (t >= T) t = 2 * (T - 1) - t;
-  return t;
-}
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
 
 constexpr int BM = 128, BK = 64, ROWB = BK * 2;  // 128-byte LDS rows
 
@@ -95,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmArgs g, int tiles
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int ts = a_t[i] + off;
-      if (g.pad_mode == PAD_REFLECT && a_t[i] >= 0) ts = reflect_i(ts, T);
+      if (g.pad_mode == PAD_REFLECT && a_t[i] >= 0) ts = reflect_idx(ts, T);
       const bool ok = ts >= 0 && ts < T;
       const bf16_t* src = ok ? A + (a_off[i] + ts) * g.lda + nx_c0 + a_sw[i] : zp;
       glds16(src, sa + (wave * 32 + i * 8) * ROWB);
@@ -109,11 +96,11 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmArgs g, int tiles
     }
   };
 
-  f32x4v acc[4][NT];
+  f32x4 acc[4][NT];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int fr = lane & 15, fq = lane >> 4;
   // fragment addresses: row r, logical chunk c = 4 * kstep + fq -> byte r * 128 + ((c ^ ((r >> 1) & 7)) << 4)
   int a_rd[4], a_sx[4], w_rd[NT], w_sx[NT];
@@ -138,11 +125,11 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmArgs g, int tiles
     const unsigned char* sb = smem + buf * STAGE;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[4], wf[NT];
+      half8_bits af[4], wf[NT];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8*>(sb + a_rd[i] + (((ks * 4 + fq) ^ a_sx[i]) << 4));
+      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const half8_bits*>(sb + a_rd[i] + (((ks * 4 + fq) ^ a_sx[i]) << 4));
 #pragma unroll
-      for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const bf16x8*>(sb + w_rd[j] + (((ks * 4 + fq) ^ w_sx[j]) << 4));
+      for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const half8_bits*>(sb + w_rd[j] + (((ks * 4 + fq) ^ w_sx[j]) << 4));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll

@@ -13,23 +13,14 @@
 // source rows), so no im2col buffer ever exists in HBM.
 #include <cstdlib>
 
+#include "itts_gemm_dev.h"
 #include "itts_kernels.h"
 
 namespace itts {
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int CK = 32;        // channels per chunk
 constexpr int LDSROW = 40;    // bf16 elements per LDS row (80 bytes)
-
-__device__ __forceinline__ int reflect_idx(int t, int T) {
-  if (t < 0) t = -t;
-  if (t >= T) t = 2 * (T - 1) - t;
-  return t;
-}
 
 // DEPTH = chunk pairs in flight per thread (register ring).  The K loop of one workgroup costs one memory latency per
 // refill; with DEPTH pairs requested ahead the refill rate is DEPTH x higher, which is what the few-tile / long-K shapes
@@ -136,11 +127,11 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmArgs g) {
     }
   };
 
-  f32x4v acc[MT][NT];
+  f32x4 acc[MT][NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d) load_pair(st[d]);  // pairs past the end load clamped addresses and are never stored
@@ -159,11 +150,11 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmArgs g) {
       load_pair(st[d]);  // slot d went to LDS one step ago; refill it with the pair DEPTH ahead
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        bf16x8 af[MT], bfr[NT];
+        half8_bits af[MT], bfr[NT];
 #pragma unroll
-        for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const bf16x8*>(&sA[buf][c][wm * WM + i * 16 + fr][fk]);
+        for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const half8_bits*>(&sA[buf][c][wm * WM + i * 16 + fr][fk]);
 #pragma unroll
-        for (int j = 0; j < NT; ++j) bfr[j] = *reinterpret_cast<const bf16x8*>(&sW[buf][c][wn * WN + j * 16 + fr][fk]);
+        for (int j = 0; j < NT; ++j) bfr[j] = *reinterpret_cast<const half8_bits*>(&sW[buf][c][wn * WN + j * 16 + fr][fk]);
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll

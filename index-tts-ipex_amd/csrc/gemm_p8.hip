@@ -30,26 +30,13 @@
 // stages 80 KB per K-tile (4 + 4 + 1 + 1 DMA instructions per thread) and fills the 160 KB of LDS exactly.
 #include <cstdlib>
 
+#include "itts_gemm_dev.h"
 #include "itts_kernels.h"
 
 namespace itts {
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 __device__ uint4 g_zero_page8[16];  // 256 bytes of zeros: the source of out-of-range conv rows
-
-__device__ __forceinline__ int reflect_i8(int t, int T) {
-  if (t < 0) t = -t;
-  if (t >= T) t = 2 * (T - 1) - t;
-  return t;
-}
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
 
 constexpr int PBK = 64, PROW = PBK * 2;  // 128-byte LDS rows
 
@@ -100,24 +87,24 @@ __device__ __forceinline__ void p8_finish8(const GemmArgs& g, int T, int m, int 
   }
   if (vec_ok && sizeof(TC) == 2) {
     if (R) {
-      const bf16x8 rv = *reinterpret_cast<const bf16x8*>(R + (size_t)m * g.ldr + pcol + ncol);
+      const half8_bits rv = *reinterpret_cast<const half8_bits*>(R + (size_t)m * g.ldr + pcol + ncol);
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] += half_bits((unsigned short)rv[e]);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] *= g.alpha;
     if (ADD) {
-      const bf16x8 av = *reinterpret_cast<const bf16x8*>(ADD + (size_t)m * g.ldadd + pcol + ncol);
+      const half8_bits av = *reinterpret_cast<const half8_bits*>(ADD + (size_t)m * g.ldadd + pcol + ncol);
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] += g.beta * half_bits((unsigned short)av[e]);
     }
-    bf16x8 o;
+    half8_bits o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const bf16_t t = (bf16_t)v[e];
       o[e] = __builtin_bit_cast(short, t);
     }
-    *reinterpret_cast<bf16x8*>(C + (size_t)m * g.ldc + pcol + ncol) = o;
+    *reinterpret_cast<half8_bits*>(C + (size_t)m * g.ldc + pcol + ncol) = o;
   } else if (vec_ok && sizeof(TC) == 4) {  // fp32 output (the GPT residual stream): two 16-byte accesses per operand
     const float* Rf = reinterpret_cast<const float*>(R);
     const float* Af = reinterpret_cast<const float*>(ADD);
@@ -233,7 +220,7 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmArgs g, int tiles_m, i
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         int ts = a_t[h][i] + off;
-        if (g.pad_mode == PAD_REFLECT && a_t[h][i] >= 0) ts = reflect_i8(ts, T);
+        if (g.pad_mode == PAD_REFLECT && a_t[h][i] >= 0) ts = reflect_idx(ts, T);
         const bool ok = ts >= 0 && ts < T;
         a_ptr[h][i] = ok ? A + (size_t)(a_b[h][i] + ts) * g.lda + cc * PBK + l_sw2 : zp;
         a_inc[h][i] = ok ? PBK : 0;
@@ -256,31 +243,31 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmArgs g, int tiles_m, i
     }
   };
 
-  f32x4v acc[8][4];
+  f32x4 acc[8][4];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int fr = lane & 15, fq = lane >> 4;
   const int sx = (fr >> 1) & 7;  // swizzle key of this lane's fragment rows (rows fr + multiples of 16)
   // byte offsets inside a buffer: A row wr * 128 + mi * 16 + fr, W row wc * 64 + nj * 16 + fr, k-step ks -> slot (4 ks + fq) ^ sx
   const int a_rd = (wr * 128 + fr) * PROW, b_rd = BOFF + (wc * 64 + fr) * PROW;
   const int ko0 = ((0 + fq) ^ sx) << 4, ko1 = ((4 + fq) ^ sx) << 4;
-  bf16x8 af[4][2], bfr[2][2];
+  half8_bits af[4][2], bfr[2][2];
   auto read_A = [&](int buf, int h) {
     const unsigned char* p = smem + buf * PBUF + a_rd + h * 64 * PROW;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
-      af[mi][0] = *reinterpret_cast<const bf16x8*>(p + mi * 16 * PROW + ko0);
-      af[mi][1] = *reinterpret_cast<const bf16x8*>(p + mi * 16 * PROW + ko1);
+      af[mi][0] = *reinterpret_cast<const half8_bits*>(p + mi * 16 * PROW + ko0);
+      af[mi][1] = *reinterpret_cast<const half8_bits*>(p + mi * 16 * PROW + ko1);
     }
   };
   auto read_B = [&](int buf, int h) {
     const unsigned char* p = smem + buf * PBUF + b_rd + h * 32 * PROW;
 #pragma unroll
     for (int nj = 0; nj < 2; ++nj) {
-      bfr[nj][0] = *reinterpret_cast<const bf16x8*>(p + nj * 16 * PROW + ko0);
-      bfr[nj][1] = *reinterpret_cast<const bf16x8*>(p + nj * 16 * PROW + ko1);
+      bfr[nj][0] = *reinterpret_cast<const half8_bits*>(p + nj * 16 * PROW + ko0);
+      bfr[nj][1] = *reinterpret_cast<const half8_bits*>(p + nj * 16 * PROW + ko1);
     }
   };
   // vmcnt counts: what may stay in flight behind the chunk the NEXT phase reads (issue order per tile: B0' B1' A1' A0'')

@@ -2,6 +2,7 @@
 // fallback for shapes the MFMA kernel does not take (odd channel counts); see gemm_mfma.hip for the
 // bf16 matrix-core path.  One kernel covers nn.Linear, Conv1d (zero/reflect pad, dilation), the
 // polyphase form of ConvTranspose1d and the nearest-upsample+conv of the DVAE decoder.
+#include "itts_gemm_dev.h"
 #include "itts_kernels.h"
 
 namespace itts {
@@ -9,13 +10,6 @@ namespace itts {
 namespace {
 
 constexpr int BM = 64, BN = 64, BK = 16;
-
-__device__ __forceinline__ int reflect_idx(int t, int T) {
-  // torch 'reflect' padding (no edge repeat); valid for |overhang| < T
-  if (t < 0) t = -t;
-  if (t >= T) t = 2 * (T - 1) - t;
-  return t;
-}
 
 template <typename TA, typename TW, typename TC>
 __global__ __launch_bounds__(256) void gemm_simple_kernel(GemmArgs g) {

@@ -69,9 +69,12 @@ __device__ __forceinline__ void stf(f16_t* p, float v) { *p = (f16_t)v; }
 #endif
 
 // ---- the half type at the bit level: two halves of a 32-bit word, the 16x16x32 matrix instruction, the 2-way dot product ----
+// (the vector types of every kernel file: one typedef per distinct type, here)
 typedef bf16_t half2_t __attribute__((ext_vector_type(2)));
 typedef short half8_bits __attribute__((ext_vector_type(8)));  // MFMA fragments travel as 8 x 16 bits
-typedef float f32x4_acc __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));       // MFMA accumulator tile / 16-byte fp32 load
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));    // 16-byte load of 8 halves
 __device__ __forceinline__ float half_lo(uint32_t w) {  // element 0 (low 16 bits) of a pair
 #ifdef ITTS_HALF_F16
   return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu));
@@ -102,7 +105,7 @@ __device__ __forceinline__ float half_dot2(uint32_t a, uint32_t b, float c) {  /
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b2, a), __builtin_bit_cast(b2, b), c, false);  // v_dot2c_f32_bf16
 #endif
 }
-__device__ __forceinline__ f32x4_acc half_mfma16(half8_bits a, half8_bits b, f32x4_acc c) {  // v_mfma_f32_16x16x32_{bf16,f16}
+__device__ __forceinline__ f32x4 half_mfma16(half8_bits a, half8_bits b, f32x4 c) {  // v_mfma_f32_16x16x32_{bf16,f16}
 #ifdef ITTS_HALF_F16
   typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
