@@ -276,6 +276,12 @@ int itts_dvae_decode(itts_engine* e, const int32_t* codes_host, int B, int T, vo
  * Needs the encoder tensors of the checkpoint (dvae.enc* / dvae.erb* / dvae.eout / dvae.codebook_sq). Synchronises. */
 int itts_dvae_encode(itts_engine* e, const void* mel_btc, int B, int T, int32_t* codes_host, itts_stream stream);
 
+/* Opt-in: let a model whose GPT projections and mel_head all carry fp8-e4m3 copies (BASELINE config 5) run its 1 - 6 row
+ * decode steps on the persistent decode engine, which then streams the fp8 bytes (bf16 build only).  Sticky per engine
+ * object, default 0 = the launch path, bit-identical results either way.  The environment variable ITTS_ENGINE_FP8, read
+ * per call, overrides it in both directions (1: on for every engine, 0: off). */
+int itts_gpt_set_engine_fp8(itts_engine* e, int on);
+
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);
 int itts_debug_enable(itts_engine* e, int on);

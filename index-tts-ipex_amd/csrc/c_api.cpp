@@ -392,6 +392,12 @@ int itts_debug_enable(itts_engine* e, int on) {
   return OK;
 }
 
+int itts_gpt_set_engine_fp8(itts_engine* e, int on) {
+  ENG(e);
+  e->e.ds.eng_fp8 = on != 0;
+  return OK;
+}
+
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems) {
   if (!e || !name) return -1;
   auto it = e->e.taps.find(name);

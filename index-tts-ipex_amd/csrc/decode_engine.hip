@@ -1,4 +1,4 @@
-// Persistent decode engine (decode batches <= 6 rows - beam rows included -, bf16 weights): ONE token step as ONE launch - the 24
+// Persistent decode engine (decode batches <= 6 rows - beam rows included -, bf16 weights or, opt-in, their fp8-e4m3 copies): ONE token step as ONE launch - the 24
 // GPT-2 blocks, then ln_f -> final_norm -> mel_head and, for greedy search, the sampler (repetition penalty, arg-max, bookkeeping,
 // next input embedding).
 //
@@ -29,6 +29,14 @@
 // to gemv_bf16_kernel + decode_attn2_kernel at 1 - 4 rows (tests/test_gpu_engine_persistent.py); 5 - 6 rows keep that
 // arithmetic row for row (the launch path runs on the matrix cores there: tolerance + row-independence tests).
 // LDS maps by row count: three weight slots (<= 2 rows), two slots with aliased edge buffers (3 - 4), a half slot B (5 - 6).
+//
+// fp8 weights (decode_engine_kernel<.., W8>; BASELINE config 5, opt-in: itts_gpt_set_engine_fp8 / ITTS_ENGINE_FP8, bf16 build
+// only): the same kernel streams the fp8-e4m3 bytes and per-row power-of-two scales that gemv_bf16_kernel<.., W8> reads - half
+// the weight bytes per step.  Same slots, same request order: a row lands as its raw K bytes (the slots are half full), the
+// scales travel with the bias in the slot header, a lane expands its 8 bytes of a fragment with v_cvt_scalef32_pk_bf16_fp8
+// into the four bf16 pairs the dot products take, and every epilogue is dot * scale + bias.  Bit-identical to the fp8 launch
+// path at 1 - 4 rows and, because a power-of-two scale commutes with fp32 rounding, to this engine on the dequantised model
+// at 1 - 6 rows (tests/test_gpu_engine_fp8.py).  The bf16 instantiations are instruction for instruction what they were.
 //
 // Every spin is bounded (wall clock, s_memrealtime) and also ends on a chip-wide abort word; a workgroup that gave up
 // runs on without waiting, so the grid always drains.  The host reads the abort word at status / fetch.
@@ -219,59 +227,110 @@ __device__ __forceinline__ void dma4(const void* gsrc, unsigned lds_addr) {  // 
                : "memory");
 }
 
-// rows [n0, n0 + ROWS) of W [N][K] -> LDS slot (64 bias floats, then compact rows of K * 2 bytes): issued by ONE wave (the
-// loader), ROWS * ceil(K / 512) + 1 instructions - the counts the loader's waits are written in
-template <int ROWS, int K>
-struct DmaCount {
-  static constexpr int NF = (K + 511) / 512, N = ROWS * NF + 1;
+// rows [n0, n0 + ROWS) of W [N][K] -> LDS slot (a 256-byte header: the rows' bias floats, then compact rows of K * 2 bytes):
+// issued by ONE wave (the loader), ROWS * ceil(K / 512) + 1 instructions - the counts the loader's waits are written in.
+// W8: the rows are the raw fp8 bytes (row stride K, the slot is half full) and the header also carries the rows' scales at
+// ENG_SCALE_OFF - one more 4-byte request per fill.  A row of K = 1280 bytes is one whole 1 KiB request and a 256-byte tail
+// issued by 16 lanes, K = 5120 five whole requests, a half row of mlp.c_proj (2560) two and a 512-byte one by 32 lanes.
+// (The W8 form is a body of its own: written over byte pointers for both forms, the bf16 kernels allocate registers
+// differently - one more spilled VGPR at 4 rows.)
+constexpr unsigned ENG_SCALE_OFF = 128;  // bytes: at most 20 rows per slot, so 80 bytes of bias and 80 of scales share the header
+template <int K, bool W8>
+struct DmaRow {  // one row of K weights as 1 KiB requests
+  static constexpr int RB = K * (W8 ? 1 : 2);             // bytes
+  static constexpr int NF = (RB + 1023) / 1024;           // requests
+  static constexpr int TAILL = (RB - (NF - 1) * 1024) / 16;  // lanes that issue the last one (16 bytes each)
+  static_assert(RB % 16 == 0 && TAILL >= 1 && TAILL <= 64, "16 bytes per lane, rows start 16-byte aligned");
 };
+template <int ROWS, int K, bool W8 = false>
+struct DmaCount {
+  static constexpr int NF = DmaRow<K, W8>::NF, N = ROWS * NF + 1 + (W8 ? 1 : 0);
+};
+static_assert(DmaCount<5, 1280>::N == 16 && DmaCount<5, 1280, true>::N == 12 && DmaRow<5120, true>::NF == 5 && DmaRow<1280, true>::TAILL == 16 &&
+                  DmaRow<2560, true>::NF == 3 && DmaRow<2560, true>::TAILL == 32,
+              "request counts");
+// W8: KN fp8 bytes of one row, src -> dst (src already holds the lane's 16-byte offset)
+template <int KN, int THIN = 0>
+__device__ __forceinline__ void dma_row8(const unsigned char* __restrict__ src, unsigned dst, int lane) {
+  using R = DmaRow<KN, true>;
+#pragma unroll
+  for (int c = 0; c < R::NF; ++c) {
+    if (R::TAILL == 64 || c != R::NF - 1) {
+      dma16(src + c * 1024, dst + c * 1024);
+    } else if (lane < R::TAILL) {
+      dma16(src + c * 1024, dst + c * 1024);
+    }
+    if (THIN > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(THIN) : "memory");
+  }
+}
 // THIN > 0: at most THIN requests in flight (the loader waits in between) - for the one projection that has to be
 // requested while this CU's gather waves are polling (MI355X_MICROARCH "gather-pass": a gather pass queued behind its own
 // CU's unthrottled refill burst takes 2 - 3 x as long)
-template <int ROWS, int K, int THIN = 0>
-__device__ __forceinline__ void dma_rows(const bf16_t* __restrict__ W, const float* __restrict__ bias, int n0, unsigned slot, int lane) {
-  constexpr int NF = (K + 511) / 512, TAIL = K - (NF - 1) * 512;  // elements in the last fragment
-  static_assert(TAIL == 512 || TAIL == 256, "whole or half last fragment");
-  for (int r = 0; r < ROWS; ++r) {
-    const bf16_t* src = W + (size_t)(n0 + r) * K + lane * 8;
-    const unsigned dst = slot + 256 + (unsigned)(r * K * 2);
+template <int ROWS, int K, bool W8, int THIN = 0>
+__device__ __forceinline__ void dma_rows(const bf16_t* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ scale, int n0,
+                                         unsigned slot, int lane) {
+  if constexpr (W8) {
+    for (int r = 0; r < ROWS; ++r)
+      dma_row8<K, THIN>(reinterpret_cast<const unsigned char*>(W) + (size_t)(n0 + r) * K + lane * 16, slot + 256 + (unsigned)(r * K), lane);
+    if (lane < ROWS) dma4(bias + n0 + lane, slot);
+    if (lane < ROWS) dma4(scale + n0 + lane, slot + ENG_SCALE_OFF);
+  } else {
+    constexpr int NF = (K + 511) / 512, TAIL = K - (NF - 1) * 512;  // elements in the last fragment
+    static_assert(TAIL == 512 || TAIL == 256, "whole or half last fragment");
+    for (int r = 0; r < ROWS; ++r) {
+      const bf16_t* src = W + (size_t)(n0 + r) * K + lane * 8;
+      const unsigned dst = slot + 256 + (unsigned)(r * K * 2);
 #pragma unroll
-    for (int c = 0; c < NF; ++c) {
-      if (TAIL == 512 || c != NF - 1) {
-        dma16(src + c * 512, dst + c * 1024);
-      } else if (lane < 32) {
-        dma16(src + c * 512, dst + c * 1024);
+      for (int c = 0; c < NF; ++c) {
+        if (TAIL == 512 || c != NF - 1) {
+          dma16(src + c * 512, dst + c * 1024);
+        } else if (lane < 32) {
+          dma16(src + c * 512, dst + c * 1024);
+        }
+        if (THIN > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(THIN) : "memory");
       }
-      if (THIN > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(THIN) : "memory");
+    }
+    if (lane < ROWS) dma4(bias + n0 + lane, slot);
+  }
+}
+// rows [n0, n0 + ROWS) of W [N][K] -> compact rows at LDS address dst, no header (5 - 6 rows: c_attn arrives in two parts)
+template <int ROWS, int K, bool W8>
+__device__ __forceinline__ void dma_rows_at(const bf16_t* __restrict__ W, int n0, unsigned dst0, int lane) {
+  if constexpr (W8) {
+    for (int r = 0; r < ROWS; ++r)
+      dma_row8<K>(reinterpret_cast<const unsigned char*>(W) + (size_t)(n0 + r) * K + lane * 16, dst0 + (unsigned)(r * K), lane);
+  } else {
+    constexpr int NF = (K + 511) / 512, TAIL = K - (NF - 1) * 512;
+    static_assert(TAIL == 512 || TAIL == 256, "whole or half last fragment");
+    for (int r = 0; r < ROWS; ++r) {
+      const bf16_t* src = W + (size_t)(n0 + r) * K + lane * 8;
+      const unsigned dst = dst0 + (unsigned)(r * K * 2);
+#pragma unroll
+      for (int c = 0; c < NF; ++c)
+        if (TAIL == 512 || c != NF - 1 || lane < 32) dma16(src + c * 512, dst + c * 1024);
     }
   }
-  if (lane < ROWS) dma4(bias + n0 + lane, slot);
 }
-// rows [n0, n0 + ROWS) of W [N][K] -> compact rows at LDS address dst, no bias row (5 - 6 rows: c_attn arrives in two parts)
-template <int ROWS, int K>
-__device__ __forceinline__ void dma_rows_at(const bf16_t* __restrict__ W, int n0, unsigned dst0, int lane) {
-  constexpr int NF = (K + 511) / 512, TAIL = K - (NF - 1) * 512;
-  static_assert(TAIL == 512 || TAIL == 256, "whole or half last fragment");
-  for (int r = 0; r < ROWS; ++r) {
-    const bf16_t* src = W + (size_t)(n0 + r) * K + lane * 8;
-    const unsigned dst = dst0 + (unsigned)(r * K * 2);
-#pragma unroll
-    for (int c = 0; c < NF; ++c)
-      if (TAIL == 512 || c != NF - 1 || lane < 32) dma16(src + c * 512, dst + c * 1024);
-  }
-}
-// columns [K0, K0 + KN) of rows [n0, n0 + ROWS) of W [N][KTOT] -> compact rows of KN * 2 bytes (5 - 6 rows: mlp.c_proj comes
-// in two K halves, the second into slot A once c_fc has been read); the bias row travels with the first part
-template <int ROWS, int KTOT, int K0, int KN>
-__device__ __forceinline__ void dma_rows_part(const bf16_t* __restrict__ W, const float* __restrict__ bias, int n0, unsigned slot, int lane) {
+// columns [K0, K0 + KN) of rows [n0, n0 + ROWS) of W [N][KTOT] -> compact rows of KN * 2 (W8: KN) bytes (5 - 6 rows: mlp.c_proj
+// comes in two K halves, the second into slot A once c_fc has been read); the header travels with the first part
+template <int ROWS, int KTOT, int K0, int KN, bool W8>
+__device__ __forceinline__ void dma_rows_part(const bf16_t* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ scale, int n0,
+                                              unsigned slot, int lane) {
   static_assert(KN % 512 == 0 && K0 % 512 == 0, "whole fragments");
-  for (int r = 0; r < ROWS; ++r) {
-    const bf16_t* src = W + (size_t)(n0 + r) * KTOT + K0 + lane * 8;
-    const unsigned dst = slot + 256 + (unsigned)(r * KN * 2);
+  if constexpr (W8) {
+    for (int r = 0; r < ROWS; ++r)
+      dma_row8<KN>(reinterpret_cast<const unsigned char*>(W) + (size_t)(n0 + r) * KTOT + K0 + lane * 16, slot + 256 + (unsigned)(r * KN), lane);
+    if (bias && lane < ROWS) dma4(bias + n0 + lane, slot);
+    if (scale && lane < ROWS) dma4(scale + n0 + lane, slot + ENG_SCALE_OFF);
+  } else {
+    for (int r = 0; r < ROWS; ++r) {
+      const bf16_t* src = W + (size_t)(n0 + r) * KTOT + K0 + lane * 8;
+      const unsigned dst = slot + 256 + (unsigned)(r * KN * 2);
 #pragma unroll
-    for (int c = 0; c < KN / 512; ++c) dma16(src + c * 512, dst + c * 1024);
+      for (int c = 0; c < KN / 512; ++c) dma16(src + c * 512, dst + c * 1024);
+    }
+    if (bias && lane < ROWS) dma4(bias + n0 + lane, slot);
   }
-  if (bias && lane < ROWS) dma4(bias + n0 + lane, slot);
 }
 // the loader waits until at most N of its requests are outstanding: everything older has landed in LDS (vmcnt is in-order)
 template <int N>
@@ -280,18 +339,38 @@ __device__ __forceinline__ void dma_wait_keep() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// one weight fragment of a lane as four bf16 pairs: 16 bytes of bf16, or (W8) 8 fp8 bytes expanded the way
+// gemv_bf16_kernel<.., W8> expands them (dword h2 -> pairs 2 * h2 and 2 * h2 + 1; a conflict-free ds_read_b64)
+__device__ __forceinline__ u32x4 fp8x8_pairs(u32x2 q) {
+  u32x4 w = {0u, 0u, 0u, 0u};
+#ifndef ITTS_HALF_F16  // (the IEEE-half build has no fp8 form: fp8 expands to bf16 pairs)
+#pragma unroll
+  for (int h2 = 0; h2 < 2; ++h2) {
+    w[2 * h2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[h2], 1.0f, false));
+    w[2 * h2 + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[h2], 1.0f, true));
+  }
+#endif
+  return w;
+}
+template <bool W8>
+__device__ __forceinline__ u32x4 wfrag(const unsigned char* __restrict__ p) {
+  if constexpr (W8) return fp8x8_pairs(*reinterpret_cast<const u32x2*>(p));
+  return *reinterpret_cast<const u32x4*>(p);
+}
+
 // acc[b] += W[row] . x[b] in gemv_bf16_kernel's order (fragments ascending, four v_dot2c per fragment); W from its LDS slot
-template <int NB, int K>
+// (W8: the row is K fp8 bytes, lane l of fragment c reads the 8 bytes at c * 512 + l * 8)
+template <int NB, int K, bool W8>
 __device__ __forceinline__ void dots(const unsigned char* __restrict__ wrow, const uint32_t* __restrict__ sxb, int lane,
                                      float (&acc)[NB]) {
-  constexpr int NCH = (K + 511) / 512;
+  constexpr int NCH = (K + 511) / 512, ES = W8 ? 1 : 2;
   const int klast = (NCH - 1) * 512 + lane * 8;
   const bool kok = klast < K;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int k = c == NCH - 1 ? (kok ? klast : K - 8) : c * 512 + lane * 8;
     // lanes past the end of a half last fragment multiply by x = 0 like the launch path; they read a valid (finite) weight
-    const u32x4 w = *reinterpret_cast<const u32x4*>(wrow + c * 1024 + ((c == NCH - 1 && !kok) ? (lane & 31) : lane) * 16);
+    const u32x4 w = wfrag<W8>(wrow + c * 512 * ES + ((c == NCH - 1 && !kok) ? (lane & 31) : lane) * 8 * ES);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       u32x4 xq = *reinterpret_cast<const u32x4*>(sxb + (b * K + k) / 2);
@@ -305,13 +384,14 @@ __device__ __forceinline__ void dots(const unsigned char* __restrict__ wrow, con
 }
 
 // the same over fragments [C0, C0 + NC) of a K = KTOT row whose part lies compact at wpart (whole fragments only)
-template <int NB, int KTOT, int C0, int NC>
+template <int NB, int KTOT, int C0, int NC, bool W8>
 __device__ __forceinline__ void dots_part(const unsigned char* __restrict__ wpart, const uint32_t* __restrict__ sxb, int lane,
                                           float (&acc)[NB]) {
+  constexpr int ES = W8 ? 1 : 2;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int k = (C0 + c) * 512 + lane * 8;
-    const u32x4 w = *reinterpret_cast<const u32x4*>(wpart + c * 1024 + lane * 16);
+    const u32x4 w = wfrag<W8>(wpart + c * 512 * ES + lane * 8 * ES);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       const u32x4 xq = *reinterpret_cast<const u32x4*>(sxb + (b * KTOT + k) / 2);
@@ -319,6 +399,15 @@ __device__ __forceinline__ void dots_part(const unsigned char* __restrict__ wpar
       for (int e = 0; e < 4; ++e) acc[b] = half_dot2(w[e], xq[e], acc[b]);
     }
   }
+}
+
+// a projection's output from its dot product and the slot header: dot + bias, or (W8) dot * scale + bias as
+// gemv_bf16_kernel<.., W8> writes it (the scale is a power of two)
+template <bool W8>
+__device__ __forceinline__ float slot_out(const unsigned char* __restrict__ slot, int r, float dot) {
+  const float* hdr = reinterpret_cast<const float*>(slot);
+  if constexpr (W8) return dot * hdr[ENG_SCALE_OFF / 4 + r] + hdr[r];
+  return dot + hdr[r];
 }
 
 // LayerNorm without affine of xf [NB][K] fp32 -> bf16 pairs sxb [NB][K/2]: the prologue of gemv_bf16_kernel<.., PRO = 1>.
@@ -483,7 +572,9 @@ __device__ __forceinline__ void ln2_to_sxb(const float* __restrict__ xf, uint32_
 // ---------------------------------------------------------------------------------------------
 // ANC: beam rows - the cache is never re-ordered when the beams are; key j of beam row b lives in the physical row its
 // ancestry names (decode2.hip, decode_attn2_kernel<.., ANC>: the same gather, the same arithmetic)
-template <int NB, bool ANC>
+// W8: every projection (and the head) streams its fp8-e4m3 copy - the bytes and per-row power-of-two scales of
+// gemv_bf16_kernel<.., W8> - through the same slots (half full), the same requests in the same order; y = dot * scale + bias
+template <int NB, bool ANC, bool W8>
 __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
   constexpr int D = ENG_D, H = ENG_H, DH = 64, NCU = ENG_NCU;
   constexpr int GPH = NCU / H;       // workgroups per head group (12)
@@ -497,6 +588,8 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
   constexpr int SD = 2;  // rows in flight beyond the register window (the launch path takes 4: same rows, same order)
   static_assert(ATTN_NSPLIT == NSPLIT, "split count of the launch path");
   static_assert(NB <= ENG_MAX_ROWS, "LDS budget");
+  constexpr int ES = W8 ? 1 : 2;     // bytes per weight in the LDS slots
+  static_assert(FO * 4 <= (int)ENG_SCALE_OFF && ENG_SCALE_OFF + FO * 4 <= 256, "bias and scales share the slot header");
 
   // LDS map.  Three weight slots (bias row + rows): slot A holds c_attn, then c_fc; slot B mlp.c_proj; slot C c_proj.  A slot is
   // refilled only once every compute wave has finished the phase that read its previous occupant (the `own` counter).
@@ -587,13 +680,15 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
   // (3 - 4 rows, two slots: B1 -> c_proj(l) -> B, B3 -> c_fc(l) -> A, B4 -> mlp.c_proj(l) -> B, B5 -> c_attn(l + 1) -> A, and the
   // loader waits in front of every barrier for the one request before it)
   if (lw) {
-    if (SLOT3) dma_rows<HO, D>(a.L[0].wp, a.L[0].bp, cu * HO, S2, lane);
+    if (SLOT3) dma_rows<HO, D, W8>(a.L[0].wp, a.L[0].bp, a.S[0].sp, cu * HO, S2, lane);
     if (qcu && HALFB) {  // (5 - 6 rows: c_attn lives in two parts - rows 0..9 behind the half of mlp.c_proj that shares slot A)
-      dma_rows_at<QA1, D>(a.L[0].wa, an0, S0 + QOFF1, lane);
-      dma_rows_at<QO - QA1, D>(a.L[0].wa, an0 + QA1, S0 + 256, lane);
+      dma_rows_at<QA1, D, W8>(a.L[0].wa, an0, S0 + QOFF1, lane);
+      dma_rows_at<QO - QA1, D, W8>(a.L[0].wa, an0 + QA1, S0 + 256, lane);
       if (lane < QO) dma4(a.L[0].ba + an0 + lane, S0);
+      if constexpr (W8)
+        if (lane < QO) dma4(a.S[0].sa + an0 + lane, S0 + ENG_SCALE_OFF);
     } else if (qcu) {
-      dma_rows<QO, D>(a.L[0].wa, a.L[0].ba, an0, S0, lane);
+      dma_rows<QO, D, W8>(a.L[0].wa, a.L[0].ba, a.S[0].sa, an0, S0, lane);
     }
   }
   if (t < NB * HO) hown[(t / HO) * 8 + t % HO] = a.h[(size_t)(t / HO) * D + cu * HO + t % HO];
@@ -603,6 +698,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
   constexpr size_t OQKV = 0, OCTX = (size_t)NB * 3 * D, OH1 = OCTX + NB * D / 2, OACT = OH1 + NB * D, OH2 = OACT + NB * 2 * D;
   for (int l = 0; l < a.NL; ++l) {
     const EngLayerW& w = a.L[l];
+    const EngLayerS& ws = a.S[W8 ? l : 0];  // (read by the W8 form only)
     // per-thread indices re-derived from an opaque copy each layer: hipcc otherwise hoists every per-thread address of
     // the five phases out of the layer loop and spills them (53 VGPRs of scratch traffic inside the hand-off waits)
     int tl = t;
@@ -687,7 +783,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     } else if (lw) {
       if (HALFB && l > 0 && qcu) {  // the rest of this block's c_attn -> A: every compute wave is through the last block's mlp.c_proj
         wait_own(own_lds, NCW * phase, rt);
-        dma_rows_at<QO - QA1, D>(w.wa, an0 + QA1, S0 + 256, ll);
+        dma_rows_at<QO - QA1, D, W8>(w.wa, an0 + QA1, S0 + 256, ll);
       }
       dma_wait_keep<0>();  // c_attn (and, before it, c_proj) of this block
       if (early_kv) kv_issue(Ic0{}, IcE{});
@@ -700,9 +796,9 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     // Not on an attention workgroup: its loader is one of the 16 attention waves, and the cache rows it requests next would
     // queue behind these 50 KB (vmcnt is in-order) - there mlp.c_proj follows behind the second LayerNorm
     if (SLOT3) {
-      if (lw && !acu) dma_rows<HO, 4 * D>(w.w2, w.b2, cu * HO, S1, ll);
+      if (lw && !acu) dma_rows<HO, 4 * D, W8>(w.w2, w.b2, ws.s2, cu * HO, S1, ll);
     } else if (lw) {
-      dma_rows<HO, D>(w.wp, w.bp, cu * HO, S1, ll);  // c_proj -> B (every wave is past the last block's mlp.c_proj)
+      dma_rows<HO, D, W8>(w.wp, w.bp, ws.sp, cu * HO, S1, ll);  // c_proj -> B (every wave is past the last block's mlp.c_proj)
     }
     if (qcu && cwv) {
 #pragma unroll
@@ -712,7 +808,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           float acc[NB];
 #pragma unroll
           for (int b = 0; b < NB; ++b) acc[b] = 0.f;
-          dots<NB, D>(HALFB ? (r < QA1 ? W0 + QOFF1 + r * D * 2 : W0 + 256 + (r - QA1) * D * 2) : W0 + 256 + r * D * 2, xn, ll, acc);
+          dots<NB, D, W8>(HALFB ? (r < QA1 ? W0 + QOFF1 + r * D * ES : W0 + 256 + (r - QA1) * D * ES) : W0 + 256 + r * D * ES, xn, ll, acc);
           float mine = 0.f;
 #pragma unroll
           for (int b = 0; b < NB; ++b) {
@@ -720,8 +816,8 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
             mine = ll == b ? x : mine;
           }
           if (ll < NB) {
-            st_gran(G + OQKV + (size_t)ll * 3 * D + an0 + r, rt.tag, __float_as_uint(mine + reinterpret_cast<const float*>(W0)[r]));
-            if (a.dbg && l == a.dbg_layer) a.dbg[(size_t)ll * 3 * D + an0 + r] = mine + reinterpret_cast<const float*>(W0)[r];
+            st_gran(G + OQKV + (size_t)ll * 3 * D + an0 + r, rt.tag, __float_as_uint(slot_out<W8>(W0, r, mine)));
+            if (a.dbg && l == a.dbg_layer) a.dbg[(size_t)ll * 3 * D + an0 + r] = slot_out<W8>(W0, r, mine);
           }
         }
       }
@@ -736,7 +832,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     if (a.early_fc > 0 && lw && !acu) {
       wait_own(own_lds, NCW * phase, rt);
       for (int z = 0; z < a.early_fc; ++z) __builtin_amdgcn_s_sleep(1);
-      dma_rows<FO, D>(w.wf, w.bf, cu * FO, S0, ll);
+      dma_rows<FO, D, W8>(w.wf, w.bf, ws.sf, cu * FO, S0, ll);
     }
     ENG_STAMP(8)
 
@@ -938,15 +1034,15 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     __syncthreads();
     if (lw && !(a.early_fc > 0 && !acu)) {  // c_fc -> A: every wave is past c_attn
       if (a.thin_fc)
-        dma_rows<FO, D, 12>(w.wf, w.bf, cu * FO, S0, ll);
+        dma_rows<FO, D, W8, 4 * DmaCount<1, D, W8>::NF>(w.wf, w.bf, ws.sf, cu * FO, S0, ll);  // four rows' requests in flight (bf16: 12)
       else
-        dma_rows<FO, D>(w.wf, w.bf, cu * FO, S0, ll);
+        dma_rows<FO, D, W8>(w.wf, w.bf, ws.sf, cu * FO, S0, ll);
     }
     if (cwv && cw < HO) {
       float acc[NB];
 #pragma unroll
       for (int b = 0; b < NB; ++b) acc[b] = 0.f;
-      dots<NB, D>(W2 + 256 + cw * D * 2, xc, ll, acc);
+      dots<NB, D, W8>(W2 + 256 + cw * D * ES, xc, ll, acc);
       float mine = 0.f;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
@@ -954,7 +1050,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         mine = ll == b ? x : mine;
       }
       if (ll < NB) {
-        const float hn = hown[ll * 8 + cw] + (mine + reinterpret_cast<const float*>(W2)[cw]);
+        const float hn = hown[ll * 8 + cw] + slot_out<W8>(W2, cw, mine);
         hown[ll * 8 + cw] = hn;
         st_gran(G + OH1 + (size_t)ll * D + cu * HO + cw, rt.tag, __float_as_uint(hn));
         if (a.dbg && l == a.dbg_layer) a.dbg[(size_t)NB * 3 * D + (size_t)ll * D + cu * HO + cw] = hn;
@@ -974,12 +1070,12 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     ENG_STAMP(12)
     ln_to_sxb<NB, D>(xf, xn, red, tl, a.eps);
     if (SLOT3) {
-      if (lw && acu) dma_rows<HO, 4 * D>(w.w2, w.b2, cu * HO, S1, ll);
-      if (lw && l + 1 < a.NL) dma_rows<HO, D>(a.L[l + 1].wp, a.L[l + 1].bp, cu * HO, S2, ll);  // next c_proj -> C: all past this one's
+      if (lw && acu) dma_rows<HO, 4 * D, W8>(w.w2, w.b2, ws.s2, cu * HO, S1, ll);
+      if (lw && l + 1 < a.NL) dma_rows<HO, D, W8>(a.L[l + 1].wp, a.L[l + 1].bp, a.S[l + 1].sp, cu * HO, S2, ll);  // next c_proj -> C: all past this one's
     } else if (lw && HALFB) {
-      dma_rows_part<HO, 4 * D, 0, 2 * D>(w.w2, w.b2, cu * HO, S1, ll);  // first half of mlp.c_proj -> B: all past c_proj
+      dma_rows_part<HO, 4 * D, 0, 2 * D, W8>(w.w2, w.b2, ws.s2, cu * HO, S1, ll);  // first half of mlp.c_proj -> B: all past c_proj
     } else if (lw) {
-      dma_rows<HO, 4 * D>(w.w2, w.b2, cu * HO, S1, ll);  // mlp.c_proj -> B: all past c_proj
+      dma_rows<HO, 4 * D, W8>(w.w2, w.b2, ws.s2, cu * HO, S1, ll);  // mlp.c_proj -> B: all past c_proj
     }
     ENG_STAMP(13)
     if (cwv && cw < FO / 2) {  // an adjacent pair of features per wave: one bf16-pair granule per batch row
@@ -988,7 +1084,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       for (int r = 0; r < 2; ++r) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc[r][b] = 0.f;
-        dots<NB, D>(W0 + 256 + (2 * cw + r) * D * 2, xn, ll, acc[r]);
+        dots<NB, D, W8>(W0 + 256 + (2 * cw + r) * D * ES, xn, ll, acc[r]);
       }
       float mine = 0.f;
 #pragma unroll
@@ -999,7 +1095,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           mine = ll == r * NB + b ? x : mine;
         }
       ENG_STAMP(14)
-      const float v = gelu_new_rn(mine + reinterpret_cast<const float*>(W0)[2 * cw + (ll < NB ? 0 : 1)]);
+      const float v = gelu_new_rn(slot_out<W8>(W0, 2 * cw + (ll < NB ? 0 : 1), mine));
       const float v1 = __shfl_down(v, NB, 64);  // (feature 1, batch row ll) for lanes < NB
       if (ll < NB) {
         st_gran(G + OACT + (size_t)ll * 2 * D + cu * (FO / 2) + cw, rt.tag, pack_bf16(v, v1));
@@ -1020,13 +1116,13 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       sweep2<(NB * D + 255) / 256, false>(G + OACT, NB * D / a.fake_div, tl, rt, [&](int i, uint32_t v) { xa[i] = v; }, a.act_delay);
     } else if (lw && HALFB) {
       wait_own(own_lds, NCW * phase, rt);  // every compute wave is through c_fc: slot A is free
-      dma_rows_part<HO, 4 * D, 2 * D, 2 * D>(w.w2, nullptr, cu * HO, S0, ll);  // second half of mlp.c_proj -> A
+      dma_rows_part<HO, 4 * D, 2 * D, 2 * D, W8>(w.w2, nullptr, nullptr, cu * HO, S0, ll);  // second half of mlp.c_proj -> A
       dma_wait_keep<0>();
     } else if (lw && !SLOT3) {
       dma_wait_keep<0>();  // mlp.c_proj (requested behind LN2)
     } else if (lw && acu) {  // mlp.c_proj was requested behind LN2 here; the next block's c_proj (if any) is younger
       if (l + 1 < a.NL)
-        dma_wait_keep<DmaCount<HO, D>::N>();
+        dma_wait_keep<DmaCount<HO, D, W8>::N>();
       else
         dma_wait_keep<0>();
     }  // (elsewhere mlp.c_proj is older in the loader's queue than c_fc: it landed before this block's c_fc barrier)
@@ -1035,21 +1131,23 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     ENG_STAMP(7)
     if (HALFB) {  // rows 0..9 of the next c_attn -> the part of A that the second half of mlp.c_proj leaves free (+ its bias row)
       if (lw && qcu && l + 1 < a.NL) {
-        dma_rows_at<QA1, D>(a.L[l + 1].wa, an0, S0 + QOFF1, ll);
+        dma_rows_at<QA1, D, W8>(a.L[l + 1].wa, an0, S0 + QOFF1, ll);
         if (ll < QO) dma4(a.L[l + 1].ba + an0 + ll, S0);
+        if constexpr (W8)
+          if (ll < QO) dma4(a.S[l + 1].sa + an0 + ll, S0 + ENG_SCALE_OFF);
       }
     } else if (lw && qcu && l + 1 < a.NL) {
-      dma_rows<QO, D>(a.L[l + 1].wa, a.L[l + 1].ba, an0, S0, ll);  // next c_attn -> A: all past c_fc
+      dma_rows<QO, D, W8>(a.L[l + 1].wa, a.L[l + 1].ba, a.S[l + 1].sa, an0, S0, ll);  // next c_attn -> A: all past c_fc
     }
     if (cwv && cw < HO) {
       float acc[NB];
 #pragma unroll
       for (int b = 0; b < NB; ++b) acc[b] = 0.f;
       if (HALFB) {
-        dots_part<NB, 4 * D, 0, 5>(W1 + 256 + cw * 2 * D * 2, xa, ll, acc);
-        dots_part<NB, 4 * D, 5, 5>(W0 + 256 + cw * 2 * D * 2, xa, ll, acc);
+        dots_part<NB, 4 * D, 0, 5, W8>(W1 + 256 + cw * 2 * D * ES, xa, ll, acc);
+        dots_part<NB, 4 * D, 5, 5, W8>(W0 + 256 + cw * 2 * D * ES, xa, ll, acc);
       } else {
-        dots<NB, 4 * D>(W1 + 256 + cw * 4 * D * 2, xa, ll, acc);
+        dots<NB, 4 * D, W8>(W1 + 256 + cw * 4 * D * ES, xa, ll, acc);
       }
       float mine = 0.f;
 #pragma unroll
@@ -1058,7 +1156,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         mine = ll == b ? x : mine;
       }
       if (ll < NB) {
-        const float hn = hown[ll * 8 + cw] + (mine + reinterpret_cast<const float*>(W1)[cw]);
+        const float hn = hown[ll * 8 + cw] + slot_out<W8>(W1, cw, mine);
         hown[ll * 8 + cw] = hn;
         if (a.dbg && l == a.dbg_layer) a.dbg[(size_t)NB * 8 * D + (size_t)ll * D + cu * HO + cw] = hn;
         if (l + 1 < a.NL || a.head_w)
@@ -1078,8 +1176,9 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     asm volatile("" : "+v"(tl));
     const int ll = tl & 63;
     const int rows_per = a.V / NCU, extra = a.V % NCU;
-    u32x4 wh[3][3];
-    float bh[3];
+    using WFrag = std::conditional_t<W8, u32x2, u32x4>;  // a lane's 8 weights of a fragment: fp8 bytes or bf16 pairs
+    WFrag wh[3][3];
+    float bh[3], sh[3];
     int hn_[3];
     if (cwv) {
       const int klast = 2 * 512 + ll * 8;
@@ -1091,9 +1190,13 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const int k = c == 2 ? (klast < D ? klast : D - 8) : c * 512 + ll * 8;
-          wh[r][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.head_w + (size_t)n * D + k));
+          if constexpr (W8)
+            wh[r][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(a.head_w) + (size_t)n * D + k));
+          else
+            wh[r][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.head_w + (size_t)n * D + k));
         }
         bh[r] = a.head_b[n];
+        if constexpr (W8) sh[r] = a.head_s[n];
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1122,9 +1225,13 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) xq[e] = kok ? xq[e] : 0u;
 #pragma unroll
-          for (int r = 0; r < 3; ++r)
+          for (int r = 0; r < 3; ++r) {
+            u32x4 wv;
+            if constexpr (W8) wv = fp8x8_pairs(wh[r][c]);
+            else wv = wh[r][c];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(wh[r][c][e], xq[e], acc[r][b]);
+            for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(wv[e], xq[e], acc[r][b]);
+          }
         }
       }
       float mine = 0.f;
@@ -1139,7 +1246,8 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         const int r = ll / NB, b = ll % NB;
         const int n = r == 0 ? hn_[0] : (r == 1 ? hn_[1] : hn_[2]);
         const float bias = r == 0 ? bh[0] : (r == 1 ? bh[1] : bh[2]);
-        if (n >= 0) a.logits[(size_t)b * a.V + n] = mine + bias;
+        const float scl = r == 0 ? sh[0] : (r == 1 ? sh[1] : sh[2]);
+        if (n >= 0) a.logits[(size_t)b * a.V + n] = W8 ? mine * scl + bias : mine + bias;
       }
       if (a.fold_sampler && ll < 3 * NB) {  // this lane's candidate of row b: penalty / stop suppression as sampler2_kernel
         const int r = ll / NB, b = ll % NB;
@@ -1147,7 +1255,8 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         const float bias = r == 0 ? bh[0] : (r == 1 ? bh[1] : bh[2]);
         float* cv = so;                                      // [NB][36] candidate scores (the attention scratch is idle)
         int* ci = reinterpret_cast<int*>(so + ENG_MAX_ROWS * 36);       // [NB][36] ids
-        cv[b * 36 + cw * 3 + r] = n >= 0 ? sampler_score(a.samp, a.samp.seen + (size_t)b * a.V, mine + bias, n) : -INFINITY;
+        const float scl = r == 0 ? sh[0] : (r == 1 ? sh[1] : sh[2]);
+        cv[b * 36 + cw * 3 + r] = n >= 0 ? sampler_score(a.samp, a.samp.seen + (size_t)b * a.V, W8 ? mine * scl + bias : mine + bias, n) : -INFINITY;
         ci[b * 36 + cw * 3 + r] = n >= 0 ? n : 0x7fffffff;
       }
     }
@@ -1272,29 +1381,43 @@ size_t eng_gran_count(int layers) { return (size_t)layers * ENG_MAX_ROWS * ENG_D
 int decode_engine_layers(const EngArgs& a, hipStream_t s) {
   ITTS_REQUIRE(a.B >= 1 && a.B <= ENG_MAX_ROWS && a.NL >= 1 && a.NL <= ENG_MAX_LAYERS && a.gran && a.h && a.kc && a.vc && a.ctr, "decode_engine: bad arguments");
   const size_t lds = 160 * 1024;  // three weight slots + edge buffers: the whole LDS of a CU, one workgroup per CU
-#define ITTS_ENG_GO(NB, ANC_)                                                                                                   \
+#define ITTS_ENG_GO(NB, ANC_, W8_)                                                                                              \
   {                                                                                                                             \
     static bool attr = false;                                                                                                   \
     if (!attr) {                                                                                                                \
-      ITTS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_engine_kernel<NB, ANC_>),                        \
+      ITTS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_engine_kernel<NB, ANC_, W8_>),                   \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                \
       attr = true;                                                                                                              \
     }                                                                                                                           \
-    hipLaunchKernelGGL((decode_engine_kernel<NB, ANC_>), dim3(ENG_NCU), dim3(1024), lds, s, a);                                 \
+    hipLaunchKernelGGL((decode_engine_kernel<NB, ANC_, W8_>), dim3(ENG_NCU), dim3(1024), lds, s, a);                            \
   }
-  if (a.anc) {  // beam rows (>= 2 rows per batch item)
-    ITTS_REQUIRE(a.nb >= 2 && a.nb <= a.B && a.B % a.nb == 0, "decode_engine: beam ancestry needs B to be a multiple of 2 <= nb <= B");
-    if (a.B == 2) ITTS_ENG_GO(2, true)
-    else if (a.B == 3) ITTS_ENG_GO(3, true)
-    else if (a.B == 4) ITTS_ENG_GO(4, true)
-    else if (a.B == 5) ITTS_ENG_GO(5, true)
-    else ITTS_ENG_GO(6, true)
-  } else if (a.B == 1) ITTS_ENG_GO(1, false)
-  else if (a.B == 2) ITTS_ENG_GO(2, false)
-  else if (a.B == 3) ITTS_ENG_GO(3, false)
-  else if (a.B == 4) ITTS_ENG_GO(4, false)
-  else if (a.B == 5) ITTS_ENG_GO(5, false)
-  else ITTS_ENG_GO(6, false)
+#define ITTS_ENG_ROWS(W8_)                                                                                                      \
+  if (a.anc) { /* beam rows (>= 2 rows per batch item) */                                                                       \
+    if (a.B == 2) ITTS_ENG_GO(2, true, W8_)                                                                                     \
+    else if (a.B == 3) ITTS_ENG_GO(3, true, W8_)                                                                                \
+    else if (a.B == 4) ITTS_ENG_GO(4, true, W8_)                                                                                \
+    else if (a.B == 5) ITTS_ENG_GO(5, true, W8_)                                                                                \
+    else ITTS_ENG_GO(6, true, W8_)                                                                                              \
+  } else if (a.B == 1) ITTS_ENG_GO(1, false, W8_)                                                                               \
+  else if (a.B == 2) ITTS_ENG_GO(2, false, W8_)                                                                                 \
+  else if (a.B == 3) ITTS_ENG_GO(3, false, W8_)                                                                                 \
+  else if (a.B == 4) ITTS_ENG_GO(4, false, W8_)                                                                                 \
+  else if (a.B == 5) ITTS_ENG_GO(5, false, W8_)                                                                                 \
+  else ITTS_ENG_GO(6, false, W8_)
+  if (a.anc) ITTS_REQUIRE(a.nb >= 2 && a.nb <= a.B && a.B % a.nb == 0, "decode_engine: beam ancestry needs B to be a multiple of 2 <= nb <= B");
+  if (a.w8) {  // every projection (and the head, if it is inside the launch) as fp8 bytes + row scales
+#ifdef ITTS_HALF_F16
+    ITTS_REQUIRE(false, "decode_engine: fp8 weights need the bf16 build (fp8 expands to bf16 pairs)");
+#else
+    for (int l = 0; l < a.NL; ++l)
+      ITTS_REQUIRE(a.S[l].sa && a.S[l].sp && a.S[l].sf && a.S[l].s2, "decode_engine: fp8 weights without row scales");
+    ITTS_REQUIRE(!a.head_w || a.head_s, "decode_engine: fp8 head without row scales");
+    ITTS_ENG_ROWS(true)
+#endif
+  } else {
+    ITTS_ENG_ROWS(false)
+  }
+#undef ITTS_ENG_ROWS
 #undef ITTS_ENG_GO
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;

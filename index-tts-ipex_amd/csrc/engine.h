@@ -155,12 +155,14 @@ struct DecodeState {
   int* fuse_err = nullptr;
   int fuse_failed = 0;                 // a hand-off timed out: two launches from then on
   int fuse = 0, graph_fuse = 0;        // opt-in (ITTS_FUSE_QKV_ATTN=1 / debug bit 3): measured 1.5 % slower than two launches; 0 again after a hand-off timeout
-  // persistent decode engine (decode_engine.hip): the step as one launch, <= 6 rows (beam rows included), bf16, no fp8
+  // persistent decode engine (decode_engine.hip): the step as one launch, <= 6 rows (beam rows included), bf16 weights - or,
+  // opt-in (eng_fp8 / ITTS_ENGINE_FP8), the fp8 copies of every projection and the head (bf16 build only)
   unsigned long long* eng_gran = nullptr;
   unsigned* eng_ctr = nullptr;           // [0] step counter, [1] abort word
   int eng_off = 0;                       // debug bit 4 / ITTS_ENGINE=0: keep the five-launches-per-layer path (A/B)
   int eng_force = 0;                     // debug bit 5: use the engine whatever ITTS_ENGINE / the default says
   int eng_failed = 0;                    // a hand-off timed out: launch path from then on
+  int eng_fp8 = 0;                       // itts_gpt_set_engine_fp8: a model with fp8 GPT weights may use the engine (sticky; default: launch path)
   int graph_eng = 0;
   int graph_mode = 0;                    // last_mode of the captured step
   float typical_mass = 0.f, graph_typical = 0.f;  // TypicalLogitsWarper pre-pass (0 = off)
@@ -282,6 +284,7 @@ struct Engine {
   int gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, bool write_cache, hipStream_t s);
   int decode_step_launch(hipStream_t s);
   bool engine_usable() const;
+  bool engine_fp8_model() const;  // every projection of every block and the head carry an fp8 copy + row scales
   int ensure_engine_state(hipStream_t s);
   int engine_check(hipStream_t s);
   int head_and_sample(hipStream_t s, bool have_logits = false, bool sampled = false);

@@ -1,4 +1,4 @@
-// Persistent decode engine (decode_engine.hip): one launch for the 24 GPT-2 blocks of a token step, decode batches <= 4.
+// Persistent decode engine (decode_engine.hip): one launch for the 24 GPT-2 blocks of a token step, decode batches <= 6.
 #pragma once
 #include "itts_common.h"
 #include "itts_decode.h"
@@ -10,11 +10,14 @@ constexpr int ENG_MAX_LAYERS = 24;
 constexpr bool ENG_DEFAULT_ON = true;   // ITTS_ENGINE=0 keeps the five-launches-per-block path  // IndexTTS-1.5 GPT on the 256 CUs of an MI355X
 
 struct EngLayerW {  // one GPT-2 block: bf16 [N][K] projections (LayerNorm affine folded in by the packer), fp32 biases
-  const bf16_t *wa, *wp, *wf, *w2;
+  const bf16_t *wa, *wp, *wf, *w2;  // (EngArgs::w8: the fp8-e4m3 bytes [N][K] of the same projections)
   const float *ba, *bp, *bf, *b2;
 };
+struct EngLayerS {  // EngArgs::w8: fp32 power-of-two scale of every output row of the block's four projections
+  const float *sa = nullptr, *sp = nullptr, *sf = nullptr, *s2 = nullptr;
+};
 
-struct EngArgs {
+struct EngArgs {  // passed by value: it must stay inside the 4 KB kernel-argument segment (static_assert below)
   EngLayerW L[ENG_MAX_LAYERS];        // in the kernel-argument segment: block l's pointers are scalar loads (a table in global
                                       // memory is re-read with VECTOR loads wherever hipcc cannot prove it unaliased - a dependent
                                       // memory latency, and a vmcnt(0) in front of the weight-prefetch issue, in every phase)
@@ -52,8 +55,13 @@ struct EngArgs {
   float* dbg = nullptr;               // debugging aid (ITTS_TAP_LAYER): qkv [B][3D], h1 [B][D], act [B][4D], h2 [B][D] of block dbg_layer
   int dbg_layer = -1;
   unsigned* stamp = nullptr;          // debugging aid (ITTS_ENGINE_STAMPS): [256][NL][12] wall-clock stamps (100 MHz) of one step
+  // fp8 weights (behind everything else: the bf16 kernels' argument offsets are what they were)
+  int w8 = 0;                         // the weight pointers carry fp8-e4m3 bytes: decode_engine_kernel<.., W8> (bf16 build only)
+  const float* head_s = nullptr;      // [V] w8: row scales of the fp8 mel_head (head_w then holds its fp8 bytes)
+  EngLayerS S[ENG_MAX_LAYERS];        // w8: row scales of block l (scalar loads, like L)
 };
 
+static_assert(sizeof(EngArgs) <= 3072, "EngArgs is a kernel argument: keep it well under 4 KB");
 size_t eng_gran_count(int layers);  // 8-byte words of the granule buffer (sized for ENG_MAX_ROWS rows; the last ENG_CAND_WORDS: sampler candidates)
 constexpr size_t ENG_CAND_WORDS = (size_t)ENG_MAX_ROWS * ENG_NCU * 2;
 int decode_engine_layers(const EngArgs& a, hipStream_t s);

@@ -162,8 +162,18 @@ int Engine::ensure_decode_tiles(hipStream_t s) {
 }
 
 // The persistent decode engine (decode_engine.hip) replaces the 120 per-layer launches of a step when the step is the
-// launch-bound small-batch bf16 one it was built for: IndexTTS-1.5 GPT dims, <= 6 rows (beam rows included: cache ancestry), no fp8
-// copies, a whole MI355X (256 CUs) to itself.  ITTS_ENGINE=0 (or debug bit 4) keeps the launch path.
+// launch-bound small-batch bf16 one it was built for: IndexTTS-1.5 GPT dims, <= 6 rows (beam rows included: cache ancestry),
+// a whole MI355X (256 CUs) to itself.  ITTS_ENGINE=0 (or debug bit 4) keeps the launch path.
+// fp8 weight copies (BASELINE config 5) keep the launch path unless the engine object opted in (itts_gpt_set_engine_fp8, or
+// ITTS_ENGINE_FP8=1 for every engine; ITTS_ENGINE_FP8=0 overrides the setter) AND this is the bf16 build AND all four projections
+// of every block and the head carry an fp8 copy with its row scales - a mixed model stays on the launch path.
+bool Engine::engine_fp8_model() const {
+  if (!gpt.head.w8 || !gpt.head.wscale) return false;
+  for (const GptLayerW& L : gpt.layers)
+    for (const Lin* l : {&L.attn, &L.proj, &L.fc, &L.proj2})
+      if (!l->w8 || !l->wscale) return false;
+  return true;
+}
 bool Engine::engine_usable() const {
   const char* ev = getenv("ITTS_ENGINE");  // read per call: tests flip it inside one process
   const bool env_off = ev ? atoi(ev) == 0 : !ENG_DEFAULT_ON;
@@ -184,7 +194,19 @@ bool Engine::engine_usable() const {
   if (c.model_dim != ENG_D || c.heads != ENG_H || c.layers < 1 || c.layers > ENG_MAX_LAYERS || ds.Smax > 2048 || ds.Smax % 256 != 0) return false;
   for (const GptLayerW& L : gpt.layers)
     for (const Lin* l : {&L.attn, &L.proj, &L.fc, &L.proj2})
-      if (l->dt != BF16 || l->w8 || !l->b || l->taps != 1) return false;
+      if (l->dt != BF16 || !l->b || l->taps != 1) return false;
+  bool any8 = false;  // (an fp8 head alone, as before, only keeps the head out of the launch)
+  for (const GptLayerW& L : gpt.layers)
+    for (const Lin* l : {&L.attn, &L.proj, &L.fc, &L.proj2}) any8 = any8 || l->w8;
+  if (any8) {
+#ifdef ITTS_HALF_F16
+    return false;  // the fp8 readers expand to bf16 pairs
+#else
+    const char* e8 = getenv("ITTS_ENGINE_FP8");  // read per call, like ITTS_ENGINE
+    const bool opted = e8 ? atoi(e8) != 0 : ds.eng_fp8 != 0;
+    if (!opted || !engine_fp8_model()) return false;
+#endif
+  }
   return true;
 }
 
@@ -738,10 +760,18 @@ int Engine::decode_step_launch(hipStream_t s) {
   if (engine_usable()) {  // <= 6 rows: the 24 blocks (+ head, + greedy sampler) as ONE persistent launch
     ITTS_REQUIRE(ds.eng_gran && ds.eng_ctr, "decode engine: state not allocated (prefill first)");
     EngArgs ea;
+    const bool w8 = gpt.layers[0].attn.w8 != nullptr;  // engine_usable(): then every projection and the head carry an fp8 copy
+    ea.w8 = w8;
     for (int l = 0; l < c.layers; ++l) {
       const GptLayerW& L = gpt.layers[l];
-      ea.L[l] = {(const bf16_t*)L.attn.w, (const bf16_t*)L.proj.w, (const bf16_t*)L.fc.w, (const bf16_t*)L.proj2.w,
-                 L.attn.b, L.proj.b, L.fc.b, L.proj2.b};
+      if (w8) {
+        ea.L[l] = {(const bf16_t*)L.attn.w8, (const bf16_t*)L.proj.w8, (const bf16_t*)L.fc.w8, (const bf16_t*)L.proj2.w8,
+                   L.attn.b, L.proj.b, L.fc.b, L.proj2.b};
+        ea.S[l] = {L.attn.wscale, L.proj.wscale, L.fc.wscale, L.proj2.wscale};
+      } else {
+        ea.L[l] = {(const bf16_t*)L.attn.w, (const bf16_t*)L.proj.w, (const bf16_t*)L.fc.w, (const bf16_t*)L.proj2.w,
+                   L.attn.b, L.proj.b, L.fc.b, L.proj2.b};
+      }
     }
     ea.gran = ds.eng_gran;
     ea.h = ds.h;
@@ -791,8 +821,10 @@ int Engine::decode_step_launch(hipStream_t s) {
     if (debug && e_stamps && !dry) ea.stamp = (unsigned*)ds.scores2;  // [16][V] fp32 scratch of the typical filter (off in this mode) >= 256 * 24 * 16 words
     ds.last_mode = eng_first > 0;
     // the head (ln_f -> final_norm -> mel_head) inside the same launch when the engine runs every block (ITTS_ENGINE_HEAD=0: own launch)
-    static const bool e_head = !(getenv("ITTS_ENGINE_HEAD") && atoi(getenv("ITTS_ENGINE_HEAD")) == 0);
-    const bool fold_head = e_head && eng_first == c.layers && gpt.head.dt == BF16 && !gpt.head.w8 && gpt.head.b && gpt.head.Cin == ENG_D &&
+    // (read per call - i.e. whenever an engine object captures its step -, so one process can compare both forms on fresh engine objects)
+    const char* e_head_env = getenv("ITTS_ENGINE_HEAD");
+    const bool e_head = !(e_head_env && atoi(e_head_env) == 0);
+    const bool fold_head = e_head && eng_first == c.layers && gpt.head.dt == BF16 && (gpt.head.w8 != nullptr) == w8 && gpt.head.b && gpt.head.Cin == ENG_D &&
                            gpt.ln_f.g && gpt.ln_f.b && (c.number_mel_codes + ENG_NCU - 1) / ENG_NCU <= 33;
     // ... and the greedy sampler behind it (ITTS_ENGINE_SAMPLER=0: own launch): plain greedy search only - sampling, beams,
     // typical filtering and host-side sampling keep their kernels
@@ -804,7 +836,8 @@ int Engine::decode_step_launch(hipStream_t s) {
       ea.cand = ds.eng_gran + eng_gran_count(c.layers) - ENG_CAND_WORDS;
     }
     if (fold_head) {
-      ea.head_w = (const bf16_t*)gpt.head.w;
+      ea.head_w = (const bf16_t*)(w8 ? gpt.head.w8 : gpt.head.w);
+      ea.head_s = w8 ? gpt.head.wscale : nullptr;
       ea.head_b = gpt.head.b;
       ea.lnf_g = gpt.ln_f.g;
       ea.lnf_b = gpt.ln_f.b;

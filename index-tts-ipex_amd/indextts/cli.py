@@ -4,7 +4,7 @@ import os
 import sys
 
 
-def main():
+def build_parser():
     p = argparse.ArgumentParser(description="IndexTTS Command Line (MI355X HIP engine)")
     p.add_argument("text", type=str, help="Text to be synthesized")
     p.add_argument("-v", "--voice", type=str, required=True, help="Path to the audio prompt file (wav format)")
@@ -15,6 +15,13 @@ def main():
     p.add_argument("--fp32", action="store_true", help="fp32 parity engine")
     p.add_argument("-f", "--force", action="store_true", default=False)
     p.add_argument("-d", "--device", type=str, default=None)
+    p.add_argument("--gpt-fp8", action="store_true", default=False,
+                   help="store the GPT weights as fp8-e4m3 (bfloat16 engine; the decode steps stream the fp8 bytes)")
+    return p
+
+
+def main():
+    p = build_parser()
     a = p.parse_args()
     if not a.text.strip():
         print("ERROR: Text is empty.")
@@ -31,7 +38,7 @@ def main():
         sys.exit(1)
     from indextts.infer import IndexTTS
 
-    tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device)
+    tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

@@ -24,7 +24,10 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     protection always apply);
   * `is_fp16=True` selects the IEEE-half engine (the reference's own GPU precision; ITTS_HALF=bf16: the bfloat16 engine, same
     speed), `False` the fp32 parity engine; `use_cuda_kernel` is accepted
-    and ignored (the fused HIP activation is always used).
+    and ignored (the fused HIP activation is always used);
+  * `gpt_fp8=True` (not in the reference; needs `is_fp16=True`) stores the GPT projections and mel_head as fp8-e4m3 with
+    power-of-two row scales (pack.quantize_gpt_fp8), runs on the bfloat16 engine - the fp8 readers expand to bf16 pairs - and
+    lets the 1 - 6 row decode steps stream the fp8 bytes on the persistent decode engine.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -48,7 +51,7 @@ from indextts.utils.front import TextNormalizer, TextTokenizer
 
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
-                 use_cuda_kernel=None, state_dicts=None, cfg=None):
+                 use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False):
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -60,9 +63,15 @@ class IndexTTS:
         self.model_dir = model_dir
         # is_fp16=True is IEEE half in the reference (autocast(dtype=torch.float16) + .half(), infer.py:39,44,52): the f16 build of the
         # library.  ITTS_HALF=bf16 selects the bfloat16 engine instead (same speed, 8 instead of 11 significand bits, wider range)
-        self.half = os.environ.get("ITTS_HALF", "f16") if self.is_fp16 else None
+        self.half = os.environ.get("ITTS_HALF", "bf16" if gpt_fp8 else "f16") if self.is_fp16 else None
         if self.half not in (None, "f16", "bf16"):
             raise ValueError(f"ITTS_HALF={self.half}: expected f16 or bf16")
+        # gpt_fp8: fp8-e4m3 GPT weights.  The fp8 readers expand to bf16 pairs, so it is a mode of the bfloat16 engine only
+        self.gpt_fp8 = bool(gpt_fp8)
+        if self.gpt_fp8 and not self.is_fp16:
+            raise ValueError("gpt_fp8=True needs is_fp16=True: the fp8 GPT weights run on the bfloat16 engine, not the fp32 one")
+        if self.gpt_fp8 and self.half != "bf16":
+            raise ValueError("gpt_fp8=True needs the bfloat16 engine: fp8 weights expand to bf16 pairs (unset ITTS_HALF=f16)")
         self.dtype = (torch.float16 if self.half == "f16" else torch.bfloat16) if self.is_fp16 else torch.float32
         self.stop_mel_token = self.cfg.gpt.stop_mel_token
         sds = dict(state_dicts or {})
@@ -75,11 +84,16 @@ class IndexTTS:
             sds["bigvgan"] = read_state_dict(self.bigvgan_path, key="generator")
             print(">> bigvgan weights restored from:", self.bigvgan_path)
         self.engine = ieng.Engine(self.cfg, self.half if self.is_fp16 else "fp32", self.device)
-        self.engine.load_packed(pack.pack_gpt(sds["gpt"], self.cfg))
+        packed_gpt = pack.pack_gpt(sds["gpt"], self.cfg)
+        if self.gpt_fp8:
+            packed_gpt = pack.quantize_gpt_fp8(packed_gpt, keep_bytes=True)
+        self.engine.load_packed(packed_gpt)
         self.engine.load_packed(pack.pack_bigvgan(sds["bigvgan"], self.cfg))
         if "dvae" in sds:
             self.engine.load_packed(pack.pack_dvae(sds["dvae"], self.cfg))
         self.engine.finalize()
+        if self.gpt_fp8:
+            self.engine.set_engine_fp8(True)
         self.gpt = UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])

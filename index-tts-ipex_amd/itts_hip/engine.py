@@ -293,6 +293,12 @@ class Engine:
         """1 if the last decode step ran on the persistent decode engine, 0 for the five-launches-per-block path."""
         return int(self.lib.itts_gpt_decode_mode(self.h))
 
+    def set_engine_fp8(self, on: bool = True):
+        """Opt-in: a model whose GPT projections and mel_head all carry fp8 copies (build_engine(gpt_fp8="fp8")) runs its 1 - 6 row
+        decode steps on the persistent decode engine, streaming the fp8 bytes; off (the default) it keeps the launch path.
+        Same codes and logits either way.  ITTS_ENGINE_FP8=0 / 1 in the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_engine_fp8(self.h, int(bool(on))), "gpt_set_engine_fp8")
+
     def decode(self, nsteps: int):
         self._ck(self.lib.itts_gpt_decode(self.h, nsteps, self._s()), "gpt_decode")
 
@@ -580,10 +586,11 @@ def _dvae_code_len(T: int, layers: int) -> int:
 
 
 def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1234, parts=("gpt", "bigvgan", "dvae"),
-                 state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "") -> Engine:
+                 state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
-    "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference)."""
+    "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
+    engine_fp8: Engine.set_engine_fp8(True) - the fp8 model's small-batch decode steps on the persistent decode engine."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -598,4 +605,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
     if "dvae" in parts:
         eng.load_packed(pack.pack_dvae(sds.get("dvae") or synth.dvae_state_dict(cfg, seed), cfg))
     eng.finalize()
+    if engine_fp8:
+        eng.set_engine_fp8(True)
     return eng
