@@ -14,6 +14,7 @@
 // KV-cache ancestry rows (see decode_attn2_kernel ANC - the cache itself is never copied), and prepare the next
 // step's input embeddings.
 #include "itts_decode.h"
+#include "itts_sampler_dev.h"
 #include "itts_wave_dev.h"
 
 namespace itts {
@@ -38,30 +39,6 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid) {
   for (int i = 0; i < 16; ++i) r += red[i];
   __syncthreads();
   return r;
-}
-
-// bitonic sort of BEAM_MAX_CAND (value, index) pairs in LDS by ONE wave (lanes 0..63 = the BEAM_MAX_CAND / 2 comparators of a stage): a
-// wave's LDS operations execute in program order, so the 28 stages need no workgroup barrier (at 16 waves each barrier
-// costs ~0.4 us and the block form spent 11 us per sort); the fence only pins the compiler's order.
-// BY_SCORE: descending value, ascending index on ties; else ascending index.
-template <bool BY_SCORE>
-__device__ __forceinline__ void sort_cands_wave(float* cv, int* ci, int lane) {
-  static_assert(BEAM_MAX_CAND == 128, "one comparator per lane");
-  for (int kq = 2; kq <= BEAM_MAX_CAND; kq <<= 1)
-    for (int j = kq >> 1; j > 0; j >>= 1) {
-      const int lo = ((lane & ~(j - 1)) << 1) | (lane & (j - 1)), hi = lo | j;
-      const bool up = (lo & kq) == 0;
-      const float v0 = cv[lo], v1 = cv[hi];
-      const int i0 = ci[lo], i1 = ci[hi];
-      const bool second_first = BY_SCORE ? (v1 > v0 || (v1 == v0 && i1 < i0)) : (i1 < i0);
-      if (second_first == up) {
-        cv[lo] = v1;
-        cv[hi] = v0;
-        ci[lo] = i1;
-        ci[hi] = i0;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
 }
 
 __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {

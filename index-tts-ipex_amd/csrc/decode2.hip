@@ -8,6 +8,7 @@
 
 #include "itts_decode.h"
 #include "itts_sampler_dev.h"
+#include "itts_attn_dev.h"
 #include "itts_wave_dev.h"
 #include "decode_pinned.h"
 
@@ -227,6 +228,38 @@ __global__ __launch_bounds__(256) void gemv2_kernel(GemvArgs g) {
 #define GEMV_STAMP(i)
 #endif
 
+// ---- pieces shared by gemv_bf16_kernel, fused_gemv_part (qkv_attn_fused_kernel) and, gemv_reduce apart, gemv_wave_kernel ----
+// one 16-byte weight fragment (8 bf16) times 8 activations held as bf16 pairs (XQ: u32x4 or uint32_t[4]): 4 x v_dot2c
+template <typename XQ>
+__device__ __forceinline__ float gemv_dot8(const u32x4& w, const XQ& xq, float acc) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc = half_dot2(w[e], xq[e], acc);
+  return acc;
+}
+// wave reduction of every (row, batch) sum, then one lane per output: lane l < RPW * NB keeps (row l / NB, batch l % NB)
+template <int RPW, int NB>
+__device__ __forceinline__ float gemv_reduce(const float (&acc)[RPW][NB], int lane) {
+  float mine = 0.f;
+#pragma unroll
+  for (int r = 0; r < RPW; ++r)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const float t = wave_sum_rl(acc[r][b]);
+      mine = lane == r * NB + b ? t : mine;
+    }
+  return mine;
+}
+// the output value: fp8 row scale (1 for bf16 weights), bias, activation
+__device__ __forceinline__ float gemv_out(const GemvArgs& g, float mine, float spre, float bpre) {
+  const float v = mine * spre + (g.bias ? bpre : 0.f);
+  return g.act == ACT_GELU_NEW ? gelu_new_rn(v) : act_apply(g.act, v);
+}
+
+// 8 bf16 weights of row n at column k, read exactly once per step: non-temporal (gemv_bf16_kernel, fused_gemv_part)
+__device__ __forceinline__ u32x4 gemv_load_w(const bf16_t* __restrict__ W, int n, int K, int k) {
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(W + (size_t)n * K + k));
+}
+
 // WAVES per workgroup: 4, or 5 so that the per-layer projections (3840 / 1280 / 5120 rows) split into exactly 256
 // workgroups - one per CU, every CU streaming the same share of the weights and loading x once.
 template <int NB, int RPW, int NCH, int PRO, bool XBF, bool YBF, bool W8 = false, int WAVES = 4>
@@ -295,7 +328,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_bf16_kernel(GemvArgs g) {
       if constexpr (W8)
         w8[r][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(Wq + (size_t)min(n0 + r, g.N - 1) * K + k));
       else
-        w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(W + (size_t)min(n0 + r, g.N - 1) * K + k));
+        w[r][c] = gemv_load_w(W, min(n0 + r, g.N - 1), K, k);
     }
   }
   // epilogue operands of the output this lane will finish, (row lane / NB, batch lane % NB): bias, fp8 row scale and the
@@ -443,25 +476,16 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_bf16_kernel(GemvArgs g) {
             acc[r][b] = half_dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, true)), xq[2 * h2 + 1], acc[r][b]);
           }
         } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(w[r][c][e], xq[e], acc[r][b]);
+          acc[r][b] = gemv_dot8(w[r][c], xq, acc[r][b]);
         }
       }
     }
   }
   // wave reduction, then one lane per output: lane l < RPW * NB stores (row l / NB, batch l % NB)
-  float mine = 0.f;
-#pragma unroll
-  for (int r = 0; r < RPW; ++r)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const float t = wave_sum_rl(acc[r][b]);
-      mine = lane == r * NB + b ? t : mine;
-    }
+  const float mine = gemv_reduce(acc, lane);
   GEMV_STAMP(4)
   if (lane < RPW * NB && n0 + er < g.N && eb < g.B) {
-    float v = mine * spre + (g.bias ? bpre : 0.f);
-    v = g.act == ACT_GELU_NEW ? gelu_new_rn(v) : act_apply(g.act, v);
+    const float v = gemv_out(g, mine, spre, bpre);
     const size_t o = (size_t)eb * g.ldy + en;
     if (YBF)
       ((bf16_t*)g.Y)[o] = (bf16_t)v;
@@ -618,12 +642,11 @@ __global__ __launch_bounds__(256) void gemv_wave_kernel(GemvArgs g) {
       } else {
 #pragma unroll
         for (int b = 0; b < NB; ++b)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(w[r][c][e], xq[b][c][e], acc[r][b]);
+          acc[r][b] = gemv_dot8(w[r][c], xq[b][c], acc[r][b]);
       }
     }
   // ---- 4. wave reduction, then one lane per output ----
-  float mine = 0.f;
+  float mine = 0.f;  // (written out here: gemv_reduce changes this kernel's code)
 #pragma unroll
   for (int r = 0; r < RPW; ++r)
 #pragma unroll
@@ -633,8 +656,7 @@ __global__ __launch_bounds__(256) void gemv_wave_kernel(GemvArgs g) {
     }
   GEMV_STAMP(4)
   if (lane < RPW * NB && n0 + er < g.N && eb < g.B) {
-    float v = mine * spre + (g.bias ? bpre : 0.f);
-    v = g.act == ACT_GELU_NEW ? gelu_new_rn(v) : act_apply(g.act, v);
+    const float v = gemv_out(g, mine, spre, bpre);
     const size_t o = (size_t)eb * g.ldy + en;
     if (YBF)
       ((bf16_t*)g.Y)[o] = (bf16_t)v;
@@ -795,18 +817,7 @@ __global__ __launch_bounds__(NT) void decode_attn2_kernel(TO* __restrict__ ctx, 
   float m = -INFINITY, l = 0.f, acc[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-  // score of one cached key row for this slot (the LPK lanes of the key hold VEC dims each; DPP sums them: quad swaps,
-  // half-row mirror, row mirror - no LDS crossbar trips)
-  auto score = [&](const CacheVec<TC>& kk) {
-    float sc = 0.f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) sc = fmaf(qr[i], kk.get(i), sc);
-    sc = dpp_add<0xB1>(sc);
-    sc = dpp_add<0x4E>(sc);
-    sc = dpp_add<0x141>(sc);
-    if (LPK == 16) sc = dpp_add<0x140>(sc);
-    return sc;
-  };
+  auto score = [&](const CacheVec<TC>& kk) { return attn_score<LPK>(qr, kk); };  // itts_attn_dev.h; the lambda stays
   // (e) the register window in two phases, as torch.softmax does it: all scores, their maximum, then one exp per key and
   //     the weighted sum - half the VALU work of a per-key online update (no rescale of the accumulator per key), and the
   //     16 waves of a workgroup share 4 SIMDs, so this phase is issue-bound.  The row appended by this step (j == pos)
@@ -852,16 +863,7 @@ __global__ __launch_bounds__(NT) void decode_attn2_kernel(TO* __restrict__ ctx, 
   }
   // online update for rows beyond the window (never the appended row when it lies inside the window)
   auto consume = [&](const CacheVec<TC>& kk, const CacheVec<TC>& vv, int j) {
-    const bool ok = j < S && j >= ks && j != pos;
-    float sc = score(kk);
-    sc = ok ? sc : -INFINITY;  // also discards whatever an out-of-range row produced
-    const float mn = fmaxf(m, sc);
-    const float corr = mn > -INFINITY ? __expf(m - mn) : 1.f;
-    const float p = ok ? __expf(sc - mn) : 0.f;
-    l = fmaf(l, corr, p);  // contraction pinned: same operation in every build of this loop (decode_pinned.h)
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, ok ? vv.get(i) : 0.f, acc[i] * corr);
-    m = mn;
+    attn_consume<LPK>(m, l, acc, qr, kk, vv, j < S && j >= ks && j != pos);
   };
   // sequences longer than the register-resident window: stream the rest two rows at a time
   for (int cb = 2 * NIT; (cb * NSPLIT + sp) * SLOTS < S; cb += SD) {  // chunk cb of this split = rows (cb*NSPLIT+sp)*SLOTS ..
@@ -877,33 +879,19 @@ __global__ __launch_bounds__(NT) void decode_attn2_kernel(TO* __restrict__ ctx, 
   }
   ATTN_STAMP(3)
   // merge the 64/LPK key slots of this wave (lanes with equal `sub`)
-  // merge across the wave without the LDS crossbar: lane ^ 8 is a DPP rotate inside the 16-lane row; lane ^ 16 and
-  // lane ^ 32 are v_permlane16_swap / v_permlane32_swap (CDNA4), which hand every lane BOTH partners' values
-  // (tools/probe_permlane.hip prints the lane maps) - a sum or max of the two results is the butterfly step
-  auto bfly_max = [&](float x, int o) {
-    if (o == 8) return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true)));
-    const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
-                            : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  };
-  auto bfly_sum = [&](float x, int o) {
-    if (o == 8) return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true));
-    const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
-                            : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  };
+  // (wave_bfly_max / wave_bfly_sum, itts_wave_dev.h: no LDS crossbar)
   float M = m;
 #pragma unroll
-  for (int o = LPK; o < 64; o <<= 1) M = bfly_max(M, o);
+  for (int o = LPK; o < 64; o <<= 1) M = wave_bfly_max(M, o);
   const float sc0 = M > -INFINITY ? __expf(m - M) : 0.f;
   l *= sc0;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc[i] *= sc0;
 #pragma unroll
   for (int o = LPK; o < 64; o <<= 1) {
-    l = bfly_sum(l, o);
+    l = wave_bfly_sum(l, o);
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = bfly_sum(acc[i], o);
+    for (int i = 0; i < VEC; ++i) acc[i] = wave_bfly_sum(acc[i], o);
   }
   if (lane < LPK)
 #pragma unroll
@@ -956,22 +944,18 @@ __global__ __launch_bounds__(NT) void decode_attn2_kernel(TO* __restrict__ ctx, 
 template <int NB, int RPW, int NCH>
 __device__ __forceinline__ void fused_gemv_part(const GemvArgs& g, int blk, unsigned long long* __restrict__ gran,
                                                 const int* __restrict__ len, const int* __restrict__ prefix) {
-  constexpr int PRO = 1, WAVES = 4;
-  constexpr bool XBF = false, W8 = false;
-  constexpr int NTHR = WAVES * 64;
-  constexpr int EPC = XBF ? 8 : 4;                                  // elements per 16-byte chunk
+  // gemv_bf16_kernel<NB, RPW, NCH, 1, false, false, false, 4> (one LayerNorm without affine, fp32 x, bf16 weights) up to its store
+  constexpr int WAVES = 4, NTHR = WAVES * 64;
+  constexpr int EPC = 4;                                            // elements per 16-byte chunk
   constexpr int KCH = (NCH * 512 + NTHR * EPC - 1) / (NTHR * EPC);  // chunks per row per thread
   extern __shared__ __attribute__((aligned(16))) uint32_t sxb[];    // [NB][K/2] bf16 pairs
-  __shared__ float red[2][WAVES][2 * NB];
+  __shared__ float red[WAVES][2 * NB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = g.K;
   const float invK = 1.f / (float)K;  // off the critical path: the LayerNorm chain multiplies instead of dividing
   const int n0 = (blk * WAVES + wave) * RPW;
-  // ---- 1. activations (+ LayerNorm parameters) first, weights second; all unconditional ----
-  u32x4 xr[NB][KCH];  // XBF: 8 bf16; else 4 floats
-  f32x4 pm[PRO == 3 ? NB : 1][KCH], pl[PRO == 3 ? NB : 1][KCH], po[PRO == 3 ? NB : 1][KCH][ATTN_NSPLIT][2];
-  static_assert(PRO != 3 || (XBF && ATTN_NSPLIT == 4), "prologue 3 feeds bf16 pairs and reads 4 partials as one float4");
-  f32x4 gm[PRO == 2 ? KCH : 1], bt[PRO == 2 ? KCH : 1];
+  // ---- 1. activations first, weights second; all unconditional ----
+  u32x4 xr[NB][KCH];  // 4 floats
   bool xok[KCH];
 #pragma unroll
   for (int j = 0; j < KCH; ++j) {
@@ -981,64 +965,35 @@ __device__ __forceinline__ void fused_gemv_part(const GemvArgs& g, int blk, unsi
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       const size_t ro = (size_t)min(b, g.B - 1) * K + ic;
-      if constexpr (PRO == 3) {
-        // x is the attention output, still in ATTN_NSPLIT partials: this thread's 8 dims of head ic / 64
-        const size_t bh = (size_t)min(b, g.B - 1) * (K >> 6) + (ic >> 6);
-        const float* ml = g.attn_ml + bh * 2 * ATTN_NSPLIT;
-        pm[b][j] = *reinterpret_cast<const f32x4*>(ml);
-        pl[b][j] = *reinterpret_cast<const f32x4*>(ml + ATTN_NSPLIT);
-#pragma unroll
-        for (int sp = 0; sp < ATTN_NSPLIT; ++sp) {
-          const float* po_ = g.attn_o + (bh * ATTN_NSPLIT + sp) * 64 + (ic & 63);
-          po[b][j][sp][0] = *reinterpret_cast<const f32x4*>(po_);
-          po[b][j][sp][1] = *reinterpret_cast<const f32x4*>(po_ + 4);
-        }
-      } else if (XBF) {
-        xr[b][j] = *reinterpret_cast<const u32x4*>((const bf16_t*)g.X + ro);
-      } else {
-        xr[b][j] = *reinterpret_cast<const u32x4*>(g.X + ro);
-      }
-    }
-    if (PRO == 2) {
-      gm[j] = *reinterpret_cast<const f32x4*>(g.ln_gamma + ic);
-      bt[j] = *reinterpret_cast<const f32x4*>(g.ln_beta + ic);
+      xr[b][j] = *reinterpret_cast<const u32x4*>(g.X + ro);
     }
   }
   float pivot[NB];
 #pragma unroll
-  for (int b = 0; b < NB; ++b) pivot[b] = (PRO == 1 || PRO == 2) ? g.X[(size_t)min(b, g.B - 1) * K] : 0.f;
+  for (int b = 0; b < NB; ++b) pivot[b] = g.X[(size_t)min(b, g.B - 1) * K];
   const bf16_t* __restrict__ W = (const bf16_t*)g.W;
-  const uint8_t* __restrict__ Wq = (const uint8_t*)g.W8;
-  u32x4 w[W8 ? 1 : RPW][W8 ? 1 : NCH];
-  u32x2 w8[W8 ? RPW : 1][W8 ? NCH : 1];  // 8 fp8 weights per lane and chunk
+  u32x4 w[RPW][NCH];
   const int klast = (NCH - 1) * 512 + lane * 8;
   const bool kok = klast < K;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int k = c == NCH - 1 ? (kok ? klast : K - 8) : c * 512 + lane * 8;
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      if constexpr (W8)
-        w8[r][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(Wq + (size_t)min(n0 + r, g.N - 1) * K + k));
-      else
-        w[r][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(W + (size_t)min(n0 + r, g.N - 1) * K + k));
-    }
+    for (int r = 0; r < RPW; ++r) w[r][c] = gemv_load_w(W, min(n0 + r, g.N - 1), K, k);
   }
-  // epilogue operands of the output this lane will finish, (row lane / NB, batch lane % NB): bias, fp8 row scale and the
-  // residual-stream value it accumulates into are requested now (youngest loads, unconditional), so the epilogue has no
-  // dependent memory latency of its own
+  // epilogue operand of the output this lane will finish, (row lane / NB, batch lane % NB): the bias is requested now (youngest
+  // load, unconditional), so the epilogue has no dependent memory latency of its own
   const int er = min(lane / NB, RPW - 1), eb = lane % NB;
   const int en = min(n0 + er, g.N - 1);
-  const float* bp = g.bias ? g.bias : reinterpret_cast<const float*>(W8 ? g.W8 : g.W);  // any readable address when there is no bias
+  const float* bp = g.bias ? g.bias : reinterpret_cast<const float*>(g.W);  // any readable address when there is no bias
   const float bpre = bp[en];
-  const float spre = W8 ? g.wscale[en] : 1.f;
   // (no residual read: the q/k/v outputs are published, not accumulated)
   // every request of this kernel is now in flight.  The fence keeps it that way: without it the machine scheduler sinks
   // most of the weight loads below the first wait on X (fewer live registers), i.e. two thirds of the weight stream
   // would be requested one memory latency late
   __builtin_amdgcn_sched_barrier(0);
-  // ---- 2. LayerNorm(s) in registers (one barrier each), bf16 pairs to LDS ----
-  if (!XBF) {
+  // ---- 2. LayerNorm in registers (one barrier), bf16 pairs to LDS ----
+  {
     float xv[NB][KCH][4];
 #pragma unroll
     for (int b = 0; b < NB; ++b)
@@ -1046,52 +1001,44 @@ __device__ __forceinline__ void fused_gemv_part(const GemvArgs& g, int blk, unsi
       for (int j = 0; j < KCH; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) xv[b][j][e] = __uint_as_float(xr[b][j][e]);
+    float s[NB], q[NB];
 #pragma unroll
-    for (int pass = 0; pass < PRO; ++pass) {
-      float s[NB], q[NB];
+    for (int b = 0; b < NB; ++b) {
+      s[b] = q[b] = 0.f;
+#pragma unroll
+      for (int j = 0; j < KCH; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = xok[j] ? xv[b][j][e] - pivot[b] : 0.f;
+          s[b] += d;
+          q[b] = fmaf(d, d, q[b]);
+        }
+      s[b] = wave_sum_rl(s[b]);
+      q[b] = wave_sum_rl(q[b]);
+    }
+    if (lane == 0)
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        s[b] = q[b] = 0.f;
-        const float pv = pass == 0 ? pivot[b] : 0.f;
-#pragma unroll
-        for (int j = 0; j < KCH; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float d = xok[j] ? xv[b][j][e] - pv : 0.f;
-            s[b] += d;
-            q[b] = fmaf(d, d, q[b]);
-          }
-        s[b] = wave_sum_rl(s[b]);
-        q[b] = wave_sum_rl(q[b]);
+        red[wave][2 * b] = s[b];
+        red[wave][2 * b + 1] = q[b];
       }
-      if (lane == 0)
+    __syncthreads();
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          red[pass][wave][2 * b] = s[b];
-          red[pass][wave][2 * b + 1] = q[b];
-        }
-      __syncthreads();
+    for (int b = 0; b < NB; ++b) {
+      float S = 0.f, Q = 0.f;
 #pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        float S = 0.f, Q = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < WAVES; ++ww) {
-          S += red[pass][ww][2 * b];
-          Q += red[pass][ww][2 * b + 1];
-        }
-        // contraction pinned (decode_pinned.h): the persistent engine repeats these operations bit for bit
-        const float md = __fmul_rn(S, invK);
-        const float mean = __fadd_rn(pass == 0 ? pivot[b] : 0.f, md);
-        const float rstd = __builtin_amdgcn_rsqf(__fadd_rn(fmaxf(ln_var_rn(Q, invK, md), 0.f), g.ln_eps));
-#pragma unroll
-        for (int j = 0; j < KCH; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float v = (xv[b][j][e] - mean) * rstd;
-            if (PRO == 2 && pass == 0) v = v * gm[j][e] + bt[j][e];
-            xv[b][j][e] = v;
-          }
+      for (int ww = 0; ww < WAVES; ++ww) {
+        S += red[ww][2 * b];
+        Q += red[ww][2 * b + 1];
       }
+      // contraction pinned (decode_pinned.h): the persistent engine repeats these operations bit for bit
+      const float md = __fmul_rn(S, invK);
+      const float mean = __fadd_rn(pivot[b], md);
+      const float rstd = __builtin_amdgcn_rsqf(__fadd_rn(fmaxf(ln_var_rn(Q, invK, md), 0.f), g.ln_eps));
+#pragma unroll
+      for (int j = 0; j < KCH; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xv[b][j][e] = (xv[b][j][e] - mean) * rstd;
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b)
@@ -1104,38 +1051,6 @@ __device__ __forceinline__ void fused_gemv_part(const GemvArgs& g, int blk, unsi
           p.y = pack_bf16(xv[b][j][2], xv[b][j][3]);
           *reinterpret_cast<uint2*>(sxb + (b * K + i) / 2) = p;
         }
-  } else {
-    if constexpr (PRO == 3) {
-      // merge the split-attention partials: weights exp(max_p - max), one division per head
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int j = 0; j < KCH; ++j) {
-          const float M = fmaxf(fmaxf(pm[b][j][0], pm[b][j][1]), fmaxf(pm[b][j][2], pm[b][j][3]));
-          float wgt[ATTN_NSPLIT], L = 0.f;
-#pragma unroll
-          for (int sp = 0; sp < ATTN_NSPLIT; ++sp) {
-            wgt[sp] = pm[b][j][sp] > -INFINITY ? __expf(pm[b][j][sp] - M) : 0.f;
-            L = fmaf(wgt[sp], pl[b][j][sp], L);
-          }
-          const float inv = 1.f / L;
-          float xm[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            float a = 0.f;
-#pragma unroll
-            for (int sp = 0; sp < ATTN_NSPLIT; ++sp) a = fmaf(wgt[sp], po[b][j][sp][e >> 2][e & 3], a);
-            xm[e] = a * inv;
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) xr[b][j][e] = pack_bf16(xm[2 * e], xm[2 * e + 1]);
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int j = 0; j < KCH; ++j)
-        if (xok[j]) *reinterpret_cast<u32x4*>(sxb + (b * K + (tid + j * NTHR) * 8) / 2) = xr[b][j];
   }
   __syncthreads();
   // ---- 3. dot products: 4 x v_dot2c per weight fragment and batch row ----
@@ -1154,33 +1069,14 @@ __device__ __forceinline__ void fused_gemv_part(const GemvArgs& g, int blk, unsi
 #pragma unroll
         for (int e = 0; e < 4; ++e) xq[e] = kok ? xq[e] : 0u;
 #pragma unroll
-      for (int r = 0; r < RPW; ++r) {
-        if constexpr (W8) {
-#pragma unroll
-          for (int h2 = 0; h2 < 2; ++h2) {
-            const uint32_t q = w8[r][c][h2];  // 4 fp8: bytes 0,1 -> pair 2*h2, bytes 2,3 -> pair 2*h2 + 1
-            acc[r][b] = half_dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, false)), xq[2 * h2], acc[r][b]);
-            acc[r][b] = half_dot2(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q, 1.0f, true)), xq[2 * h2 + 1], acc[r][b]);
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[r][b] = half_dot2(w[r][c][e], xq[e], acc[r][b]);
-        }
-      }
+      for (int r = 0; r < RPW; ++r)
+        acc[r][b] = gemv_dot8(w[r][c], xq, acc[r][b]);
     }
   }
   // wave reduction, then one lane per output: lane l < RPW * NB stores (row l / NB, batch l % NB)
-  float mine = 0.f;
-#pragma unroll
-  for (int r = 0; r < RPW; ++r)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const float t = wave_sum_rl(acc[r][b]);
-      mine = lane == r * NB + b ? t : mine;
-    }
+  const float mine = gemv_reduce(acc, lane);
   if (lane < RPW * NB && n0 + er < g.N && eb < g.B) {
-    float v = mine * spre + (g.bias ? bpre : 0.f);
-    v = g.act == ACT_GELU_NEW ? gelu_new_rn(v) : act_apply(g.act, v);
+    const float v = gemv_out(g, mine, 1.f, bpre);
     // publish as one 8-byte {value, tag} granule (sc1: write-through, L2-served for the polling consumer on any XCD); the
     // tag's two scalars are read here, at the end: nothing in front of the weight requests waits for them
     const unsigned tag = ((unsigned)prefix[1] << 12) | (unsigned)(len[0] + 1);
@@ -1301,18 +1197,7 @@ __device__ __forceinline__ void fused_attn_part(const unsigned long long* __rest
   float m = -INFINITY, l = 0.f, acc[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-  // score of one cached key row for this slot (the LPK lanes of the key hold VEC dims each; DPP sums them: quad swaps,
-  // half-row mirror, row mirror - no LDS crossbar trips)
-  auto score = [&](const CacheVec<TC>& kk) {
-    float sc = 0.f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) sc = fmaf(qr[i], kk.get(i), sc);
-    sc = dpp_add<0xB1>(sc);
-    sc = dpp_add<0x4E>(sc);
-    sc = dpp_add<0x141>(sc);
-    if (LPK == 16) sc = dpp_add<0x140>(sc);
-    return sc;
-  };
+  auto score = [&](const CacheVec<TC>& kk) { return attn_score<LPK>(qr, kk); };  // itts_attn_dev.h; the lambda stays
   // (e) the register window in two phases, as torch.softmax does it: all scores, their maximum, then one exp per key and
   //     the weighted sum - half the VALU work of a per-key online update (no rescale of the accumulator per key), and the
   //     16 waves of a workgroup share 4 SIMDs, so this phase is issue-bound.  The row appended by this step (j == pos)
@@ -1358,16 +1243,7 @@ __device__ __forceinline__ void fused_attn_part(const unsigned long long* __rest
   }
   // online update for rows beyond the window (never the appended row when it lies inside the window)
   auto consume = [&](const CacheVec<TC>& kk, const CacheVec<TC>& vv, int j) {
-    const bool ok = j < S && j >= ks && j != pos;
-    float sc = score(kk);
-    sc = ok ? sc : -INFINITY;  // also discards whatever an out-of-range row produced
-    const float mn = fmaxf(m, sc);
-    const float corr = mn > -INFINITY ? __expf(m - mn) : 1.f;
-    const float p = ok ? __expf(sc - mn) : 0.f;
-    l = fmaf(l, corr, p);  // contraction pinned: same operation in every build of this loop (decode_pinned.h)
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, ok ? vv.get(i) : 0.f, acc[i] * corr);
-    m = mn;
+    attn_consume<LPK>(m, l, acc, qr, kk, vv, j < S && j >= ks && j != pos);
   };
   // sequences longer than the register-resident window: stream the rest two rows at a time
   for (int cb = 2 * NIT; (cb * NSPLIT + sp) * SLOTS < S; cb += SD) {  // chunk cb of this split = rows (cb*NSPLIT+sp)*SLOTS ..
@@ -1382,33 +1258,19 @@ __device__ __forceinline__ void fused_attn_part(const unsigned long long* __rest
     for (int u = 0; u < SD; ++u) consume(k2[u], v2[u], ((cb + u) * NSPLIT + sp) * SLOTS + slot);
   }
   // merge the 64/LPK key slots of this wave (lanes with equal `sub`)
-  // merge across the wave without the LDS crossbar: lane ^ 8 is a DPP rotate inside the 16-lane row; lane ^ 16 and
-  // lane ^ 32 are v_permlane16_swap / v_permlane32_swap (CDNA4), which hand every lane BOTH partners' values
-  // (tools/probe_permlane.hip prints the lane maps) - a sum or max of the two results is the butterfly step
-  auto bfly_max = [&](float x, int o) {
-    if (o == 8) return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true)));
-    const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
-                            : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  };
-  auto bfly_sum = [&](float x, int o) {
-    if (o == 8) return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true));
-    const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
-                            : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  };
+  // (wave_bfly_max / wave_bfly_sum, itts_wave_dev.h: no LDS crossbar)
   float M = m;
 #pragma unroll
-  for (int o = LPK; o < 64; o <<= 1) M = bfly_max(M, o);
+  for (int o = LPK; o < 64; o <<= 1) M = wave_bfly_max(M, o);
   const float sc0 = M > -INFINITY ? __expf(m - M) : 0.f;
   l *= sc0;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc[i] *= sc0;
 #pragma unroll
   for (int o = LPK; o < 64; o <<= 1) {
-    l = bfly_sum(l, o);
+    l = wave_bfly_sum(l, o);
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = bfly_sum(acc[i], o);
+    for (int i = 0; i < VEC; ++i) acc[i] = wave_bfly_sum(acc[i], o);
   }
   if (lane < LPK)
 #pragma unroll
@@ -1629,26 +1491,7 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
     }
   }
   __syncthreads();
-  // bitonic sort in LDS by ONE wave (64 lanes = the BEAM_MAX_CAND / 2 comparators of a stage; a wave's LDS operations execute in
-  // program order, so the 28 stages need no workgroup barrier): descending score, ascending index on ties
-  static_assert(BEAM_MAX_CAND == 128, "one comparator per lane");
-  if (tid < 64) {
-    for (int kq = 2; kq <= BEAM_MAX_CAND; kq <<= 1)
-      for (int j = kq >> 1; j > 0; j >>= 1) {
-        const int lo = ((lane & ~(j - 1)) << 1) | (lane & (j - 1)), hi = lo | j;
-        const bool up = (lo & kq) == 0;
-        const float v0 = cval[lo], v1 = cval[hi];
-        const int i0 = cidx[lo], i1 = cidx[hi];
-        const bool second_first = v1 > v0 || (v1 == v0 && i1 < i0);
-        if (second_first == up) {
-          cval[lo] = v1;
-          cval[hi] = v0;
-          cidx[lo] = i1;
-          cidx[hi] = i0;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      }
-  }
+  if (tid < 64) sort_cands_wave<true>(cval, cidx, lane);  // one wave, no barrier: descending score, ascending index on ties
   __syncthreads();
   if (tid < 64) {
     // wave 0: the exponentials and quotients in parallel (lane r and r + 64 of the sorted candidates), the running sums

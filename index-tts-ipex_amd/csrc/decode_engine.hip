@@ -45,6 +45,7 @@
 
 #include "itts_decode.h"
 #include "itts_engine_kernel.h"
+#include "itts_attn_dev.h"
 #include "itts_sampler_dev.h"
 #include "itts_wave_dev.h"
 #include "decode_pinned.h"
@@ -877,15 +878,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       float m = -INFINITY, lsum = 0.f, acc[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      auto score = [&](const V8<bf16_t>& kk) {
-        float sc = 0.f;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) sc = fmaf(qr[i], kk.get(i), sc);
-        sc = dpp_add<0xB1>(sc);
-        sc = dpp_add<0x4E>(sc);
-        sc = dpp_add<0x141>(sc);
-        return sc;
-      };
+      auto score = [&](const V8<bf16_t>& kk) { return attn_score<LPK>(qr, kk); };  // itts_attn_dev.h; the lambda stays
       {
         float sc[2 * NIT + 1];
 #pragma unroll
@@ -926,16 +919,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         }
       }
       auto consume = [&](const V8<bf16_t>& kk, const V8<bf16_t>& vv, int j) {
-        const bool ok = j < S && j >= ks && j != pos;
-        float sc = score(kk);
-        sc = ok ? sc : -INFINITY;
-        const float mn = fmaxf(m, sc);
-        const float corr = mn > -INFINITY ? __expf(m - mn) : 1.f;
-        const float p = ok ? __expf(sc - mn) : 0.f;
-        lsum = fmaf(lsum, corr, p);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, ok ? vv.get(i) : 0.f, acc[i] * corr);
-        m = mn;
+        attn_consume<LPK>(m, lsum, acc, qr, kk, vv, j < S && j >= ks && j != pos);
       };
       for (int cb = 2 * NIT; (cb * NSPLIT + sp) * SLOTS < S; cb += SD) {
         V8<bf16_t> k2[SD], v2[SD];
@@ -948,30 +932,18 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
 #pragma unroll
         for (int u = 0; u < SD; ++u) consume(k2[u], v2[u], ((cb + u) * NSPLIT + sp) * SLOTS + slot);
       }
-      auto bfly_max = [&](float x, int o) {
-        if (o == 8) return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true)));
-        const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
-                                : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-      };
-      auto bfly_sum = [&](float x, int o) {
-        if (o == 8) return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true));
-        const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
-                                : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-      };
       float M = m;
 #pragma unroll
-      for (int o = LPK; o < 64; o <<= 1) M = bfly_max(M, o);
+      for (int o = LPK; o < 64; o <<= 1) M = wave_bfly_max(M, o);
       const float sc0 = M > -INFINITY ? __expf(m - M) : 0.f;
       lsum *= sc0;
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] *= sc0;
 #pragma unroll
       for (int o = LPK; o < 64; o <<= 1) {
-        lsum = bfly_sum(lsum, o);
+        lsum = wave_bfly_sum(lsum, o);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = bfly_sum(acc[i], o);
+        for (int i = 0; i < VEC; ++i) acc[i] = wave_bfly_sum(acc[i], o);
       }
       if (ll < LPK)
 #pragma unroll

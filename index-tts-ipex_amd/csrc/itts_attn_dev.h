@@ -1,0 +1,45 @@
+// The per-key arithmetic of the single-query cache attention, ONE definition for the three kernels that must agree bit for bit:
+// decode_attn2_kernel and the attention part of qkv_attn_fused_kernel (decode2.hip, the launch path) and phase P2 of
+// decode_engine_kernel (decode_engine.hip) - tests/test_gpu_engine_persistent.py and tests/test_gpu_fullsize.py compare them.
+// Every kernel keeps its own skeleton (shared memory, the order of its loads, how it obtains this step's q / k / v, its waits
+// and stamps, where the result goes) and calls these through a one-line lambda of its own: that is the form in which the three
+// kernels stay instruction-identical to their hand-written text (the window softmax and the merges are
+// still written out per kernel, section 7 says why).
+//
+// Thread <-> key mapping: LPK lanes share one key row (VEC dims each).  KV is the register fragment of one row (CacheVec<> or
+// V8<>: get(i)).
+#pragma once
+#include "itts_wave_dev.h"
+
+namespace itts {
+
+// score of one key row for this slot (the LPK lanes of the key hold VEC dims each; DPP sums them: quad swaps, half-row mirror, row
+// mirror - no LDS crossbar trips)
+template <int LPK, int VEC, typename KV>
+__device__ __forceinline__ float attn_score(const float (&qr)[VEC], const KV& kk) {
+  float sc = 0.f;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) sc = fmaf(qr[i], kk.get(i), sc);
+  sc = dpp_add<0xB1>(sc);
+  sc = dpp_add<0x4E>(sc);
+  sc = dpp_add<0x141>(sc);
+  if (LPK == 16) sc = dpp_add<0x140>(sc);
+  return sc;
+}
+
+// online update for a row beyond the window (ok: inside the sequence and not the appended row)
+template <int LPK, int VEC, typename KV>
+__device__ __forceinline__ void attn_consume(float& m, float& l, float (&acc)[VEC], const float (&qr)[VEC], const KV& kk, const KV& vv,
+                                             bool ok) {
+  float sc = attn_score<LPK>(qr, kk);
+  sc = ok ? sc : -INFINITY;  // also discards whatever an out-of-range row produced
+  const float mn = fmaxf(m, sc);
+  const float corr = mn > -INFINITY ? __expf(m - mn) : 1.f;
+  const float p = ok ? __expf(sc - mn) : 0.f;
+  l = fmaf(l, corr, p);  // contraction pinned: same operation in every build of this loop (decode_pinned.h)
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, ok ? vv.get(i) : 0.f, acc[i] * corr);
+  m = mn;
+}
+
+}  // namespace itts

@@ -1,5 +1,6 @@
 // Device-side bookkeeping shared by the sampler kernels (decode2.hip) and the persistent decode engine's in-launch greedy
 // sampler (decode_engine.hip): HF greedy search / sample() commit of one token per row + the next step's input embedding.
+// sampler_sample_kernel (decode2.hip) and beam_cand_kernel (beam.hip) share sort_cands_wave: one order, one tie rule.
 #pragma once
 #include "itts_decode.h"
 
@@ -48,6 +49,30 @@ __device__ __forceinline__ void sampler_next_embedding(const SamplerArgs& a, int
       a.h_next[(size_t)b * a.D + i] = v;
     }
   }
+}
+
+// bitonic sort of BEAM_MAX_CAND (value, index) pairs in LDS by ONE wave (lanes 0..63 = the BEAM_MAX_CAND / 2 comparators of a stage): a
+// wave's LDS operations execute in program order, so the 28 stages need no workgroup barrier (at 16 waves each barrier
+// costs ~0.4 us and the block form spent 11 us per sort); the fence only pins the compiler's order.
+// BY_SCORE: descending value, ascending index on ties; else ascending index.
+template <bool BY_SCORE>
+__device__ __forceinline__ void sort_cands_wave(float* cv, int* ci, int lane) {
+  static_assert(BEAM_MAX_CAND == 128, "one comparator per lane");
+  for (int kq = 2; kq <= BEAM_MAX_CAND; kq <<= 1)
+    for (int j = kq >> 1; j > 0; j >>= 1) {
+      const int lo = ((lane & ~(j - 1)) << 1) | (lane & (j - 1)), hi = lo | j;
+      const bool up = (lo & kq) == 0;
+      const float v0 = cv[lo], v1 = cv[hi];
+      const int i0 = ci[lo], i1 = ci[hi];
+      const bool second_first = BY_SCORE ? (v1 > v0 || (v1 == v0 && i1 < i0)) : (i1 < i0);
+      if (second_first == up) {
+        cv[lo] = v1;
+        cv[hi] = v0;
+        ci[lo] = i1;
+        ci[hi] = i0;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
 }
 
 }  // namespace itts

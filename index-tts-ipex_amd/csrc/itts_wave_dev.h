@@ -1,7 +1,8 @@
 // Wave-level device helpers shared by kernels that must produce the same bits as each other: the launch path's decode GEMVs
-// and attention (decode2.hip) and the persistent decode engine (decode_engine.hip) reduce with the same tree and pack with the
-// same rounding because both include this file; the single-beam sampler (decode2.hip) and the beam kernels (beam.hip) share
-// the top-k primitives.
+// and attention (decode2.hip) and the persistent decode engine (decode_engine.hip) reduce with the same tree, the same slot
+// butterflies (wave_bfly_max / wave_bfly_sum: decode_attn2_kernel, qkv_attn_fused_kernel, the engine's attention phase) and pack
+// with the same rounding because both include this file; the single-beam sampler (decode2.hip) and the beam kernels (beam.hip)
+// share the top-k primitives (order_key, hist_add_wave).
 #pragma once
 #include "itts_common.h"
 
@@ -47,6 +48,22 @@ __device__ __forceinline__ float wave_sum_rl(float v) {
 __device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
   half2_t v = {(bf16_t)a, (bf16_t)b};
   return __builtin_bit_cast(uint32_t, v);
+}
+
+// butterfly step of a reduction over the lanes lane ^ o, o = 8, 16, 32, without the LDS crossbar: lane ^ 8 is a DPP rotate
+// inside the 16-lane row; lane ^ 16 and lane ^ 32 are v_permlane16_swap / v_permlane32_swap (CDNA4), which hand every lane BOTH
+// partners' values (tools/probe_permlane.hip prints the lane maps) - a sum or max of the two results is the butterfly step
+__device__ __forceinline__ float wave_bfly_max(float x, int o) {
+  if (o == 8) return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true)));
+  const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
+                          : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float wave_bfly_sum(float x, int o) {
+  if (o == 8) return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true));
+  const u32x2 r = o == 16 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false)
+                          : __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
 // order-preserving key of a score: larger float <=> larger unsigned
