@@ -115,6 +115,24 @@ struct DvaeW {
   const float* codebook_sq = nullptr;
 };
 
+// What a captured decode step has baked into its nodes: the graph is replayed only while this compares equal.
+// Everything SamplerArgs carries by value is baked into the captured nodes: max_gen is the ids row stride and the
+// `k < max_gen` bound, so a per-request max_mel_tokens must re-capture (same B / Smax notwithstanding).
+// Whatever SamplerArgs, BeamArgs or EngArgs come to carry by value belongs here (and in Engine::graph_key()).
+struct GraphKey {
+  int B = 0, Smax = 0, max_gen = 0, use_forced = 0, input_n = 0, host_sample = 0;
+  int fuse = 0, eng = 0;  // derived: fuse && !fuse_failed, engine_usable()
+  int nb = 1, beam_sample = 1, suppress_stop = 0, do_sample = 0, top_k = 0;
+  float length_penalty = 0.f, typical_mass = 0.f, penalty = 0.f, top_p = 1.f, temperature = 1.f;  // compared as floats: a NaN re-captures
+  bool operator==(const GraphKey& o) const {
+    return B == o.B && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
+           host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample &&
+           length_penalty == o.length_penalty && typical_mass == o.typical_mass && penalty == o.penalty &&
+           suppress_stop == o.suppress_stop && do_sample == o.do_sample && top_k == o.top_k && top_p == o.top_p &&
+           temperature == o.temperature;
+  }
+};
+
 struct DecodeState {
   int B = 0, Smax = 0, prefix = 0, max_gen = 0;
   size_t cache_bytes = 0;
@@ -131,16 +149,23 @@ struct DecodeState {
   float penalty = 1.f;
   int suppress_stop = 0;
   hipGraphExec_t graph = nullptr, graphK = nullptr;  // one decode step / ITTS_GRAPH_STEPS (8) steps per launch
-  int graph_B = 0, graph_Smax = 0, graph_suppress = 0, graph_max_gen = 0;
+  GraphKey graph_key;                                // what they were captured with
+  void drop_graphs() {                               // (the caller synchronises the stream first where a replay may be in flight)
+    for (hipGraphExec_t* ge : {&graph, &graphK})
+      if (*ge) {
+        (void)hipGraphExecDestroy(*ge);
+        *ge = nullptr;
+      }
+  }
   // multinomial sampling (itts_gpt_set_sampling): parameters baked into the captured step, uniforms [max_gen][B]
-  int do_sample = 0, top_k = 0, graph_sample = 0, graph_top_k = 0;
-  float top_p = 1.f, temperature = 1.f, graph_top_p = 1.f, graph_temperature = 1.f;
+  int do_sample = 0, top_k = 0;
+  float top_p = 1.f, temperature = 1.f;
   float* uniforms = nullptr;
   size_t uniforms_cap = 0;
   // beam-sample (itts_gpt_set_beam_sample): B = batch items * nb rows; state of beam.hip
-  int nb = 1, graph_nb = 1;          // beams per batch item (1 = off)
-  int beam_sample = 1, graph_beam_sample = 1;  // 1: beam_sample (draws), 0: beam_search (deterministic top-2nb)
-  float length_penalty = 0.f, graph_length_penalty = 0.f;
+  int nb = 1;                         // beams per batch item (1 = off)
+  int beam_sample = 1;                // 1: beam_sample (draws), 0: beam_search (deterministic top-2nb)
+  float length_penalty = 0.f;
   int* beam_ids = nullptr;           // [2][B][max_gen]
   uint8_t* anc = nullptr;            // [2][B][Smax]
   float* beam_scores = nullptr;      // [B]
@@ -154,7 +179,7 @@ struct DecodeState {
   unsigned long long* gran = nullptr;  // [layers][cap_B <= 4][3 * D]
   int* fuse_err = nullptr;
   int fuse_failed = 0;                 // a hand-off timed out: two launches from then on
-  int fuse = 0, graph_fuse = 0;        // opt-in (ITTS_FUSE_QKV_ATTN=1 / debug bit 3): measured 1.5 % slower than two launches; 0 again after a hand-off timeout
+  int fuse = 0;                        // opt-in (ITTS_FUSE_QKV_ATTN=1 / debug bit 3): measured 1.5 % slower than two launches; 0 again after a hand-off timeout
   // persistent decode engine (decode_engine.hip): the step as one launch, <= 6 rows (beam rows included), bf16 weights - or,
   // opt-in (eng_fp8 / ITTS_ENGINE_FP8), the fp8 copies of every projection and the head (bf16 build only)
   unsigned long long* eng_gran = nullptr;
@@ -163,16 +188,14 @@ struct DecodeState {
   int eng_force = 0;                     // debug bit 5: use the engine whatever ITTS_ENGINE / the default says
   int eng_failed = 0;                    // a hand-off timed out: launch path from then on
   int eng_fp8 = 0;                       // itts_gpt_set_engine_fp8: a model with fp8 GPT weights may use the engine (sticky; default: launch path)
-  int graph_eng = 0;
   int graph_mode = 0;                    // last_mode of the captured step
-  float typical_mass = 0.f, graph_typical = 0.f;  // TypicalLogitsWarper pre-pass (0 = off)
+  float typical_mass = 0.f;                        // TypicalLogitsWarper pre-pass (0 = off)
   float* scores2 = nullptr;                        // [cap_B][V] its output
   int* forced = nullptr;  // [cap_B][cap_gen] forced token per (row, step) or -1; allocated with ids
-  int use_forced = 0, graph_forced = 0;
-  int host_sample = 0, graph_host_sample = 0;  // the caller picks every token (itts_gpt_commit): the step stops behind the head
-  int input_n = 0, graph_input_n = 0;  // forced steps that are HF input_tokens (positions k + 1 instead of k + 2)
+  int use_forced = 0;
+  int host_sample = 0;  // the caller picks every token (itts_gpt_commit): the step stops behind the head
+  int input_n = 0;      // forced steps that are HF input_tokens (positions k + 1 instead of k + 2)
   int last_mode = 0;                   // 1: the last captured / launched decode step ran on the persistent engine
-  float graph_penalty = 0.f;
   bool active = false;
 };
 
@@ -283,6 +306,9 @@ struct Engine {
   // internals
   int gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, bool write_cache, hipStream_t s);
   int decode_step_launch(hipStream_t s);
+  GraphKey graph_key() const;
+  EngArgs engine_args(int& eng_first, bool& fold_head, bool& fold_samp) const;
+  bool rows_on_mfma(int B) const;  // the batched decode step: weights streamed once, batch on MFMA
   bool engine_usable() const;
   bool engine_fp8_model() const;  // every projection of every block and the head carry an fp8 copy + row scales
   int ensure_engine_state(hipStream_t s);

@@ -133,6 +133,10 @@ static int dev_alloc(void** p, size_t bytes) {
 
 // The batched decode step (B > 4, bf16) streams its weights from fragment-tiled copies (wtile_off): made once per loaded
 // checkpoint, on the first batched generation (+ 2 bytes per GPT weight; ITTS_NO_TILED_W=1 keeps the row-major stream).
+bool Engine::rows_on_mfma(int B) const {
+  const int D = cfg.model_dim;
+  return adt == BF16 && B > 4 && D % 32 == 0 && D <= 2048;
+}
 int Engine::ensure_decode_tiles(hipStream_t s) {
   static const bool off = getenv("ITTS_NO_TILED_W") != nullptr;
   if (gpt_tiles || off || !gpt.ok) return OK;
@@ -234,16 +238,12 @@ int Engine::ensure_decode_state(int B, int Smax, int max_gen, hipStream_t s) {
   const itts_config& c = cfg;
   const int D = c.model_dim, H = c.heads, dh = D / H, V = c.number_mel_codes;
   DecodeState& d = ds;
-  if (adt == BF16 && B > 4 && D % 32 == 0 && D <= 2048) ITTS_TRY(ensure_decode_tiles(s));
+  if (rows_on_mfma(B)) ITTS_TRY(ensure_decode_tiles(s));
   const size_t need = (size_t)c.layers * B * H * Smax * dh * es;
   const bool regrow = B > d.cap_B || max_gen > d.cap_gen;
   if (need > d.cache_bytes || regrow || B != d.B || Smax != d.Smax) {
     ITTS_HIP_CHECK(hipStreamSynchronize(s));
-    for (hipGraphExec_t* ge : {&d.graph, &d.graphK})
-      if (*ge) {
-        (void)hipGraphExecDestroy(*ge);
-        *ge = nullptr;
-      }
+    d.drop_graphs();
   }
   if (need > d.cache_bytes) {
     ITTS_TRY(dev_alloc(&d.kc, need));
@@ -295,11 +295,7 @@ int Engine::ensure_beam_state(int rows, int max_gen, int Smax, hipStream_t s) {
   DecodeState& d = ds;
   if (rows <= d.beam_rows && max_gen <= d.beam_gen && Smax <= d.beam_smax && d.beam_ids) return OK;
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
-  for (hipGraphExec_t* ge : {&d.graph, &d.graphK})  // captured nodes hold the old pointers
-    if (*ge) {
-      (void)hipGraphExecDestroy(*ge);
-      *ge = nullptr;
-    }
+  d.drop_graphs();  // captured nodes hold the old pointers
   const int r = std::max(rows, d.beam_rows), g = std::max(max_gen, d.beam_gen), sm = std::max(Smax, d.beam_smax);
   ITTS_TRY(dev_alloc((void**)&d.beam_ids, (size_t)2 * r * g * 4));
   ITTS_TRY(dev_alloc((void**)&d.anc, (size_t)2 * r * sm));
@@ -486,11 +482,7 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
                  "gpt_prefill: sampling enabled but fewer uniforms than max_gen * B (* 2 * num_beams) were supplied");
     if (need_u > ds.uniforms_cap) {
       ITTS_HIP_CHECK(hipStreamSynchronize(s));
-      for (hipGraphExec_t* ge : {&ds.graph, &ds.graphK})  // the captured samplers hold the old pointer
-        if (*ge) {
-          (void)hipGraphExecDestroy(*ge);
-          *ge = nullptr;
-        }
+      ds.drop_graphs();  // the captured samplers hold the old pointer
       ITTS_TRY(dev_alloc((void**)&ds.uniforms, need_u * 4));
       ds.uniforms_cap = need_u;
     }
@@ -589,7 +581,7 @@ int Engine::head_and_sample(hipStream_t s, bool have_logits, bool sampled) {
   g.ln_beta = gpt.ln_f.b;
   g.ln2_gamma = nullptr;  // final_norm's affine is folded into mel_head by the packer
   g.ln2_beta = nullptr;
-  if (adt == BF16 && B > 4 && D % 32 == 0 && D <= 2048) {
+  if (rows_on_mfma(B)) {
     // batched decode: ln_f -> final_norm as a row kernel (bf16), head on the matrix cores
     ITTS_TRY(ln_rows_bf16(ds.hn, ds.h, gpt.ln_f.g, gpt.ln_f.b, B, D, 1e-5f, 2, ds.partial, ds.pend_split, ds.pend_bias, 1, s));
     ds.pend_split = 0;
@@ -745,6 +737,120 @@ SamplerArgs Engine::greedy_sampler_args(const float* lg_in, bool typical) const 
   return sa;
 }
 
+// arguments of the persistent decode engine's launch (decode_engine_layers) from the decode state.  eng_first: the blocks
+// [0, eng_first) run on the engine; fold_head / fold_samp: the head / the greedy sampler run inside the same launch
+EngArgs Engine::engine_args(int& eng_first, bool& fold_head, bool& fold_samp) const {
+  const itts_config& c = cfg;
+  const int dh = c.model_dim / c.heads, B = ds.B;
+  EngArgs ea;
+  const bool w8 = gpt.layers[0].attn.w8 != nullptr;  // engine_usable(): then every projection and the head carry an fp8 copy
+  ea.w8 = w8;
+  for (int l = 0; l < c.layers; ++l) {
+    const GptLayerW& L = gpt.layers[l];
+    if (w8) {
+      ea.L[l] = {(const bf16_t*)L.attn.w8, (const bf16_t*)L.proj.w8, (const bf16_t*)L.fc.w8, (const bf16_t*)L.proj2.w8,
+                 L.attn.b, L.proj.b, L.fc.b, L.proj2.b};
+      ea.S[l] = {L.attn.wscale, L.proj.wscale, L.fc.wscale, L.proj2.wscale};
+    } else {
+      ea.L[l] = {(const bf16_t*)L.attn.w, (const bf16_t*)L.proj.w, (const bf16_t*)L.fc.w, (const bf16_t*)L.proj2.w,
+                 L.attn.b, L.proj.b, L.fc.b, L.proj2.b};
+    }
+  }
+  ea.gran = ds.eng_gran;
+  ea.h = ds.h;
+  ea.kc = (bf16_t*)ds.kc;
+  ea.vc = (bf16_t*)ds.vc;
+  ea.len = ds.len;
+  ea.kv_start = ds.kv_start;
+  ea.prefix = ds.prefix_dev;
+  ea.ctr = ds.eng_ctr;
+  ea.anc = ds.nb > 1 ? ds.anc : nullptr;  // beam rows gather their keys through the ancestry table (no cache re-ordering)
+  ea.nb = ds.nb;
+  // ITTS_ENGINE_LAYERS=n (debugging aid): blocks [0, n) on the engine, the rest as launches
+  static const int e_nl = getenv("ITTS_ENGINE_LAYERS") ? atoi(getenv("ITTS_ENGINE_LAYERS")) : -1;
+  eng_first = e_nl >= 0 && e_nl < c.layers ? e_nl : c.layers;
+  ea.NL = eng_first;
+  ea.B = B;
+  ea.Smax = ds.Smax;
+  ea.scale = 1.f / std::sqrt((float)dh);
+  static const int e_tap = getenv("ITTS_TAP_LAYER") ? atoi(getenv("ITTS_TAP_LAYER")) : -1;
+  if (debug && e_tap >= 0 && e_tap < eng_first && !dry) {  // debugging aid: the engine's view of one block's edges
+    ea.dbg = ds.act;  // [16][4D] fp32 scratch of the launch path, unused by the engine: room for the 9 B D floats of the dump
+    ea.dbg_layer = e_tap;
+  }
+  // gather pacing (s_sleep units of 64 clocks): a publish needs ~0.4 us to become visible; earlier passes fail AND slow the
+  // stores down.  Defaults from tools/eng_pacing_rows.sh (profiles/r03_engine_pacing_sweep.txt): 14 / 16 at <= 2 rows, 12 / 8
+  // at 3 - 4 rows, 12 / 4 at 5 - 6 (more granules per pass: the first pass itself takes longer)
+  static const int e_fd_env = getenv("ITTS_ENGINE_FIRST_DELAY") ? atoi(getenv("ITTS_ENGINE_FIRST_DELAY")) : -1;
+  static const int e_ad_env = getenv("ITTS_ENGINE_ACT_DELAY") ? atoi(getenv("ITTS_ENGINE_ACT_DELAY")) : -1;
+  const int e_fd = e_fd_env >= 0 ? e_fd_env : (B <= 2 ? 14 : 12);
+  const int e_ad = e_ad_env >= 0 ? e_ad_env : (B <= 2 ? 16 : B <= 4 ? 8 : 4);
+  static const int e_ps = getenv("ITTS_ENGINE_PASS_SLEEP") ? atoi(getenv("ITTS_ENGINE_PASS_SLEEP")) : 1;
+  static const int e_thin = getenv("ITTS_ENGINE_THIN_FC") ? atoi(getenv("ITTS_ENGINE_THIN_FC")) : 0;
+  ea.thin_fc = e_thin;
+  static const int e_early = getenv("ITTS_ENGINE_EARLY_FC") ? atoi(getenv("ITTS_ENGINE_EARLY_FC")) : -1;
+  ea.early_fc = e_early >= 0 ? e_early : 74;  // tools/ab_early.sh, tools/eng_pacing_rows.sh (profiles/r03_engine_early_fc.txt)
+  ea.first_delay = e_fd;
+  static const int e_fake = getenv("ITTS_ENG_FAKE_DIV") ? atoi(getenv("ITTS_ENG_FAKE_DIV")) : 1;
+  ea.fake_div = e_fake < 1 ? 1 : e_fake;
+  static const int e_ekv = getenv("ITTS_ENGINE_EARLY_KV") ? atoi(getenv("ITTS_ENGINE_EARLY_KV")) : 1;
+  ea.early_kv = e_ekv;
+  static const int e_cd = getenv("ITTS_ENGINE_CTX_DELAY") ? atoi(getenv("ITTS_ENGINE_CTX_DELAY")) : 0;
+  ea.ctx_delay = e_cd;
+  ea.act_delay = e_ad;
+  ea.pass_sleep = e_ps;
+  if (const char* tt = getenv("ITTS_ENGINE_TIMEOUT_TICKS")) ea.timeout_ticks = (unsigned)atol(tt);  // tests: force the give-up path (read per call)
+  static const bool e_stamps = getenv("ITTS_ENGINE_STAMPS") != nullptr;
+  if (debug && e_stamps && !dry) ea.stamp = (unsigned*)ds.scores2;  // [16][V] fp32 scratch of the typical filter (off in this mode) >= 256 * 24 * 16 words
+  // the head (ln_f -> final_norm -> mel_head) inside the same launch when the engine runs every block (ITTS_ENGINE_HEAD=0: own launch)
+  // (read per call - i.e. whenever an engine object captures its step -, so one process can compare both forms on fresh engine objects)
+  const char* e_head_env = getenv("ITTS_ENGINE_HEAD");
+  const bool e_head = !(e_head_env && atoi(e_head_env) == 0);
+  fold_head = e_head && eng_first == c.layers && gpt.head.dt == BF16 && (gpt.head.w8 != nullptr) == w8 && gpt.head.b && gpt.head.Cin == ENG_D &&
+              gpt.ln_f.g && gpt.ln_f.b && (c.number_mel_codes + ENG_NCU - 1) / ENG_NCU <= 33;
+  // ... and the greedy sampler behind it (ITTS_ENGINE_SAMPLER=0: own launch): plain greedy search only - sampling, beams,
+  // typical filtering and host-side sampling keep their kernels
+  static const bool e_samp = !(getenv("ITTS_ENGINE_SAMPLER") && atoi(getenv("ITTS_ENGINE_SAMPLER")) == 0);
+  fold_samp = fold_head && e_samp && !ds.do_sample && ds.nb == 1 && !ds.host_sample && !(ds.typical_mass > 0.f);
+  if (fold_samp) {
+    ea.fold_sampler = 1;
+    ea.samp = greedy_sampler_args(ds.logits, false);
+    ea.cand = ds.eng_gran + eng_gran_count(c.layers) - ENG_CAND_WORDS;
+  }
+  if (fold_head) {
+    ea.head_w = (const bf16_t*)(w8 ? gpt.head.w8 : gpt.head.w);
+    ea.head_s = w8 ? gpt.head.wscale : nullptr;
+    ea.head_b = gpt.head.b;
+    ea.lnf_g = gpt.ln_f.g;
+    ea.lnf_b = gpt.ln_f.b;
+    ea.logits = ds.logits;
+    ea.V = c.number_mel_codes;
+  }
+  return ea;
+}
+
+// a projection's GEMV arguments from its Lin; the call site adds X / Y, the prologue, the activation and the activation formats
+static GemvArgs lin_gemv(const Lin& w, int B) {
+  GemvArgs g;
+  g.B = B;
+  g.W = w.w;
+  g.bias = w.b;
+  g.N = g.ldy = w.N;
+  g.K = w.Cin;
+  g.w8src = w.w8 ? &w : nullptr;
+  g.Wt = w.wt;
+  return g;
+}
+
+// fp8 copy of the projection (BASELINE config 5) in place of W: the same weight bytes on every path (decode only; prefill /
+// latent use the bf16 dequantisation of it), fragment-tiled for skinny_mfma
+static void attach_fp8(GemvArgs& g, bool tiled) {
+  if (!g.w8src) return;
+  g.W8 = g.w8src->w8;
+  g.wscale = g.w8src->wscale;
+  if (tiled) g.W8t = g.w8src->wt8;
+}
+
 // one decode step: 24 x {LN+QKV gemv, cache attention (+append), proj gemv (+res),
 // LN+FC gemv (gelu), proj2 gemv (+res)} -> head.  Every length / position is read from device memory, so the
 // captured graph is identical for every step and every prefix length.
@@ -753,97 +859,15 @@ int Engine::decode_step_launch(hipStream_t s) {
   const int D = c.model_dim, H = c.heads, dh = D / H, B = ds.B;
   // ds.h already holds mel_emb[tok] + mel_pos[...] of this step (written by the previous step's sampler)
   const bool fast = adt == BF16 && B <= 4;  // bf16 activations between the decode kernels (ctx, act)
-  const bool skinny = adt == BF16 && B > 4 && D % 32 == 0 && D <= 2048;  // weights once, batch on MFMA
+  const bool skinny = rows_on_mfma(B);      // weights once, batch on MFMA
   ds.pend_split = 0;
   ds.last_mode = 0;
   int eng_first = 0;
   if (engine_usable()) {  // <= 6 rows: the 24 blocks (+ head, + greedy sampler) as ONE persistent launch
     ITTS_REQUIRE(ds.eng_gran && ds.eng_ctr, "decode engine: state not allocated (prefill first)");
-    EngArgs ea;
-    const bool w8 = gpt.layers[0].attn.w8 != nullptr;  // engine_usable(): then every projection and the head carry an fp8 copy
-    ea.w8 = w8;
-    for (int l = 0; l < c.layers; ++l) {
-      const GptLayerW& L = gpt.layers[l];
-      if (w8) {
-        ea.L[l] = {(const bf16_t*)L.attn.w8, (const bf16_t*)L.proj.w8, (const bf16_t*)L.fc.w8, (const bf16_t*)L.proj2.w8,
-                   L.attn.b, L.proj.b, L.fc.b, L.proj2.b};
-        ea.S[l] = {L.attn.wscale, L.proj.wscale, L.fc.wscale, L.proj2.wscale};
-      } else {
-        ea.L[l] = {(const bf16_t*)L.attn.w, (const bf16_t*)L.proj.w, (const bf16_t*)L.fc.w, (const bf16_t*)L.proj2.w,
-                   L.attn.b, L.proj.b, L.fc.b, L.proj2.b};
-      }
-    }
-    ea.gran = ds.eng_gran;
-    ea.h = ds.h;
-    ea.kc = (bf16_t*)ds.kc;
-    ea.vc = (bf16_t*)ds.vc;
-    ea.len = ds.len;
-    ea.kv_start = ds.kv_start;
-    ea.prefix = ds.prefix_dev;
-    ea.ctr = ds.eng_ctr;
-    ea.anc = ds.nb > 1 ? ds.anc : nullptr;  // beam rows gather their keys through the ancestry table (no cache re-ordering)
-    ea.nb = ds.nb;
-    // ITTS_ENGINE_LAYERS=n (debugging aid): blocks [0, n) on the engine, the rest as launches
-    static const int e_nl = getenv("ITTS_ENGINE_LAYERS") ? atoi(getenv("ITTS_ENGINE_LAYERS")) : -1;
-    eng_first = e_nl >= 0 && e_nl < c.layers ? e_nl : c.layers;
-    ea.NL = eng_first;
-    ea.B = B;
-    ea.Smax = ds.Smax;
-    ea.scale = 1.f / std::sqrt((float)dh);
-    static const int e_tap = getenv("ITTS_TAP_LAYER") ? atoi(getenv("ITTS_TAP_LAYER")) : -1;
-    if (debug && e_tap >= 0 && e_tap < eng_first && !dry) {  // debugging aid: the engine's view of one block's edges
-      ea.dbg = ds.act;  // [16][4D] fp32 scratch of the launch path, unused by the engine: room for the 9 B D floats of the dump
-      ea.dbg_layer = e_tap;
-    }
-    // gather pacing (s_sleep units of 64 clocks): a publish needs ~0.4 us to become visible; earlier passes fail AND slow the
-    // stores down.  Defaults from tools/eng_pacing_rows.sh (profiles/r03_engine_pacing_sweep.txt): 14 / 16 at <= 2 rows, 12 / 8
-    // at 3 - 4 rows, 12 / 4 at 5 - 6 (more granules per pass: the first pass itself takes longer)
-    static const int e_fd_env = getenv("ITTS_ENGINE_FIRST_DELAY") ? atoi(getenv("ITTS_ENGINE_FIRST_DELAY")) : -1;
-    static const int e_ad_env = getenv("ITTS_ENGINE_ACT_DELAY") ? atoi(getenv("ITTS_ENGINE_ACT_DELAY")) : -1;
-    const int e_fd = e_fd_env >= 0 ? e_fd_env : (B <= 2 ? 14 : 12);
-    const int e_ad = e_ad_env >= 0 ? e_ad_env : (B <= 2 ? 16 : B <= 4 ? 8 : 4);
-    static const int e_ps = getenv("ITTS_ENGINE_PASS_SLEEP") ? atoi(getenv("ITTS_ENGINE_PASS_SLEEP")) : 1;
-    static const int e_thin = getenv("ITTS_ENGINE_THIN_FC") ? atoi(getenv("ITTS_ENGINE_THIN_FC")) : 0;
-    ea.thin_fc = e_thin;
-    static const int e_early = getenv("ITTS_ENGINE_EARLY_FC") ? atoi(getenv("ITTS_ENGINE_EARLY_FC")) : -1;
-    ea.early_fc = e_early >= 0 ? e_early : 74;  // tools/ab_early.sh, tools/eng_pacing_rows.sh (profiles/r03_engine_early_fc.txt)
-    ea.first_delay = e_fd;
-    static const int e_fake = getenv("ITTS_ENG_FAKE_DIV") ? atoi(getenv("ITTS_ENG_FAKE_DIV")) : 1;
-    ea.fake_div = e_fake < 1 ? 1 : e_fake;
-    static const int e_ekv = getenv("ITTS_ENGINE_EARLY_KV") ? atoi(getenv("ITTS_ENGINE_EARLY_KV")) : 1;
-    ea.early_kv = e_ekv;
-    static const int e_cd = getenv("ITTS_ENGINE_CTX_DELAY") ? atoi(getenv("ITTS_ENGINE_CTX_DELAY")) : 0;
-    ea.ctx_delay = e_cd;
-    ea.act_delay = e_ad;
-    ea.pass_sleep = e_ps;
-    if (const char* tt = getenv("ITTS_ENGINE_TIMEOUT_TICKS")) ea.timeout_ticks = (unsigned)atol(tt);  // tests: force the give-up path (read per call)
-    static const bool e_stamps = getenv("ITTS_ENGINE_STAMPS") != nullptr;
-    if (debug && e_stamps && !dry) ea.stamp = (unsigned*)ds.scores2;  // [16][V] fp32 scratch of the typical filter (off in this mode) >= 256 * 24 * 16 words
+    bool fold_head = false, fold_samp = false;
+    const EngArgs ea = engine_args(eng_first, fold_head, fold_samp);
     ds.last_mode = eng_first > 0;
-    // the head (ln_f -> final_norm -> mel_head) inside the same launch when the engine runs every block (ITTS_ENGINE_HEAD=0: own launch)
-    // (read per call - i.e. whenever an engine object captures its step -, so one process can compare both forms on fresh engine objects)
-    const char* e_head_env = getenv("ITTS_ENGINE_HEAD");
-    const bool e_head = !(e_head_env && atoi(e_head_env) == 0);
-    const bool fold_head = e_head && eng_first == c.layers && gpt.head.dt == BF16 && (gpt.head.w8 != nullptr) == w8 && gpt.head.b && gpt.head.Cin == ENG_D &&
-                           gpt.ln_f.g && gpt.ln_f.b && (c.number_mel_codes + ENG_NCU - 1) / ENG_NCU <= 33;
-    // ... and the greedy sampler behind it (ITTS_ENGINE_SAMPLER=0: own launch): plain greedy search only - sampling, beams,
-    // typical filtering and host-side sampling keep their kernels
-    static const bool e_samp = !(getenv("ITTS_ENGINE_SAMPLER") && atoi(getenv("ITTS_ENGINE_SAMPLER")) == 0);
-    const bool fold_samp = fold_head && e_samp && !ds.do_sample && ds.nb == 1 && !ds.host_sample && !(ds.typical_mass > 0.f);
-    if (fold_samp) {
-      ea.fold_sampler = 1;
-      ea.samp = greedy_sampler_args(ds.logits, false);
-      ea.cand = ds.eng_gran + eng_gran_count(c.layers) - ENG_CAND_WORDS;
-    }
-    if (fold_head) {
-      ea.head_w = (const bf16_t*)(w8 ? gpt.head.w8 : gpt.head.w);
-      ea.head_s = w8 ? gpt.head.wscale : nullptr;
-      ea.head_b = gpt.head.b;
-      ea.lnf_g = gpt.ln_f.g;
-      ea.lnf_b = gpt.ln_f.b;
-      ea.logits = ds.logits;
-      ea.V = c.number_mel_codes;
-    }
     if (eng_first > 0) ITTS_TRY(decode_engine_layers(ea, s));
     if (ea.stamp) ITTS_TRY(tap("eng_stamps", ea.stamp, F32, (int64_t)ENG_NCU * eng_first * 16, s));
     if (ea.dbg) {
@@ -866,11 +890,7 @@ int Engine::decode_step_launch(hipStream_t s) {
         g.x_tiled = 1;
       }
       g.y_tiled = g.y_bf16;
-      if (g.w8src) {
-        g.W8 = g.w8src->w8;
-        g.wscale = g.w8src->wscale;
-        g.W8t = g.w8src->wt8;
-      }
+      attach_fp8(g, true);
       return skinny_mfma(g, s);
     }
     if (skinny) {
@@ -893,18 +913,11 @@ int Engine::decode_step_launch(hipStream_t s) {
       }
       g.x_tiled = 1;           // every bf16 activation of this path (hn, ctx, act) is fragment-tiled
       g.y_tiled = g.y_bf16;
-      if (g.w8src) {  // fp8 copy of this projection (BASELINE config 5): the same weight bytes the GEMV path streams
-        g.W8 = g.w8src->w8;
-        g.wscale = g.w8src->wscale;
-        g.W8t = g.w8src->wt8;
-      }
+      attach_fp8(g, true);
       return skinny_mfma(g, s);
     }
     if (fast && gemv_bf16_supported(g)) {
-      if (g.w8src) {  // fp8 copy of this projection (decode only; prefill / latent use the bf16 dequantisation of it)
-        g.W8 = g.w8src->w8;
-        g.wscale = g.w8src->wscale;
-      }
+      attach_fp8(g, false);
       return gemv_bf16(g, s);
     }
     ITTS_REQUIRE(!g.x_bf16 && !g.y_bf16, "decode: bf16 activation without the bf16 GEMV");
@@ -920,20 +933,12 @@ int Engine::decode_step_launch(hipStream_t s) {
   const bool bf_ctx = skinny || (fast && gemv_bf16_supported(probe));
   for (int l = eng_first; l < c.layers; ++l) {
     const GptLayerW& L = gpt.layers[l];
-    GemvArgs g;  // qkv = LN1(h) Wqkv + b
-    g.B = B;
+    GemvArgs g = lin_gemv(L.attn, B);  // qkv = LN1(h) Wqkv + b
     g.X = ds.h;
-    g.W = L.attn.w;
     g.Y = ds.qkv;
-    g.bias = L.attn.b;
-    g.N = 3 * D;
-    g.K = D;
-    g.ldy = 3 * D;
     g.prologue = 1;
     g.ln_gamma = L.ln1.g;
     g.ln_beta = L.ln1.b;
-    g.w8src = L.attn.w8 ? &L.attn : nullptr;
-    g.Wt = L.attn.wt;
     const size_t lo = (size_t)l * B * H * ds.Smax * dh * es;
     // few (row, head) pairs: the keys of each pair go to ATTN_NSPLIT workgroups and the projection merges the partials
     static const bool no_split = getenv("ITTS_ATTN_NOSPLIT") != nullptr;
@@ -958,16 +963,10 @@ int Engine::decode_step_launch(hipStream_t s) {
       ITTS_TRY(decode_attn2(ds.ctx, bf_ctx ? BF16 : F32, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start,
                             ds.prefix_dev, B, H, dh, ds.Smax, adt, s, skinny ? 1 : 0, nullptr, nullptr,
                             ds.nb > 1 ? ds.anc : nullptr, ds.nb));
-    GemvArgs p;  // h += ctx Wproj + b
-    p.B = B;
+    GemvArgs p = lin_gemv(L.proj, B);  // h += ctx Wproj + b
     p.X = ds.ctx;
     p.x_bf16 = bf_ctx;
-    p.W = L.proj.w;
     p.Y = ds.h;
-    p.bias = L.proj.b;
-    p.N = D;
-    p.K = D;
-    p.ldy = D;
     p.accumulate = 1;
     if (split) {
       p.prologue = 3;
@@ -975,41 +974,23 @@ int Engine::decode_step_launch(hipStream_t s) {
       p.attn_ml = ds.attn_ml;
       ITTS_REQUIRE(gemv_bf16_supported(p), "decode: split attention needs the bf16 GEMV with prologue 3");
     }
-    p.w8src = L.proj.w8 ? &L.proj : nullptr;
-    p.Wt = L.proj.wt;
     ITTS_TRY(run(p, L.proj.dt));
     if (l == l_tap) ITTS_TRY(tap("lp_h1", ds.h, F32, (int64_t)B * D, s));
-    GemvArgs f;  // act = gelu_new(LN2(h) Wfc + b)
-    f.B = B;
+    GemvArgs f = lin_gemv(L.fc, B);  // act = gelu_new(LN2(h) Wfc + b)
     f.X = ds.h;
-    f.W = L.fc.w;
     f.Y = ds.act;
     f.y_bf16 = bf_act;
-    f.bias = L.fc.b;
-    f.N = 4 * D;
-    f.K = D;
-    f.ldy = 4 * D;
     f.act = ACT_GELU_NEW;
     f.prologue = 1;
     f.ln_gamma = L.ln2.g;
     f.ln_beta = L.ln2.b;
-    f.w8src = L.fc.w8 ? &L.fc : nullptr;
-    f.Wt = L.fc.wt;
     ITTS_TRY(run(f, L.fc.dt));
     if (l == l_tap) ITTS_TRY(tap("lp_act", ds.act, bf_act ? BF16 : F32, (int64_t)B * 4 * D, s));
-    GemvArgs q;  // h += act Wproj2 + b
-    q.B = B;
+    GemvArgs q = lin_gemv(L.proj2, B);  // h += act Wproj2 + b
     q.X = ds.act;
     q.x_bf16 = bf_act;
-    q.W = L.proj2.w;
     q.Y = ds.h;
-    q.bias = L.proj2.b;
-    q.N = D;
-    q.K = 4 * D;
-    q.ldy = D;
     q.accumulate = 1;
-    q.w8src = L.proj2.w8 ? &L.proj2 : nullptr;
-    q.Wt = L.proj2.wt;
     ITTS_TRY(run(q, L.proj2.dt));
     if (l == l_tap) ITTS_TRY(tap("lp_h2", ds.h, F32, (int64_t)B * D, s));
   }
@@ -1078,37 +1059,15 @@ int Engine::gpt_commit(const int32_t* tokens_host, hipStream_t s) {
     ITTS_HIP_CHECK(hipMemcpyAsync(ds.forced + (size_t)b * ds.max_gen + lens[b], tokens_host + b, 4, hipMemcpyHostToDevice, s));
   }
   ITTS_HIP_CHECK(hipStreamSynchronize(s));  // tokens_host is the caller's buffer
-  const int keep = ds.host_sample, forced = ds.use_forced;
-  ds.host_sample = 0;
-  ds.use_forced = 1;
-  const float* lg = ds.logits;
-  (void)lg;
   // the sampler's commit path with the forced table: argmax is computed and overridden, bookkeeping as in every other mode
-  SamplerArgs sa;
-  sa.logits = ds.logits;
-  sa.seen = ds.seen;
-  sa.ids = ds.ids;
-  sa.cur_tok = ds.cur_tok;
-  sa.unfinished = ds.unfinished;
-  sa.step = ds.len;
-  sa.V = cfg.number_mel_codes;
-  sa.max_gen = ds.max_gen;
-  sa.stop = cfg.stop_mel_token;
-  sa.suppress_stop = ds.suppress_stop;
-  sa.penalty = ds.penalty;
-  sa.h_next = ds.h;
-  sa.emb = gpt.mel_emb;
-  sa.pos = gpt.mel_pos;
-  sa.D = cfg.model_dim;
-  sa.pos_rows = cfg.max_mel_tokens + 3;
-  sa.emb_bf16 = adt == BF16;
+  SamplerArgs sa = greedy_sampler_args(ds.logits, false);
   sa.forced = ds.forced;
   sa.input_n = 0;
-  sa.B = ds.B;
-  const int st = sampler2_step(sa, ds.B, s);
-  ds.host_sample = keep;
-  ds.use_forced = forced;
-  return st;
+  // plain greedy arguments whatever an earlier sampled generation left in the decode state (sampler2_kernel reads none of them)
+  sa.do_sample = sa.top_k = 0;
+  sa.top_p = sa.temperature = 1.f;
+  sa.uniforms = nullptr;
+  return sampler2_step(sa, ds.B, s);
 }
 
 // Host-side beam_sample (the generate() kwargs the device beam sampler does not cover: top_k = 0 / None or > 128 with several
@@ -1210,16 +1169,37 @@ int Engine::gpt_decode(int nsteps, hipStream_t s) {
   return rc;
 }
 
+// the values a captured step depends on (GraphKey, engine.h), from the decode state of the current request
+GraphKey Engine::graph_key() const {
+  const DecodeState& d = ds;
+  GraphKey k;
+  k.B = d.B;
+  k.Smax = d.Smax;
+  k.max_gen = d.max_gen;
+  k.use_forced = d.use_forced;
+  k.input_n = d.input_n;
+  k.host_sample = d.host_sample;
+  k.fuse = d.fuse && !d.fuse_failed;
+  k.eng = (int)engine_usable();
+  k.nb = d.nb;
+  k.beam_sample = d.beam_sample;
+  k.length_penalty = d.length_penalty;
+  k.typical_mass = d.typical_mass;
+  k.penalty = d.penalty;
+  k.suppress_stop = d.suppress_stop;
+  k.do_sample = d.do_sample;
+  k.top_k = d.top_k;
+  k.top_p = d.top_p;
+  k.temperature = d.temperature;
+  return k;
+}
+
 int Engine::gpt_decode_steps(int nsteps, hipStream_t s) {
   ITTS_REQUIRE(nsteps >= 0, "gpt_decode: nsteps < 0");
   if (use_graph && s != nullptr) {
     DecodeState& d = ds;
-    // everything SamplerArgs carries by value is baked into the captured nodes: max_gen is the ids row stride and the
-    // `k < max_gen` bound, so a per-request max_mel_tokens must re-capture (same B / Smax notwithstanding)
-    const bool stale = !d.graph || d.graph_B != d.B || d.graph_Smax != d.Smax || d.graph_max_gen != d.max_gen ||
-                       d.graph_forced != d.use_forced || d.graph_input_n != d.input_n || d.graph_host_sample != d.host_sample || d.graph_fuse != (d.fuse && !d.fuse_failed) || d.graph_eng != (int)engine_usable() || d.graph_nb != d.nb || d.graph_beam_sample != d.beam_sample ||
-                       d.graph_length_penalty != d.length_penalty || d.graph_typical != d.typical_mass || d.graph_penalty != d.penalty || d.graph_suppress != d.suppress_stop || d.graph_sample != d.do_sample ||
-                       d.graph_top_k != d.top_k || d.graph_top_p != d.top_p || d.graph_temperature != d.temperature;
+    const GraphKey key = graph_key();
+    const bool stale = !d.graph || !(d.graph_key == key);
     // two executables: one step, and GK steps back to back (one launch per GK tokens: the gap between consecutive graph
     // launches is paid once per GK steps; every step reads its lengths from device memory, so any mix is valid)
     static const int GK = [] {
@@ -1228,11 +1208,7 @@ int Engine::gpt_decode_steps(int nsteps, hipStream_t s) {
       return v < 1 ? 1 : (v > 32 ? 32 : v);
     }();
     if (stale && nsteps > 0) {
-      for (hipGraphExec_t* ge : {&d.graph, &d.graphK})
-        if (*ge) {
-          (void)hipGraphExecDestroy(*ge);
-          *ge = nullptr;
-        }
+      d.drop_graphs();
       for (int which = 0; which < (GK > 1 ? 2 : 1); ++which) {
         hipGraph_t g = nullptr;
         ITTS_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -1247,25 +1223,8 @@ int Engine::gpt_decode_steps(int nsteps, hipStream_t s) {
         ITTS_HIP_CHECK(hipGraphInstantiate(which ? &d.graphK : &d.graph, g, nullptr, nullptr, 0));
         (void)hipGraphDestroy(g);
       }
-      d.graph_B = d.B;
-      d.graph_Smax = d.Smax;
-      d.graph_max_gen = d.max_gen;
-      d.graph_forced = d.use_forced;
-      d.graph_input_n = d.input_n;
-      d.graph_host_sample = d.host_sample;
-      d.graph_fuse = d.fuse && !d.fuse_failed;
-      d.graph_eng = (int)engine_usable();
+      d.graph_key = key;
       d.graph_mode = d.last_mode;  // what the captured step runs on
-      d.graph_nb = d.nb;
-      d.graph_beam_sample = d.beam_sample;
-      d.graph_length_penalty = d.length_penalty;
-      d.graph_typical = d.typical_mass;
-      d.graph_penalty = d.penalty;
-      d.graph_suppress = d.suppress_stop;
-      d.graph_sample = d.do_sample;
-      d.graph_top_k = d.top_k;
-      d.graph_top_p = d.top_p;
-      d.graph_temperature = d.temperature;
     }
     d.last_mode = d.graph_mode;  // a replayed graph: the mode it was captured with
     int left = nsteps;
@@ -1281,7 +1240,7 @@ int Engine::gpt_decode_steps(int nsteps, hipStream_t s) {
 // abort word of the persistent decode engine: a hand-off wait gave up, so the codes of this generation are not valid.
 // The engine is switched off for this Engine (launch path from the next generation on) and its state re-initialised.
 int Engine::engine_check(hipStream_t s) {
-  if (ds.fuse_err && (ds.fuse || ds.graph_fuse)) {  // the opt-in fused projection + attention launch: checked at fetch too
+  if (ds.fuse_err && (ds.fuse || ds.graph_key.fuse)) {  // the opt-in fused projection + attention launch: checked at fetch too
     int ferr = 0;
     ITTS_HIP_CHECK(hipMemcpyAsync(&ferr, ds.fuse_err, 4, hipMemcpyDeviceToHost, s));
     ITTS_HIP_CHECK(hipStreamSynchronize(s));
