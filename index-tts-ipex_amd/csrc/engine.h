@@ -253,6 +253,8 @@ struct Engine {
   int ensure_decode_tiles(hipStream_t s);
   ~Engine();
 
+  // the GemmArgs fields a layer determines (W, N, Cin, taps, bias, BN affine) and the operand geometry; callers set only what differs
+  static GemmArgs conv_args(const void* A, int lda, const Lin& w, void* C, int ldc, int M, int T);
   // op wrappers (skip launches in dry mode)
   int lin(void* C, int tc, const void* A, int ta, int lda, const Lin& w, int M, int ldc, hipStream_t s, int act = ACT_NONE,
           const void* R = nullptr, int ldr = 0, float alpha = 1.f);

@@ -64,8 +64,7 @@ int Engine::tap(const char* name, const void* p, int dt, int64_t n, hipStream_t 
   return OK;
 }
 
-int Engine::lin(void* C, int tc, const void* A, int ta, int lda, const Lin& w, int M, int ldc, hipStream_t s, int act,
-                const void* R, int ldr, float alpha) {
+GemmArgs Engine::conv_args(const void* A, int lda, const Lin& w, void* C, int ldc, int M, int T) {
   GemmArgs g;
   g.A = A;
   g.W = w.w;
@@ -73,13 +72,20 @@ int Engine::lin(void* C, int tc, const void* A, int ta, int lda, const Lin& w, i
   g.M = M;
   g.N = w.N;
   g.Cin = w.Cin;
-  g.taps = 1;
+  g.taps = w.taps;
   g.lda = lda;
   g.ldc = ldc;
+  g.T = T;
   g.bias = w.b;
-  g.act = act;
-  g.scale = w.bn_scale;
+  g.scale = w.bn_scale;  // null unless the layer carries an eval-mode BatchNorm
   g.shift = w.bn_shift;
+  return g;
+}
+
+int Engine::lin(void* C, int tc, const void* A, int ta, int lda, const Lin& w, int M, int ldc, hipStream_t s, int act,
+                const void* R, int ldr, float alpha) {
+  GemmArgs g = conv_args(A, lda, w, C, ldc, M, 0);
+  g.act = act;
   g.R = R;
   g.ldr = ldr;
   g.alpha = alpha;

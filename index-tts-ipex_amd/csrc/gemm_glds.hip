@@ -33,10 +33,7 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmArgs g, int tiles
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE];  // ONE LDS object (see the guide: a second one de-pipelines)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  // ---- XCD-aware, bijective remap: consecutive logical ids (= the column tiles of one row tile) land on one XCD ----
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wgid = xcd_remap(blockIdx.x, gridDim.x);
   const int per_phase = tiles_m * tiles_n;
   const int phase = wgid / per_phase, rem = wgid - phase * per_phase;
   const int tm = rem / tiles_n, tn = rem - tm * tiles_n;
@@ -198,11 +195,10 @@ int launch(const GemmArgs& g, hipStream_t s) {
 // (N = 192, BigVGAN stage 3: 1.1-1.5x), and loses on short K (k = 3, the 1280-deep GPT projections) and on the
 // polyphase transposed convs - those stay on the register-staged kernel.
 bool gemm_glds_supported(const GemmArgs& g, int ta, int tw, int tc) {
-  if (ta != BF16 || tw != BF16 || (tc != BF16 && tc != F32)) return false;
-  if (g.Cin % 64 != 0 || g.lda % 8 != 0 || g.in_up != 1 || g.nphase < 1 || g.nphase > 8) return false;
-  if (((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return false;
+  if (!gemm_operands_ok(g, ta, tw, tc)) return false;
+  if (g.Cin % 64 != 0 || g.in_up != 1 || g.nphase < 1 || g.nphase > 8) return false;
   if (g.N < 64 || g.M < 256) return false;
-  const int bn = (g.N % 128 != 0 && g.N % 64 == 0 && g.N < 256) ? 64 : 128;
+  const int bn = gemm_ragged128(g) ? 64 : 128;
   const long tiles = (long)((g.M + BM - 1) / BM) * ((g.N + bn - 1) / bn) * g.nphase;
   if (g.nphase != 1) return false;
   // enough tiles to fill the chip twice over on the K-deep or 64-wide shapes; the narrow convolutions (N <= 512: the weight panel
@@ -216,7 +212,7 @@ int gemm_glds(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
   ITTS_REQUIRE(gemm_glds_supported(g, ta, tw, tc), "gemm_glds: unsupported shape/dtype");
   const int T = g.T > 0 ? g.T : g.M;
   ITTS_REQUIRE(g.M % T == 0 && g.lda >= g.Cin && g.ldc >= g.N * g.nphase, "gemm_glds: bad dims");
-  const bool bn64 = g.N % 128 != 0 && g.N % 64 == 0 && g.N < 256;
+  const bool bn64 = gemm_ragged128(g);
   if (tc == BF16) return bn64 ? launch<64, bf16_t>(g, s) : launch<128, bf16_t>(g, s);
   return bn64 ? launch<64, float>(g, s) : launch<128, float>(g, s);
 }

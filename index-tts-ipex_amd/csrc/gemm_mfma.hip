@@ -249,9 +249,7 @@ int dispatch(const GemmArgs& g, hipStream_t s) {
   if (force == 2 && g.N >= 64) return launch<128, 64, TC, 2>(g, s);
   if (force == 3 && g.N >= 64) return launch<64, 64, TC, 4>(g, s);
   if (g.N <= 32) return launch<128, 32, TC, 1>(g, s);
-  // N = 192 (BigVGAN stage 3): two 128-wide tiles would waste a quarter of the MFMA work, three 64-wide tiles none
-  const bool ragged128 = g.N % 128 != 0 && g.N % 64 == 0 && g.N < 256;
-  if (g.N >= 128 && tiles(128, 128) >= 768 && !ragged128)
+  if (g.N >= 128 && tiles(128, 128) >= 768 && !gemm_ragged128(g))
     return tiles(128, 128) >= 1536 ? launch<128, 128, TC, 1>(g, s) : launch<128, 128, TC, 2>(g, s);
   if (tiles(128, 64) >= 512 || g.M <= 64) {
     if (g.M <= 64) return launch<64, 64, TC, 4>(g, s);
@@ -263,9 +261,7 @@ int dispatch(const GemmArgs& g, hipStream_t s) {
 }  // namespace
 
 bool gemm_mfma_supported(const GemmArgs& g, int ta, int tw, int tc) {
-  if (ta != BF16 || tw != BF16 || (tc != BF16 && tc != F32)) return false;
-  if (g.Cin % 8 != 0 || g.lda % 8 != 0) return false;
-  if (((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return false;
+  if (!gemm_operands_ok(g, ta, tw, tc) || g.Cin % 8 != 0) return false;
   if (g.M < 16) return false;  // tiny M (speaker-conditioning 1x1 convs): the vector kernel is fine
   return true;
 }

@@ -149,10 +149,7 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmArgs g, int tiles_m, i
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave / WN, wc = wave % WN;
   const int grp = wave >> 2;  // waves w and w + 4 share a SIMD: the second group runs half a phase behind the first
-  // ---- XCD-aware, bijective remap: consecutive logical ids (= the column tiles of one row tile) land on one XCD ----
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wgid = xcd_remap(blockIdx.x, gridDim.x);
   const int per_phase = tiles_m * tiles_n;
   // K split (g.ksplit > 1, nphase == 1): the splits of one tile are consecutive logical ids (same XCD: they read different K ranges,
   // but the tile's A and W rows interleave in the same L2 sets either way) - split = id % ksplit
@@ -415,16 +412,14 @@ int launch_p8(const GemmArgs& g, hipStream_t s) {
 // 256 x 256 tile, a multiple of 128 the 512 x 128 tile.
 static bool p8_wide(const GemmArgs& g) { return g.N % 256 == 0; }
 // Number of tiles the launch would have, 0 where the kernel cannot run the shape at all.  WHEN it is the right kernel is the
-// selector's business (c_api.cpp gemm_which): >= 200 tiles always; 64..199 where the 128-wide LDS-DMA kernel has no better claim.
+// selector's business (gemm_select.cpp gemm_which): >= 200 tiles always; 64..199 where the 128-wide LDS-DMA kernel has no better claim.
 long gemm_p8_tiles(const GemmArgs& g, int ta, int tw, int tc) {
-  if (ta != BF16 || tw != BF16 || (tc != BF16 && tc != F32)) return 0;
-  if (g.Cin % 64 != 0 || g.lda % 8 != 0 || g.in_up != 1 || g.nphase < 1 || g.nphase > 8) return 0;
-  if (((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return 0;
+  if (!gemm_operands_ok(g, ta, tw, tc)) return 0;
+  if (g.Cin % 64 != 0 || g.in_up != 1 || g.nphase < 1 || g.nphase > 8) return 0;
   if (g.N < 192 || g.N % 64 != 0 || (long)g.taps * g.Cin < 256) return 0;
   const int bm = p8_wide(g) ? 256 : 512, bn = p8_wide(g) ? 256 : 128;
   return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * g.nphase;
 }
-bool gemm_p8_supported(const GemmArgs& g, int ta, int tw, int tc) { return gemm_p8_tiles(g, ta, tw, tc) * (g.ksplit > 1 ? g.ksplit : 1) >= 64; }
 
 int gemm_p8(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
   ITTS_REQUIRE(g.A && g.W && g.C, "gemm_p8: null pointer");

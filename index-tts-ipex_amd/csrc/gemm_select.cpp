@@ -1,0 +1,84 @@
+// Which kernel of the shift-GEMM family runs a shape (gemm_which), the dispatcher on top of it (gemm), and the K-split planner
+// of the few-tile deep-K shapes (gemm_ksplit_plan).  Pure host code: no HIP call before the launch itself.
+#include <algorithm>
+#include <cstdlib>
+
+#include "itts_kernels.h"
+
+namespace itts {
+
+// what every matrix-core kernel of the family needs of its operands: 16-bit A and W read as 16-byte fragments, 16-bit or fp32 C
+bool gemm_operands_ok(const GemmArgs& g, int ta, int tw, int tc) {
+  if (ta != BF16 || tw != BF16 || (tc != BF16 && tc != F32)) return false;
+  return g.lda % 8 == 0 && !((uintptr_t)g.A & 15) && !((uintptr_t)g.W & 15);
+}
+
+// N = 192 (BigVGAN stage 3): two 128-wide column tiles would waste a quarter of the MFMA work, three 64-wide tiles none
+bool gemm_ragged128(const GemmArgs& g) { return g.N % 128 != 0 && g.N % 64 == 0 && g.N < 256; }
+
+namespace {
+
+// The A/B switches of the selector, read once per call (tests and tools/bench_gemm.py flip them between two calls of one process).
+// The planner and the selector both ask this struct, so they cannot disagree about which kernels are allowed.
+struct Switches {
+  bool conv_lds = !getenv("ITTS_NO_CONV_LDS");                               // the LDS-tiled narrow conv
+  bool lds_dma = !getenv("ITTS_NO_GEMM_GLDS") && !getenv("ITTS_GEMM_FORCE_OLD");  // gemm_glds / gemm_p8; off = the register-staged kernel everywhere
+  bool p8 = lds_dma;                                                        // ITTS_GEMM_P8=0: without the 256 x 256 eight-phase kernel
+  int ksplit = -1;                                                          // ITTS_GEMM_KSPLIT: 0 = off, n = forced where eligible, -1 = measured rule
+  Switches() {
+    const char* e = getenv("ITTS_GEMM_P8");
+    if (e && atoi(e) == 0) p8 = false;
+    if ((e = getenv("ITTS_GEMM_KSPLIT"))) ksplit = atoi(e);
+  }
+};
+
+}  // namespace
+
+// K split for the few-tile, deep-K shapes (batch-1 latent pass: 1242 rows x 1280 features over K = 5120 is 25 tiles of 256 x 256 - a
+// tenth of the CUs, each MFMA-bound for 70 us; BigVGAN conv_pre and stage 0 likewise): the tile's K-tiles go to S workgroups that
+// write raw fp32 sums to the caller's workspace, a second launch adds them in split order (deterministic) and runs the epilogue.
+// Returns S (1 = no split).  ITTS_GEMM_KSPLIT=0 turns it off, =n forces n where the shape is eligible (A/B).
+int gemm_ksplit_plan(const GemmArgs& g, int ta, int tw, int tc, size_t ws_bytes) {
+  const Switches sw;
+  const int forced = sw.ksplit;
+  if (forced == 0 || g.nphase != 1 || !sw.p8) return 1;
+  if (sw.conv_lds && conv_lds_supported(g, ta, tw, tc)) return 1;
+  const long tiles = gemm_p8_tiles(g, ta, tw, tc);
+  const long nk = (long)g.taps * (g.Cin / 64);
+  // measured (tools/bench_gemm.py --batch 1 --ksplit, profiles/r04_gemm_ksplit_b1.txt): pays below 64 tiles with K >= 2048 (conv_pre
+  // 126 -> 50 us, stage-0 k = 11 conv 146 -> 67, latent mlp.c_proj 70 -> 41); at 75 - 100 tiles or K = 1280 the reduction launch
+  // costs more than the idle CUs did (c_attn 34 -> 36, c_proj 23 -> 27)
+  if (tiles <= 0 || tiles >= (forced > 0 ? 128 : 64) || nk < (forced > 0 ? 16 : 32)) return 1;
+  long S = forced > 0 ? forced : 224 / tiles;
+  S = std::min(S, 8L);
+  S = std::min(S, nk / 4);                                            // at least four K-tiles per split (the pipeline's fill)
+  S = std::min(S, (long)(ws_bytes / ((size_t)g.M * g.N * 4)));
+  while (S > 1 && (S - 1) * ((nk + S - 1) / S) >= nk) --S;            // every split owns at least one K-tile
+  return S < 2 ? 1 : (int)S;
+}
+
+// which kernel family the dispatcher takes for a shape: 0 vector ALU, 1 register-staged MFMA (gemm_mfma), 2 LDS-DMA staged 128-wide
+// tiles (gemm_glds), 3 256 x 256 eight-phase (gemm_p8), 4 LDS-tiled narrow conv (conv_lds)
+int gemm_which(const GemmArgs& g, int ta, int tw, int tc) {
+  if (g.ksplit > 1) return 3;  // planned by gemm_ksplit_plan (Engine::conv): gemm_p8 with its reduction launch
+  const Switches sw;
+  if (sw.conv_lds && conv_lds_supported(g, ta, tw, tc)) return 4;
+  const long p8_tiles = sw.p8 ? gemm_p8_tiles(g, ta, tw, tc) : 0;
+  if (p8_tiles >= 200) return 3;
+  if (sw.lds_dma && gemm_glds_supported(g, ta, tw, tc)) return 2;
+  if (p8_tiles >= 64) return 3;  // a quarter of the CUs busy with the deep pipeline still beats the register-staged kernel
+  if (gemm_mfma_supported(g, ta, tw, tc)) return 1;
+  return 0;
+}
+
+int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
+  switch (gemm_which(g, ta, tw, tc)) {
+    case 4: return conv_lds(g, s);
+    case 3: return gemm_p8(g, ta, tw, tc, s);
+    case 2: return gemm_glds(g, ta, tw, tc, s);
+    case 1: return gemm_mfma(g, ta, tw, tc, s);
+    default: return gemm_simple(g, ta, tw, tc, s);
+  }
+}
+
+}  // namespace itts

@@ -1,5 +1,5 @@
 // Device helpers shared by the shift-GEMM kernels (gemm_simple / gemm_mfma / gemm_glds / gemm_p8): the reflect-padding row
-// index and the LDS-DMA wrapper.
+// index, the LDS-DMA wrapper and the XCD-aware workgroup order.
 #pragma once
 #include "itts_common.h"
 
@@ -16,6 +16,13 @@ __device__ __forceinline__ int reflect_idx(int t, int T) {
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                    (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+}
+
+// XCD-aware, bijective remap of a 1-D grid: workgroup `orig` of `nwg` runs on XCD orig & 7, so consecutive LOGICAL ids (= the
+// column tiles of one row tile) are handed to workgroups of one XCD and their A rows hit that L2
+__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
+  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
 }
 
 }  // namespace itts

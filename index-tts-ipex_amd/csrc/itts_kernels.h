@@ -6,16 +6,17 @@
 
 namespace itts {
 
-// ---- GEMM / conv family (gemm_simple.hip, gemm_mfma.hip) ----
+// ---- GEMM / conv family (gemm_simple.hip, gemm_mfma.hip, gemm_glds.hip, gemm_p8.hip, conv_lds.hip; selector: gemm_select.cpp) ----
 int gemm_simple(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
+bool gemm_operands_ok(const GemmArgs& g, int ta, int tw, int tc);  // the operand gate of the three matrix-core GEMMs: half A / W, half or fp32 C, lda % 8, 16-byte aligned
+bool gemm_ragged128(const GemmArgs& g);                             // N = 192-like shapes: 64-wide column tiles instead of 128-wide
 bool gemm_mfma_supported(const GemmArgs& g, int ta, int tw, int tc);
 int gemm_mfma(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
 bool gemm_glds_supported(const GemmArgs& g, int ta, int tw, int tc);  // LDS-DMA staged 128 x 128 / 128 x 64 tiles (gemm_glds.hip)
 int gemm_glds(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
 long gemm_p8_tiles(const GemmArgs& g, int ta, int tw, int tc);      // 0 = cannot run the shape
-bool gemm_p8_supported(const GemmArgs& g, int ta, int tw, int tc);
-int gemm_ksplit_plan(const GemmArgs& g, int ta, int tw, int tc, size_t ws_bytes);  // K split of the few-tile deep-K shapes (c_api.cpp); 1 = none  // 256 x 256 tile, 8-phase LDS-DMA pipeline (gemm_p8.hip)
-int gemm_p8(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
+int gemm_p8(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);  // 256 x 256 tile, 8-phase LDS-DMA pipeline (gemm_p8.hip)
+int gemm_ksplit_plan(const GemmArgs& g, int ta, int tw, int tc, size_t ws_bytes);  // K split of the few-tile deep-K shapes; 1 = none
 bool conv_lds_supported(const GemmArgs& g, int ta, int tw, int tc);
 bool conv_lds_act_supported(const GemmArgs& g, int ta, int tw, int tc);  // ... with Activation1d fused into the tile load (g.pre_*)
 int conv_lds(const GemmArgs& g, hipStream_t s);

@@ -95,24 +95,11 @@ int Engine::ecapa(const void* mel, int B, int F, float* spk_out, hipStream_t s) 
   ITTS_REQUIRE(F > std::max(c.ec_kernels[0] / 2, maxdil), "ecapa: prompt shorter than the reflect padding");
   const int M = B * F, C = chs[0], hc = C / c.ec_scale, CC = chs[3] * 3, C4 = chs[4], att = c.ec_att;
   auto tdnn = [&](void* out, int ldc, const void* in, int lda, const Lin& w, int dil) -> int {
-    GemmArgs g;
-    g.A = in;
-    g.W = w.w;
-    g.C = out;
-    g.M = M;
-    g.N = w.N;
-    g.Cin = w.Cin;
-    g.taps = w.taps;
-    g.lda = lda;
-    g.ldc = ldc;
-    g.T = F;
+    GemmArgs g = conv_args(in, lda, w, out, ldc, M, F);
     g.dil = dil;
     g.pad_left = dil * (w.taps - 1) / 2;
     g.pad_mode = PAD_REFLECT;
-    g.bias = w.b;
     g.act = ACT_RELU;
-    g.scale = w.bn_scale;
-    g.shift = w.bn_shift;
     return conv(g, adt, w.dt, adt, s);
   };
   auto body = [&]() -> int {
@@ -171,21 +158,10 @@ int Engine::ecapa(const void* mel, int B, int F, float* spk_out, hipStream_t s) 
     ITTS_TRY(lin(gb, F32, ms, F32, 2 * C4, ec.asp_ms, B, att, s));
     void* a1 = alloc((size_t)M * att * es);
     {
-      GemmArgs g;
-      g.A = mf;
-      g.W = ec.asp_x.w;
-      g.C = a1;
-      g.M = M;
-      g.N = att;
-      g.Cin = C4;
-      g.lda = C4;
-      g.ldc = att;
-      g.T = F;
+      GemmArgs g = conv_args(mf, C4, ec.asp_x, a1, att, M, F);
       g.bias = gb;
       g.bias_bstride = att;
       g.act = ACT_RELU;
-      g.scale = ec.asp_x.bn_scale;
-      g.shift = ec.asp_x.bn_shift;
       g.act2 = ACT_TANH;
       ITTS_TRY(conv(g, adt, ec.asp_x.dt, adt, s));
     }
@@ -223,17 +199,7 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
     // conv_pre (k7, pad 3) + cond
     void* x = alloc((size_t)B * T * C0 * es);
     {
-      GemmArgs g;
-      g.A = latent;
-      g.W = bv.conv_pre.w;
-      g.C = x;
-      g.M = B * T;
-      g.N = C0;
-      g.Cin = c.bv_gpt_dim;
-      g.taps = 7;
-      g.lda = c.bv_gpt_dim;
-      g.ldc = C0;
-      g.T = T;
+      GemmArgs g = conv_args(latent, c.bv_gpt_dim, bv.conv_pre, x, C0, B * T, T);
       g.pad_left = 3;
       g.bias = cbias;
       g.bias_bstride = C0;
@@ -255,17 +221,7 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
       // ConvTranspose1d as u polyphase GEMMs: out[q*u + ph] = sum_m x[q + floor((ph+p)/u) - m] . W[ph][m]
       void* xu = alloc((size_t)B * To * cout * es);
       {
-        GemmArgs g;
-        g.A = x;
-        g.W = up.w;
-        g.C = xu;
-        g.M = B * Tc;
-        g.N = cout;
-        g.Cin = ch;
-        g.taps = k / u;
-        g.lda = ch;
-        g.ldc = u * cout;
-        g.T = Tc;
+        GemmArgs g = conv_args(x, ch, up, xu, u * cout, B * Tc, Tc);
         g.dil = -1;
         g.pad_left = 0;
         g.nphase = u;
@@ -302,30 +258,12 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
         const void* cur = xu;
         for (int l = 0; l < nd; ++l) {
           const int d = c.bv_res_dils[j][l];
-          GemmArgs g;
-          g.W = A.c1[l].w;
-          g.C = t2;
-          g.M = B * Tc;
-          g.N = ch;
-          g.Cin = ch;
-          g.taps = ks;
-          g.lda = g.ldc = ch;
-          g.T = Tc;
+          GemmArgs g = conv_args(nullptr, ch, A.c1[l], t2, ch, B * Tc, Tc);  // (A: act_conv)
           g.dil = d;
           g.pad_left = (ks * d - d) / 2;
-          g.bias = A.c1[l].b;
           ITTS_TRY(act_conv(g, cur, A.a1[l], A.b1[l], t1, A.c1[l].dt));
-          GemmArgs h;
-          h.W = A.c2[l].w;
-          h.M = B * Tc;
-          h.N = ch;
-          h.Cin = ch;
-          h.taps = ks;
-          h.lda = h.ldc = ch;
-          h.T = Tc;
-          h.dil = 1;
+          GemmArgs h = conv_args(nullptr, ch, A.c2[l], nullptr, ch, B * Tc, Tc);  // (A: act_conv, C: below)
           h.pad_left = (ks - 1) / 2;
-          h.bias = A.c2[l].b;
           h.R = cur;
           h.ldr = ch;
           const bool last = l == nd - 1;
@@ -352,19 +290,8 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
     void* t1 = alloc((size_t)B * Tc * ch * es);
     K(snake_aa(t1, x, bv.post_alpha, bv.post_beta, bv.filter, bv.filter, B, Tc, ch, adt, s));
     {
-      GemmArgs g;
-      g.A = t1;
-      g.W = bv.conv_post.w;
-      g.C = wav;
-      g.M = B * Tc;
-      g.N = 1;
-      g.Cin = ch;
-      g.taps = 7;
-      g.lda = ch;
-      g.ldc = 1;
-      g.T = Tc;
+      GemmArgs g = conv_args(t1, ch, bv.conv_post, wav, 1, B * Tc, Tc);
       g.pad_left = 3;
-      g.bias = bv.conv_post.b;
       g.act = ACT_TANH;
       ITTS_TRY(conv(g, adt, bv.conv_post.dt, F32, s));
     }
@@ -387,20 +314,9 @@ int Engine::dvae_decode(const int32_t* codes_host, int B, int T, void* mel_out, 
     ITTS_REQUIRE(codes_host[i] >= 0 && codes_host[i] < c.dv_tokens, "dvae_decode: code out of range");
   const int inner = c.dv_hidden << (c.dv_layers - 1), cb = c.dv_codebook;
   auto conv1d = [&](void* out, int tc, const void* in, const Lin& w, int Tn, int act, const void* R, int up) -> int {
-    GemmArgs g;
-    g.A = in;
-    g.W = w.w;
-    g.C = out;
-    g.M = B * Tn;
-    g.N = w.N;
-    g.Cin = w.Cin;
-    g.taps = w.taps;
-    g.lda = w.Cin;
-    g.ldc = w.N;
-    g.T = Tn;
+    GemmArgs g = conv_args(in, w.Cin, w, out, w.N, B * Tn, Tn);
     g.pad_left = (w.taps - 1) / 2;
     g.in_up = up;
-    g.bias = w.b;
     g.act = act;
     g.R = R;
     g.ldr = w.N;
@@ -457,19 +373,8 @@ int Engine::dvae_encode(const void* mel, int B, int T, int32_t* codes_host, hipS
   ITTS_REQUIRE(mel && codes_host && B > 0 && T > 0, "dvae_encode: bad arguments");
   const int inner = c.dv_hidden << (c.dv_layers - 1);
   auto conv1d = [&](void* out, int tc, const void* in, const Lin& w, int Tn, int act, const void* R, int pad_left) -> int {
-    GemmArgs g;
-    g.A = in;
-    g.W = w.w;
-    g.C = out;
-    g.M = B * Tn;
-    g.N = w.N;
-    g.Cin = w.Cin;
-    g.taps = w.taps;
-    g.lda = w.Cin;
-    g.ldc = w.N;
-    g.T = Tn;
+    GemmArgs g = conv_args(in, w.Cin, w, out, w.N, B * Tn, Tn);
     g.pad_left = pad_left;
-    g.bias = w.b;
     g.act = act;
     g.R = R;
     g.ldr = w.N;

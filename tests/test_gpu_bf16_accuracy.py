@@ -134,7 +134,7 @@ def test_bf16_latent(eng16s, mel, gold, control, accuracy):
 
 def test_ksplit_changes_only_the_summation_order(eng16s, mel, gold, control, accuracy, monkeypatch):
     """The few-tile GEMMs of small batches (one-sentence prefill mlp.c_proj, batch-1 latent pass) split K over workgroups and add
-    the shares in split order (c_api.cpp gemm_ksplit_plan): a different fp32 summation order than the unsplit kernels of large
+    the shares in split order (gemm_select.cpp gemm_ksplit_plan): a different fp32 summation order than the unsplit kernels of large
     batches, so bit-identity ACROSS batch sizes holds only with ITTS_GEMM_KSPLIT=0 (tested in test_gpu_configs.py /
     test_gpu_fullsize.py).  Here: what the order change costs - prefill logits and the T = 480 latent with and without the split
     differ by less than the bf16 engine differs from the reference (control), and both modes meet the reference bound."""

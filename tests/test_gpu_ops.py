@@ -73,12 +73,13 @@ def test_snake_vs_oracle(lib, shape, dt):
 
 def run_gemm(lib, A, W, Cshape, dt_a, dt_w, dt_c, force_simple=0, **kw):
     kw_ws = {"ws": kw.pop("ws", None)}
+    out = kw.pop("out", None)  # caller-owned output buffer (pre-filled, padded rows) instead of a fresh one
     g = L.GemmArgs()
     for k in ("dil", "in_up", "nphase", "taps"):
         setattr(g, k, 1)
     g.alpha = 1.0
     g.A, g.W = A.data_ptr(), W.data_ptr()
-    Cout = torch.empty(Cshape, dtype=torch.float32 if dt_c == L.F32 else torch.bfloat16, device=DEV)
+    Cout = out if out is not None else torch.empty(Cshape, dtype=torch.float32 if dt_c == L.F32 else torch.bfloat16, device=DEV)
     g.C = Cout.data_ptr()
     keep = []
     for k, v in kw.items():
@@ -506,7 +507,7 @@ def test_gemm_glds_conv(lib, case, out_f32):
     A = x.transpose(1, 2).contiguous().to(DEV)
     W = torch.from_numpy(pack.conv_w(w.float().numpy())).to(torch.bfloat16).to(DEV)
     R, ADD = res.transpose(1, 2).contiguous().to(DEV), add.transpose(1, 2).contiguous().to(DEV)
-    outs = []
+    outs, which = [], []
     for env in (None, "1"):  # the glds kernel, then the register-staged one on the same arguments
         import os
 
@@ -516,11 +517,79 @@ def test_gemm_glds_conv(lib, case, out_f32):
             outs.append(run_gemm(lib, A, W, (B, T, Cout), L.BF16, L.BF16, L.F32 if out_f32 else L.BF16, 0, M=B * T, N=Cout, Cin=Cin,
                                  taps=k, lda=Cin, ldc=Cout, T=T, dil=dil, pad_left=pad, pad_mode=1 if mode == "reflect" else 0,
                                  bias=bias.to(DEV), bias_bstride=Cout, R=R, ldr=Cout, alpha=1.0 / 3.0, ADD=ADD, ldadd=Cout, beta=0.5))
+            which.append(run_gemm.which)
         finally:
             os.environ.pop("ITTS_GEMM_FORCE_OLD", None)
+    # (the K = 4096 linear has enough 256 x 256 tiles for the eight-phase kernel: tests/test_gemm_selector.py pins the table)
+    assert which == ([3, 1] if case == GLDS_CASES[3] else [2, 1]), which
     assert relerr(outs[0].float().transpose(1, 2), ref) < (3e-3 if out_f32 else 2e-2)
     # both kernels accumulate the same bf16 products in fp32: they agree far inside the bf16 output rounding
     assert relerr(outs[0].float(), outs[1].float()) < (1e-4 if out_f32 else 1e-2)
+
+
+
+# ---- the whole GemmArgs epilogue on the two matrix-core kernels that write it out per 16 x 16 accumulator tile (gemm_mfma, gemm_glds) ----
+EPI_CASES = [
+    # B, T, Cin, Cout, k, dil, mode, family
+    (2, 70, 24, 40, 3, 2, "reflect", 1),      # gemm_mfma: partial 32-channel chunk, N ragged in the last 16-wide tile, rows past M and
+                                              # the batch boundary inside one 64-row tile
+    (2, 16400, 128, 72, 9, 1, "zeros", 2),    # gemm_glds: 257 row tiles, the last holds 32 of its 128 rows; N ragged in a 128-wide tile
+    (2, 16400, 128, 72, 9, 3, "reflect", 2),
+]
+_epi_ref = {}
+
+
+def epi_inputs(case):
+    """Operands and the fp32 torch convolution of a case, computed once and shared by its four parametrisations (read only)."""
+    if case not in _epi_ref:
+        B, T, Cin, Cout, k, dil, mode, _ = case
+        x = rnd(f"ep.x{case}", (B, Cin, T)).to(torch.bfloat16)
+        w = rnd(f"ep.w{case}", (Cout, Cin, k), 1.0 / np.sqrt(Cin * k)).to(torch.bfloat16)
+        pad = dil * (k - 1) // 2
+        xp = F.pad(x.float(), (pad, pad), mode="reflect") if mode == "reflect" else F.pad(x.float(), (pad, pad))
+        _epi_ref[case] = dict(
+            conv=F.conv1d(xp, w.float(), None, dilation=dil), A=x.transpose(1, 2).contiguous().to(DEV),
+            W=torch.from_numpy(pack.conv_w(w.float().numpy())).to(torch.bfloat16).to(DEV),
+            bias=rnd(f"ep.b{case}", (B, Cout), 0.3), sc=rnd(f"ep.sc{case}", (Cout,), 0.2) + 1, sh=rnd(f"ep.sh{case}", (Cout,), 0.2),
+            res=rnd(f"ep.r{case}", (B, Cout, T)), add=rnd(f"ep.a{case}", (B, Cout, T)))
+    return _epi_ref[case]
+
+
+@pytest.mark.parametrize("case", EPI_CASES)
+@pytest.mark.parametrize("out_f32", [False, True])
+@pytest.mark.parametrize("acts", [("relu", "tanh"), ("gelu_new", "none")])
+def test_gemm_full_epilogue_chain(lib, case, out_f32, acts):
+    """Per-batch bias, act, BN affine, act2, residual, alpha, beta * ADD in one launch (the ECAPA attention form relu / tanh, and
+    NewGELU in its fast form) on gemm_mfma and gemm_glds, against torch and against the vector kernel on the same arguments; the
+    output buffer starts as NaN, so an element the kernel skips or a store outside the N columns of a row shows."""
+    B, T, Cin, Cout, k, dil, mode, family = case
+    d = epi_inputs(case)
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    res, add = d["res"].to(odt), d["add"].to(odt)
+    v = d["conv"] + d["bias"][:, :, None]
+    v = F.relu(v) if acts[0] == "relu" else F.gelu(v, approximate="tanh")
+    v = v * d["sc"][None, :, None] + d["sh"][None, :, None]
+    if acts[1] == "tanh":
+        v = torch.tanh(v)
+    ref = (v + res.float()) * (1.0 / 3.0) + 0.5 * add.float()
+    R, ADD = res.transpose(1, 2).contiguous().to(DEV), add.transpose(1, 2).contiguous().to(DEV)
+    ldc = Cout + 8 if acts[1] == "tanh" else Cout  # once with padded rows: the eight pad columns stay untouched
+    kw = dict(M=B * T, N=Cout, Cin=Cin, taps=k, lda=Cin, ldc=ldc, T=T, dil=dil, pad_left=dil * (k - 1) // 2,
+              pad_mode=1 if mode == "reflect" else 0, bias=d["bias"].to(DEV), bias_bstride=Cout, act=L.ACT[acts[0]],
+              scale=d["sc"].to(DEV), shift=d["sh"].to(DEV), act2=L.ACT[acts[1]], R=R, ldr=Cout, alpha=1.0 / 3.0, ADD=ADD, ldadd=Cout, beta=0.5)
+    outs = []
+    for simple in (0, 1):
+        buf = torch.full((B, T, ldc), float("nan"), dtype=odt, device=DEV)
+        run_gemm(lib, d["A"], d["W"], None, L.BF16, L.BF16, L.F32 if out_f32 else L.BF16, simple, out=buf, **kw)
+        assert run_gemm.which == (0 if simple else family)
+        assert torch.isfinite(buf[:, :, :Cout]).all()
+        assert torch.isnan(buf[:, :, Cout:]).all()
+        outs.append(buf[:, :, :Cout].float())
+    err = relerr(outs[0].transpose(1, 2), ref)
+    print(f"epilogue chain {case} f32={out_f32} {acts}: vs torch {err:.3e}, vs vector kernel {relerr(outs[0], outs[1]):.3e}")
+    assert err < (3e-3 if out_f32 else 2e-2)
+    if acts[0] != "gelu_new":  # the vector kernel evaluates NewGELU with tanhf, the tile epilogue with its exp form
+        assert relerr(outs[0], outs[1]) < (1e-4 if out_f32 else 1e-2)
 
 
 def test_gemm_glds_transposed_conv(lib):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of the shift-GEMM kernels on the BigVGAN / GPT shapes of the bench (through the C ABI, HIP events):
 gemm_glds (LDS-DMA staged, default where supported) vs gemm_mfma (register staged, ITTS_GEMM_FORCE_OLD=1).
-    python tools/bench_gemm.py [--batch 1|32]   -> TFLOP/s per shape, both kernels"""
+    python tools/bench_gemm.py [--batch 1|32] [--reps N]   -> TFLOP/s per shape, both kernels"""
 import argparse
 import ctypes as C
 import os
@@ -68,6 +68,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--ksplit", action="store_true", help="K-split sweep (itts_gemm_ws): no split / auto / 2 / 4 / 8 per shape")
+    ap.add_argument("--reps", type=int, default=10, help="timed launches per figure (more = a narrower spread between two runs)")
     a = ap.parse_args()
     lib = L.load()
     rows = 2 * a.batch  # sentences
@@ -92,15 +93,15 @@ def main():
         for nm, M, T, N, Cin, taps, dil, nph in shapes + extra:
             cols = []
             for ks in (None, "auto", 2, 4, 8):
-                us, tf, wh = run(lib, M, T, N, Cin, taps, dil, nph, ksplit=ks)
+                us, tf, wh = run(lib, M, T, N, Cin, taps, dil, nph, reps=a.reps, ksplit=ks)
                 cols.append(f"{names[wh]:>5s} {us:7.1f}us")
             print(f"{nm:30s} {M:7d}  " + "  ".join(cols), flush=True)
         return
     print(f"{'shape':28s} {'M':>9s}  {'default':>8s} {'us':>9s} {'TF/s':>7s}   {'no-p8':>7s} {'us':>9s} {'TF/s':>7s}   {'old us':>9s} {'TF/s':>7s}  default vs no-p8")
     for nm, M, T, N, Cin, taps, dil, nph in shapes:
-        new = run(lib, M, T, N, Cin, taps, dil, nph)
-        mid = run(lib, M, T, N, Cin, taps, dil, nph, p8=False)
-        old = run(lib, M, T, N, Cin, taps, dil, nph, old=True)
+        new = run(lib, M, T, N, Cin, taps, dil, nph, reps=a.reps)
+        mid = run(lib, M, T, N, Cin, taps, dil, nph, reps=a.reps, p8=False)
+        old = run(lib, M, T, N, Cin, taps, dil, nph, reps=a.reps, old=True)
         print(f"{nm:28s} {M:9d}  {names[new[2]]:>8s} {new[0]:9.1f} {new[1]:7.1f}   {names[mid[2]]:>7s} {mid[0]:9.1f} {mid[1]:7.1f}   {old[0]:9.1f} {old[1]:7.1f}  "
               f"{mid[0] / new[0]:5.2f}x", flush=True)
 
