@@ -21,7 +21,9 @@
 //     granule block, so a tag can only match a value of THIS step; nothing is reset between launches (graph replay safe);
 //   * one attention workgroup per (row, head) - workgroup `row` of the head's group - runs the four key splits of
 //     decode_attn2_kernel<.., 256, 4> on its 16 waves and merges them in LDS: no cross-CU hop for the partials.  Its K/V
-//     rows are requested right after the layer's first gather, one projection ahead of the scores.
+//     rows are requested right after the layer's first gather, one projection ahead of the scores.  This step's own k / v row
+//     stays packed in registers of wave 0 (scored like a cache row) and is appended to the cache BEHIND the publish of the
+//     context, one 16-byte store per lane: no other wave waits for a serial tail of that wave at the merge barrier.
 //
 // Arithmetic is the launch path's, operation for operation (same lane <-> k mapping and accumulation order of the GEMV
 // dot products, same LayerNorm reduction tree - itts_wave_dev.h, one definition for both paths -, same attention window /
@@ -40,6 +42,9 @@
 //
 // Every spin is bounded (wall clock, s_memrealtime) and also ends on a chip-wide abort word; a workgroup that gave up
 // runs on without waiting, so the grid always drains.  The host reads the abort word at status / fetch.
+//
+// Probes (phase stamps, the taps of one block's edges, the gather divisor) are compiled only with -DITTS_PROBES, into
+// libitts_hip_probes.so (`make probes`); the product kernels carry none of their state.
 #include <cstdlib>
 #include <type_traits>
 
@@ -75,10 +80,22 @@ struct Rt {
   int first_delay, pass_sleep;  // s_sleep units before the first pass of a gather / between passes
 };
 
+// Probe code - the stamps, the taps of one block's edges (EngArgs::dbg) and the gather divisor (EngArgs::fake_div, wrong
+// results) - is compiled only with -DITTS_PROBES (libitts_hip_probes.so, `make probes`): the product kernels carry none of its
+// scalar state through the block loop.  EngArgs keeps the fields either way (one argument layout for every build).
+#ifdef ITTS_PROBES
 // debugging aid (EngArgs::stamp): wall-clock (100 MHz) stamp i of block l of this workgroup
 #define ENG_STAMP(i)                                                                                              \
   if (a.stamp && (tl & 63) == 0 && (i < 8 ? tl == 0 : tl == 320))                                                \
     a.stamp[((size_t)cu * a.NL + l) * 16 + (i)] = (unsigned)__builtin_amdgcn_s_memrealtime();
+#define ENG_TAP(off, val) \
+  if (a.dbg && l == a.dbg_layer) a.dbg[off] = (val);
+#define ENG_FAKE_DIV(n) ((n) / a.fake_div)
+#else
+#define ENG_STAMP(i)
+#define ENG_TAP(off, val)
+#define ENG_FAKE_DIV(n) (n)
+#endif
 
 __device__ __forceinline__ u64 ld_gran(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_gran(u64* p, unsigned tag, uint32_t v) {
@@ -651,7 +668,9 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
 
   Rt rt;
   rt.t0 = __builtin_amdgcn_s_memrealtime();
+#ifdef ITTS_PROBES
   const u64 clk0 = __builtin_amdgcn_s_memtime();
+#endif
   rt.limit = a.timeout_ticks;
   rt.ctr = a.ctr;
   rt.dead = false;
@@ -778,7 +797,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing the compiler counts stays pending past the gather branch
       } else {
         wait_own(own_lds, NCW * phase, rt);
-        sweep2<(NB * D / 2 + 255) / 256, false>(G - LSTRIDE + OH2, NB * D / 2 / a.fake_div, tl, rt, [&](int i, uint32_t v) { xf[i] = __uint_as_float(v); }, rt.first_delay);
+        sweep2<(NB * D / 2 + 255) / 256, false>(G - LSTRIDE + OH2, ENG_FAKE_DIV(NB * D / 2), tl, rt, [&](int i, uint32_t v) { xf[i] = __uint_as_float(v); }, rt.first_delay);
       }
       if (early_kv) kv_issue(Ic0{}, IcE{});
     } else if (lw) {
@@ -818,7 +837,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           }
           if (ll < NB) {
             st_gran(G + OQKV + (size_t)ll * 3 * D + an0 + r, rt.tag, __float_as_uint(slot_out<W8>(W0, r, mine)));
-            if (a.dbg && l == a.dbg_layer) a.dbg[(size_t)ll * 3 * D + an0 + r] = slot_out<W8>(W0, r, mine);
+            ENG_TAP((size_t)ll * 3 * D + an0 + r, slot_out<W8>(W0, r, mine))
           }
         }
       }
@@ -868,13 +887,17 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       const bool own = atid < LPK && sp == 0;  // slot 0 of split 0 appends this step's row
 #pragma unroll
       for (int i = 0; i < VEC; ++i) qr[i] = qkvs[sub * VEC + i] * a.scale;
-      if (own) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-          kb[(size_t)pos * DH + sub * VEC + i] = (bf16_t)qkvs[DH + sub * VEC + i];
-          vb[(size_t)pos * DH + sub * VEC + i] = (bf16_t)qkvs[2 * DH + sub * VEC + i];
-        }
-      }
+      // This step's k / v fragment of the lane in the packed form of a cache row (two 16-byte LDS reads each, rounded once with the
+      // cache's conversion): the score and the PV term of the appended row read it like any other row, and the append behind the
+      // publish stores it.  Only wave 0 holds `own` lanes (wave-uniform test: the other fifteen waves branch round the reads).
+      V8<bf16_t> ka, va;
+      ka.raw = va.raw = u32x4{0u, 0u, 0u, 0u};
+      const bool own_wave = wave == 0;
+      auto row_frag = [&](const float* __restrict__ src) {
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(src + sub * VEC), hi = *reinterpret_cast<const f32x4*>(src + sub * VEC + 4);
+        return u32x4{pack_bf16(lo[0], lo[1]), pack_bf16(lo[2], lo[3]), pack_bf16(hi[0], hi[1]), pack_bf16(hi[2], hi[3])};
+      };
+      if (own_wave) ka.raw = row_frag(qkvs + DH);
       float m = -INFINITY, lsum = 0.f, acc[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
@@ -890,18 +913,12 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
             sc[u] = (j < S && j >= ks && j != pos) ? tt : -INFINITY;
           }
         }
-        {  // the row appended by this step, with the cache's rounding, from LDS
-          float tt = 0.f;
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) tt = fmaf(qr[i], own ? (float)(bf16_t)qkvs[DH + sub * VEC + i] : 0.f, tt);
-          tt = dpp_add<0xB1>(tt);
-          tt = dpp_add<0x4E>(tt);
-          tt = dpp_add<0x141>(tt);
-          sc[2 * NIT] = (slot == 0 && sp == 0) ? tt : -INFINITY;
-        }
+        // the row appended by this step, with the cache's rounding (only the `own` lanes' score is kept: slot 0 of split 0)
+        sc[2 * NIT] = (slot == 0 && sp == 0) ? score(ka) : -INFINITY;
         float mw = sc[0];
 #pragma unroll
         for (int u = 1; u <= 2 * NIT; ++u) mw = fmaxf(mw, sc[u]);
+        if (own_wave) va.raw = row_frag(qkvs + 2 * DH);
         if (mw > -INFINITY) {
 #pragma unroll
           for (int u = 0; u < 2 * NIT; ++u)
@@ -914,7 +931,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           const float p = __expf(sc[2 * NIT] - mw);
           lsum += p;
 #pragma unroll
-          for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, own ? (float)(bf16_t)qkvs[2 * DH + sub * VEC + i] : 0.f, acc[i]);
+          for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, own ? va.get(i) : 0.f, acc[i]);  // (the select stays: p * v could flip the sign of a zero)
           m = mw;
         }
       }
@@ -990,6 +1007,14 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         }
         st_gran(G + OCTX + (size_t)gm * (D / 2) + gh * (DH / 2) + tl, rt.tag, pack_bf16(xm[0], xm[1]));
       }
+      // Cache append, BEHIND the publish (the other workgroups wait for the context, nobody for this): the eight `own` lanes write
+      // the 128-byte K row and V row of position pos, one 16-byte store each.  Nothing in this launch reads row pos: only this
+      // workgroup works on (row gm, head gh) of block l (beam rows: the ancestry names rows of positions < pos only), its window and
+      // streaming loads mask j == pos, and the next reader is the next step's launch, behind a kernel boundary.
+      if (own) {
+        *reinterpret_cast<u32x4*>(kb + (size_t)pos * DH + sub * VEC) = ka.raw;
+        *reinterpret_cast<u32x4*>(vb + (size_t)pos * DH + sub * VEC) = va.raw;
+      }
       ENG_STAMP(3)
     }
 
@@ -1025,7 +1050,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
         const float hn = hown[ll * 8 + cw] + slot_out<W8>(W2, cw, mine);
         hown[ll * 8 + cw] = hn;
         st_gran(G + OH1 + (size_t)ll * D + cu * HO + cw, rt.tag, __float_as_uint(hn));
-        if (a.dbg && l == a.dbg_layer) a.dbg[(size_t)NB * 3 * D + (size_t)ll * D + cu * HO + cw] = hn;
+        ENG_TAP((size_t)NB * 3 * D + (size_t)ll * D + cu * HO + cw, hn)
       }
     }
     phase_done(ll);
@@ -1033,7 +1058,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     // ================= P4: residual stream -> LN2 -> c_fc -> gelu_new =================
     if (gw) {
       wait_own(own_lds, NCW * phase, rt);
-      sweep2<(NB * D / 2 + 255) / 256, false>(G + OH1, NB * D / 2 / a.fake_div, tl, rt, [&](int i, uint32_t v) { xf[i] = __uint_as_float(v); }, rt.first_delay);
+      sweep2<(NB * D / 2 + 255) / 256, false>(G + OH1, ENG_FAKE_DIV(NB * D / 2), tl, rt, [&](int i, uint32_t v) { xf[i] = __uint_as_float(v); }, rt.first_delay);
     } else if (lw) {
       dma_wait_keep<0>();  // c_fc (and, before it, mlp.c_proj)
     }
@@ -1071,11 +1096,8 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       const float v1 = __shfl_down(v, NB, 64);  // (feature 1, batch row ll) for lanes < NB
       if (ll < NB) {
         st_gran(G + OACT + (size_t)ll * 2 * D + cu * (FO / 2) + cw, rt.tag, pack_bf16(v, v1));
-        if (a.dbg && l == a.dbg_layer) {
-          float* d = a.dbg + (size_t)NB * 4 * D + (size_t)ll * 4 * D + cu * FO + 2 * cw;
-          d[0] = (float)(bf16_t)v;
-          d[1] = (float)(bf16_t)v1;
-        }
+        ENG_TAP((size_t)NB * 4 * D + (size_t)ll * 4 * D + cu * FO + 2 * cw, (float)(bf16_t)v)
+        ENG_TAP((size_t)NB * 4 * D + (size_t)ll * 4 * D + cu * FO + 2 * cw + 1, (float)(bf16_t)v1)
       }
     }
 
@@ -1085,7 +1107,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     // ================= P5: gelu(fc) -> mlp.c_proj + residual =================
     if (gw) {
       wait_own(own_lds, NCW * phase, rt);
-      sweep2<(NB * D + 255) / 256, false>(G + OACT, NB * D / a.fake_div, tl, rt, [&](int i, uint32_t v) { xa[i] = v; }, a.act_delay);
+      sweep2<(NB * D + 255) / 256, false>(G + OACT, ENG_FAKE_DIV(NB * D), tl, rt, [&](int i, uint32_t v) { xa[i] = v; }, a.act_delay);
     } else if (lw && HALFB) {
       wait_own(own_lds, NCW * phase, rt);  // every compute wave is through c_fc: slot A is free
       dma_rows_part<HO, 4 * D, 2 * D, 2 * D, W8>(w.w2, nullptr, nullptr, cu * HO, S0, ll);  // second half of mlp.c_proj -> A
@@ -1130,7 +1152,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       if (ll < NB) {
         const float hn = hown[ll * 8 + cw] + slot_out<W8>(W1, cw, mine);
         hown[ll * 8 + cw] = hn;
-        if (a.dbg && l == a.dbg_layer) a.dbg[(size_t)NB * 8 * D + (size_t)ll * D + cu * HO + cw] = hn;
+        ENG_TAP((size_t)NB * 8 * D + (size_t)ll * D + cu * HO + cw, hn)
         if (l + 1 < a.NL || a.head_w)
           st_gran(G + OH2 + (size_t)ll * D + cu * HO + cw, rt.tag, __float_as_uint(hn));
         else
@@ -1336,6 +1358,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
   // advance the step counter (never 0): every workgroup read it before its first publish, and this workgroup got here
   // only after gathering from all of them
   if (cu == 0 && t == 0) a.ctr[0] = rt.tag + 1 == 0 ? 1u : rt.tag + 1;
+#ifdef ITTS_PROBES
   if (a.stamp && t == 0) {  // shader clock over the launch: cycles per 10 ns tick, x 1000 (stamp 15 of block 0)
     const u64 c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     a.stamp[(size_t)cu * a.NL * 16 + 15] = (unsigned)((c1 - clk0) * 1000 / (r1 - rt.t0 + 1));
@@ -1344,6 +1367,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       a.stamp[((size_t)cu * a.NL + 2) * 16 + 15] = (unsigned)r1;
     }
   }
+#endif
 }
 
 }  // namespace

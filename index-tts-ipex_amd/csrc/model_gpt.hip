@@ -773,11 +773,17 @@ EngArgs Engine::engine_args(int& eng_first, bool& fold_head, bool& fold_samp) co
   ea.B = B;
   ea.Smax = ds.Smax;
   ea.scale = 1.f / std::sqrt((float)dh);
+#ifdef ITTS_PROBES  // the probes library (make probes): the product kernels have no tap, stamp or divisor code to switch on
   static const int e_tap = getenv("ITTS_TAP_LAYER") ? atoi(getenv("ITTS_TAP_LAYER")) : -1;
   if (debug && e_tap >= 0 && e_tap < eng_first && !dry) {  // debugging aid: the engine's view of one block's edges
     ea.dbg = ds.act;  // [16][4D] fp32 scratch of the launch path, unused by the engine: room for the 9 B D floats of the dump
     ea.dbg_layer = e_tap;
   }
+  static const int e_fake = getenv("ITTS_ENG_FAKE_DIV") ? atoi(getenv("ITTS_ENG_FAKE_DIV")) : 1;
+  ea.fake_div = e_fake < 1 ? 1 : e_fake;
+  static const bool e_stamps = getenv("ITTS_ENGINE_STAMPS") != nullptr;
+  if (debug && e_stamps && !dry) ea.stamp = (unsigned*)ds.scores2;  // [16][V] fp32 scratch of the typical filter (off in this mode) >= 256 * 24 * 16 words
+#endif
   // gather pacing (s_sleep units of 64 clocks): a publish needs ~0.4 us to become visible; earlier passes fail AND slow the
   // stores down.  Defaults from tools/eng_pacing_rows.sh (profiles/r03_engine_pacing_sweep.txt): 14 / 16 at <= 2 rows, 12 / 8
   // at 3 - 4 rows, 12 / 4 at 5 - 6 (more granules per pass: the first pass itself takes longer)
@@ -791,8 +797,6 @@ EngArgs Engine::engine_args(int& eng_first, bool& fold_head, bool& fold_samp) co
   static const int e_early = getenv("ITTS_ENGINE_EARLY_FC") ? atoi(getenv("ITTS_ENGINE_EARLY_FC")) : -1;
   ea.early_fc = e_early >= 0 ? e_early : 74;  // tools/ab_early.sh, tools/eng_pacing_rows.sh (profiles/r03_engine_early_fc.txt)
   ea.first_delay = e_fd;
-  static const int e_fake = getenv("ITTS_ENG_FAKE_DIV") ? atoi(getenv("ITTS_ENG_FAKE_DIV")) : 1;
-  ea.fake_div = e_fake < 1 ? 1 : e_fake;
   static const int e_ekv = getenv("ITTS_ENGINE_EARLY_KV") ? atoi(getenv("ITTS_ENGINE_EARLY_KV")) : 1;
   ea.early_kv = e_ekv;
   static const int e_cd = getenv("ITTS_ENGINE_CTX_DELAY") ? atoi(getenv("ITTS_ENGINE_CTX_DELAY")) : 0;
@@ -800,8 +804,6 @@ EngArgs Engine::engine_args(int& eng_first, bool& fold_head, bool& fold_samp) co
   ea.act_delay = e_ad;
   ea.pass_sleep = e_ps;
   if (const char* tt = getenv("ITTS_ENGINE_TIMEOUT_TICKS")) ea.timeout_ticks = (unsigned)atol(tt);  // tests: force the give-up path (read per call)
-  static const bool e_stamps = getenv("ITTS_ENGINE_STAMPS") != nullptr;
-  if (debug && e_stamps && !dry) ea.stamp = (unsigned*)ds.scores2;  // [16][V] fp32 scratch of the typical filter (off in this mode) >= 256 * 24 * 16 words
   // the head (ln_f -> final_norm -> mel_head) inside the same launch when the engine runs every block (ITTS_ENGINE_HEAD=0: own launch)
   // (read per call - i.e. whenever an engine object captures its step -, so one process can compare both forms on fresh engine objects)
   const char* e_head_env = getenv("ITTS_ENGINE_HEAD");
@@ -953,7 +955,11 @@ int Engine::decode_step_launch(hipStream_t s) {
     } else {
       ITTS_TRY(run(g, L.attn.dt));
     }
+#ifdef ITTS_PROBES
     static const int l_tap = getenv("ITTS_TAP_LAYER") ? atoi(getenv("ITTS_TAP_LAYER")) : -1;
+#else
+    constexpr int l_tap = -1;  // (the launch path's side of tools/eng_tap.py: probes library only)
+#endif
     if (l == l_tap) ITTS_TRY(tap("lp_qkv", ds.qkv, F32, (int64_t)B * 3 * D, s));
     if (fused) {
     } else if (split)

@@ -1,5 +1,8 @@
 """Debugging aid for the persistent decode engine: one decode step after the same prefill, engine vs launch path,
-bitwise and by magnitude.  ITTS_ENGINE_LAYERS=n runs blocks [0, n) on the engine and the rest as launches."""
+bitwise and by magnitude.  ITTS_ENGINE_LAYERS=n runs blocks [0, n) on the engine and the rest as launches.
+Needs the probes library (`make -C index-tts-ipex_amd/csrc probes`): the product library compiles the engine's stamps, block taps and
+gather divisor out and ignores their switches.  Select it through the usual override:
+ITTS_HIP_LIB=index-tts-ipex_amd/csrc/libitts_hip_probes.so python tools/eng_debug.py ..."""
 import os
 import sys
 

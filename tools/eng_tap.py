@@ -1,4 +1,7 @@
-"""Debugging aid: the edges of ONE block (ITTS_TAP_LAYER) of the first decode step, persistent engine vs launch path."""
+"""Debugging aid: the edges of ONE block (ITTS_TAP_LAYER) of the first decode step, persistent engine vs launch path.
+Needs the probes library (`make -C index-tts-ipex_amd/csrc probes`): the product library compiles the engine's stamps, block taps and
+gather divisor out and ignores their switches.  Select it through the usual override:
+ITTS_HIP_LIB=index-tts-ipex_amd/csrc/libitts_hip_probes.so python tools/eng_tap.py ..."""
 import os
 import sys
 

@@ -1,7 +1,10 @@
 """Debugging aid: phase timeline of the persistent decode engine (ITTS_ENGINE_STAMPS=1), one decode step.
 Stamps per workgroup and block (100 MHz wall clock): 0 E1 gathered, 1 after B1, 2 q/k/v polled (attention WGs), 3 context
 published, 4 E3 gathered, 5 E4 gathered, 6 E5 gathered, 7 after B5; compute side: 8 q/k/v published, 9 c_proj published,
-10 c_fc published, 11 mlp.c_proj published."""
+10 c_fc published, 11 mlp.c_proj published.
+Needs the probes library (`make -C index-tts-ipex_amd/csrc probes`): the product library compiles the engine's stamps, block taps and
+gather divisor out and ignores their switches.  Select it through the usual override:
+ITTS_HIP_LIB=index-tts-ipex_amd/csrc/libitts_hip_probes.so python tools/eng_timeline.py ..."""
 import os
 import sys
 
