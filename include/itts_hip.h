@@ -73,6 +73,10 @@ int itts_gemm(const itts_gemm_args* args, itts_stream stream);
 /* Which kernel family itts_gemm takes for these arguments (no launch): 0 vector ALU, 1 register-staged MFMA, 2 LDS-DMA staged
  * 128-wide tiles, 3 the 256 x 256 eight-phase kernel, 4 the LDS-tiled narrow conv.  Tests and tools/bench_gemm.py use it. */
 int itts_gemm_which(const itts_gemm_args* args);
+/* Which instantiation the bf16 decode GEMV of the launch path (1-4 rows) takes for a call (no launch): -1 = it does not take the
+ * call, else nb | rpw << 4 | nch << 8 | waves << 16 (batch rows compiled in, weight rows per wave, 512-column chunks per lane, waves
+ * per workgroup).  w5 = the ITTS_GEMV_W5 rows.  tests/test_gemv_selector.py uses it. */
+int itts_gemv_which(int B, int N, int K, int prologue, int x_bf16, int y_bf16, int w5);
 /* itts_gemm with a caller-owned fp32 workspace (16-byte aligned, ws_bytes long): few-tile, deep-K shapes (M x N in fewer than 128
  * tiles of 256 x 256, K >= 1024) split K over up to 8 workgroups per tile - raw sums into ws[split][M][N], a second launch adds
  * them in split order (deterministic) and runs the epilogue.  Other shapes run exactly as itts_gemm.  itts_gemm_ksplit returns the

@@ -87,6 +87,15 @@ int itts_gemm_which(const itts_gemm_args* a) {
   return a->force_simple ? 0 : gemm_which(g, a->dtype_a, a->dtype_w, a->dtype_c);
 }
 
+int itts_gemv_which(int B, int N, int K, int prologue, int x_bf16, int y_bf16, int w5) {
+  static const float partials = 0.f;  // prologue 3: a real call has its two partial buffers; the selector only asks whether they are there
+  GemvArgs g;
+  g.B = B, g.N = N, g.K = K, g.prologue = prologue, g.x_bf16 = x_bf16, g.y_bf16 = y_bf16;
+  if (prologue == 3) g.attn_o = g.attn_ml = &partials;
+  GemvPick p;
+  return gemv_bf16_pick(g, w5 != 0, &p) ? p.nb | p.rpw << 4 | p.nch << 8 | p.waves << 16 : -1;
+}
+
 int itts_layernorm(void* y, int dtype_y, const void* x, int dtype_x, const float* gamma, const float* beta, int rows,
                    int D, float eps, itts_stream stream) {
   (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)

@@ -4,7 +4,7 @@
 //
 // Reference hot loop: GPT2InferenceModel.forward, indextts/gpt/model.py:115-192 (HF 4.36.2 GPT2Block: LN -> c_attn ->
 // attention over the cache -> c_proj + residual -> LN -> c_fc -> gelu_new -> c_proj + residual).  The launch path
-// (decode2.hip, five graph-captured kernels per layer) is bound by its 120 dependent kernel boundaries per token, not by
+// (decode_gemv / decode_attn / decode_fused / decode_sampler.hip, five graph-captured kernels per layer) is bound by its 120 dependent kernel boundaries per token, not by
 // HBM.  Here every one of the chip's 256 CUs holds ONE 1024-thread workgroup for the whole step:
 //
 //   * each workgroup owns a fixed slice of every projection's output features (16 of c_attn - a head's q / k / v rows are
@@ -589,7 +589,7 @@ __device__ __forceinline__ void ln2_to_sxb(const float* __restrict__ xf, uint32_
 
 // ---------------------------------------------------------------------------------------------
 // ANC: beam rows - the cache is never re-ordered when the beams are; key j of beam row b lives in the physical row its
-// ancestry names (decode2.hip, decode_attn2_kernel<.., ANC>: the same gather, the same arithmetic)
+// ancestry names (decode_attn.hip, decode_attn2_kernel<.., ANC>: the same gather, the same arithmetic)
 // W8: every projection (and the head) streams its fp8-e4m3 copy - the bytes and per-row power-of-two scales of
 // gemv_bf16_kernel<.., W8> - through the same slots (half full), the same requests in the same order; y = dot * scale + bias
 template <int NB, bool ANC, bool W8>

@@ -1,5 +1,5 @@
 // Floating-point expressions of the <= 4-row decode step whose contraction must not be left to the compiler: the
-// persistent engine (decode_engine.hip) and the launch path (decode2.hip) have to produce the same bits, and hipcc fuses
+// persistent engine (decode_engine.hip) and the launch path (decode_gemv.hip, decode_attn.hip) have to produce the same bits, and hipcc fuses
 // `a * b + c` differently depending on what the SLP vectoriser found around it (measured: LayerNorm's variance came out
 // as fma(-md, md, Q / K) in one kernel and fma(Q, 1 / K, -(md * md)) in the other - a one-ulp difference in rstd that
 // flipped a bf16 rounding in block 20).  Every operation here is a single correctly rounded instruction.

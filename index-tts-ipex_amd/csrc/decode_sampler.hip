@@ -1,0 +1,255 @@
+// Samplers and step embedding of the launch path's decode step: sampler2_kernel (greedy), sampler_sample_kernel (do_sample=True),
+// each with the token commit and the next step's input embedding fused in (itts_sampler_dev.h), and decode_embed2_kernel, the
+// embedding of a step whose token the host supplies.
+#include "itts_decode.h"
+#include "itts_sampler_dev.h"
+#include "itts_wave_dev.h"
+
+namespace itts {
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// sampler2: repetition penalty + argmax + bookkeeping, one 1024-thread block per row; the per-row length
+// counter is advanced by the row's own block (no cross-block step counter, no extra launch).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void sampler2_kernel(SamplerArgs a) {
+  __shared__ float sv[16];
+  __shared__ int si[16];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* __restrict__ lg = a.logits + (size_t)b * a.V;
+  uint8_t* seen = a.seen + (size_t)b * a.V;
+  const int k_pre = a.step[b], unf_pre = a.unfinished[b];  // requested with the logits: nothing to wait for after the argmax
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  auto take = [&](float v, int i) {
+    if (v > best || (v == best && i < bi)) {
+      best = v;
+      bi = i;
+    }
+  };
+  auto score = [&](float v, int i) { return sampler_score(a, seen, v, i); };
+  // 8 consecutive logits per thread as two 16-byte loads (rows are dword aligned), the tail scalar
+  const int nvec = a.V >> 3;
+  for (int c = tid; c < nvec; c += 1024) {
+    const float4 q0 = *reinterpret_cast<const float4*>(lg + c * 8), q1 = *reinterpret_cast<const float4*>(lg + c * 8 + 4);
+    const float q[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) take(score(q[e], c * 8 + e), c * 8 + e);
+  }
+  for (int i = nvec * 8 + tid; i < a.V; i += 1024) take(score(lg[i], i), i);
+  // wave argmax without the LDS crossbar: DPP inside the 16-lane rows, v_permlane16/32_swap across them
+  auto merge = [&](float ov, int oi) {
+    if (ov > best || (ov == best && oi < bi)) {
+      best = ov;
+      bi = oi;
+    }
+  };
+#define SAMPLER_DPP(CTRL)                                                                                  \
+  merge(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best), CTRL, 0xf, 0xf, true)),       \
+        __builtin_amdgcn_update_dpp(0, bi, CTRL, 0xf, 0xf, true))
+  SAMPLER_DPP(0xB1);
+  SAMPLER_DPP(0x4E);
+  SAMPLER_DPP(0x141);
+  SAMPLER_DPP(0x140);
+#undef SAMPLER_DPP
+  {
+    const u32x2 v16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(best), __float_as_uint(best), false, false);
+    const u32x2 i16 = __builtin_amdgcn_permlane16_swap((unsigned)bi, (unsigned)bi, false, false);
+    best = __uint_as_float(v16[0]);
+    bi = (int)i16[0];
+    merge(__uint_as_float(v16[1]), (int)i16[1]);
+    const u32x2 v32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(best), __float_as_uint(best), false, false);
+    const u32x2 i32 = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
+    best = __uint_as_float(v32[0]);
+    bi = (int)i32[0];
+    merge(__uint_as_float(v32[1]), (int)i32[1]);
+  }
+  if (lane == 0) {
+    sv[wave] = best;
+    si[wave] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 16; ++w)
+      if (sv[w] > best || (sv[w] == best && si[w] < bi)) {
+        best = sv[w];
+        bi = si[w];
+      }
+    sampler_commit(a, b, bi, si, k_pre, unf_pre);
+  }
+  __syncthreads();
+  sampler_next_embedding(a, b, si, tid);
+}
+
+// ---------------------------------------------------------------------------------------------
+// sampler_sample: the do_sample=True path of HF 4.36.2 GenerationMixin.sample as infer.py:116-124 configures it
+// (RepetitionPenaltyLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax ->
+// multinomial), one 1024-thread block per row.  Scores live in LDS; the k-th largest score is found by a 4-pass
+// radix select on order-preserving keys (no sort of the vocabulary), the <= 128 survivors are bitonic-sorted by one
+// wave, top-p and the draw run serially over them in the order torch.cumsum uses.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
+  extern __shared__ float ssc[];  // [V] processed scores
+  __shared__ unsigned hist[256];
+  __shared__ int s_bin, s_k, s_cnt;
+  __shared__ float cval[BEAM_MAX_CAND];
+  __shared__ int cidx[BEAM_MAX_CAND];
+  __shared__ int si[2];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const float* __restrict__ lg = a.logits + (size_t)b * a.V;
+  const uint8_t* seen = a.seen + (size_t)b * a.V;
+  const int k_pre = a.step[b], unf_pre = a.unfinished[b];
+  for (int i = tid; i < a.V; i += 1024) {
+    float v = lg[i];
+    if (!a.preprocessed) {
+      if (a.penalty != 1.f && seen[i]) v = v < 0.f ? v * a.penalty : v / a.penalty;
+      if (a.suppress_stop && i == a.stop) v = -INFINITY;
+    }
+    if (a.temperature != 1.f) v = v / a.temperature;  // TemperatureLogitsWarper: scores / temperature
+    ssc[i] = v;
+  }
+  // ---- radix select: key of the top_k-th largest score ----
+  unsigned prefix = 0;
+  int kk = min(a.top_k, a.V);
+  for (int pass = 3; pass >= 0; --pass) {
+    const int shift = pass * 8;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < a.V; i0 += 1024) {  // every lane takes part in every round (wave-aggregated atomics)
+      const int i = i0 + tid;
+      const unsigned key = i < a.V ? order_key(ssc[i]) : 0u;
+      const bool act = i < a.V && (pass == 3 || (key >> (shift + 8)) == (prefix >> (shift + 8)));
+      hist_add_wave(hist, (key >> shift) & 255u, act, lane);
+    }
+    __syncthreads();
+    if (tid < 64) {
+      const unsigned h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+      const unsigned own = h0 + h1 + h2 + h3;
+      unsigned x = own;  // inclusive suffix sum over lanes (higher lanes = larger keys)
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const unsigned t = __shfl_down(x, off, 64);
+        if (lane + off < 64) x += t;
+      }
+      const unsigned above = x - own;
+      if (above < (unsigned)kk && (unsigned)kk <= x) {  // exactly one lane
+        unsigned acc = above;
+        int bin = 4 * lane + 3;
+        const unsigned hb[4] = {h0, h1, h2, h3};
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+          if (acc + hb[j] >= (unsigned)kk) {
+            bin = 4 * lane + j;
+            break;
+          }
+          acc += hb[j];
+        }
+        s_bin = bin;
+        s_k = kk - (int)acc;
+      }
+    }
+    __syncthreads();
+    prefix |= (unsigned)s_bin << shift;
+    kk = s_k;
+  }
+  // ---- gather the survivors (score >= k-th largest; ties kept as HF's `scores < kth` mask keeps them, up to BEAM_MAX_CAND) ----
+  if (tid == 0) s_cnt = 0;
+  if (tid < BEAM_MAX_CAND) {
+    cval[tid] = -INFINITY;
+    cidx[tid] = 0x7fffffff;
+  }
+  __syncthreads();
+  for (int i = tid; i < a.V; i += 1024) {
+    const float v = ssc[i];
+    // -inf scores never count: with fewer than top_k finite scores HF's `scores < kth` (kth = -inf) keeps exactly the finite ones
+    if (order_key(v) >= prefix && v > -INFINITY) {
+      const int pos = atomicAdd(&s_cnt, 1);
+      if (pos < BEAM_MAX_CAND) {
+        cval[pos] = v;
+        cidx[pos] = i;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 64) sort_cands_wave<true>(cval, cidx, lane);  // one wave, no barrier: descending score, ascending index on ties
+  __syncthreads();
+  if (tid < 64) {
+    // wave 0: the exponentials and quotients in parallel (lane r and r + 64 of the sorted candidates), the running sums
+    // sequentially in the restatement's order, every lane carrying them (values broadcast lane by lane)
+    const int n = min(s_cnt, BEAM_MAX_CAND);
+    const float m = cval[0];
+    const float e0 = lane < n ? expf(cval[lane] - m) : 0.f, e1 = lane + 64 < n ? expf(cval[lane + 64] - m) : 0.f;
+    auto ev = [&](int r) { return r < 64 ? lane_val(e0, r) : lane_val(e1, r - 64); };
+    float Z = 0.f;
+    for (int r = 0; r < n; ++r) Z += ev(r);
+    int R = n;
+    if (a.top_p < 1.f) {
+      // TopPLogitsWarper: ascending cumulative probability <= 1 - top_p is removed; the best token always stays
+      const float t0 = e0 / Z, t1 = e1 / Z;
+      float tail = 0.f;
+      R = 1;
+      for (int r = n - 1; r >= 1; --r) {
+        tail += r < 64 ? lane_val(t0, r) : lane_val(t1, r - 64);
+        if (!(tail <= 1.f - a.top_p)) {
+          R = r + 1;
+          break;
+        }
+      }
+    }
+    float total = 0.f;
+    for (int r = 0; r < R; ++r) total += ev(r);
+    const int k = k_pre;
+    const float u = a.uniforms[(size_t)min(k, a.max_gen - 1) * a.B + b];
+    const float target = u * total;
+    int pick = R - 1;
+    float c = 0.f;
+    for (int r = 0; r < R; ++r) {
+      c += ev(r);
+      if (c >= target) {
+        pick = r;
+        break;
+      }
+    }
+    if (lane == 0) sampler_commit(a, b, cidx[pick], si, k_pre, unf_pre);
+  }
+  __syncthreads();
+  sampler_next_embedding(a, b, si, tid);
+}
+
+template <typename TW>
+__global__ void decode_embed2_kernel(float* __restrict__ h, const TW* __restrict__ emb, const TW* __restrict__ pos,
+                                     const int* __restrict__ tok, const int* __restrict__ len, int D) {
+  const int b = blockIdx.x;
+  const int t = tok[b];
+  const int p = len[b] + 1;  // positions 0, 2, 3, ... (model.py:153-155)
+  for (int i = threadIdx.x; i < D; i += blockDim.x)
+    h[(size_t)b * D + i] = ldf(emb + (size_t)t * D + i) + ldf(pos + (size_t)p * D + i);
+}
+
+}  // namespace
+
+int sampler2_step(const SamplerArgs& a, int B, hipStream_t s) {
+  if (a.do_sample) {
+    ITTS_REQUIRE(a.uniforms && a.top_k >= 1 && a.top_k <= 128 && a.temperature > 0.f && a.top_p > 0.f && a.B == B,
+                 "sampler: sampling needs uniforms, 1 <= top_k <= 128, temperature > 0, top_p > 0");
+    ITTS_REQUIRE((size_t)a.V * 4 <= 60 * 1024, "sampler: vocabulary too large for the LDS-resident sampler");
+    hipLaunchKernelGGL(sampler_sample_kernel, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
+    ITTS_HIP_CHECK(hipGetLastError());
+    return OK;
+  }
+  hipLaunchKernelGGL(sampler2_kernel, dim3(B), dim3(1024), 0, s, a);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, const int* len, int B, int D, int tw,
+                  hipStream_t s) {
+  if (tw == F32)
+    hipLaunchKernelGGL(decode_embed2_kernel<float>, dim3(B), dim3(256), 0, s, h, (const float*)emb, (const float*)pos, tok, len, D);
+  else
+    hipLaunchKernelGGL(decode_embed2_kernel<bf16_t>, dim3(B), dim3(256), 0, s, h, (const bf16_t*)emb, (const bf16_t*)pos, tok, len, D);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+}  // namespace itts

@@ -138,7 +138,7 @@ struct DecodeState {
   size_t cache_bytes = 0;
   void *kc = nullptr, *vc = nullptr;  // [layers][B][H][Smax][dh]
   float *h = nullptr, *qkv = nullptr, *ctx = nullptr, *act = nullptr, *hn = nullptr, *logits = nullptr;
-  float *attn_o = nullptr, *attn_ml = nullptr;  // split decode attention partials (decode2.hip ATTN_NSPLIT), small batches
+  float *attn_o = nullptr, *attn_ml = nullptr;  // split decode attention partials (decode_attn.hip, ATTN_NSPLIT), small batches
   float* partial = nullptr;           // [4][B][D] split-K partial sums of the residual projections (batched decode)
   int pend_split = 0;                 // launch-time bookkeeping: partials waiting to be absorbed by the next LayerNorm
   const float* pend_bias = nullptr;
@@ -175,7 +175,7 @@ struct DecodeState {
   float *hyp_score = nullptr, *hyp_worst = nullptr;
   size_t beam_cap = 0;               // bytes-independent capacity key: rows * max_gen * Smax the beam buffers were sized for
   int beam_rows = 0, beam_gen = 0, beam_smax = 0;
-  // LN + c_attn + cache attention in one launch (decode2.hip qkv_attn_fused): per-layer granule buffers + error flag
+  // LN + c_attn + cache attention in one launch (decode_fused.hip qkv_attn_fused): per-layer granule buffers + error flag
   unsigned long long* gran = nullptr;  // [layers][cap_B <= 4][3 * D]
   int* fuse_err = nullptr;
   int fuse_failed = 0;                 // a hand-off timed out: two launches from then on

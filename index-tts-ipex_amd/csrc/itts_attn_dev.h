@@ -1,5 +1,5 @@
 // The per-key arithmetic of the single-query cache attention, ONE definition for the three kernels that must agree bit for bit:
-// decode_attn2_kernel and the attention part of qkv_attn_fused_kernel (decode2.hip, the launch path) and phase P2 of
+// decode_attn2_kernel (decode_attn.hip) and the attention part of qkv_attn_fused_kernel (decode_fused.hip), the launch path, and phase P2 of
 // decode_engine_kernel (decode_engine.hip) - tests/test_gpu_engine_persistent.py and tests/test_gpu_fullsize.py compare them.
 // Every kernel keeps its own skeleton (shared memory, the order of its loads, how it obtains this step's q / k / v, its waits
 // and stamps, where the result goes) and calls these through a one-line lambda of its own: that is the form in which the three
@@ -12,6 +12,33 @@
 #include "itts_wave_dev.h"
 
 namespace itts {
+
+// the register fragment of one K/V cache row as LPK lanes hold it (VEC dims each): decode_attn2_kernel (decode_attn.hip) and the
+// attention part of qkv_attn_fused_kernel (decode_fused.hip)
+template <typename TC> struct CacheVec;
+template <> struct CacheVec<bf16_t> {
+  static constexpr int VEC = 8, LPK = 8;
+  uint4 raw;
+#ifdef ITTS_KV_PLAIN_LOADS
+  __device__ __forceinline__ void load(const bf16_t* p) { raw = *reinterpret_cast<const uint4*>(p); }
+#else
+  // the cache is read once per step and never again before it has left every cache: nontemporal (streaming) loads
+  __device__ __forceinline__ void load(const bf16_t* p) {
+    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+    raw = make_uint4(t[0], t[1], t[2], t[3]);
+  }
+#endif
+  __device__ __forceinline__ float get(int i) const {
+    const uint32_t w = (&raw.x)[i >> 1];
+    return (i & 1) ? half_hi(w) : half_lo(w);
+  }
+};
+template <> struct CacheVec<float> {
+  static constexpr int VEC = 4, LPK = 16;
+  float4 raw;
+  __device__ __forceinline__ void load(const float* p) { raw = *reinterpret_cast<const float4*>(p); }
+  __device__ __forceinline__ float get(int i) const { return (&raw.x)[i]; }
+};
 
 // score of one key row for this slot (the LPK lanes of the key hold VEC dims each; DPP sums them: quad swaps, half-row mirror, row
 // mirror - no LDS crossbar trips)

@@ -1,4 +1,4 @@
-// Decode-step kernels (decode.hip).
+// Decode-step kernels: decode.hip (first generation), decode_gemv / decode_attn / decode_fused / decode_sampler.hip, decode_mfma.hip.
 #pragma once
 #include "itts_common.h"
 
@@ -147,20 +147,26 @@ int double_ln(float* y, const float* x, const float* g1, const float* b1, const 
               int D, float eps, hipStream_t s);
 int kv_scatter(void* kc, void* vc, const void* qkv, int B, int S, int H, int dh, int Smax, int tq, int tc, hipStream_t s);
 
-// second generation (decode2.hip)
+// second generation, one file per kernel family.  decode_gemv.hip:
 bool gemv2_supported(const GemvArgs& g);
 int gemv2(const GemvArgs& g, int tw, hipStream_t s);
+// the bf16 GEMV's selector: false = gemv_bf16 has no kernel for this call, else the instantiation it launches (the prologue and
+// the two element types stay what GemvArgs says).  w5: the ITTS_GEMV_W5 rows.  No GPU work (itts_gemv_which)
+struct GemvPick { int nb, rpw, nch, waves; };
+bool gemv_bf16_pick(const GemvArgs& g, bool w5, GemvPick* p);
+bool gemv_bf16_supported(const GemvArgs& g);  // gemv_bf16_pick(g, false, ..)
+int gemv_bf16(const GemvArgs& g, hipStream_t s);
+// decode_attn.hip
+constexpr int ATTN_NSPLIT = 4;  // workgroups per (row, head) in the split form of decode_attn2
 int decode_attn2(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
                  const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled = 0,
                  float* part_o = nullptr, float* part_ml = nullptr, const uint8_t* anc = nullptr, int nb = 1);
-// LN + c_attn projection and the cache attention of one layer in one launch (decode2.hip qkv_attn_fused_kernel)
+// decode_fused.hip: LN + c_attn projection and the cache attention of one layer in one launch (qkv_attn_fused_kernel)
 bool qkv_attn_fused_supported(const GemvArgs& g, int H, int dh);
 int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* kc, void* vc, const int* len,
                    const int* kv_start, const int* prefix_dev, int H, int dh, int Smax, float* part_o, float* part_ml,
                    const uint8_t* anc, int nb, hipStream_t s);
-constexpr int ATTN_NSPLIT = 4;  // workgroups per (row, head) in the split form of decode_attn2
-bool gemv_bf16_supported(const GemvArgs& g);
-int gemv_bf16(const GemvArgs& g, hipStream_t s);
+// decode_sampler.hip
 int sampler2_step(const SamplerArgs& a, int B, hipStream_t s);
 int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, const int* len, int B, int D, int tw,
                   hipStream_t s);

@@ -1,6 +1,6 @@
-// Device-side bookkeeping shared by the sampler kernels (decode2.hip) and the persistent decode engine's in-launch greedy
+// Device-side bookkeeping shared by the sampler kernels (decode_sampler.hip) and the persistent decode engine's in-launch greedy
 // sampler (decode_engine.hip): HF greedy search / sample() commit of one token per row + the next step's input embedding.
-// sampler_sample_kernel (decode2.hip) and beam_cand_kernel (beam.hip) share sort_cands_wave: one order, one tie rule.
+// sampler_sample_kernel (decode_sampler.hip) and beam_cand_kernel (beam.hip) share sort_cands_wave: one order, one tie rule.
 #pragma once
 #include "itts_decode.h"
 

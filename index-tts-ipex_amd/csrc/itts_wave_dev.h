@@ -1,7 +1,7 @@
 // Wave-level device helpers shared by kernels that must produce the same bits as each other: the launch path's decode GEMVs
-// and attention (decode2.hip) and the persistent decode engine (decode_engine.hip) reduce with the same tree, the same slot
+// and attention (decode_gemv.hip, decode_attn.hip, decode_fused.hip) and the persistent decode engine (decode_engine.hip) reduce with the same tree, the same slot
 // butterflies (wave_bfly_max / wave_bfly_sum: decode_attn2_kernel, qkv_attn_fused_kernel, the engine's attention phase) and pack
-// with the same rounding because both include this file; the single-beam sampler (decode2.hip) and the beam kernels (beam.hip)
+// with the same rounding because both include this file; the single-beam sampler (decode_sampler.hip) and the beam kernels (beam.hip)
 // share the top-k primitives (order_key, hist_add_wave).
 #pragma once
 #include "itts_common.h"

@@ -1,7 +1,7 @@
 """GPU: parity at the BENCHMARK shapes (L = 105 text tokens, 660 decode steps so S passes 768, latent T = 480, 64 vocoder
 frames) against fixtures produced by the real reference modules (oracle/make_golden.py --long).  Every variant of the
 cache-attention kernel is driven past its register window, so the streaming online-softmax loop
-(csrc/decode2.hip `for (int cb = 2 * NIT; ...)`) executes under an oracle comparison:
+(csrc/decode_attn.hip `for (int cb = 2 * NIT; ...)`) executes under an oracle comparison:
 
   engine  rows  kernel                                   register window (keys)
   fp32    1, 2  decode_attn2<float, 1024 threads>        384

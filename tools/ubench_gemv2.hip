@@ -1,4 +1,4 @@
-// Phase timeline of the PRODUCTION decode GEMV (decode2.hip compiled with -DITTS_GEMV_STAMPS) for the four projections
+// Phase timeline of the PRODUCTION decode GEMV (decode_gemv.hip and decode_attn.hip compiled with -DITTS_GEMV_STAMPS) for the four projections
 // of one GPT layer at 2 rows.  Ticks are s_memtime counts; only differences inside one block are meaningful.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iindex-tts-ipex_amd/csrc -Iinclude -DITTS_GEMV_STAMPS -o /tmp/ug2 tools/ubench_gemv2.hip
 #include <hip/hip_runtime.h>
@@ -7,7 +7,8 @@
 #include <vector>
 #include <algorithm>
 namespace itts { static thread_local std::string g_err; void set_error(const std::string& m) { g_err = m; } const char* last_error() { return g_err.c_str(); } }
-#include "../index-tts-ipex_amd/csrc/decode2.hip"
+#include "../index-tts-ipex_amd/csrc/decode_gemv.hip"
+#include "../index-tts-ipex_amd/csrc/decode_attn.hip"
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1;} } while (0)
 using namespace itts;
 
