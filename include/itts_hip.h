@@ -99,6 +99,17 @@ int itts_gemv(float* Y, const float* X, const void* W, const float* bias, int B,
               int prologue, const float* ln_gamma, const float* ln_beta, const float* ln2_gamma, const float* ln2_beta,
               int dtype_w, int version, itts_stream stream);
 
+/* The bf16 decode GEMV of the launch path (1-4 rows, csrc/decode_gemv.hip gemv_bf16), as the decode step calls it:
+ * Y[b, n] (+)= act(prologue(X)[b, :] . W[n, :] + bias[n]), X [B, K] fp32 or bf16 (x_bf16), Y [B, N] fp32 or bf16 (y_bf16, no
+ * accumulate), W bf16 [N, K] - or W8, [N, K] OCP e4m3 bytes with one fp32 scale per output row (wscale), used instead of W when
+ * set.  bias may be null.  prologue 0 none (bf16 X), 1 LayerNorm without affine (eps 1e-5; fp32 X), 2 LayerNorm(ln_gamma,
+ * ln_beta) then LayerNorm without affine (fp32 X), 3 X is merged from the split-attention partials attn_o
+ * [B][K/64][4][64] / attn_ml [B][K/64][2][4] (X unused, K % 64 == 0).  Calls itts_gemv_which answers -1 for are refused with an
+ * error and nothing is launched; ITTS_GEMV_MODE / ITTS_GEMV_W5 (read once per process) choose the kernel form as in the engine. */
+int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W, const float* bias, int B, int N, int K, int act,
+                   int accumulate, int prologue, const float* ln_gamma, const float* ln_beta, const float* attn_o,
+                   const float* attn_ml, const void* W8, const float* wscale, itts_stream stream);
+
 /* Decode-step projections at batch > 4 (same Conv1D call sites): X bf16 [B, K], W bf16 [N, K], weights streamed once,
  * batch on MFMA; Y fp32 [B, N] (store, or += when accumulate) or bf16 when y_bf16.  K % 32 == 0, B <= 128.
  * ksplit > 1 splits K over workgroups: raw sums go to partial[ksplit][B][N] (no bias / act / Y), to be absorbed by

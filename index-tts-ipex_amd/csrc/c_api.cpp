@@ -123,6 +123,21 @@ int itts_gemv(float* Y, const float* X, const void* W, const float* bias, int B,
   return gemv(g, dtype_w, (hipStream_t)stream);
 }
 
+int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W, const float* bias, int B, int N, int K, int act,
+                   int accumulate, int prologue, const float* ln_gamma, const float* ln_beta, const float* attn_o,
+                   const float* attn_ml, const void* W8, const float* wscale, itts_stream stream) {
+  (void)hipGetLastError();
+  GemvArgs g;
+  g.X = (const float*)X; g.x_bf16 = x_bf16; g.W = W; g.Y = (float*)Y; g.y_bf16 = y_bf16; g.bias = bias; g.B = B; g.N = N; g.K = K;
+  g.ldy = N; g.act = act; g.accumulate = accumulate; g.prologue = prologue; g.ln_gamma = ln_gamma; g.ln_beta = ln_beta;
+  g.attn_o = attn_o; g.attn_ml = attn_ml; g.W8 = W8; g.wscale = wscale;
+  if (prologue == 2 && !(ln_gamma && ln_beta)) {  // the kernel reads both unconditionally
+    set_error("itts_gemv_bf16: prologue 2 needs ln_gamma and ln_beta");
+    return E_INVALID;
+  }
+  return gemv_bf16(g, (hipStream_t)stream);
+}
+
 int itts_skinny_gemm(void* Y, int y_bf16, const void* X, const void* W, const float* bias, int B, int N, int K, int act,
                      int accumulate, int ksplit, float* partial, int layout, itts_stream stream) {
   (void)hipGetLastError();

@@ -688,6 +688,9 @@ bool gemv_bf16_pick(const GemvArgs& g, bool w5, GemvPick* p) {
   // the shapes of the decode step; rows per wave from the tools/ubench_gemv.hip sweep
   p->nb = g.B;
   p->nch = nch <= 1 ? 1 : nch <= 3 ? 3 : nch <= 4 ? 4 : 10;
+  // gemv_bf16_kernel masks only its last chunk: every earlier one must lie inside K (fp32 x at 2 chunks would run the 3-chunk
+  // kernel, bf16 x at 5-9 chunks the 10-chunk one, reading the next row's weights and activations); those calls fall to gemv2
+  if (g.K < (p->nch - 1) * 512) return false;
   p->rpw = nch <= 1 ? 1 : g.prologue == 2 ? 4 : 2;  // micro configs 1, the head 4, the per-layer projections 2
   p->waves = 4;
   if (w5 && g.B <= 2) {

@@ -598,9 +598,11 @@ int Engine::head_and_sample(hipStream_t s, bool have_logits, bool sampled) {
     g.W8 = gpt.head.w8;
     g.wscale = gpt.head.wscale;
     ITTS_TRY(gemv_bf16(g, s));
-  } else if (gemv2_supported(g)) {
+  } else if (gemv2_supported(g) && !(adt == BF16 && D <= 2048)) {
     ITTS_TRY(gemv2(g, gpt.head.dt, s));
   } else {
+    // (also the bf16 engine at a width the bf16 GEMV refuses: gemv2 hands the elements of its LayerNorm rows to the threads by
+    // their position in the batch, so identical rows would differ in the last ulp; these two kernels treat every row alike)
     ITTS_TRY(double_ln(ds.hn, ds.h, gpt.ln_f.g, gpt.ln_f.b, nullptr, nullptr, B, D, 1e-5f, s));
     g.X = ds.hn;
     g.prologue = 0;
@@ -923,6 +925,9 @@ int Engine::decode_step_launch(hipStream_t s) {
       return gemv_bf16(g, s);
     }
     ITTS_REQUIRE(!g.x_bf16 && !g.y_bf16, "decode: bf16 activation without the bf16 GEMV");
+    // the bf16 engine's rows do not depend on their place in the batch: gemv2 maps the elements of its LayerNorm rows to threads
+    // by batch position (its sums differ in the last ulp between identical rows), the generic kernel maps every row alike
+    if (adt == BF16 && g.prologue == 1) return gemv(g, dt, s);
     return gemv2_supported(g) ? gemv2(g, dt, s) : gemv(g, dt, s);
   };
   GemvArgs probe;

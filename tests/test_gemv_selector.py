@@ -6,7 +6,11 @@ The expectations were written down from the commit BEFORE the selector existed, 
 `gemv_bf16_supported()` (restated here as parent_supported) and the if-ladder `dispatch_gemv_bf16<NB>()` (PINNED).  One corner
 the two did not agree on, kept as it was: fp32 input with prologue 3 passes the gate (K <= 1536) although no kernel is
 instantiated for it - gemv_bf16 answers "no instantiation for this shape"; no caller builds that call.  It is part of the
-acceptance sweep and left out of PINNED."""
+acceptance sweep and left out of PINNED.
+
+One thing the selector changed on purpose since: the block-cooperative kernel masks only its last 512-column chunk, so a call
+is taken only when K reaches that chunk, K >= (NCH - 1) * 512.  parent_supported stays the parent's table; the sweep expects it
+less exactly those calls (test_dropped_calls_are_the_two_unmasked_ranges)."""
 import itertools
 
 import pytest
@@ -93,11 +97,36 @@ def sweep(which):
     return {c: which(*c) for c in itertools.product(range(6), NS, KS, range(4), (0, 1), (0, 1))}
 
 
+def ladder_nch(K):
+    """The chunk count compiled into the kernel a call gets, as the ladder states it: 1, 3, 4 or 10 chunks of 512 columns."""
+    nch = (K + 511) // 512
+    return 1 if nch <= 1 else 3 if nch <= 3 else 4 if nch <= 4 else 10
+
+
 def test_acceptance_set_unchanged(sweep):
+    """What the parent accepted, less the calls whose K does not reach the kernel's last chunk: gemv_bf16_kernel masks only chunk
+    NCH - 1, so every earlier chunk has to lie inside K (K >= (NCH - 1) * 512)."""
     assert len(sweep) == 6 * len(NS) * len(KS) * 4 * 2 * 2
-    wrong = [c for c, got in sweep.items() if (got is not None) != parent_supported(c[0], c[2], c[3], c[4], c[5])]
+    want = {c: parent_supported(c[0], c[2], c[3], c[4], c[5]) and c[2] >= (ladder_nch(c[2]) - 1) * 512 for c in sweep}
+    wrong = [c for c, got in sweep.items() if (got is not None) != want[c]]
     assert not wrong, (len(wrong), wrong[:8])
     assert sum(got is not None for got in sweep.values()) > 10000  # the sweep does reach the accepted side
+
+
+def test_dropped_calls_are_the_two_unmasked_ranges(sweep):
+    """Relative to the parent exactly two K ranges left the acceptance set: fp32 x at two chunks (512 < K < 1024, which ran the
+    3-chunk kernel) and bf16 x at 2048 < K < 4608 (5 to 9 chunks, which ran the 10-chunk kernel).  Nothing was added."""
+    dropped = {c for c, got in sweep.items() if got is None and parent_supported(c[0], c[2], c[3], c[4], c[5])}
+    added = [c for c, got in sweep.items() if got is not None and not parent_supported(c[0], c[2], c[3], c[4], c[5])]
+    assert not added, added[:8]
+    fp32_two_chunks = {c for c in sweep if parent_supported(c[0], c[2], c[3], c[4], c[5]) and not c[4] and 512 < c[2] < 1024}
+    bf16_mid = {c for c in sweep if parent_supported(c[0], c[2], c[3], c[4], c[5]) and c[4] and 2048 < c[2] < 4608}
+    assert dropped == fp32_two_chunks | bf16_mid
+    assert fp32_two_chunks and bf16_mid and not (fp32_two_chunks & bf16_mid)
+    assert {(c[2] + 511) // 512 for c in fp32_two_chunks} == {2} and {(c[2] + 511) // 512 for c in bf16_mid} == {5, 6, 7, 8, 9}
+    assert {c[2] for c in fp32_two_chunks} == {K for K in KS if K % 8 == 0 and 512 < K < 1024}
+    assert {c[2] for c in bf16_mid} == {K for K in KS if K % 8 == 0 and 2048 < K < 4608}
+    assert {c[3] for c in fp32_two_chunks} == {1, 2, 3} and {c[3] for c in bf16_mid} == {0}  # (bf16 x, prologue 3 never had 5+ chunks)
 
 
 def test_acceptance_does_not_depend_on_w5(which, sweep):
