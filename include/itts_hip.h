@@ -110,6 +110,17 @@ int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W
                    int accumulate, int prologue, const float* ln_gamma, const float* ln_beta, const float* attn_o,
                    const float* attn_ml, const void* W8, const float* wscale, itts_stream stream);
 
+/* One sampler launch of the decode step (csrc/decode_sampler.hip) on caller memory, stateless: HF 4.36.2 sample() for B rows -
+ * RepetitionPenalty (seen: [B, V] bytes, non-zero = the row has seen the id; null = none) and stop suppression (both skipped
+ * when preprocessed) -> / temperature -> TopK -> TopP -> the inverse-CDF draw of uniforms[b] over the kept tokens in
+ * descending-score order (lower id first on ties).  logits fp32 [B, V]; tok int32 [B] the drawn ids; kept int32 [B] the number
+ * of tokens that survived the warpers.  1 <= top_k <= 128 runs the narrow kernel (V <= 15360; kept is then -1), top_k <= 0
+ * (TopK off) or > 128 the whole-vocabulary kernel (V <= 16384).  scratch: B * (V + 16) bytes, 4-byte aligned, overwritten;
+ * no caller array is modified.  0 < top_p <= 1, temperature > 0. */
+int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
+                     int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
+                     void* scratch, size_t scratch_bytes, itts_stream stream);
+
 /* Decode-step projections at batch > 4 (same Conv1D call sites): X bf16 [B, K], W bf16 [N, K], weights streamed once,
  * batch on MFMA; Y fp32 [B, N] (store, or += when accumulate) or bf16 when y_bf16.  K % 32 == 0, B <= 128.
  * ksplit > 1 splits K over workgroups: raw sums go to partial[ksplit][B][N] (no bias / act / Y), to be absorbed by
@@ -174,7 +185,9 @@ int itts_ecapa(itts_engine* e, const void* mel_bfc, int B, int F, float* spk_out
  * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax -> one draw).  The draw is the inverse CDF
  * of uniforms_host[k * B + b] (step k, row b; host array of n_uniforms >= max_gen * B floats in [0, 1)) over the kept
  * tokens in descending-score order, so a caller-side RNG fixes the sequence.  do_sample = 0 returns to greedy.
- * 1 <= top_k <= 128, 0 < top_p <= 1, temperature > 0. */
+ * Any top_k: <= 0 switches the TopK warper off (HF `top_k = 0 / None`, stored as 0); 1 .. 128 runs the narrow sampler, 0 and
+ * > 128 the whole-vocabulary sampler (number_mel_codes <= 16384; parallel fp32 sums: the same distribution as torch's, the
+ * top-p boundary within 64 * 2^-24 of it).  0 < top_p <= 1, temperature > 0. */
 int itts_gpt_set_sampling(itts_engine* e, int do_sample, int top_k, float top_p, float temperature, const float* uniforms_host,
                           int64_t n_uniforms);
 

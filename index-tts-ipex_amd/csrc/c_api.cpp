@@ -138,6 +138,37 @@ int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W
   return gemv_bf16(g, (hipStream_t)stream);
 }
 
+int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
+                     int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
+                     void* scratch, size_t scratch_bytes, itts_stream stream) {
+  (void)hipGetLastError();
+  if (!tok || !kept || !logits || !uniforms || !scratch || B < 1 || V < 1 || stop < 0 || stop >= V || ((uintptr_t)scratch & 3) ||
+      scratch_bytes < (size_t)B * ((size_t)V + 16)) {
+    set_error("itts_sample_rows: bad arguments (tok, kept, logits, uniforms, a 4-byte aligned scratch of B * (V + 16) bytes, 0 <= stop < V)");
+    return E_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // the samplers' bookkeeping of a one-step generation, on the caller's scratch: step 0, every row running, a private copy of
+  // the seen bytes (the commit marks the drawn token in it)
+  int* step = (int*)scratch;
+  int* unfinished = step + B;
+  int* ids = unfinished + B;
+  uint8_t* seen_copy = (uint8_t*)(ids + B);
+  ITTS_HIP_CHECK(hipMemsetAsync(step, 0, (size_t)B * 4, s));
+  ITTS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)unfinished, 1, (size_t)B, s));
+  if (seen)
+    ITTS_HIP_CHECK(hipMemcpyAsync(seen_copy, seen, (size_t)B * V, hipMemcpyDeviceToDevice, s));
+  else
+    ITTS_HIP_CHECK(hipMemsetAsync(seen_copy, 0, (size_t)B * V, s));
+  ITTS_HIP_CHECK(hipMemsetAsync(kept, 0xFF, (size_t)B * 4, s));  // -1: the narrow kernel does not report it
+  SamplerArgs a;
+  a.logits = logits; a.seen = seen_copy; a.ids = ids; a.cur_tok = tok; a.unfinished = unfinished; a.step = step;
+  a.V = V; a.max_gen = 1; a.stop = stop; a.suppress_stop = suppress_stop; a.penalty = penalty; a.preprocessed = preprocessed;
+  a.do_sample = 1; a.top_k = top_k < 1 ? 0 : top_k; a.B = B; a.top_p = top_p; a.temperature = temperature; a.uniforms = uniforms;
+  a.kept = kept;
+  return sampler2_step(a, B, s);
+}
+
 int itts_skinny_gemm(void* Y, int y_bf16, const void* X, const void* W, const float* bias, int B, int N, int K, int act,
                      int accumulate, int ksplit, float* partial, int layout, itts_stream stream) {
   (void)hipGetLastError();

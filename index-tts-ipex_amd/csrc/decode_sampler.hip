@@ -1,6 +1,9 @@
-// Samplers and step embedding of the launch path's decode step: sampler2_kernel (greedy), sampler_sample_kernel (do_sample=True),
+// Samplers and step embedding of the launch path's decode step: sampler2_kernel (greedy), sampler_sample_kernel (do_sample=True,
+// 1 <= top_k <= 128), sampler_wide_kernel (do_sample=True over the whole vocabulary: top_k < 1 or > 128),
 // each with the token commit and the next step's input embedding fused in (itts_sampler_dev.h), and decode_embed2_kernel, the
 // embedding of a step whose token the host supplies.
+#include <atomic>
+
 #include "itts_decode.h"
 #include "itts_sampler_dev.h"
 #include "itts_wave_dev.h"
@@ -216,6 +219,195 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
   sampler_next_embedding(a, b, si, tid);
 }
 
+// ---------------------------------------------------------------------------------------------
+// sampler_wide: the same HF 4.36.2 sample() step when the TopK warper is off (top_k < 1) or wider than the 128 candidates
+// sampler_sample_kernel keeps (top_k > 128): thousands of tokens can survive, so the whole vocabulary is sorted.  One
+// 1024-thread block per row, V <= 16384:
+//   1. scores (sampler_score, / temperature) and ids into LDS, padded to NP = the power of two >= max(V, 1024)
+//   2. block bitonic sort: descending score, lower id first on ties; -inf scores and the padding sort last and never count
+//   3. TopK (top_k >= 1 only): the n ranks whose score is >= the score at rank min(top_k, V) - 1 stay (ties with it stay, as
+//      HF's `scores < kth` mask keeps them); without TopK the n finite scores
+//   4. TopP (top_p < 1): e_r = expf(s_r - s_0); rank r >= 1 goes iff tail_r = sum_{j >= r} e_j <= (1 - top_p) * tail_0
+//   5. draw: the first of the R kept ranks whose inclusive prefix sum of e is >= u * (the sum over the R ranks), else R - 1
+//   6. sampler_commit / sampler_next_embedding, as in the other samplers
+// Sums: every thread owns a run of NP / 1024 (<= 16) consecutive ranks; tail_r and the prefix sums are block scans of the run
+// sums (wave scan by shuffles, then the sums of the other waves in wave order) finished inside the run - no fp32 atomics, the
+// same bits on every run and in every batch.  The longest chain of dependent fp32 additions behind any sum is 53: <= 15 for
+// a run's own sum, 6 levels of the wave scan, <= 15 wave sums, 1 to join them with the wave's part, <= 16 along the run.
+// ---------------------------------------------------------------------------------------------
+constexpr int WIDE_MAX_V = 16384;  // NP * 6 bytes of LDS: 96 KiB
+
+// exclusive block scan of one value per thread in thread order (REV: from the last thread down); one barrier
+template <bool REV>
+__device__ __forceinline__ float wide_scan_excl(float mine, float* wsum, int lane, int wave) {
+  float inc = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = REV ? __shfl_down(inc, o, 64) : __shfl_up(inc, o, 64);
+    if (REV ? lane + o < 64 : lane >= o) inc += t;
+  }
+  float ex = REV ? __shfl_down(inc, 1, 64) : __shfl_up(inc, 1, 64);
+  if (lane == (REV ? 63 : 0)) ex = 0.f;
+  if (lane == (REV ? 0 : 63)) wsum[wave] = inc;
+  __syncthreads();
+  float wb = 0.f;
+  if (REV) {
+    for (int w = 15; w > wave; --w) wb += wsum[w];
+  } else {
+    for (int w = 0; w < wave; ++w) wb += wsum[w];
+  }
+  return wb + ex;
+}
+
+__global__ __launch_bounds__(1024) void sampler_wide_kernel(SamplerArgs a, int NP) {
+  extern __shared__ unsigned char wsm[];
+  float* keys = reinterpret_cast<float*>(wsm);                                     // [NP] scores, sorted in place
+  unsigned short* idx = reinterpret_cast<unsigned short*>(wsm + (size_t)NP * 4);  // [NP] their token ids
+  __shared__ float wsum_tail[16], wsum_pre[16];
+  __shared__ float s_thr, s_total;
+  __shared__ int s_n, s_R, s_pick;
+  __shared__ int si[2];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = a.V;
+  const float* __restrict__ lg = a.logits + (size_t)b * V;
+  const uint8_t* seen = a.seen + (size_t)b * V;
+  const int k_pre = a.step[b], unf_pre = a.unfinished[b];
+  const float u = a.uniforms[(size_t)min(k_pre, a.max_gen - 1) * a.B + b];
+  if (tid == 0) {
+    s_n = 0;
+    s_R = 1;  // the best token always stays
+    s_pick = 0x7fffffff;
+  }
+  for (int i = tid; i < NP; i += 1024) {
+    float v = -INFINITY;
+    if (i < V) {
+      v = sampler_score(a, seen, lg[i], i);
+      if (a.temperature != 1.f) v = v / a.temperature;  // TemperatureLogitsWarper: scores / temperature
+      v = v > -INFINITY ? v : -INFINITY;                 // (a NaN would leave the sort without an order)
+    }
+    keys[i] = v;
+    idx[i] = (unsigned short)(i < V ? i : 0xFFFF);  // the padding sorts behind every -inf score
+  }
+  __syncthreads();
+  // ---- bitonic sort: descending score, ascending id on ties ----
+  auto compare_swap = [&](int t, int j, int kk) {
+    const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+    const bool up = (lo & kk) == 0;
+    const float k0 = keys[lo], k1 = keys[hi];
+    const unsigned short i0 = idx[lo], i1 = idx[hi];
+    const bool behind = k0 < k1 || (k0 == k1 && i0 > i1);  // entry lo belongs behind entry hi
+    if (behind == up) {
+      keys[lo] = k1;
+      keys[hi] = k0;
+      idx[lo] = i1;
+      idx[hi] = i0;
+    }
+  };
+  for (int kk = 2; kk <= NP; kk <<= 1) {
+    int j = kk >> 1;
+    for (; j > 64; j >>= 1) {
+      for (int t = tid; t < NP / 2; t += 1024) compare_swap(t, j, kk);
+      __syncthreads();
+    }
+    // j <= 64: the 64 comparators of a wave stay inside 128 entries no other wave touches, and a wave's LDS operations
+    // execute in program order (sort_cands_wave): these stages need no workgroup barrier
+    for (int t = tid; t < NP / 2; t += 1024)
+      for (int jj = j; jj > 0; jj >>= 1) {
+        compare_swap(t, jj, kk);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      }
+    __syncthreads();
+  }
+  // ---- TopK: the kept ranks are a prefix [0, n) of the sorted order ----
+  const int per = NP >> 10, r0 = tid * per;  // this thread's run of ranks
+  const float s0 = keys[0];
+  const float kth = a.top_k >= 1 ? keys[min(a.top_k, V) - 1] : -INFINITY;
+  float e[16];
+  int nk = 0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    e[q] = 0.f;
+    if (q < per) {
+      const float v = keys[r0 + q];
+      if (v >= kth && v > -INFINITY) {
+        e[q] = expf(v - s0);
+        ++nk;
+      }
+    }
+  }
+  if (nk) atomicAdd(&s_n, nk);
+  __syncthreads();
+  const int n = max(s_n, 1);  // (no finite score at all: rank 0, the lowest id, is drawn)
+  // ---- TopP: tail_r by a block scan from the last rank down ----
+  int R = n;
+  if (a.top_p < 1.f) {  // block-uniform
+    float mine = 0.f;
+#pragma unroll
+    for (int q = 15; q >= 0; --q)
+      if (q < per) mine += e[q];
+    const float base = wide_scan_excl<true>(mine, wsum_tail, lane, wave);
+    if (tid == 0) {
+      float c = base;
+#pragma unroll
+      for (int q = 15; q >= 0; --q)
+        if (q < per) c += e[q];
+      s_thr = (1.f - a.top_p) * c;  // c = tail_0 = Z
+    }
+    __syncthreads();
+    const float thr = s_thr;
+    float c = base;
+    int rmax = 0;
+#pragma unroll
+    for (int q = 15; q >= 0; --q)
+      if (q < per) {
+        c += e[q];
+        const int r = r0 + q;
+        if (r >= 1 && r < n && !(c <= thr)) rmax = max(rmax, r + 1);
+      }
+    if (rmax) atomicMax(&s_R, rmax);
+    __syncthreads();
+    R = s_R;
+  }
+  // ---- draw: inverse CDF of u over the R kept ranks ----
+  float mine = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+    if (q < per) {
+      if (r0 + q >= R) e[q] = 0.f;
+      mine += e[q];
+    }
+  const float base = wide_scan_excl<false>(mine, wsum_pre, lane, wave);
+  {
+    float c = base;
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      if (q < per) {
+        c += e[q];
+        if (r0 + q == R - 1) s_total = c;
+      }
+  }
+  __syncthreads();
+  const float target = u * s_total;
+  {
+    float c = base;
+    int first = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      if (q < per) {
+        c += e[q];
+        if (r0 + q < R && c >= target) first = min(first, r0 + q);
+      }
+    if (first != 0x7fffffff) atomicMin(&s_pick, first);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int pick = min(s_pick, R - 1);
+    if (a.kept) a.kept[b] = R;
+    sampler_commit(a, b, idx[pick], si, k_pre, unf_pre);
+  }
+  __syncthreads();
+  sampler_next_embedding(a, b, si, tid);
+}
+
 template <typename TW>
 __global__ void decode_embed2_kernel(float* __restrict__ h, const TW* __restrict__ emb, const TW* __restrict__ pos,
                                      const int* __restrict__ tok, const int* __restrict__ len, int D) {
@@ -228,12 +420,32 @@ __global__ void decode_embed2_kernel(float* __restrict__ h, const TW* __restrict
 
 }  // namespace
 
+// sampler_wide_kernel's 96 KiB of dynamic LDS have to be allowed once on every device ordinal that launches it; gpt_prefill
+// calls this outside the capture of the decode step
+int sampler_wide_prepare() {
+  static std::atomic<int> done_on[64];
+  int dev = 0;
+  ITTS_HIP_CHECK(hipGetDevice(&dev));
+  if (done_on[dev & 63].load(std::memory_order_acquire)) return OK;
+  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)sampler_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_MAX_V * 6));
+  done_on[dev & 63].store(1, std::memory_order_release);
+  return OK;
+}
+
 int sampler2_step(const SamplerArgs& a, int B, hipStream_t s) {
   if (a.do_sample) {
-    ITTS_REQUIRE(a.uniforms && a.top_k >= 1 && a.top_k <= 128 && a.temperature > 0.f && a.top_p > 0.f && a.B == B,
-                 "sampler: sampling needs uniforms, 1 <= top_k <= 128, temperature > 0, top_p > 0");
-    ITTS_REQUIRE((size_t)a.V * 4 <= 60 * 1024, "sampler: vocabulary too large for the LDS-resident sampler");
-    hipLaunchKernelGGL(sampler_sample_kernel, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
+    ITTS_REQUIRE(a.uniforms && a.temperature > 0.f && a.top_p > 0.f && a.B == B,
+                 "sampler: sampling needs uniforms, temperature > 0, top_p > 0");
+    if (a.top_k >= 1 && a.top_k <= BEAM_MAX_CAND) {
+      ITTS_REQUIRE((size_t)a.V * 4 <= 60 * 1024, "sampler: vocabulary too large for the LDS-resident sampler");
+      hipLaunchKernelGGL(sampler_sample_kernel, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
+    } else {  // TopK off or wider than the narrow kernel's candidates: the whole vocabulary
+      ITTS_REQUIRE(a.V >= 1 && a.V <= WIDE_MAX_V, "sampler: top_k outside [1, 128] needs a vocabulary of at most 16384");
+      ITTS_TRY(sampler_wide_prepare());
+      int np = 1024;
+      while (np < a.V) np <<= 1;
+      hipLaunchKernelGGL(sampler_wide_kernel, dim3(B), dim3(1024), (size_t)np * 6, s, a, np);
+    }
     ITTS_HIP_CHECK(hipGetLastError());
     return OK;
   }

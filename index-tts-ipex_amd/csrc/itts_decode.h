@@ -79,6 +79,7 @@ struct SamplerArgs {
   const int* forced = nullptr;  // [B][max_gen]
   int input_n = 0;  // the first input_n forced tokens are HF `input_tokens`: token k is fed at mel position k + 1, not k + 2
   int preprocessed = 0;  // logits already went through typical_filter (penalty, stop suppression done)
+  int* kept = nullptr;   // [B] sampler_wide_kernel writes the number of kept ranks here (the operator entry point sets it)
 };
 
 // one beam-sample step for every batch item (beam.hip): HF 4.36.2 beam_sample + BeamSearchScorer.process on the device
@@ -168,6 +169,7 @@ int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* 
                    const uint8_t* anc, int nb, hipStream_t s);
 // decode_sampler.hip
 int sampler2_step(const SamplerArgs& a, int B, hipStream_t s);
+int sampler_wide_prepare();  // once per device ordinal, outside graph capture: sampler_wide_kernel's dynamic LDS limit
 int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, const int* len, int B, int D, int tw,
                   hipStream_t s);
 

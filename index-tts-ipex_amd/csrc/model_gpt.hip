@@ -476,6 +476,7 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
     ITTS_HIP_CHECK(hipGetLastError());
   }
   if (engine_usable()) ITTS_TRY(ensure_engine_state(s));  // allocations must not happen inside the graph capture of the step
+  if (ds.do_sample && nbeam == 1 && (ds.top_k < 1 || ds.top_k > BEAM_MAX_CAND)) ITTS_TRY(sampler_wide_prepare());  // nor this
   if (ds.do_sample || (nbeam > 1 && beam_do_sample && !ds.host_sample)) {
     const size_t need_u = nbeam > 1 ? (size_t)max_gen * B_items * 2 * nbeam : (size_t)max_gen * B;
     ITTS_REQUIRE(sample_uniforms.size() >= need_u,
@@ -1009,18 +1010,18 @@ int Engine::decode_step_launch(hipStream_t s) {
 }
 
 // HF GenerationMixin.sample configuration of infer.py:116-124 (do_sample, top_k, top_p, temperature); the random
-// draws are supplied by the caller as uniforms in [0, 1), one per (step, row): row-major [max_gen][B]
+// draws are supplied by the caller as uniforms in [0, 1), one per (step, row): row-major [max_gen][B].  Any top_k: <= 0 is HF's
+// "TopK warper off"
 int Engine::gpt_set_sampling(int do_sample, int top_k, float top_p, float temperature, const float* uniforms_host, long n) {
   if (!do_sample) {
     ds.do_sample = 0;
     sample_uniforms.clear();
     return OK;
   }
-  ITTS_REQUIRE(top_k >= 1 && top_k <= 128, "gpt_set_sampling: top_k must be in [1, 128]");
   ITTS_REQUIRE(top_p > 0.f && top_p <= 1.f && temperature > 0.f, "gpt_set_sampling: need 0 < top_p <= 1 and temperature > 0");
   ITTS_REQUIRE(uniforms_host && n > 0, "gpt_set_sampling: uniforms missing");
   ds.do_sample = 1;
-  ds.top_k = top_k;
+  ds.top_k = top_k < 1 ? 0 : top_k;  // 0: HF's TopK warper off; 0 and > 128 run on sampler_wide_kernel (sampler2_step)
   ds.top_p = top_p;
   ds.temperature = temperature;
   sample_uniforms.assign(uniforms_host, uniforms_host + n);

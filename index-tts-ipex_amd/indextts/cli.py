@@ -15,6 +15,9 @@ def build_parser():
     p.add_argument("--fp32", action="store_true", help="fp32 parity engine")
     p.add_argument("-f", "--force", action="store_true", default=False)
     p.add_argument("-d", "--device", type=str, default=None)
+    p.add_argument("--wide-sampler", choices=("device", "host"), default=None,
+                   help="where sampling with one beam and top_k = 0 or > 128 picks its tokens: host (torch's arithmetic, one sync per "
+                        "token; the default) or device (the whole-vocabulary HIP sampler); unset: ITTS_WIDE_SAMPLER")
     p.add_argument("--gpt-fp8", action="store_true", default=False,
                    help="store the GPT weights as fp8-e4m3 (bfloat16 engine; the decode steps stream the fp8 bytes)")
     return p
@@ -38,7 +41,8 @@ def main():
         sys.exit(1)
     from indextts.infer import IndexTTS
 
-    tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8)
+    tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8,
+                   wide_sampler=a.wide_sampler)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

@@ -4,6 +4,7 @@ as tensor-in / tensor-out calls.  torch is used for device memory and streams on
 from __future__ import annotations
 
 import ctypes as C
+import os
 import threading
 from typing import Dict, List, Optional, Tuple
 
@@ -319,14 +320,23 @@ class Engine:
                  suppress_stop: bool = False, check_every: int = 16, do_sample: bool = False, top_k: int = 30,
                  top_p: float = 0.8, temperature: float = 1.0, seed: Optional[int] = None,
                  uniforms: Optional[np.ndarray] = None, num_beams: int = 1, typical_mass: float = 0.0,
-                 length_penalty: float = 0.0, num_return_sequences: int = 1) -> np.ndarray:
+                 length_penalty: float = 0.0, num_return_sequences: int = 1, wide_sampler: Optional[str] = None) -> np.ndarray:
         """Greedy decode (do_sample=False, num_beams=1 of tests/padding_test.py:35-46) or, with do_sample, HF
         GenerationMixin.sample (top-k / top-p / temperature, num_beams=1; draws from `uniforms` or a numpy Generator
         seeded with `seed`).  Returns int64 codes [B, n] with n <= max_gen: HF stops when every row has emitted stop
         or at max length.  num_beams > 1: HF beam_sample (do_sample; uniforms [max_gen, B, 2 * num_beams]) or beam_search
         (not do_sample) over num_beams beams per row; returns the best finalized hypothesis per row, or with
-        num_return_sequences = n the n best of every row ([B * n, len], best first)."""
-        kw = dict(repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
+        num_return_sequences = n the n best of every row ([B * n, len], best first).
+        wide_sampler: how do_sample with one beam and top_k outside 1 .. 128 (0 / None = HF's TopK warper off) runs - "host"
+        (the default): the token choice on the host with torch's arithmetic, bit for bit, one stream sync per token; "device":
+        sampler_wide_kernel, no sync per token, graph replay - the same distribution with parallel fp32 sums, so the top-p
+        boundary and the draw agree with the host's to 64 * 2^-24 of the mass, not to the last bit.  None: the environment's
+        ITTS_WIDE_SAMPLER, else "host".  Requests with beams ignore it."""
+        if wide_sampler is None:
+            wide_sampler = os.environ.get("ITTS_WIDE_SAMPLER") or "host"
+        if wide_sampler not in ("host", "device"):
+            raise ValueError(f"wide_sampler must be 'host' or 'device', not {wide_sampler!r}")
+        kw = dict(wide_sampler=wide_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, uniforms=uniforms, num_beams=num_beams,
                   typical_mass=typical_mass, length_penalty=length_penalty, num_return_sequences=num_return_sequences)
         try:
@@ -339,19 +349,23 @@ class Engine:
             return self._generate_once(cond, text_ids, max_gen, **kw)
 
     def _generate_once(self, cond, text_ids, max_gen, repetition_penalty, suppress_stop, check_every, do_sample, top_k, top_p,
-                       temperature, seed, uniforms, num_beams, typical_mass, length_penalty, num_return_sequences) -> np.ndarray:
+                       temperature, seed, uniforms, num_beams, typical_mass, length_penalty, num_return_sequences,
+                       wide_sampler="host") -> np.ndarray:
         beams = num_beams > 1
         if num_return_sequences != 1 and not beams:
             raise ValueError("num_return_sequences > 1 without beams: repeat the rows (indextts/gpt/model.py does, as HF does)")
         nrow = np.asarray(text_ids).shape[0]
         if do_sample and (not top_k or int(top_k) < 1 or int(top_k) > 128):
-            # HF: TopK warper off (top_k = 0 / None) or wider than the device samplers' 128 candidates - exact on the host
+            # HF: TopK warper off (top_k = 0 / None) or wider than the narrow device samplers' 128 candidates - exact on the
+            # host, or (one beam, wide_sampler="device") the whole-vocabulary device sampler through the ordinary loop below
             if beams:
                 return self._generate_host_beams(cond, text_ids, max_gen, repetition_penalty, suppress_stop, int(top_k or 0), top_p,
                                                  temperature, seed, uniforms, typical_mass, num_beams, length_penalty,
                                                  num_return_sequences)
-            return self._generate_host_sampled(cond, text_ids, max_gen, repetition_penalty, suppress_stop, int(top_k or 0), top_p,
-                                               temperature, seed, uniforms, typical_mass)
+            if wide_sampler != "device":
+                return self._generate_host_sampled(cond, text_ids, max_gen, repetition_penalty, suppress_stop, int(top_k or 0),
+                                                   top_p, temperature, seed, uniforms, typical_mass)
+            top_k = int(top_k or 0)
         typical = bool(typical_mass)
         if typical:  # typical_sampling=True (model.py:690-697): TypicalLogitsWarper behind the repetition penalty, in every mode
             self._ck(self.lib.itts_gpt_set_typical(self.h, float(typical_mass)), "gpt_set_typical")
@@ -398,7 +412,8 @@ class Engine:
                                uniforms, typical_mass) -> np.ndarray:
         """HF sample() with the token choice on the host (infer_core.host_sample_step: warpers over the WHOLE vocabulary): the
         step stops behind the head GEMV, the logits come back, the chosen tokens go in through itts_gpt_commit.  One stream
-        sync per token - the price of a mode the device samplers (<= 128 kept candidates) do not cover."""
+        sync per token - the price of torch's own arithmetic, bit for bit.  generate(wide_sampler="device") runs the same mode on
+        the device (sampler_wide_kernel: no sync per token; parallel fp32 sums, equal to this path within 64 * 2^-24 of the mass)."""
         from . import infer_core
 
         nrow = np.asarray(text_ids).shape[0]

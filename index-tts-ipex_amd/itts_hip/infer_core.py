@@ -83,9 +83,11 @@ def sampling_kwargs(do_sample, num_beams, top_k, top_p, temperature, typical_sam
       typical_sampling               the reference's TypicalLogitsWarper(typical_mass) behind the repetition penalty - a logits
                                      PROCESSOR in the reference (model.py:690-697), so greedy and beam search run it too
     Limits of the device samplers (the web UI offers num_beams 1..10 and top_k 0..100): num_beams <= 10; at most 128 kept
-    candidates per row.  top_k = 0 / None (HF: TopK warper off) or > 128 is exact all the same: the token choice then runs
-    on the host over the whole vocabulary (host_sample_step / host_beam_step below, one logits read-back per token) - with
-    one beam or several.  The seed is drawn from torch's global RNG so that torch.manual_seed governs the run as it does for
+    candidates per row in the narrow samplers.  top_k = 0 / None (HF: TopK warper off) or > 128 is exact all the same: by default
+    the token choice then runs on the host over the whole vocabulary (host_sample_step / host_beam_step below, one logits
+    read-back per token) - with one beam or several.  With one beam, Engine.generate(wide_sampler="device") / ITTS_WIDE_SAMPLER=device
+    runs it on the whole-vocabulary device sampler instead (no read-back; the same distribution, parallel fp32 sums: top-p
+    boundary and draw within 64 * 2^-24 of the mass of torch's).  The seed is drawn from torch's global RNG so that torch.manual_seed governs the run as it does for
     the reference's torch.multinomial."""
     import warnings
 
