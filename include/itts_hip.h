@@ -121,6 +121,22 @@ int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uin
                      int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
                      void* scratch, size_t scratch_bytes, itts_stream stream);
 
+/* The whole-vocabulary beam sampler (csrc/beam.hip beam_wide_cand_kernel + beam_wide_pick_kernel) on caller memory, stateless: one
+ * step of HF 4.36.2 beam_sample up to (not including) BeamSearchScorer.process for `items` batch items of num_beams beams.  Per
+ * beam row: log_softmax -> RepetitionPenalty over fake_id, start_tok and the row's k ids (ids int32 [items * num_beams][ids_stride],
+ * may be null when k = 0) -> stop suppression (all three skipped when preprocessed) -> / temperature -> TopK (top_k >= 1 only,
+ * min_tokens_to_keep = 2, ties with the k-th score stay) -> TopP (min_tokens_to_keep = 2) -> + beam_scores[row]; then 2 * num_beams
+ * draws without replacement by inverse CDF of uniforms [items][2 * num_beams] over the item's kept tokens in flat (beam-major,
+ * token-ascending) order.  pick_score / pick_tok / pick_beam [items][2 * num_beams] in draw order, kept int32 [items * num_beams].
+ * Always these two kernels, 1 <= top_k <= 128 included.  All pointers are device pointers; scratch: (items * num_beams * (V + 1) +
+ * items) * 4 bytes, 4-byte aligned, overwritten.  V <= 16384, 2 <= num_beams <= 10, top_p > 0, temperature > 0: anything else is
+ * refused with an error status before any launch. */
+int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_beam, int32_t* kept, const float* logits,
+                          const int32_t* ids, int ids_stride, int k, const float* beam_scores, int items, int num_beams, int V,
+                          float penalty, int stop, int suppress_stop, int start_tok, int fake_id, int preprocessed, int top_k,
+                          float top_p, float temperature, const float* uniforms, void* scratch, size_t scratch_bytes,
+                          itts_stream stream);
+
 /* Decode-step projections at batch > 4 (same Conv1D call sites): X bf16 [B, K], W bf16 [N, K], weights streamed once,
  * batch on MFMA; Y fp32 [B, N] (store, or += when accumulate) or bf16 when y_bf16.  K % 32 == 0, B <= 128.
  * ksplit > 1 splits K over workgroups: raw sums go to partial[ksplit][B][N] (no bias / act / Y), to be absorbed by
@@ -206,8 +222,10 @@ int itts_gpt_set_beam_sample(itts_engine* e, int num_beams, int top_k, float top
 /* The general beam entry point (itts_gpt_set_beam_sample = do_sample 1, length_penalty 0): do_sample = 0 selects HF
  * beam_search - deterministic, per step the 2 * num_beams best of log_softmax + repetition penalty + beam score, no warpers,
  * no uniforms - which is what `num_beams > 1, do_sample=False` means to generate(); length_penalty enters
- * BeamHypotheses' score = sum_logprobs / generated_len ** length_penalty (infer.py:121 passes 0.0).  2 <= num_beams <= 10,
- * top_k <= 128 (the web UI offers num_beams 1..10, top_k 0..100). */
+ * BeamHypotheses' score = sum_logprobs / generated_len ** length_penalty (infer.py:121 passes 0.0).  2 <= num_beams <= 10
+ * (the web UI offers num_beams 1..10, top_k 0..100).  do_sample with any top_k: <= 0 switches the TopK warper off (HF `top_k = 0 /
+ * None`, stored as 0); 1 .. 128 runs the narrow pair of kernels, 0 and > 128 the whole-vocabulary pair (number_mel_codes <= 16384;
+ * parallel fp32 sums: the same distribution as torch's, boundaries within 512 * 2^-24 of the mass of it). */
 int itts_gpt_set_beams(itts_engine* e, int num_beams, int do_sample, int top_k, float top_p, float temperature, float length_penalty,
                        const float* uniforms_host, int64_t n_uniforms);
 
@@ -268,6 +286,12 @@ int itts_gpt_commit(itts_engine* e, const int32_t* tokens_host, itts_stream stre
 int itts_gpt_beam_state(itts_engine* e, int32_t* ids_host, float* scores_host, int32_t* done_host, int* step_host, itts_stream stream);
 int itts_gpt_commit_beams(itts_engine* e, const float* pick_score_host, const int32_t* pick_tok_host, const int32_t* pick_beam_host,
                           itts_stream stream);
+
+/* After a step of a device-sampled beam generation with top_k <= 0 or > 128 (no host sampling): that step's 2 * num_beams picks
+ * per batch item IN DRAW ORDER (score_host, tok_host, beam_host: [B][2 * num_beams]) and the number of tokens every beam row kept
+ * behind the warpers (kept_host int32 [B * num_beams]), copied from the sampler's device buffers; any pointer may be null.  An item
+ * that was already done, and a step that took a given `input_tokens` token, leave the earlier content in place. */
+int itts_gpt_beam_picks(itts_engine* e, float* score_host, int32_t* tok_host, int32_t* beam_host, int32_t* kept_host, itts_stream stream);
 
 /* G1/G3/G4 step 0: prepare_gpt_inputs (model.py:591-654) + prefill + first greedy token.
  * cond fp32 [latents, D]; text ids host int32 [B, L] (may hold start/stop padding ids, stripped per row).

@@ -13,6 +13,12 @@
 // (finished hypotheses, worst score, done test).  Then all threads re-order what the beams own: id histories and the
 // KV-cache ancestry rows (see decode_attn2_kernel ANC - the cache itself is never copied), and prepare the next
 // step's input embeddings.
+//
+// top_k < 1 (HF: TopK warper off) or > BEAM_MAX_CAND: thousands of tokens per beam can survive, so beam_wide_cand_kernel sorts
+// each beam row's whole vocabulary and beam_wide_pick_kernel draws over the flat nb * V scores; beam_select_kernel then takes the
+// picks in draw order exactly as it takes the host's (BeamArgs::host_sc / host_tok / host_beam): three launches per step.
+#include <atomic>
+
 #include "itts_decode.h"
 #include "itts_sampler_dev.h"
 #include "itts_wave_dev.h"
@@ -511,6 +517,233 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(BeamArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// beam_sample over the whole vocabulary (top_k < 1 or > BEAM_MAX_CAND), first launch.  Grid (nb, B), one 1024-thread workgroup
+// per beam row, V <= 16384, dynamic LDS NP * 6 bytes with NP = the power of two >= max(V, 1024):
+//   1. scores as beam_cand_kernel computes them (log_softmax unless preprocessed, repetition penalty over the beam's own id
+//      history, stop suppression, / temperature), NaN -> -inf, with their ids into LDS
+//   2. wide_sort_desc: descending score, lower id first on ties; -inf scores and the padding sort last and never count
+//   3. TopK (top_k >= 1 only): kk = min(max(top_k, 2), V); the n ranks whose score is >= the score at rank kk - 1 stay (HF masks
+//      `scores < kth`); without TopK the n finite scores
+//   4. TopP (top_p < 1, min_tokens_to_keep = 2): e_r = expf(s_r - s_0); rank r >= 2 goes iff tail_r = sum_{j >= r} e_j <=
+//      (1 - top_p) * tail_0; R = clamp(last staying rank + 1, 2, n) (n when n < 2)
+//   5. in token order: w.sc[row][t] = score + beam_scores[row] for the R kept tokens, -inf for every other t < V; w.kept[row] = R
+// Sums.  log-sum-exp: <= 16 strided terms per thread, 6 butterfly levels, 16 wave sums in order (beam_cand_kernel's block_sum).
+// tail_r: a thread's run of NP / 1024 <= 16 consecutive ranks, wide_scan_excl from the last thread down, finished inside the
+// run.  The longest chain of dependent fp32 additions behind any sum of this kernel is 53: <= 15 for a run's own sum, 6 levels
+// of the wave scan, <= 15 wave sums, 1 to join them with the wave's part, <= 16 along the run.  No fp32 atomics.
+// Nothing is written when the step is past the end (graph replays), the batch item is done, or the step takes a given token.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void beam_wide_cand_kernel(BeamArgs a, BeamWide w, int NP) {
+  extern __shared__ unsigned char bwsm[];
+  float* keys = reinterpret_cast<float*>(bwsm);                                     // [NP] scores, sorted in place
+  unsigned short* idx = reinterpret_cast<unsigned short*>(bwsm + (size_t)NP * 4);  // [NP] their token ids
+  __shared__ unsigned seenw[512];  // V <= 16384 bits
+  __shared__ float red[16], wsum_tail[16];
+  __shared__ float s_thr;
+  __shared__ int s_n, s_R;
+  const int r = blockIdx.x, bi = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = a.nb, V = a.V, Beff = a.B * nb, mg = a.max_gen;
+  const int k = a.len[bi * nb];
+  if ((k >= mg && !w.one_step) || a.done[bi] || (a.forced && k < a.input_n)) return;  // block-uniform
+  const int* ids_old = w.one_step ? a.ids : a.ids + (size_t)(k & 1) * Beff * mg;
+  const int row = bi * nb + r;
+  const float* __restrict__ lg = a.logits + (size_t)row * V;
+  if (tid == 0) {
+    s_n = 0;
+    s_R = 2;  // min_tokens_to_keep
+  }
+  // ---- log_softmax (a.preprocessed: the typical pre-pass already did this, the penalty and the suppression) ----
+  float lse = 0.f;
+  if (!a.preprocessed) {
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, lg[i]);
+    mx = block_max(mx, red, tid);
+    float se = 0.f;
+    for (int i = tid; i < V; i += 1024) se += expf(lg[i] - mx);
+    se = block_sum(se, red, tid);
+    lse = mx + logf(se);
+  }
+  // ---- ids this beam has seen: the fake prompt ids + its history (ids outside the vocabulary have no score to penalise) ----
+  for (int i = tid; i < (V + 31) / 32; i += 1024) seenw[i] = 0u;
+  __syncthreads();
+  if (tid == 0) {
+    if ((unsigned)a.fake_id < (unsigned)V) atomicOr(&seenw[a.fake_id >> 5], 1u << (a.fake_id & 31));
+    if ((unsigned)a.start_tok < (unsigned)V) atomicOr(&seenw[a.start_tok >> 5], 1u << (a.start_tok & 31));
+  }
+  for (int i = tid; i < k; i += 1024) {
+    const int t = ids_old[(size_t)row * mg + i];
+    if ((unsigned)t < (unsigned)V) atomicOr(&seenw[t >> 5], 1u << (t & 31));
+  }
+  __syncthreads();
+  for (int i = tid; i < NP; i += 1024) {
+    float v = -INFINITY;
+    if (i < V) {
+      v = lg[i] - lse;
+      if (!a.preprocessed) {
+        if (a.penalty != 1.f && ((seenw[i >> 5] >> (i & 31)) & 1u)) v = v < 0.f ? v * a.penalty : v / a.penalty;
+        if (a.suppress_stop && i == a.stop) v = -INFINITY;
+      }
+      if (a.temperature != 1.f) v = v / a.temperature;
+      v = v > -INFINITY ? v : -INFINITY;  // (a NaN would leave the sort without an order)
+    }
+    keys[i] = v;
+    idx[i] = (unsigned short)(i < V ? i : 0xFFFF);  // the padding sorts behind every -inf score
+  }
+  __syncthreads();
+  wide_sort_desc(keys, idx, NP, tid);
+  // ---- TopK: the kept ranks are a prefix [0, n) of the sorted order ----
+  const int per = NP >> 10, r0 = tid * per;  // this thread's run of ranks
+  const float s0 = keys[0];
+  const float kth = a.top_k >= 1 ? keys[min(max(a.top_k, 2), V) - 1] : -INFINITY;
+  float e[16];
+  int nk = 0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    e[q] = 0.f;
+    if (q < per) {
+      const float v = keys[r0 + q];
+      if (v >= kth && v > -INFINITY) {
+        e[q] = expf(v - s0);
+        ++nk;
+      }
+    }
+  }
+  if (nk) atomicAdd(&s_n, nk);
+  __syncthreads();
+  const int n = s_n;
+  // ---- TopP: tail_r by a block scan from the last rank down ----
+  int R = n;
+  if (a.top_p < 1.f) {  // block-uniform
+    float mine = 0.f;
+#pragma unroll
+    for (int q = 15; q >= 0; --q)
+      if (q < per) mine += e[q];
+    const float base = wide_scan_excl<true>(mine, wsum_tail, lane, wave);
+    if (tid == 0) {
+      float c = base;
+#pragma unroll
+      for (int q = 15; q >= 0; --q)
+        if (q < per) c += e[q];
+      s_thr = (1.f - a.top_p) * c;  // c = tail_0 = Z
+    }
+    __syncthreads();
+    const float thr = s_thr;
+    float c = base;
+    int rmax = 0;
+#pragma unroll
+    for (int q = 15; q >= 0; --q)
+      if (q < per) {
+        c += e[q];
+        const int rk = r0 + q;
+        if (rk >= 2 && rk < n && !(c <= thr)) rmax = max(rmax, rk + 1);
+      }
+    if (rmax) atomicMax(&s_R, rmax);
+    __syncthreads();
+    R = min(max(s_R, 2), n);
+  }
+  // ---- the kept tokens' scores, beam score included, in token order; every other token of the row -inf ----
+  const float bs = a.beam_scores[row];
+  float* __restrict__ out = w.sc + (size_t)row * V;
+  for (int j = tid; j < NP; j += 1024) {
+    const unsigned short ix = idx[j];
+    if (ix != 0xFFFF) out[ix] = j < R ? keys[j] + bs : -INFINITY;  // (every token id sits at exactly one rank)
+  }
+  if (tid == 0) w.kept[row] = R;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Second launch: grid (B), one 1024-thread workgroup per batch item, the 2 * nb draws WITHOUT replacement over the item's
+// nb * V scores of w.sc in flat order f = r * V + t (beam-major, token-ascending: next_token_scores.view(batch, beams * vocab),
+// the order of infer_core.host_beam_step).  -inf entries are dead; m = the largest score, e_f = expf(s_f - m).
+// Thread t owns the run of L = ceil(nb * V / 1024) <= 160 consecutive entries from t * L (the part of a run beyond nb * V is
+// masked).  Per draw j: the run sums go through wide_scan_excl (wave scan, then the other waves' sums in wave order); total =
+// the 16 wave sums added in wave order; target = uniforms[(k * B + bi) * 2 nb + j] * total; every thread walks its run from its
+// scan base, and the pick is the first live f whose inclusive prefix is >= target - the last live entry when there is none.
+// The picked entry becomes -inf in w.sc (it contributes exactly 0.0f from then on) and only its owner re-walks its run for the
+// new run sum: every sum keeps one fixed association, so the picks repeat bit for bit in any batch and under graph replay.
+// No fp32 atomics.  The longest chain of dependent fp32 additions behind any sum is L + 6 + 15 + 1 + L (<= 342): <= L for a
+// run's own sum, 6 levels of the wave scan, <= 15 wave sums, 1 to join them with the wave's part, <= L along the run.
+// With no live entry left the pick is (-inf, stop, 0), as in beam_select_kernel.  Picks go to w.pick_* [B][2 * nb] in draw order.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void beam_wide_pick_kernel(BeamArgs a, BeamWide w) {
+  __shared__ float red[16], wsum[16];
+  __shared__ int s_pick, s_last;
+  const int bi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = a.nb, V = a.V, nd = 2 * nb, N = nb * V;
+  const int k = a.len[bi * nb];
+  if ((k >= a.max_gen && !w.one_step) || a.done[bi] || (a.forced && k < a.input_n)) return;  // block-uniform, as beam_wide_cand_kernel
+  float* sc = w.sc + (size_t)bi * N;
+  const int L = (N + 1023) >> 10, f0 = min(tid * L, N), f1 = min(f0 + L, N);
+  const float* u = a.uniforms + (w.one_step ? (size_t)bi : (size_t)k * a.B + bi) * nd;
+  if (tid == 0) {
+    s_pick = 0x7fffffff;
+    s_last = -1;
+  }
+  float mloc = -INFINITY;
+  for (int f = f0; f < f1; ++f) mloc = fmaxf(mloc, sc[f]);
+  const float m = block_max(mloc, red, tid);  // (-inf: no live entry at all)
+  // this thread's run: the sum of its live e_f in flat order, and its last live entry
+  float mine = 0.f;
+  int last = -1;
+  for (int f = f0; f < f1; ++f) {
+    const float v = sc[f];
+    if (v > -INFINITY) {
+      mine += expf(v - m);
+      last = f;
+    }
+  }
+  for (int j = 0; j < nd; ++j) {
+    const float base = wide_scan_excl<false>(mine, wsum, lane, wave);
+    float total = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) total += wsum[q];
+    const float target = u[j] * total;
+    if (last >= 0) {
+      float c = base;
+      for (int f = f0; f <= last; ++f) {
+        const float v = sc[f];
+        if (v > -INFINITY) {
+          c += expf(v - m);
+          if (c >= target) {
+            atomicMin(&s_pick, f);
+            break;
+          }
+        }
+      }
+      atomicMax(&s_last, last);
+    }
+    __syncthreads();
+    const int pick = s_pick != 0x7fffffff ? s_pick : s_last;
+    __syncthreads();  // every thread has read the pick: thread 0 may reset it
+    if (tid == 0) {
+      s_pick = 0x7fffffff;  // (the barrier of the next draw's scan lies between this and the next atomicMin)
+      s_last = -1;
+      if (pick < 0) {  // fewer live candidates than picks: repeat a stop
+        w.pick_sc[(size_t)bi * nd + j] = -INFINITY;
+        w.pick_tok[(size_t)bi * nd + j] = a.stop;
+        w.pick_beam[(size_t)bi * nd + j] = 0;
+      }
+    }
+    if (pick >= f0 && pick < f1) {  // the owner: record, kill, re-walk the run
+      const int rb = pick / V;
+      w.pick_sc[(size_t)bi * nd + j] = sc[pick];
+      w.pick_tok[(size_t)bi * nd + j] = pick - rb * V;
+      w.pick_beam[(size_t)bi * nd + j] = rb;
+      sc[pick] = -INFINITY;
+      mine = 0.f;
+      last = -1;
+      for (int f = f0; f < f1; ++f) {
+        const float v = f == pick ? -INFINITY : sc[f];
+        if (v > -INFINITY) {
+          mine += expf(v - m);
+          last = f;
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // TypicalLogitsWarper as a pre-pass (the reference's optional `typical_sampling=True`, gpt/model.py:690-697 +
 // utils/typical_sampling.py:9-30): HF places it in the logits_processor list right after RepetitionPenalty, i.e. before
 // the Temperature / TopK / TopP warpers.  One 1024-thread workgroup per row: processed scores (log_softmax first under
@@ -661,10 +894,49 @@ int typical_filter(const TypicalArgs& a, int rows, hipStream_t s) {
   return OK;
 }
 
-int beam_sample_step(const BeamArgs& a, hipStream_t s) {
+// beam_wide_cand_kernel's 96 KiB of dynamic LDS have to be allowed once on every device ordinal that launches it; gpt_prefill
+// calls this outside the capture of the decode step
+int beam_wide_prepare() {
+  static std::atomic<int> done_on[64];
+  int dev = 0;
+  ITTS_HIP_CHECK(hipGetDevice(&dev));
+  if (done_on[dev & 63].load(std::memory_order_acquire)) return OK;
+  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)beam_wide_cand_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BEAM_WIDE_MAX_V * 6));
+  done_on[dev & 63].store(1, std::memory_order_release);
+  return OK;
+}
+
+int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s) {
+  ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB && a.B >= 1, "beam_sample (whole vocabulary): 2 <= num_beams <= 10");
+  ITTS_REQUIRE(a.V >= 2 && a.V <= BEAM_WIDE_MAX_V, "beam_sample: top_k outside [1, 128] needs a vocabulary of at most 16384");
+  ITTS_REQUIRE(a.top_p > 0.f && a.temperature > 0.f, "beam_sample: top_p > 0, temperature > 0");
+  ITTS_REQUIRE(a.stop >= 0 && a.stop < a.V && a.max_gen >= 1, "beam_sample: stop token outside the vocabulary");
+  ITTS_REQUIRE(a.logits && a.uniforms && a.ids && a.len && a.done && a.beam_scores, "beam_sample: null state");
+  ITTS_REQUIRE(w.sc && w.kept && w.pick_sc && w.pick_tok && w.pick_beam, "beam_sample: whole-vocabulary scratch missing");
+  ITTS_TRY(beam_wide_prepare());
+  int np = 1024;
+  while (np < a.V) np <<= 1;
+  hipLaunchKernelGGL(beam_wide_cand_kernel, dim3(a.nb, a.B), dim3(1024), (size_t)np * 6, s, a, w, np);
+  hipLaunchKernelGGL(beam_wide_pick_kernel, dim3(a.B), dim3(1024), 0, s, a, w);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w) {
   ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB, "beam_sample: 2 <= num_beams <= 10");
-  ITTS_REQUIRE(!a.do_sample || (a.top_k >= 1 && a.top_k <= BEAM_MAX_CAND && a.top_p > 0.f && a.temperature > 0.f),
-               "beam_sample: 1 <= top_k <= 128, top_p > 0, temperature > 0");
+  if (a.do_sample && (a.top_k < 1 || a.top_k > BEAM_MAX_CAND)) {  // TopK off or wider than beam_cand_kernel's candidates
+    ITTS_REQUIRE(w, "beam_sample: whole-vocabulary scratch missing");
+    ITTS_REQUIRE(a.anc && a.hyp_tok, "beam_sample: null state");
+    ITTS_TRY(beam_wide_pair(a, *w, s));
+    BeamArgs sel = a;  // beam_select_kernel takes the picks in draw order where it takes the host's
+    sel.host_sc = w->pick_sc;
+    sel.host_tok = w->pick_tok;
+    sel.host_beam = w->pick_beam;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(1024), 0, s, sel);
+    ITTS_HIP_CHECK(hipGetLastError());
+    return OK;
+  }
+  ITTS_REQUIRE(!a.do_sample || (a.top_p > 0.f && a.temperature > 0.f), "beam_sample: top_p > 0, temperature > 0");
   ITTS_REQUIRE(a.V <= 15000, "beam_sample: vocabulary too large for the LDS-resident sampler");
   ITTS_REQUIRE(a.logits && (a.uniforms || !a.do_sample) && a.ids && a.anc && a.len && a.hyp_tok && a.done, "beam_sample: null state");
   ITTS_REQUIRE(a.cand_sc && a.cand_tok && a.cand_n, "beam_sample: candidate scratch missing");

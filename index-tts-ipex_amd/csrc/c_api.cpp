@@ -169,6 +169,49 @@ int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uin
   return sampler2_step(a, B, s);
 }
 
+int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_beam, int32_t* kept, const float* logits,
+                          const int32_t* ids, int ids_stride, int k, const float* beam_scores, int items, int num_beams, int V,
+                          float penalty, int stop, int suppress_stop, int start_tok, int fake_id, int preprocessed, int top_k,
+                          float top_p, float temperature, const float* uniforms, void* scratch, size_t scratch_bytes,
+                          itts_stream stream) {
+  (void)hipGetLastError();
+  if (!pick_score || !pick_tok || !pick_beam || !kept || !logits || !beam_scores || !uniforms || !scratch || items < 1 || k < 0 ||
+      (k > 0 && (!ids || ids_stride < k)) || ((uintptr_t)scratch & 3)) {
+    set_error("itts_beam_sample_rows: bad arguments (picks, kept, logits, beam_scores, uniforms, a 4-byte aligned scratch; ids [rows][ids_stride >= k])");
+    return E_INVALID;
+  }
+  if (num_beams < 2 || num_beams > 10 || V < 2 || V > BEAM_WIDE_MAX_V || stop < 0 || stop >= V || start_tok < 0 || start_tok >= V ||
+      fake_id < 0 || fake_id >= V || !(top_p > 0.f) || !(temperature > 0.f)) {
+    set_error("itts_beam_sample_rows: 2 <= num_beams <= 10, 2 <= V <= 16384, stop / start_tok / fake_id inside the vocabulary, top_p > 0, temperature > 0");
+    return E_INVALID;
+  }
+  const int rows = items * num_beams;
+  if (scratch_bytes < ((size_t)rows * ((size_t)V + 1) + (size_t)items) * 4) {
+    set_error("itts_beam_sample_rows: scratch shorter than (items * num_beams * (V + 1) + items) * 4 bytes");
+    return E_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // the kernels' view of a generation at step k on the caller's scratch: every beam row k tokens long, no item done
+  BeamWide w;
+  w.sc = (float*)scratch;
+  int* len = (int*)(w.sc + (size_t)rows * V);
+  int* done = len + rows;
+  w.kept = kept;
+  w.pick_sc = pick_score;
+  w.pick_tok = pick_tok;
+  w.pick_beam = pick_beam;
+  w.one_step = 1;
+  ITTS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)len, k, (size_t)rows, s));
+  ITTS_HIP_CHECK(hipMemsetAsync(done, 0, (size_t)items * 4, s));
+  BeamArgs a;
+  a.logits = logits; a.V = V; a.max_gen = ids_stride > 0 ? ids_stride : 1; a.stop = stop; a.suppress_stop = suppress_stop;
+  a.nb = num_beams; a.B = items; a.top_k = top_k < 1 ? 0 : top_k; a.start_tok = start_tok; a.fake_id = fake_id; a.penalty = penalty;
+  a.top_p = top_p; a.temperature = temperature; a.uniforms = uniforms; a.len = len; a.ids = (int*)ids; a.beam_scores = (float*)beam_scores;
+  a.done = done; a.preprocessed = preprocessed; a.do_sample = 1;
+  if (!a.ids) a.ids = len;  // k = 0: never read
+  return beam_wide_pair(a, w, s);
+}
+
 int itts_skinny_gemm(void* Y, int y_bf16, const void* X, const void* W, const float* bias, int B, int N, int K, int act,
                      int accumulate, int ksplit, float* partial, int layout, itts_stream stream) {
   (void)hipGetLastError();
@@ -338,6 +381,10 @@ int itts_gpt_commit_beams(itts_engine* e, const float* pick_score_host, const in
                           itts_stream s) {
   ENG(e);
   return e->e.gpt_commit_beams(pick_score_host, pick_tok_host, pick_beam_host, (hipStream_t)s);
+}
+int itts_gpt_beam_picks(itts_engine* e, float* score_host, int32_t* tok_host, int32_t* beam_host, int32_t* kept_host, itts_stream s) {
+  ENG(e);
+  return e->e.gpt_beam_picks(score_host, tok_host, beam_host, kept_host, (hipStream_t)s);
 }
 int itts_gpt_set_forced(itts_engine* e, const int32_t* ids_host, int B, int n) {
   ENG(e);

@@ -237,28 +237,6 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
 // ---------------------------------------------------------------------------------------------
 constexpr int WIDE_MAX_V = 16384;  // NP * 6 bytes of LDS: 96 KiB
 
-// exclusive block scan of one value per thread in thread order (REV: from the last thread down); one barrier
-template <bool REV>
-__device__ __forceinline__ float wide_scan_excl(float mine, float* wsum, int lane, int wave) {
-  float inc = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float t = REV ? __shfl_down(inc, o, 64) : __shfl_up(inc, o, 64);
-    if (REV ? lane + o < 64 : lane >= o) inc += t;
-  }
-  float ex = REV ? __shfl_down(inc, 1, 64) : __shfl_up(inc, 1, 64);
-  if (lane == (REV ? 63 : 0)) ex = 0.f;
-  if (lane == (REV ? 0 : 63)) wsum[wave] = inc;
-  __syncthreads();
-  float wb = 0.f;
-  if (REV) {
-    for (int w = 15; w > wave; --w) wb += wsum[w];
-  } else {
-    for (int w = 0; w < wave; ++w) wb += wsum[w];
-  }
-  return wb + ex;
-}
-
 __global__ __launch_bounds__(1024) void sampler_wide_kernel(SamplerArgs a, int NP) {
   extern __shared__ unsigned char wsm[];
   float* keys = reinterpret_cast<float*>(wsm);                                     // [NP] scores, sorted in place
@@ -288,35 +266,7 @@ __global__ __launch_bounds__(1024) void sampler_wide_kernel(SamplerArgs a, int N
     idx[i] = (unsigned short)(i < V ? i : 0xFFFF);  // the padding sorts behind every -inf score
   }
   __syncthreads();
-  // ---- bitonic sort: descending score, ascending id on ties ----
-  auto compare_swap = [&](int t, int j, int kk) {
-    const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-    const bool up = (lo & kk) == 0;
-    const float k0 = keys[lo], k1 = keys[hi];
-    const unsigned short i0 = idx[lo], i1 = idx[hi];
-    const bool behind = k0 < k1 || (k0 == k1 && i0 > i1);  // entry lo belongs behind entry hi
-    if (behind == up) {
-      keys[lo] = k1;
-      keys[hi] = k0;
-      idx[lo] = i1;
-      idx[hi] = i0;
-    }
-  };
-  for (int kk = 2; kk <= NP; kk <<= 1) {
-    int j = kk >> 1;
-    for (; j > 64; j >>= 1) {
-      for (int t = tid; t < NP / 2; t += 1024) compare_swap(t, j, kk);
-      __syncthreads();
-    }
-    // j <= 64: the 64 comparators of a wave stay inside 128 entries no other wave touches, and a wave's LDS operations
-    // execute in program order (sort_cands_wave): these stages need no workgroup barrier
-    for (int t = tid; t < NP / 2; t += 1024)
-      for (int jj = j; jj > 0; jj >>= 1) {
-        compare_swap(t, jj, kk);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      }
-    __syncthreads();
-  }
+  wide_sort_desc(keys, idx, NP, tid);  // descending score, ascending id on ties
   // ---- TopK: the kept ranks are a prefix [0, n) of the sorted order ----
   const int per = NP >> 10, r0 = tid * per;  // this thread's run of ranks
   const float s0 = keys[0];

@@ -175,6 +175,11 @@ struct DecodeState {
   float *hyp_score = nullptr, *hyp_worst = nullptr;
   size_t beam_cap = 0;               // bytes-independent capacity key: rows * max_gen * Smax the beam buffers were sized for
   int beam_rows = 0, beam_gen = 0, beam_smax = 0;
+  // whole-vocabulary beam sampler (beam_sample with top_k < 1 or > 128 on the device): one block, carved up by beam_wide_bytes' order
+  void* wide_buf = nullptr;
+  size_t wide_cap = 0;
+  BeamWide wide;                     // pointers into wide_buf for the current request
+  int wide_valid = 0;                // a device-sampled wide step of this generation has written wide.pick_* / wide.kept
   // LN + c_attn + cache attention in one launch (decode_fused.hip qkv_attn_fused): per-layer granule buffers + error flag
   unsigned long long* gran = nullptr;  // [layers][cap_B <= 4][3 * D]
   int* fuse_err = nullptr;
@@ -292,6 +297,8 @@ struct Engine {
   int beam_beams = 1;  // requested beams for the following generations (1 = off)
   int beam_returns = 1;  // hypotheses returned per batch item (generate()'s num_return_sequences = num_beam_hyps_to_keep)
   int ensure_beam_state(int rows, int max_gen, int Smax, hipStream_t s);
+  int ensure_beam_wide_state(int rows, int nb, int V, hipStream_t s);
+  int gpt_beam_picks(float* score_host, int32_t* tok_host, int32_t* beam_host, int32_t* kept_host, hipStream_t s);
   int beam_finalize(int32_t* codes_host, hipStream_t s);
   std::vector<int32_t> forced_host;  // [forced_B][forced_n], uploaded by the next prefill
   int forced_B = 0, forced_n = 0;

@@ -127,7 +127,24 @@ struct BeamArgs {
   const int* host_beam = nullptr;
 };
 constexpr int BEAM_MAX_CAND = 128;
-int beam_sample_step(const BeamArgs& a, hipStream_t s);
+// scratch and results of the whole-vocabulary beam sampler (beam.hip beam_wide_cand_kernel / beam_wide_pick_kernel: beam_sample
+// with top_k < 1 or > BEAM_MAX_CAND); a second kernel argument, so that BeamArgs and the kernels that take it alone stay as they are
+struct BeamWide {
+  float* sc = nullptr;         // [B * nb][V] warped score + running beam score of the kept tokens, -inf everywhere else
+  int* kept = nullptr;         // [B * nb] tokens of the row that survived the warpers
+  float* pick_sc = nullptr;    // [B][2 * nb] the picks in draw order: what beam_select_kernel takes as host_sc / host_tok / host_beam
+  int* pick_tok = nullptr;
+  int* pick_beam = nullptr;
+  int one_step = 0;  // the stateless operator (itts_beam_sample_rows): ids is ONE [B * nb][max_gen] table, uniforms [B][2 * nb]
+};
+constexpr int BEAM_WIDE_MAX_V = 16384;  // NP * 6 bytes of LDS: 96 KiB
+// bytes of all five buffers for rows = B * nb beam rows of V tokens
+inline size_t beam_wide_bytes(int rows, int nb, int V) { return ((size_t)rows * V + rows + (size_t)(rows / nb) * 2 * nb * 3) * 4; }
+int beam_wide_prepare();  // once per device ordinal, outside graph capture: beam_wide_cand_kernel's dynamic LDS limit
+// the two wide launches alone (no BeamSearchScorer step): w.sc, w.kept and the picks are written, nothing of `a` is
+int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s);
+// w: needed when a.do_sample and a.top_k < 1 or > BEAM_MAX_CAND (the wide pair + beam_select_kernel on its picks)
+int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w = nullptr);
 int beam_commit_step(const BeamArgs& a, hipStream_t s);  // host picks -> scorer bookkeeping (beam_select_kernel only)
 
 // TypicalLogitsWarper pre-pass (beam.hip): processed scores of every row -> out [rows, V] with the filtered ones at -inf

@@ -75,4 +75,62 @@ __device__ __forceinline__ void sort_cands_wave(float* cv, int* ci, int lane) {
     }
 }
 
+// ---- shared by the whole-vocabulary samplers: sampler_wide_kernel (decode_sampler.hip), beam_wide_cand_kernel /
+//      beam_wide_pick_kernel (beam.hip) - one sort order, one tie rule, one summation structure ----
+
+// exclusive block scan of one value per thread in thread order (REV: from the last thread down); one barrier
+template <bool REV>
+__device__ __forceinline__ float wide_scan_excl(float mine, float* wsum, int lane, int wave) {
+  float inc = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = REV ? __shfl_down(inc, o, 64) : __shfl_up(inc, o, 64);
+    if (REV ? lane + o < 64 : lane >= o) inc += t;
+  }
+  float ex = REV ? __shfl_down(inc, 1, 64) : __shfl_up(inc, 1, 64);
+  if (lane == (REV ? 63 : 0)) ex = 0.f;
+  if (lane == (REV ? 0 : 63)) wsum[wave] = inc;
+  __syncthreads();
+  float wb = 0.f;
+  if (REV) {
+    for (int w = 15; w > wave; --w) wb += wsum[w];
+  } else {
+    for (int w = 0; w < wave; ++w) wb += wsum[w];
+  }
+  return wb + ex;
+}
+
+// block bitonic sort of NP (a power of two >= 1024) (score, u16 id) pairs in LDS by 1024 threads: descending score, ascending
+// id on ties.  The caller has put a barrier behind its writes of keys / idx; the sort ends with one
+__device__ __forceinline__ void wide_sort_desc(float* keys, unsigned short* idx, int NP, int tid) {
+  auto compare_swap = [&](int t, int j, int kk) {
+    const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+    const bool up = (lo & kk) == 0;
+    const float k0 = keys[lo], k1 = keys[hi];
+    const unsigned short i0 = idx[lo], i1 = idx[hi];
+    const bool behind = k0 < k1 || (k0 == k1 && i0 > i1);  // entry lo belongs behind entry hi
+    if (behind == up) {
+      keys[lo] = k1;
+      keys[hi] = k0;
+      idx[lo] = i1;
+      idx[hi] = i0;
+    }
+  };
+  for (int kk = 2; kk <= NP; kk <<= 1) {
+    int j = kk >> 1;
+    for (; j > 64; j >>= 1) {
+      for (int t = tid; t < NP / 2; t += 1024) compare_swap(t, j, kk);
+      __syncthreads();
+    }
+    // j <= 64: the 64 comparators of a wave stay inside 128 entries no other wave touches, and a wave's LDS operations
+    // execute in program order (sort_cands_wave): these stages need no workgroup barrier
+    for (int t = tid; t < NP / 2; t += 1024)
+      for (int jj = j; jj > 0; jj >>= 1) {
+        compare_swap(t, jj, kk);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      }
+    __syncthreads();
+  }
+}
+
 }  // namespace itts

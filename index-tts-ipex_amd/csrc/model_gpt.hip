@@ -317,6 +317,31 @@ int Engine::ensure_beam_state(int rows, int max_gen, int Smax, hipStream_t s) {
   return OK;
 }
 
+// scratch of the whole-vocabulary beam sampler (beam_wide_cand_kernel / beam_wide_pick_kernel): scores [rows][V], kept [rows], the
+// picks [items][2 * nb] x 3.  Allocated with the decode state at prefill, never inside a captured step
+int Engine::ensure_beam_wide_state(int rows, int nb, int V, hipStream_t s) {
+  DecodeState& d = ds;
+  const size_t need = beam_wide_bytes(rows, nb, V);
+  if (need > d.wide_cap) {
+    ITTS_HIP_CHECK(hipStreamSynchronize(s));
+    d.drop_graphs();  // captured nodes hold the old pointers
+    ITTS_TRY(dev_alloc(&d.wide_buf, need));
+    d.wide_cap = need;
+  }
+  BeamWide w;
+  w.sc = (float*)d.wide_buf;
+  w.kept = (int*)(w.sc + (size_t)rows * V);
+  w.pick_sc = (float*)(w.kept + rows);
+  w.pick_tok = (int*)(w.pick_sc + (size_t)(rows / nb) * 2 * nb);
+  w.pick_beam = w.pick_tok + (size_t)(rows / nb) * 2 * nb;
+  if (w.sc != d.wide.sc || w.kept != d.wide.kept || w.pick_sc != d.wide.pick_sc) {  // another carving: the nodes hold the old one
+    ITTS_HIP_CHECK(hipStreamSynchronize(s));
+    d.drop_graphs();
+  }
+  d.wide = w;
+  return OK;
+}
+
 // HF beam_sample configuration for the following generations (num_beams <= 1 switches it off): the generate() mode of
 // the reference's default kwargs (infer.py:116-124).  uniforms_host: row-major [max_gen][B][2 * num_beams] draws in [0, 1).
 // generate()'s num_return_sequences under beams: the n best hypotheses of every batch item (1 <= n <= num_beams, checked
@@ -343,7 +368,9 @@ int Engine::gpt_set_beams(int num_beams, int do_sample, int top_k, float top_p, 
   }
   ITTS_REQUIRE(num_beams <= 10, "gpt_set_beams: num_beams must be in [2, 10]");
   if (do_sample && !ds.host_sample) {  // (host sampling: the caller warps and draws itself, any top_k - gpt_commit_beams)
-    ITTS_REQUIRE(top_k >= 1 && top_k <= 128, "gpt_set_beams: top_k must be in [1, 128] (wider: itts_gpt_set_host_sampling first)");
+    // any top_k: < 1 is HF's "TopK warper off" (stored as 0); 0 and > 128 run on the whole-vocabulary pair (beam_sample_step)
+    ITTS_REQUIRE(top_k <= BEAM_MAX_CAND || cfg.number_mel_codes <= BEAM_WIDE_MAX_V,
+                 "gpt_set_beams: top_k > 128 needs number_mel_codes <= 16384");
     ITTS_REQUIRE(top_p > 0.f && top_p <= 1.f && temperature > 0.f, "gpt_set_beams: need 0 < top_p <= 1 and temperature > 0");
     ITTS_REQUIRE(uniforms_host && n > 0, "gpt_set_beams: uniforms missing");
     sample_uniforms.assign(uniforms_host, uniforms_host + n);
@@ -352,7 +379,7 @@ int Engine::gpt_set_beams(int num_beams, int do_sample, int top_k, float top_p, 
   beam_do_sample = do_sample ? 1 : 0;
   beam_length_penalty = length_penalty;
   ds.do_sample = 0;
-  ds.top_k = top_k;
+  ds.top_k = (do_sample && !ds.host_sample && top_k < 1) ? 0 : top_k;
   ds.top_p = top_p;
   ds.temperature = temperature;
   return OK;
@@ -477,6 +504,13 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
   }
   if (engine_usable()) ITTS_TRY(ensure_engine_state(s));  // allocations must not happen inside the graph capture of the step
   if (ds.do_sample && nbeam == 1 && (ds.top_k < 1 || ds.top_k > BEAM_MAX_CAND)) ITTS_TRY(sampler_wide_prepare());  // nor this
+  ds.wide_valid = 0;
+  if (nbeam > 1 && beam_do_sample && !ds.host_sample && (ds.top_k < 1 || ds.top_k > BEAM_MAX_CAND)) {  // nor these two
+    ITTS_REQUIRE(cfg.number_mel_codes <= BEAM_WIDE_MAX_V, "gpt_prefill: beam_sample with top_k outside [1, 128] needs number_mel_codes <= 16384");
+    ITTS_TRY(beam_wide_prepare());
+    ITTS_TRY(ensure_beam_wide_state(B, nbeam, cfg.number_mel_codes, s));
+    ds.wide_valid = 1;  // this generation's steps leave their picks in ds.wide (gpt_beam_picks)
+  }
   if (ds.do_sample || (nbeam > 1 && beam_do_sample && !ds.host_sample)) {
     const size_t need_u = nbeam > 1 ? (size_t)max_gen * B_items * 2 * nbeam : (size_t)max_gen * B;
     ITTS_REQUIRE(sample_uniforms.size() >= need_u,
@@ -700,7 +734,8 @@ int Engine::sample_from_logits(hipStream_t s, bool sampled) {
   }
   if (ds.nb > 1) {  // beam-sample: one workgroup per batch item over its nb rows
     const BeamArgs ba = beam_args(lg_in, typical);
-    return beam_sample_step(ba, s);
+    const bool wide = ba.do_sample && (ba.top_k < 1 || ba.top_k > BEAM_MAX_CAND);
+    return beam_sample_step(ba, s, wide ? &ds.wide : nullptr);
   }
   SamplerArgs sa = greedy_sampler_args(lg_in, typical);
   return sampler2_step(sa, B, s);
@@ -1128,6 +1163,23 @@ int Engine::gpt_commit_beams(const float* pick_score_host, const int32_t* pick_t
   const int st = beam_commit_step(ba, s);
   ITTS_HIP_CHECK(hipStreamSynchronize(s));  // the picks are the caller's buffers
   return st;
+}
+
+// The last device-sampled whole-vocabulary beam step's picks in draw order [items][2 * num_beams] (score with the running beam
+// score, token, beam) and the kept count of every beam row [items * num_beams]: they sit in the sampler's buffers until the
+// next step overwrites them.  Items that were done (or a given-token step) keep what an earlier step left there.
+int Engine::gpt_beam_picks(float* score_host, int32_t* tok_host, int32_t* beam_host, int32_t* kept_host, hipStream_t s) {
+  if (!ds.active || ds.nb <= 1 || !ds.wide_valid || !ds.wide.sc) {
+    set_error("gpt_beam_picks: needs an active beam generation that samples over the whole vocabulary on the device");
+    return E_STATE;
+  }
+  const size_t np = (size_t)(ds.B / ds.nb) * 2 * ds.nb;
+  if (score_host) ITTS_HIP_CHECK(hipMemcpyAsync(score_host, ds.wide.pick_sc, np * 4, hipMemcpyDeviceToHost, s));
+  if (tok_host) ITTS_HIP_CHECK(hipMemcpyAsync(tok_host, ds.wide.pick_tok, np * 4, hipMemcpyDeviceToHost, s));
+  if (beam_host) ITTS_HIP_CHECK(hipMemcpyAsync(beam_host, ds.wide.pick_beam, np * 4, hipMemcpyDeviceToHost, s));
+  if (kept_host) ITTS_HIP_CHECK(hipMemcpyAsync(kept_host, ds.wide.kept, (size_t)ds.B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  return OK;
 }
 
 int Engine::gpt_set_forced(const int32_t* ids_host, int B, int n) {

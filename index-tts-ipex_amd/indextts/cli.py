@@ -18,6 +18,9 @@ def build_parser():
     p.add_argument("--wide-sampler", choices=("device", "host"), default=None,
                    help="where sampling with one beam and top_k = 0 or > 128 picks its tokens: host (torch's arithmetic, one sync per "
                         "token; the default) or device (the whole-vocabulary HIP sampler); unset: ITTS_WIDE_SAMPLER")
+    p.add_argument("--wide-beam-sampler", choices=("device", "host"), default=None,
+                   help="the same choice with several beams (beam_sample with top_k = 0 or > 128): host (the default) or device (the "
+                        "whole-vocabulary HIP beam sampler); unset: ITTS_WIDE_BEAM_SAMPLER")
     p.add_argument("--gpt-fp8", action="store_true", default=False,
                    help="store the GPT weights as fp8-e4m3 (bfloat16 engine; the decode steps stream the fp8 bytes)")
     return p
@@ -42,7 +45,7 @@ def main():
     from indextts.infer import IndexTTS
 
     tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8,
-                   wide_sampler=a.wide_sampler)
+                   wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

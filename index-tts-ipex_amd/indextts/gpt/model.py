@@ -71,10 +71,12 @@ class UnifiedVoice:
         search (do_sample=False, num_beams > 1) with top_p, temperature, repetition_penalty, length_penalty and typical_sampling
         in HF 4.36.2 semantics: top_k in [1, 128] entirely on the device, `top_k = 0 / None` (warper off) or > 128 with the warpers
         and draws on the host over the whole vocabulary (one or several beams) - or, with one beam and `wide_sampler="device"`
-        (Engine.generate), on the whole-vocabulary device sampler.  `input_tokens` [b or 1, n] (model.py:672-686):
+        (Engine.generate), on the whole-vocabulary device sampler; with several beams and `wide_beam_sampler="device"` on the
+        whole-vocabulary beam sampler.  `input_tokens` [b or 1, n] (model.py:672-686):
         given mel tokens the generation continues after; like the reference, the returned codes start after them - with
         num_return_sequences > 1 as well (the reference's row expansion, see below)."""
         wide_sampler = hf_generate_kwargs.pop("wide_sampler", None)  # not an HF kwarg: Engine.generate's switch
+        wide_beam_sampler = hf_generate_kwargs.pop("wide_beam_sampler", None)  # likewise, for several beams
         nrs = int(num_return_sequences)
         if nrs < 1:
             raise ValueError("num_return_sequences has to be >= 1")
@@ -138,7 +140,8 @@ class UnifiedVoice:
             try:
                 # max_length = trunc_index + max_generate_length with trunc_index counting the given tokens (model.py:687,695)
                 codes = self._eng.generate(cond, ids, max_gen + n_forced, repetition_penalty=rep,
-                                           num_return_sequences=nrs if nbeams > 1 else 1, wide_sampler=wide_sampler, **sample_kw)
+                                           num_return_sequences=nrs if nbeams > 1 else 1, wide_sampler=wide_sampler,
+                                           wide_beam_sampler=wide_beam_sampler, **sample_kw)
             finally:
                 if n_forced:
                     self._eng.set_input_tokens(None)

@@ -51,7 +51,8 @@ from indextts.utils.front import TextNormalizer, TextTokenizer
 
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
-                 use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None):
+                 use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
+                 wide_beam_sampler=None):
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -71,6 +72,8 @@ class IndexTTS:
         # how do_sample with one beam and top_k = 0 / None or > 128 runs: "host" (torch's arithmetic, one sync per token), "device"
         # (the whole-vocabulary device sampler), None: ITTS_WIDE_SAMPLER, else "host" (Engine.generate)
         self.wide_sampler = wide_sampler
+        # the same choice for several beams (beam_sample with top_k = 0 / None or > 128): None: ITTS_WIDE_BEAM_SAMPLER, else "host"
+        self.wide_beam_sampler = wide_beam_sampler
         if self.gpt_fp8 and not self.is_fp16:
             raise ValueError("gpt_fp8=True needs is_fp16=True: the fp8 GPT weights run on the bfloat16 engine, not the fp32 one")
         if self.gpt_fp8 and self.half != "bf16":
@@ -165,7 +168,7 @@ class IndexTTS:
             grp = sents[lo:lo + cap]
             ids = infer_core.pad_tokens_cat(grp, self.cfg.gpt.stop_text_token)
             codes = self.engine.generate(cond, ids, g["max_mel_tokens"], repetition_penalty=g["repetition_penalty"],
-                                         wide_sampler=self.wide_sampler, **sample_kw)
+                                         wide_sampler=self.wide_sampler, wide_beam_sampler=self.wide_beam_sampler, **sample_kw)
             rows.extend(codes[r] for r in range(len(grp)))
         return rows
 

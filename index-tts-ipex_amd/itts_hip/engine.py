@@ -320,7 +320,8 @@ class Engine:
                  suppress_stop: bool = False, check_every: int = 16, do_sample: bool = False, top_k: int = 30,
                  top_p: float = 0.8, temperature: float = 1.0, seed: Optional[int] = None,
                  uniforms: Optional[np.ndarray] = None, num_beams: int = 1, typical_mass: float = 0.0,
-                 length_penalty: float = 0.0, num_return_sequences: int = 1, wide_sampler: Optional[str] = None) -> np.ndarray:
+                 length_penalty: float = 0.0, num_return_sequences: int = 1, wide_sampler: Optional[str] = None,
+                 wide_beam_sampler: Optional[str] = None) -> np.ndarray:
         """Greedy decode (do_sample=False, num_beams=1 of tests/padding_test.py:35-46) or, with do_sample, HF
         GenerationMixin.sample (top-k / top-p / temperature, num_beams=1; draws from `uniforms` or a numpy Generator
         seeded with `seed`).  Returns int64 codes [B, n] with n <= max_gen: HF stops when every row has emitted stop
@@ -331,12 +332,21 @@ class Engine:
         (the default): the token choice on the host with torch's arithmetic, bit for bit, one stream sync per token; "device":
         sampler_wide_kernel, no sync per token, graph replay - the same distribution with parallel fp32 sums, so the top-p
         boundary and the draw agree with the host's to 64 * 2^-24 of the mass, not to the last bit.  None: the environment's
-        ITTS_WIDE_SAMPLER, else "host".  Requests with beams ignore it."""
+        ITTS_WIDE_SAMPLER, else "host".  Requests with beams ignore it.
+        wide_beam_sampler: the same choice for do_sample with several beams and top_k outside 1 .. 128 - "host" (the default):
+        warpers and draws on the host (infer_core.host_beam_step: torch's arithmetic, a logits and beam-state read-back and two
+        stream syncs per token); "device": beam_wide_cand_kernel + beam_wide_pick_kernel in front of beam_select_kernel, no
+        read-back, graph replay - the same distribution with parallel fp32 sums, top-p boundary and draws within 512 * 2^-24 of
+        the mass of the host's.  None: the environment's ITTS_WIDE_BEAM_SAMPLER, else "host"."""
         if wide_sampler is None:
             wide_sampler = os.environ.get("ITTS_WIDE_SAMPLER") or "host"
         if wide_sampler not in ("host", "device"):
             raise ValueError(f"wide_sampler must be 'host' or 'device', not {wide_sampler!r}")
-        kw = dict(wide_sampler=wide_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
+        if wide_beam_sampler is None:
+            wide_beam_sampler = os.environ.get("ITTS_WIDE_BEAM_SAMPLER") or "host"
+        if wide_beam_sampler not in ("host", "device"):
+            raise ValueError(f"wide_beam_sampler must be 'host' or 'device', not {wide_beam_sampler!r}")
+        kw = dict(wide_sampler=wide_sampler, wide_beam_sampler=wide_beam_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, uniforms=uniforms, num_beams=num_beams,
                   typical_mass=typical_mass, length_penalty=length_penalty, num_return_sequences=num_return_sequences)
         try:
@@ -350,19 +360,20 @@ class Engine:
 
     def _generate_once(self, cond, text_ids, max_gen, repetition_penalty, suppress_stop, check_every, do_sample, top_k, top_p,
                        temperature, seed, uniforms, num_beams, typical_mass, length_penalty, num_return_sequences,
-                       wide_sampler="host") -> np.ndarray:
+                       wide_sampler="host", wide_beam_sampler="host") -> np.ndarray:
         beams = num_beams > 1
         if num_return_sequences != 1 and not beams:
             raise ValueError("num_return_sequences > 1 without beams: repeat the rows (indextts/gpt/model.py does, as HF does)")
         nrow = np.asarray(text_ids).shape[0]
         if do_sample and (not top_k or int(top_k) < 1 or int(top_k) > 128):
             # HF: TopK warper off (top_k = 0 / None) or wider than the narrow device samplers' 128 candidates - exact on the
-            # host, or (one beam, wide_sampler="device") the whole-vocabulary device sampler through the ordinary loop below
-            if beams:
+            # host, or (one beam, wide_sampler="device"; beams, wide_beam_sampler="device") the whole-vocabulary device samplers
+            # through the ordinary loop below
+            if beams and wide_beam_sampler != "device":
                 return self._generate_host_beams(cond, text_ids, max_gen, repetition_penalty, suppress_stop, int(top_k or 0), top_p,
                                                  temperature, seed, uniforms, typical_mass, num_beams, length_penalty,
                                                  num_return_sequences)
-            if wide_sampler != "device":
+            if not beams and wide_sampler != "device":
                 return self._generate_host_sampled(cond, text_ids, max_gen, repetition_penalty, suppress_stop, int(top_k or 0),
                                                    top_p, temperature, seed, uniforms, typical_mass)
             top_k = int(top_k or 0)
@@ -450,7 +461,8 @@ class Engine:
                              uniforms, typical_mass, num_beams, length_penalty, num_return_sequences) -> np.ndarray:
         """HF beam_sample with the warpers and the draws on the host (infer_core.host_beam_step: any top_k, whole vocabulary),
         BeamSearchScorer.process / beam re-ordering / finalize on the device (itts_gpt_commit_beams).  One logits + beam-state
-        read-back per token."""
+        read-back per token - the price of torch's own arithmetic, bit for bit.  generate(wide_beam_sampler="device") runs the same
+        mode on the device (beam_wide_cand_kernel / beam_wide_pick_kernel: no read-back; parallel fp32 sums)."""
         from . import infer_core
 
         ids_in = np.asarray(text_ids)

@@ -87,7 +87,8 @@ def sampling_kwargs(do_sample, num_beams, top_k, top_p, temperature, typical_sam
     the token choice then runs on the host over the whole vocabulary (host_sample_step / host_beam_step below, one logits
     read-back per token) - with one beam or several.  With one beam, Engine.generate(wide_sampler="device") / ITTS_WIDE_SAMPLER=device
     runs it on the whole-vocabulary device sampler instead (no read-back; the same distribution, parallel fp32 sums: top-p
-    boundary and draw within 64 * 2^-24 of the mass of torch's).  The seed is drawn from torch's global RNG so that torch.manual_seed governs the run as it does for
+    boundary and draw within 64 * 2^-24 of the mass of torch's); with several beams wide_beam_sampler="device" /
+    ITTS_WIDE_BEAM_SAMPLER=device does the same on the whole-vocabulary beam sampler (within 512 * 2^-24).  The seed is drawn from torch's global RNG so that torch.manual_seed governs the run as it does for
     the reference's torch.multinomial."""
     import warnings
 

@@ -73,6 +73,8 @@ _PROTOS = {
     "itts_gemv": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp]),
     "itts_gemv_bf16": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "itts_sample_rows": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, f32, f32, vp, vp, C.c_size_t, vp]),
+    "itts_beam_sample_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, f32, f32, vp,
+                                    vp, C.c_size_t, vp]),
     "itts_skinny_gemm": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "itts_retile_weights": (i32, [vp, vp, i32, i32, vp]),
     "itts_ln_rows_bf16": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, vp, i32, vp, i32, vp]),
@@ -95,6 +97,7 @@ _PROTOS = {
     "itts_gpt_commit": (i32, [vp, vp, vp]),
     "itts_gpt_beam_state": (i32, [vp, vp, vp, vp, C.POINTER(i32), vp]),
     "itts_gpt_commit_beams": (i32, [vp, vp, vp, vp, vp]),
+    "itts_gpt_beam_picks": (i32, [vp, vp, vp, vp, vp, vp]),
     "itts_gpt_set_typical": (i32, [vp, f32]),
     "itts_gpt_set_beams": (i32, [vp, i32, i32, i32, f32, f32, f32, vp, i64]),
     "itts_gpt_set_beam_sample": (i32, [vp, i32, i32, f32, f32, vp, i64]),
