@@ -110,6 +110,28 @@ int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W
                    int accumulate, int prologue, const float* ln_gamma, const float* ln_beta, const float* attn_o,
                    const float* attn_ml, const void* W8, const float* wscale, itts_stream stream);
 
+/* The single-query attention over the K/V cache of one decode step with this step's append fused in (csrc/decode_attn.hip
+ * decode_attn2), as the launch path calls it once per layer.  Per (row b, head h): pos = prefix[0] + len[b]; this step's k and v
+ * are rounded to the cache type and stored at cache row pos of the row's own block; the output is softmax(q . K / 8) V over the
+ * cache rows kv_start[b] <= j < pos plus that appended row.  The caller guarantees 0 <= kv_start[b] <= pos < Smax and finite cache
+ * contents (rows outside the range are multiplied by a weight of zero).  dh = 64 only.
+ *   kc, vc   [B][H][Smax][64], tc = 0 fp32 or 1 the 16-bit type of the library
+ *   qkv      [B][3 * H * 64] fp32: q, k, v of the step, heads side by side
+ *   len, kv_start int32 [B]; prefix int32 [1]
+ *   ctx      [B][H * 64] in `to` (0 fp32, 1 16-bit; an fp32 cache writes fp32 only); ctx_tiled = 1 (16-bit only): the MFMA-fragment
+ *            tiles of a [B, H * 64] matrix instead (ceil(B / 16) row tiles, rows past B are not written)
+ *   part_o   when set, the split form (16-bit cache): four workgroups per (row, head) each take every fourth group of 32 cache
+ *            rows and write an un-normalised partial, part_o [B][H][4][64] fp32 and part_ml [B][H][2][4] fp32 = the four
+ *            maxima, then the four sums (a split without a visible key: -inf, 0 and zeros) - what prologue 3 of
+ *            itts_gemv_bf16 merges; ctx is not written and may be null
+ *   anc      when set (beam ancestry): uint8 [2][B][Smax], the half anc[len[b] & 1] is read; entry [b][j] names which of the nb
+ *            physical rows of the row's batch item (rows (b / nb) * nb ..) holds position j of its history, values past nb - 1
+ *            are clamped; B % nb == 0, 1 <= nb <= 16.  The appended row always goes to the row's own block.
+ * Forms the kernel does not have are refused with an error status and nothing is launched. */
+int itts_decode_attn(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start, const int* prefix,
+                     int B, int H, int dh, int Smax, int tc, int ctx_tiled, float* part_o, float* part_ml, const uint8_t* anc, int nb,
+                     itts_stream stream);
+
 /* One sampler launch of the decode step (csrc/decode_sampler.hip) on caller memory, stateless: HF 4.36.2 sample() for B rows -
  * RepetitionPenalty (seen: [B, V] bytes, non-zero = the row has seen the id; null = none) and stop suppression (both skipped
  * when preprocessed) -> / temperature -> TopK -> TopP -> the inverse-CDF draw of uniforms[b] over the kept tokens in

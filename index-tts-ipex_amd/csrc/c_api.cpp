@@ -138,6 +138,18 @@ int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W
   return gemv_bf16(g, (hipStream_t)stream);
 }
 
+int itts_decode_attn(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start, const int* prefix,
+                     int B, int H, int dh, int Smax, int tc, int ctx_tiled, float* part_o, float* part_ml, const uint8_t* anc, int nb,
+                     itts_stream stream) {
+  (void)hipGetLastError();
+  if (!qkv || !kc || !vc || !len || !kv_start || !prefix || B < 1 || H < 1 || Smax < 1 || (!ctx && !part_o)) {
+    set_error("itts_decode_attn: bad arguments (qkv, kc, vc, len, kv_start, prefix; B, H, Smax >= 1; ctx unless part_o is given)");
+    return E_INVALID;
+  }
+  return decode_attn2(ctx, to, qkv, kc, vc, len, kv_start, prefix, B, H, dh, Smax, tc, (hipStream_t)stream, ctx_tiled, part_o, part_ml,
+                      anc, nb);
+}
+
 int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
                      int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
                      void* scratch, size_t scratch_bytes, itts_stream stream) {

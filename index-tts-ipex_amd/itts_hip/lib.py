@@ -72,6 +72,7 @@ _PROTOS = {
     "itts_attention": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, i32, vp]),
     "itts_gemv": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp]),
     "itts_gemv_bf16": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "itts_decode_attn": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "itts_sample_rows": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, f32, f32, vp, vp, C.c_size_t, vp]),
     "itts_beam_sample_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, f32, f32, vp,
                                     vp, C.c_size_t, vp]),
