@@ -22,6 +22,7 @@ typedef struct itts_engine itts_engine;
 
 #define ITTS_F32 0
 #define ITTS_BF16 1
+#define ITTS_FP8 4 /* OCP e4m3fn bytes without a scale: the opt-in K/V cache type (itts_decode_attn, itts_kv_scatter, itts_gpt_set_kv_fp8) */
 #define ITTS_F16 5 /* IEEE half: accepted by itts_snake_aa_fwd only (the reference op dispatches float/half/bf16) */
 
 /* status codes */
@@ -115,12 +116,15 @@ int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W
  * are rounded to the cache type and stored at cache row pos of the row's own block; the output is softmax(q . K / 8) V over the
  * cache rows kv_start[b] <= j < pos plus that appended row.  The caller guarantees 0 <= kv_start[b] <= pos < Smax and finite cache
  * contents (rows outside the range are multiplied by a weight of zero).  dh = 64 only.
- *   kc, vc   [B][H][Smax][64], tc = 0 fp32 or 1 the 16-bit type of the library
+ *   kc, vc   [B][H][Smax][64], tc = 0 fp32, 1 the 16-bit type of the library, or ITTS_FP8 (whole forms only, `to` 0 or 1): OCP
+ *            e4m3 bytes without a scale, 8-byte aligned; the step's k / v are clamped to [-448, 448] and rounded to nearest even
+ *            (what x.clamp(-448, 448).to(torch.float8_e4m3fn) gives: no NaN byte is ever written), and the kernel computes,
+ *            operation for operation, what the 16-bit form computes on a cache holding the same values
  *   qkv      [B][3 * H * 64] fp32: q, k, v of the step, heads side by side
  *   len, kv_start int32 [B]; prefix int32 [1]
  *   ctx      [B][H * 64] in `to` (0 fp32, 1 16-bit; an fp32 cache writes fp32 only); ctx_tiled = 1 (16-bit only): the MFMA-fragment
  *            tiles of a [B, H * 64] matrix instead (ceil(B / 16) row tiles, rows past B are not written)
- *   part_o   when set, the split form (16-bit cache): four workgroups per (row, head) each take every fourth group of 32 cache
+ *   part_o   when set, the split form (16-bit cache only; an fp8 cache is refused): four workgroups per (row, head) each take every fourth group of 32 cache
  *            rows and write an un-normalised partial, part_o [B][H][4][64] fp32 and part_ml [B][H][2][4] fp32 = the four
  *            maxima, then the four sums (a split without a visible key: -inf, 0 and zeros) - what prologue 3 of
  *            itts_gemv_bf16 merges; ctx is not written and may be null
@@ -131,6 +135,13 @@ int itts_gemv_bf16(void* Y, int y_bf16, const void* X, int x_bf16, const void* W
 int itts_decode_attn(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start, const int* prefix,
                      int B, int H, int dh, int Smax, int tc, int ctx_tiled, float* part_o, float* part_ml, const uint8_t* anc, int nb,
                      itts_stream stream);
+
+/* The prefill's K/V cache write (csrc/decode.hip kv_scatter) on caller memory: the k and v thirds of qkv [B][S][3 * H * dh]
+ * (type tq) go to rows 0 .. S - 1 of each [Smax][dh] block of kc / vc [B][H][Smax][dh] (type tc), rounded to the cache type
+ * (ITTS_FP8: clamped to [-448, 448], then nearest even); rows S .. Smax - 1 are not touched.  (tq, tc): fp32 -> fp32, 16-bit ->
+ * 16-bit, fp32 -> ITTS_FP8, 16-bit -> ITTS_FP8.  Null pointers, non-positive shapes, S > Smax and other type pairs are refused
+ * with an error status and nothing is launched. */
+int itts_kv_scatter(void* kc, void* vc, const void* qkv, int B, int S, int H, int dh, int Smax, int tq, int tc, itts_stream stream);
 
 /* One sampler launch of the decode step (csrc/decode_sampler.hip) on caller memory, stateless: HF 4.36.2 sample() for B rows -
  * RepetitionPenalty (seen: [B, V] bytes, non-zero = the row has seen the id; null = none) and stop suppression (both skipped
@@ -355,6 +366,16 @@ int itts_dvae_encode(itts_engine* e, const void* mel_btc, int B, int T, int32_t*
  * object, default 0 = the launch path, bit-identical results either way.  The environment variable ITTS_ENGINE_FP8, read
  * per call, overrides it in both directions (1: on for every engine, 0: off). */
 int itts_gpt_set_engine_fp8(itts_engine* e, int on);
+
+/* Opt-in: keep the K/V cache of the GPT decode steps as OCP e4m3 bytes without a scale instead of the engine's 16-bit type (half
+ * the bytes the batched decode step streams, half the largest allocation of a generation).  Both libraries; an fp32 engine is
+ * refused with an error.  Sticky per engine object, default 0 = the 16-bit cache, which behaves exactly as before.  The
+ * environment variable ITTS_KV_FP8 overrides it in both directions (1 / 0; fp32 engines ignore it).  The value is latched by
+ * itts_gpt_prefill for the whole generation: a change takes effect at the next prefill, which re-zeroes the cache and re-captures
+ * the step.  With an fp8 cache every decode step takes the launch path's whole-form attention (itts_gpt_decode_mode answers 0:
+ * no persistent engine, no split form, no fused qkv + attention launch); everything else - fp8 weights, samplers, beams, forced
+ * and input tokens, host sampling - is unaffected.  Accuracy and speed as measured: INTEGRATION.md, profiles/kv_fp8.txt. */
+int itts_gpt_set_kv_fp8(itts_engine* e, int on);
 
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);

@@ -150,6 +150,19 @@ int itts_decode_attn(void* ctx, int to, const float* qkv, void* kc, void* vc, co
                       anc, nb);
 }
 
+int itts_kv_scatter(void* kc, void* vc, const void* qkv, int B, int S, int H, int dh, int Smax, int tq, int tc, itts_stream stream) {
+  (void)hipGetLastError();
+  if (!kc || !vc || !qkv || B < 1 || S < 1 || H < 1 || dh < 1 || Smax < 1 || S > Smax) {
+    set_error("itts_kv_scatter: bad arguments (kc, vc, qkv; B, S, H, dh, Smax >= 1; S <= Smax)");
+    return E_INVALID;
+  }
+  if (!((tq == F32 && (tc == F32 || tc == FP8)) || (tq == BF16 && (tc == BF16 || tc == FP8)))) {
+    set_error("itts_kv_scatter: type pair (tq, tc) must be fp32 -> fp32, 16-bit -> 16-bit, or either -> fp8 (e4m3) cache");
+    return E_INVALID;
+  }
+  return kv_scatter(kc, vc, qkv, B, S, H, dh, Smax, tq, tc, (hipStream_t)stream);
+}
+
 int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
                      int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
                      void* scratch, size_t scratch_bytes, itts_stream stream) {
@@ -454,6 +467,16 @@ int itts_debug_enable(itts_engine* e, int on) {
 int itts_gpt_set_engine_fp8(itts_engine* e, int on) {
   ENG(e);
   e->e.ds.eng_fp8 = on != 0;
+  return OK;
+}
+
+int itts_gpt_set_kv_fp8(itts_engine* e, int on) {
+  ENG(e);
+  if (on && e->e.adt != BF16) {
+    set_error("itts_gpt_set_kv_fp8: the fp8 (e4m3) K/V cache needs a 16-bit engine, this one is fp32");
+    return E_INVALID;
+  }
+  e->e.ds.kv_fp8 = on != 0;  // latched by the next itts_gpt_prefill
   return OK;
 }
 

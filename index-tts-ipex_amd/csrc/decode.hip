@@ -238,6 +238,10 @@ int kv_scatter(void* kc, void* vc, const void* qkv, int B, int S, int H, int dh,
     hipLaunchKernelGGL((kv_scatter_kernel<float, float>), grid, blk, 0, s, (float*)kc, (float*)vc, (const float*)qkv, B, S, H, dh, Smax);
   else if (tq == BF16 && tc == BF16)
     hipLaunchKernelGGL((kv_scatter_kernel<bf16_t, bf16_t>), grid, blk, 0, s, (bf16_t*)kc, (bf16_t*)vc, (const bf16_t*)qkv, B, S, H, dh, Smax);
+  else if (tq == BF16 && tc == FP8)  // the opt-in e4m3 cache: the prefill's qkv is in the engine's 16-bit type
+    hipLaunchKernelGGL((kv_scatter_kernel<bf16_t, fp8_t>), grid, blk, 0, s, (fp8_t*)kc, (fp8_t*)vc, (const bf16_t*)qkv, B, S, H, dh, Smax);
+  else if (tq == F32 && tc == FP8)  // (the operator entry, itts_kv_scatter)
+    hipLaunchKernelGGL((kv_scatter_kernel<float, fp8_t>), grid, blk, 0, s, (fp8_t*)kc, (fp8_t*)vc, (const float*)qkv, B, S, H, dh, Smax);
   else {
     set_error("kv_scatter: dtype");
     return E_INVALID;

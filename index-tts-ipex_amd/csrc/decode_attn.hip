@@ -4,6 +4,8 @@
 // 1 KiB of contiguous K and 1 KiB of V per step); every key slot runs an online softmax (running max, sum,
 // partial context) so K and V are read in ONE pass with both loads of a step in flight together; slots are
 // merged with max-rescaling through shuffles and LDS.  Output type TO: fp32 or bf16 (feeds the proj GEMV).
+// Cache type TC: fp32, the 16-bit type, or (opt-in, whole forms only) OCP e4m3 bytes without a scale - fp8_t, itts_common.h;
+// CacheVec<fp8_t> keeps the 16-bit form's thread <-> key mapping with 8-byte loads, the append is one 8-byte store per lane.
 // ---------------------------------------------------------------------------------------------
 #include "itts_decode.h"
 #include "itts_attn_dev.h"
@@ -121,10 +123,18 @@ __global__ __launch_bounds__(NT) void decode_attn2_kernel(TO* __restrict__ ctx, 
     vown[i] = (float)(TC)(&vraw[i >> 2].x)[i & 3];
   }
   if (tid < LPK && sp == 0) {  // slot 0 (of split 0): its LPK lanes cover the 64 dims
+    if constexpr (sizeof(TC) == 1) {  // e4m3 cache: the lane's 8 bytes as one store (kown / vown hold e4m3 values: packing them is exact)
+      static_assert(VEC == 8, "fp8 cache: 8 dims per lane");
+      *reinterpret_cast<u32x2*>(kb + (size_t)pos * DH + sub * VEC) =
+          u32x2{fp8_pack4(kown[0], kown[1], kown[2], kown[3]), fp8_pack4(kown[4], kown[5], kown[6], kown[7])};
+      *reinterpret_cast<u32x2*>(vb + (size_t)pos * DH + sub * VEC) =
+          u32x2{fp8_pack4(vown[0], vown[1], vown[2], vown[3]), fp8_pack4(vown[4], vown[5], vown[6], vown[7])};
+    } else {
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      stf(kb + (size_t)pos * DH + sub * VEC + i, kown[i]);
-      stf(vb + (size_t)pos * DH + sub * VEC + i, vown[i]);
+      for (int i = 0; i < VEC; ++i) {
+        stf(kb + (size_t)pos * DH + sub * VEC + i, kown[i]);
+        stf(vb + (size_t)pos * DH + sub * VEC + i, vown[i]);
+      }
     }
   }
   ATTN_STAMP(2)
@@ -267,6 +277,7 @@ int decode_attn2(void* ctx, int to, const float* qkv, void* kc, void* vc, const 
   else                                      \
     ATTN_GO(TC, TO, NIT, NT, NSPLIT, false);
   if (part_o) {  // split form: 4 workgroups of 256 threads per (row, head), partials merged by the projection GEMV
+    ITTS_REQUIRE(tc != FP8, "decode_attn2: the split form has no fp8 (e4m3) cache form - an fp8 cache runs the whole forms only");
     ITTS_REQUIRE(part_ml && tc == BF16, "decode_attn2: split form needs both partial buffers and a bf16 cache");
     grid.z = ATTN_NSPLIT;
     ctx = nullptr;
@@ -289,6 +300,10 @@ int decode_attn2(void* ctx, int to, const float* qkv, void* kc, void* vc, const 
     ATTN_WHOLE(bf16_t, bf16_t)
   } else if (tc == BF16 && to == F32) {
     ATTN_WHOLE(bf16_t, float)
+  } else if (tc == FP8 && to == BF16) {  // the opt-in e4m3 cache (whole forms only): caches are bytes, 8-byte aligned
+    ATTN_WHOLE(fp8_t, bf16_t)
+  } else if (tc == FP8 && to == F32) {
+    ATTN_WHOLE(fp8_t, float)
   } else {
     set_error("decode_attn2: dtype combination");
     return E_INVALID;

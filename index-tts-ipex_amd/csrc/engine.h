@@ -123,10 +123,11 @@ struct GraphKey {
   int B = 0, Smax = 0, max_gen = 0, use_forced = 0, input_n = 0, host_sample = 0;
   int fuse = 0, eng = 0;  // derived: fuse && !fuse_failed, engine_usable()
   int nb = 1, beam_sample = 1, suppress_stop = 0, do_sample = 0, top_k = 0;
+  int ct = 0;  // element type of the K/V cache (DecodeState::ct): the attention form and every per-layer cache offset
   float length_penalty = 0.f, typical_mass = 0.f, penalty = 0.f, top_p = 1.f, temperature = 1.f;  // compared as floats: a NaN re-captures
   bool operator==(const GraphKey& o) const {
     return B == o.B && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
-           host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample &&
+           host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample && ct == o.ct &&
            length_penalty == o.length_penalty && typical_mass == o.typical_mass && penalty == o.penalty &&
            suppress_stop == o.suppress_stop && do_sample == o.do_sample && top_k == o.top_k && top_p == o.top_p &&
            temperature == o.temperature;
@@ -136,7 +137,13 @@ struct GraphKey {
 struct DecodeState {
   int B = 0, Smax = 0, prefix = 0, max_gen = 0;
   size_t cache_bytes = 0;
-  void *kc = nullptr, *vc = nullptr;  // [layers][B][H][Smax][dh]
+  void *kc = nullptr, *vc = nullptr;  // [layers][B][H][Smax][dh], elements of type ct
+  // element type of the cache: the engine's own (F32 / BF16) or, opt-in on a 16-bit engine, FP8 = e4m3 bytes (itts_gpt_set_kv_fp8 /
+  // ITTS_KV_FP8).  kv_fp8 is the sticky request; ct / ces are what the prefill latched for the whole generation
+  // (ensure_decode_state), ct_held the type whose values the allocation last held (-1: fresh).  An fp8 cache keeps the launch
+  // path's whole-form attention at every row count (engine_usable() is false, no split form, no fused qkv + attention launch).
+  int kv_fp8 = 0, ct = 0, ct_held = -1;
+  size_t ces = 4;
   float *h = nullptr, *qkv = nullptr, *ctx = nullptr, *act = nullptr, *hn = nullptr, *logits = nullptr;
   float *attn_o = nullptr, *attn_ml = nullptr;  // split decode attention partials (decode_attn.hip, ATTN_NSPLIT), small batches
   float* partial = nullptr;           // [4][B][D] split-K partial sums of the residual projections (batched decode)

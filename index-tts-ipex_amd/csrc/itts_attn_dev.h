@@ -33,6 +33,16 @@ template <> struct CacheVec<bf16_t> {
     return (i & 1) ? half_hi(w) : half_lo(w);
   }
 };
+// the opt-in e4m3 cache (decode_attn2_kernel only): the thread <-> key mapping of the 16-bit cache - 8 lanes per key row, 8 dims
+// each, one nontemporal 8-byte load per lane - so SLOTS, the blind rows, the register window, the stream step and the DPP
+// summation order are the 16-bit form's, and the kernel computes, operation for operation, what the 16-bit form computes on a
+// cache holding the same values (tests/test_gpu_decode_attn_fp8.py)
+template <> struct CacheVec<fp8_t> {
+  static constexpr int VEC = 8, LPK = 8;
+  u32x2 raw;
+  __device__ __forceinline__ void load(const fp8_t* p) { raw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p)); }
+  __device__ __forceinline__ float get(int i) const { return fp8_get(raw[i >> 2], i & 3); }
+};
 template <> struct CacheVec<float> {
   static constexpr int VEC = 4, LPK = 16;
   float4 raw;

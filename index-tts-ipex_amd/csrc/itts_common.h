@@ -17,7 +17,7 @@ typedef __bf16 bf16_t;
 #endif
 typedef _Float16 f16_t;
 
-enum DType : int { F32 = 0, BF16 = 1, I32 = 2, I64 = 3, FP8 = 4, F16 = 5 };  // F16: operator-level boundary only (itts_snake_aa_fwd)  // FP8 = OCP e4m3fn bytes (weights only)
+enum DType : int { F32 = 0, BF16 = 1, I32 = 2, I64 = 3, FP8 = 4, F16 = 5 };  // F16: operator-level boundary only (itts_snake_aa_fwd)  // FP8 = OCP e4m3fn bytes (GPT weights; the opt-in K/V cache, fp8_t below)
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_GELU_NEW = 3, ACT_GELU_ERF = 4, ACT_TANH = 5, ACT_SIGMOID = 6 };
 enum PadMode : int { PAD_ZERO = 0, PAD_REFLECT = 1 };
 
@@ -67,6 +67,35 @@ __device__ __forceinline__ void stf(bf16_t* p, float v) { *p = (bf16_t)v; }
 #ifndef ITTS_HALF_F16
 __device__ __forceinline__ void stf(f16_t* p, float v) { *p = (f16_t)v; }
 #endif
+
+// ---- one OCP e4m3fn byte of the opt-in fp8 K/V cache (itts_gpt_set_kv_fp8), no scale ----
+// Encoding: clamp to [-448, 448], then round to nearest even, subnormals included (v_med3_f32 + v_cvt_pk_fp8_f32) - what
+// x.clamp(-448, 448).to(torch.float8_e4m3fn) gives, so no NaN byte (0x7F / 0xFF) ever reaches the cache.  Decoding is exact
+// (v_cvt_pk_f32_fp8), and every finite e4m3 value is exact in bf16 and in binary16: the type exists in both libraries.
+__device__ __forceinline__ uint32_t fp8_pack2(float a, float b) {  // bytes (a, b) in the low 16 bits
+  a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f);
+  b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xFFFFu;
+}
+__device__ __forceinline__ uint32_t fp8_pack4(float a, float b, float c, float d) {  // bytes (a, b, c, d), a lowest
+  a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f);
+  b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
+  c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f);
+  d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false), true);
+}
+__device__ __forceinline__ float fp8_get(uint32_t w, int i) {  // byte i (0 .. 3) of a word of four
+  const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  return (i & 2) ? ((i & 1) ? hi[1] : hi[0]) : ((i & 1) ? lo[1] : lo[0]);
+}
+struct fp8_t {
+  uint8_t bits;
+  fp8_t() = default;
+  __device__ __forceinline__ explicit fp8_t(float x) : bits((uint8_t)fp8_pack2(x, x)) {}
+  __device__ __forceinline__ explicit operator float() const { return fp8_get(bits, 0); }
+};
+__device__ __forceinline__ float ldf(const fp8_t* p) { return (float)(*p); }
+__device__ __forceinline__ void stf(fp8_t* p, float v) { *p = fp8_t(v); }
 
 // ---- the half type at the bit level: two halves of a 32-bit word, the 16x16x32 matrix instruction, the 2-way dot product ----
 // (the vector types of every kernel file: one typedef per distinct type, here)

@@ -94,8 +94,8 @@ int Engine::gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, boo
     ITTS_TRY(ln(xn, adt, h, F32, L.ln1, M, D, s));
     ITTS_TRY(lin(qkv, adt, xn, adt, D, L.attn, M, 3 * D, s));
     if (write_cache) {
-      const size_t lo = (size_t)l * ds.B * H * ds.Smax * dh * es;
-      K(kv_scatter((char*)ds.kc + lo, (char*)ds.vc + lo, qkv, B, S, H, dh, ds.Smax, adt, adt, s));
+      const size_t lo = (size_t)l * ds.B * H * ds.Smax * dh * ds.ces;  // the cache's element size, not the engine's
+      K(kv_scatter((char*)ds.kc + lo, (char*)ds.vc + lo, qkv, B, S, H, dh, ds.Smax, adt, ds.ct, s));
     }
     AttnArgs a;
     a.q = qkv;
@@ -194,6 +194,7 @@ bool Engine::engine_usable() const {
   const itts_config& c = cfg;
   if ((env_off && !ds.eng_force) || ds.eng_off || ds.eng_failed || ncu != ENG_NCU) return false;
   if (ds.fuse && !ds.fuse_failed) return false;  // A/B switch of the fused projection + attention launch: a launch-path variant
+  if (ds.ct == FP8) return false;  // the fp8 K/V cache has a launch-path attention form only (decode_attn2_kernel<fp8_t>)
   if (adt != BF16 || ds.B < 1 || ds.B > ENG_MAX_ROWS || ds.nb < 1 || ds.B % ds.nb != 0 || (ds.nb > 1 && !ds.anc)) return false;
   if (c.model_dim != ENG_D || c.heads != ENG_H || c.layers < 1 || c.layers > ENG_MAX_LAYERS || ds.Smax > 2048 || ds.Smax % 256 != 0) return false;
   for (const GptLayerW& L : gpt.layers)
@@ -239,11 +240,30 @@ int Engine::ensure_decode_state(int B, int Smax, int max_gen, hipStream_t s) {
   const int D = c.model_dim, H = c.heads, dh = D / H, V = c.number_mel_codes;
   DecodeState& d = ds;
   if (rows_on_mfma(B)) ITTS_TRY(ensure_decode_tiles(s));
-  const size_t need = (size_t)c.layers * B * H * Smax * dh * es;
+  // the cache type of this generation, latched here (by the prefill): the engine's own, or e4m3 bytes when a 16-bit engine opted
+  // in - ITTS_KV_FP8 (read per prefill: tests flip it inside one process) overrides the setter in both directions; fp32 engines
+  // ignore both
+  int ct = adt;
+  if (adt == BF16) {
+    const char* ev = getenv("ITTS_KV_FP8");
+    if (ev ? atoi(ev) != 0 : d.kv_fp8 != 0) ct = FP8;
+  }
+  const size_t ces = dtype_size(ct);
+  const size_t need = (size_t)c.layers * B * H * Smax * dh * ces;
   const bool regrow = B > d.cap_B || max_gen > d.cap_gen;
-  if (need > d.cache_bytes || regrow || B != d.B || Smax != d.Smax) {
+  // bytes left by the other type are not values of this one: bf16 halves read as e4m3 hold NaN encodings (0x7F / 0xFF), e4m3
+  // bytes read as 16-bit pairs hold Inf / NaN - and rows past the sequence end have to be finite (below)
+  const bool retype = d.cache_bytes && d.ct_held != ct;
+  if (need > d.cache_bytes || regrow || B != d.B || Smax != d.Smax || retype) {
     ITTS_HIP_CHECK(hipStreamSynchronize(s));
     d.drop_graphs();
+  }
+  d.ct = ct;
+  d.ces = ces;
+  d.ct_held = ct;
+  if (need <= d.cache_bytes && retype) {  // the whole allocation, not just this request's share
+    ITTS_HIP_CHECK(hipMemsetAsync(d.kc, 0, d.cache_bytes, s));
+    ITTS_HIP_CHECK(hipMemsetAsync(d.vc, 0, d.cache_bytes, s));
   }
   if (need > d.cache_bytes) {
     ITTS_TRY(dev_alloc(&d.kc, need));
@@ -796,7 +816,7 @@ EngArgs Engine::engine_args(int& eng_first, bool& fold_head, bool& fold_samp) co
   }
   ea.gran = ds.eng_gran;
   ea.h = ds.h;
-  ea.kc = (bf16_t*)ds.kc;
+  ea.kc = (bf16_t*)ds.kc;  // engine_usable(): a 16-bit cache (ds.ces == 2) - the kernel's per-layer offsets count bf16_t elements
   ea.vc = (bf16_t*)ds.vc;
   ea.len = ds.len;
   ea.kv_start = ds.kv_start;
@@ -982,11 +1002,12 @@ int Engine::decode_step_launch(hipStream_t s) {
     g.prologue = 1;
     g.ln_gamma = L.ln1.g;
     g.ln_beta = L.ln1.b;
-    const size_t lo = (size_t)l * B * H * ds.Smax * dh * es;
+    const size_t lo = (size_t)l * B * H * ds.Smax * dh * ds.ces;  // the cache's element size, not the engine's
     // few (row, head) pairs: the keys of each pair go to ATTN_NSPLIT workgroups and the projection merges the partials
     static const bool no_split = getenv("ITTS_ATTN_NOSPLIT") != nullptr;
     static const bool env_fuse = getenv("ITTS_FUSE_QKV_ATTN") != nullptr && atoi(getenv("ITTS_FUSE_QKV_ATTN")) != 0;
-    const bool split = fast && bf_ctx && !no_split && (long)B * H <= 128 && D % 64 == 0;
+    // (an fp8 K/V cache has the whole forms only: neither the split form nor the fused launch below)
+    const bool split = fast && bf_ctx && !no_split && (long)B * H <= 128 && D % 64 == 0 && ds.ct != FP8;
     // projection + attention of the layer as ONE launch (the attention workgroups poll for q / k / v): bf16 weights only
     const bool fused = split && (ds.fuse || env_fuse) && !ds.fuse_failed && !g.w8src && gemv_bf16_supported(g) && qkv_attn_fused_supported(g, H, dh);
     if (fused) {
@@ -1005,10 +1026,10 @@ int Engine::decode_step_launch(hipStream_t s) {
     if (fused) {
     } else if (split)
       ITTS_TRY(decode_attn2(nullptr, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B, H,
-                            dh, ds.Smax, adt, s, 0, ds.attn_o, ds.attn_ml, ds.nb > 1 ? ds.anc : nullptr, ds.nb));
+                            dh, ds.Smax, ds.ct, s, 0, ds.attn_o, ds.attn_ml, ds.nb > 1 ? ds.anc : nullptr, ds.nb));
     else
       ITTS_TRY(decode_attn2(ds.ctx, bf_ctx ? BF16 : F32, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start,
-                            ds.prefix_dev, B, H, dh, ds.Smax, adt, s, skinny ? 1 : 0, nullptr, nullptr,
+                            ds.prefix_dev, B, H, dh, ds.Smax, ds.ct, s, skinny ? 1 : 0, nullptr, nullptr,
                             ds.nb > 1 ? ds.anc : nullptr, ds.nb));
     GemvArgs p = lin_gemv(L.proj, B);  // h += ctx Wproj + b
     p.X = ds.ctx;
@@ -1245,6 +1266,7 @@ GraphKey Engine::graph_key() const {
   k.host_sample = d.host_sample;
   k.fuse = d.fuse && !d.fuse_failed;
   k.eng = (int)engine_usable();
+  k.ct = d.ct;
   k.nb = d.nb;
   k.beam_sample = d.beam_sample;
   k.length_penalty = d.length_penalty;

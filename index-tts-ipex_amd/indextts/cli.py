@@ -23,6 +23,8 @@ def build_parser():
                         "whole-vocabulary HIP beam sampler); unset: ITTS_WIDE_BEAM_SAMPLER")
     p.add_argument("--gpt-fp8", action="store_true", default=False,
                    help="store the GPT weights as fp8-e4m3 (bfloat16 engine; the decode steps stream the fp8 bytes)")
+    p.add_argument("--kv-fp8", action="store_true", default=False,
+                   help="keep the K/V cache of the GPT decode steps as fp8-e4m3 bytes (16-bit engines; half the cache bytes per step)")
     return p
 
 
@@ -44,7 +46,7 @@ def main():
         sys.exit(1)
     from indextts.infer import IndexTTS
 
-    tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8,
+    tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8, kv_fp8=a.kv_fp8,
                    wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 

@@ -28,6 +28,8 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `gpt_fp8=True` (not in the reference; needs `is_fp16=True`) stores the GPT projections and mel_head as fp8-e4m3 with
     power-of-two row scales (pack.quantize_gpt_fp8), runs on the bfloat16 engine - the fp8 readers expand to bf16 pairs - and
     lets the 1 - 6 row decode steps stream the fp8 bytes on the persistent decode engine.
+  * `kv_fp8=True` (not in the reference; needs `is_fp16=True`, works with both 16-bit engines and together with `gpt_fp8`) keeps
+    the K/V cache of the GPT decode steps as fp8-e4m3 bytes: half the cache bytes per step; the decode steps keep the launch path.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -52,7 +54,7 @@ from indextts.utils.front import TextNormalizer, TextTokenizer
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
-                 wide_beam_sampler=None):
+                 wide_beam_sampler=None, kv_fp8=False):
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -74,6 +76,9 @@ class IndexTTS:
         self.wide_sampler = wide_sampler
         # the same choice for several beams (beam_sample with top_k = 0 / None or > 128): None: ITTS_WIDE_BEAM_SAMPLER, else "host"
         self.wide_beam_sampler = wide_beam_sampler
+        self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
+        if self.kv_fp8 and not self.is_fp16:
+            raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
         if self.gpt_fp8 and not self.is_fp16:
             raise ValueError("gpt_fp8=True needs is_fp16=True: the fp8 GPT weights run on the bfloat16 engine, not the fp32 one")
         if self.gpt_fp8 and self.half != "bf16":
@@ -100,6 +105,8 @@ class IndexTTS:
         self.engine.finalize()
         if self.gpt_fp8:
             self.engine.set_engine_fp8(True)
+        if self.kv_fp8:
+            self.engine.set_kv_fp8(True)
         self.gpt = UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("ITTS_HIP_LIB", os.path.join(CSRC, "libitts_hip.so"))
 LIB_PATH_F16 = os.environ.get("ITTS_HIP_LIB_F16", os.path.join(CSRC, "libitts_hip_f16.so"))  # the same sources, IEEE half storage
 
 F32, BF16 = 0, 1
-FP8 = 4  # OCP e4m3fn bytes (GPT decode weights, BASELINE config 5)
+FP8 = 4  # OCP e4m3fn bytes (GPT decode weights, BASELINE config 5; the opt-in K/V cache)
 F16 = 5  # IEEE half, operator-level boundary only (itts_snake_aa_fwd)
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GELU_NEW, ACT_GELU_ERF, ACT_TANH, ACT_SIGMOID = range(7)  # csrc/itts_common.h enum Act
 ACT = {"none": 0, "relu": 1, "silu": 2, "gelu_new": 3, "gelu_erf": 4, "tanh": 5, "sigmoid": 6}
@@ -73,6 +73,7 @@ _PROTOS = {
     "itts_gemv": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp]),
     "itts_gemv_bf16": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "itts_decode_attn": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "itts_kv_scatter": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "itts_sample_rows": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, f32, f32, vp, vp, C.c_size_t, vp]),
     "itts_beam_sample_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, f32, f32, vp,
                                     vp, C.c_size_t, vp]),
@@ -93,6 +94,7 @@ _PROTOS = {
     "itts_gpt_set_input_tokens": (i32, [vp, vp, i32, i32]),
     "itts_gpt_decode_mode": (i32, [vp]),
     "itts_gpt_set_engine_fp8": (i32, [vp, i32]),
+    "itts_gpt_set_kv_fp8": (i32, [vp, i32]),
     "itts_gpt_set_host_sampling": (i32, [vp, i32]),
     "itts_gpt_set_cond_per_row": (i32, [vp, i32]),
     "itts_gpt_commit": (i32, [vp, vp, vp]),
