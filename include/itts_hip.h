@@ -194,6 +194,49 @@ int itts_ln_rows_bf16(void* y, float* x, const float* gamma, const float* beta, 
 
 int itts_transpose(void* y, const void* x, int B, int R, int C, int dtype, itts_stream stream);
 
+/* One operator-level entry to the row-wise / elementwise kernels (csrc/elementwise.hip, and the two small kernels of
+ * csrc/model_vocoder.hip that feed the DVAE encoder), as the engine calls them; tests/test_gpu_elementwise.py uses it.  The struct is
+ * read per op as listed; fields an op does not name are ignored.  w / b / codes aside, pointers are in dtype_x (inputs) and dtype_y
+ * (outputs); ops with one type take dtype_x == dtype_y, ITTS_F32 or ITTS_BF16.  Activations are row-major, channels last.
+ *   LAYERNORM      y[rows][ldy] = act(LayerNorm(x[rows][ldx], D, eps) * w + b); w, b fp32 [D], both or neither; any of the four
+ *                  type pairs; act: an ITTS act code of csrc/itts_common.h (0 none, 2 SiLU)
+ *   RMSNORM_UNIT   y fp32 [rows][D] = x / max(|x|, 1e-12) * sqrt(D) * w; dtype_y = ITTS_F32
+ *   GLU            y[rows][D] = x[rows][0:D] * sigmoid(x[rows][D:2D])
+ *   GEGLU          y[rows][ldy]: columns < D = x[rows][0:D] * gelu_erf(x[rows][D:2D]), columns D .. ldy - 1 = 0
+ *   DWCONV         y[B][T][D] = depthwise conv over T, k taps, zero padding (k - 1) / 2 each side; w fp32 [D][k], b fp32 [D] or null
+ *   CONV2D_SUB2    y[B][T'][N][D'] = relu(Conv2d(1, N, 3, stride 2)) of x [B][T][D]; T' = (T - 3) / 2 + 1, D' = (D - 3) / 2 + 1;
+ *                  w fp32 [N][3][3], b fp32 [N]; T, D >= 3
+ *   CAST_COPY      y[rows * D] = x[rows * D], any of the four type pairs
+ *   COPY_ROWS      y[rows][ldy] <- x[rows][ldx], D columns
+ *   ADD_STRIDED    y[rows][ldy] = x[rows][ldx] + x2[rows][ld2], D columns
+ *   COL_MEAN       y fp32 [B][D] = mean over T of x[B][T][ldx]
+ *   COL_MEAN_STD   y fp32 [B][2 D] = that mean | the population std, sqrt(max(var, 1e-12))
+ *   SCALE_COLS_ADD y[B * T][ldy] = x[B * T][ldx] * w[B][D] (+ x2[B * T][ld2] when x2 is set)
+ *   ASP_POOL       y fp32 [B][2 D]: per (b, column) the softmax over T of x [B][T][D] weights x2 [B][T][D]: weighted mean | std
+ *                  (sqrt(max(var, 1e-12))), then * w[2 D] + b[2 D]
+ *   RELPOS_PACK    x = qkv [T][3 N D] (q | k | v, N heads of D), x2 = p [T][N D]: y [T][N][2 D] = q + w | q + b (w, b fp32 [N D]),
+ *                  y2 [T][N][2 D] = k | p
+ *   DVAE_ARGMIN    y int32 [rows] = the first n that minimises b[n] - 2 x[row][n]; x fp32 [rows][N] (dtype_x = ITTS_F32), b fp32 [N]
+ *   PAIR_ROWS      y[B][(T + 1) / 2][2 D] = x[B][2 t][:] | x[B][2 t + 1][:] (zero past T)
+ * Null required pointers, non-positive dimensions, a row stride below the row width, an unknown op or type pair and CONV2D_SUB2
+ * below 3 x 3 are refused with ITTS_E_INVALID and a message before any HIP call. */
+enum {
+  ITTS_ROWOP_LAYERNORM = 0, ITTS_ROWOP_RMSNORM_UNIT, ITTS_ROWOP_GLU, ITTS_ROWOP_GEGLU, ITTS_ROWOP_DWCONV, ITTS_ROWOP_CONV2D_SUB2,
+  ITTS_ROWOP_CAST_COPY, ITTS_ROWOP_COPY_ROWS, ITTS_ROWOP_ADD_STRIDED, ITTS_ROWOP_COL_MEAN, ITTS_ROWOP_COL_MEAN_STD,
+  ITTS_ROWOP_SCALE_COLS_ADD, ITTS_ROWOP_ASP_POOL, ITTS_ROWOP_RELPOS_PACK, ITTS_ROWOP_DVAE_ARGMIN, ITTS_ROWOP_PAIR_ROWS,
+  ITTS_ROWOP_COUNT
+};
+typedef struct {
+  void* y; void* y2;
+  const void* x; const void* x2;
+  const float* w; const float* b;
+  int dtype_x, dtype_y;
+  int rows, B, T, D, N, k;
+  int ldx, ldy, ld2;
+  int act; float eps;
+} itts_rowop_args;
+int itts_rowop(int op, const itts_rowop_args* args, itts_stream stream);
+
 /* ---- engine level ----------------------------------------------------------------------------------- */
 
 typedef struct {

@@ -276,6 +276,108 @@ int itts_transpose(void* y, const void* x, int B, int R, int C, int dtype, itts_
   return transpose_brc(y, x, B, R, C, dtype, (hipStream_t)stream);
 }
 
+int itts_rowop(int op, const itts_rowop_args* a, itts_stream stream) {
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+#define ROWOP_REQUIRE(cond, msg)                  \
+  do {                                            \
+    if (!(cond)) {                                \
+      set_error("itts_rowop: " msg " (" #cond ")"); \
+      return E_INVALID;                           \
+    }                                             \
+  } while (0)
+  ROWOP_REQUIRE(a, "null args");
+  ROWOP_REQUIRE(op >= 0 && op < ITTS_ROWOP_COUNT, "unknown op");
+  hipStream_t s = (hipStream_t)stream;
+  const int tx = a->dtype_x, ty = a->dtype_y;
+  const bool half_or_f32 = (tx == F32 || tx == BF16) && (ty == F32 || ty == BF16);
+  const bool one_type = half_or_f32 && tx == ty;  // ops with a single element type
+  const bool f32_out = half_or_f32 && ty == F32;  // statistics: fp32 results from either input type
+  switch (op) {
+    case ITTS_ROWOP_LAYERNORM:
+      ROWOP_REQUIRE(a->y && a->x && (a->w == nullptr) == (a->b == nullptr), "layernorm: null pointer, or one of w / b alone");
+      ROWOP_REQUIRE(a->rows > 0 && a->D > 0 && a->ldx >= a->D && a->ldy >= a->D, "layernorm: rows, D >= 1; ldx, ldy >= D");
+      ROWOP_REQUIRE(half_or_f32, "layernorm: dtype");
+      ROWOP_REQUIRE(a->act >= ACT_NONE && a->act <= ACT_SIGMOID, "layernorm: act");
+      return layernorm(a->y, ty, a->x, tx, a->w, a->b, a->rows, a->D, a->ldx, a->ldy, a->eps, a->act, s);
+    case ITTS_ROWOP_RMSNORM_UNIT:
+      ROWOP_REQUIRE(a->y && a->x && a->w, "rmsnorm_unit: null pointer");
+      ROWOP_REQUIRE(a->rows > 0 && a->D > 0, "rmsnorm_unit: rows, D >= 1");
+      ROWOP_REQUIRE(f32_out, "rmsnorm_unit: dtype (fp32 output)");
+      return rmsnorm_unit(a->y, ty, a->x, tx, a->w, a->rows, a->D, s);
+    case ITTS_ROWOP_GLU:
+      ROWOP_REQUIRE(a->y && a->x, "glu: null pointer");
+      ROWOP_REQUIRE(a->rows > 0 && a->D > 0, "glu: rows, D >= 1");
+      ROWOP_REQUIRE(one_type, "glu: dtype");
+      return glu(a->y, a->x, a->rows, a->D, tx, s);
+    case ITTS_ROWOP_GEGLU:
+      ROWOP_REQUIRE(a->y && a->x, "geglu: null pointer");
+      ROWOP_REQUIRE(a->rows > 0 && a->D > 0 && a->ldy >= a->D, "geglu: rows, D >= 1; ldy >= D");
+      ROWOP_REQUIRE(one_type, "geglu: dtype");
+      return geglu(a->y, a->x, a->rows, a->D, a->ldy, tx, s);
+    case ITTS_ROWOP_DWCONV:
+      ROWOP_REQUIRE(a->y && a->x && a->w, "dwconv: null pointer");
+      ROWOP_REQUIRE(a->B > 0 && a->T > 0 && a->D > 0 && a->k > 0, "dwconv: B, T, D, k >= 1");
+      ROWOP_REQUIRE(one_type, "dwconv: dtype");
+      return dwconv(a->y, a->x, a->w, a->b, a->B, a->T, a->D, a->k, tx, s);
+    case ITTS_ROWOP_CONV2D_SUB2:
+      ROWOP_REQUIRE(a->y && a->x && a->w && a->b, "conv2d_sub2: null pointer");
+      ROWOP_REQUIRE(a->B > 0 && a->N > 0, "conv2d_sub2: B, N >= 1");
+      ROWOP_REQUIRE(a->T >= 3 && a->D >= 3, "conv2d_sub2: input below 3 x 3");
+      ROWOP_REQUIRE(one_type, "conv2d_sub2: dtype");
+      return conv2d_sub2(a->y, a->x, a->w, a->b, a->B, a->T, a->D, a->N, tx, s);
+    case ITTS_ROWOP_CAST_COPY:
+      ROWOP_REQUIRE(a->y && a->x, "cast_copy: null pointer");
+      ROWOP_REQUIRE(a->rows > 0 && a->D > 0, "cast_copy: rows, D >= 1");
+      ROWOP_REQUIRE(half_or_f32, "cast_copy: dtype");
+      return cast_copy(a->y, ty, a->x, tx, (long)a->rows * a->D, s);
+    case ITTS_ROWOP_COPY_ROWS:
+      ROWOP_REQUIRE(a->y && a->x, "copy_rows: null pointer");
+      ROWOP_REQUIRE(a->rows > 0 && a->D > 0 && a->ldx >= a->D && a->ldy >= a->D, "copy_rows: rows, D >= 1; ldx, ldy >= D");
+      ROWOP_REQUIRE(one_type, "copy_rows: dtype");
+      return copy_rows(a->y, a->ldy, a->x, a->ldx, a->rows, a->D, tx, s);
+    case ITTS_ROWOP_ADD_STRIDED:
+      ROWOP_REQUIRE(a->y && a->x && a->x2, "add_strided: null pointer");
+      ROWOP_REQUIRE(a->rows > 0 && a->D > 0 && a->ldx >= a->D && a->ld2 >= a->D && a->ldy >= a->D,
+                    "add_strided: rows, D >= 1; ldx, ld2, ldy >= D");
+      ROWOP_REQUIRE(one_type, "add_strided: dtype");
+      return add_strided(a->y, a->ldy, a->x, a->ldx, a->x2, a->ld2, a->rows, a->D, tx, s);
+    case ITTS_ROWOP_COL_MEAN:
+    case ITTS_ROWOP_COL_MEAN_STD:
+      ROWOP_REQUIRE(a->y && a->x, "col_mean / col_mean_std: null pointer");
+      ROWOP_REQUIRE(a->B > 0 && a->T > 0 && a->D > 0 && a->ldx >= a->D, "col_mean / col_mean_std: B, T, D >= 1; ldx >= D");
+      ROWOP_REQUIRE(f32_out, "col_mean / col_mean_std: dtype (fp32 output)");
+      return op == ITTS_ROWOP_COL_MEAN ? col_mean((float*)a->y, a->x, a->B, a->T, a->D, a->ldx, tx, s)
+                                       : col_mean_std((float*)a->y, a->x, a->B, a->T, a->D, a->ldx, tx, s);
+    case ITTS_ROWOP_SCALE_COLS_ADD:
+      ROWOP_REQUIRE(a->y && a->x && a->w, "scale_cols_add: null pointer");
+      ROWOP_REQUIRE(a->B > 0 && a->T > 0 && a->D > 0 && a->ldx >= a->D && a->ldy >= a->D && (!a->x2 || a->ld2 >= a->D),
+                    "scale_cols_add: B, T, D >= 1; ldx, ldy, ld2 >= D");
+      ROWOP_REQUIRE(one_type, "scale_cols_add: dtype");
+      return scale_cols_add(a->y, a->ldy, a->x, a->ldx, a->w, a->x2, a->ld2, a->B, a->T, a->D, tx, s);
+    case ITTS_ROWOP_ASP_POOL:
+      ROWOP_REQUIRE(a->y && a->x && a->x2 && a->w && a->b, "asp_pool: null pointer");
+      ROWOP_REQUIRE(a->B > 0 && a->T > 0 && a->D > 0, "asp_pool: B, T, D >= 1");
+      ROWOP_REQUIRE(f32_out, "asp_pool: dtype (fp32 output)");
+      return asp_pool((float*)a->y, a->x, a->x2, a->w, a->b, a->B, a->T, a->D, tx, s);
+    case ITTS_ROWOP_RELPOS_PACK:
+      ROWOP_REQUIRE(a->y && a->y2 && a->x && a->x2 && a->w && a->b, "relpos_pack: null pointer");
+      ROWOP_REQUIRE(a->T > 0 && a->N > 0 && a->D > 0, "relpos_pack: T, N, D >= 1");
+      ROWOP_REQUIRE(one_type, "relpos_pack: dtype");
+      return relpos_pack(a->y, a->y2, a->x, a->x2, a->w, a->b, a->T, a->N, a->D, tx, s);
+    case ITTS_ROWOP_DVAE_ARGMIN:
+      ROWOP_REQUIRE(a->y && a->x && a->b, "dvae_argmin: null pointer");
+      ROWOP_REQUIRE(a->rows > 0 && a->N > 0, "dvae_argmin: rows, N >= 1");
+      ROWOP_REQUIRE(tx == F32, "dvae_argmin: dtype (fp32 dots)");
+      return dvae_argmin((int*)a->y, (const float*)a->x, a->b, a->rows, a->N, s);
+    default:  // ITTS_ROWOP_PAIR_ROWS
+      ROWOP_REQUIRE(a->y && a->x, "pair_rows: null pointer");
+      ROWOP_REQUIRE(a->B > 0 && a->T > 0 && a->D > 0, "pair_rows: B, T, D >= 1");
+      ROWOP_REQUIRE(one_type, "pair_rows: dtype");
+      return pair_rows(a->y, a->x, a->B, a->T, a->D, tx, s);
+  }
+#undef ROWOP_REQUIRE
+}
+
 int itts_engine_create(const itts_config* cfg, itts_engine** out) {
   if (!cfg || !out) {
     set_error("itts_engine_create: null argument");

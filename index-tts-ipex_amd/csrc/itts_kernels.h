@@ -55,6 +55,12 @@ int relpos_pack(void* qc, void* kc, const void* qkv, const void* p, const float*
                 int dk, int dt, hipStream_t s);
 int tanh_rows(void* y, const void* x, long n, int dt, hipStream_t s);
 
+// ---- the DVAE encoder's small kernels (model_vocoder.hip) ----
+// y[B][(Tin + 1) / 2][2 C] = x[B][2t][:] | x[B][2t + 1][:], zero past Tin (the row pairs of a stride-2 convolution)
+int pair_rows(void* y, const void* x, int B, int Tin, int C, int dt, hipStream_t s);
+// codes[r] = the first n that minimises esq[n] - 2 dots[r][n]; dots fp32 [rows][N]
+int dvae_argmin(int* codes, const float* dots, const float* esq, int rows, int N, hipStream_t s);
+
 // ---- attention (attention.hip) ----
 struct AttnArgs {
   const void* q = nullptr;  // [B, Sq] rows, element (b,i,h,d) at q[(b*Sq+i)*ldq + h*dqk + d]

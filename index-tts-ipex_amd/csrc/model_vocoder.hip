@@ -75,6 +75,26 @@ __global__ __launch_bounds__(256) void dvae_argmin_kernel(int* __restrict__ code
 
 }  // namespace
 
+int pair_rows(void* y, const void* x, int B, int Tin, int C, int dt, hipStream_t s) {
+  const int Tout = (Tin + 1) / 2;
+  if (dt == F32)
+    hipLaunchKernelGGL(pair_rows_kernel<float>, dim3(B * Tout), dim3(256), 0, s, (float*)y, (const float*)x, Tin, Tout, C);
+  else if (dt == BF16)
+    hipLaunchKernelGGL(pair_rows_kernel<bf16_t>, dim3(B * Tout), dim3(256), 0, s, (bf16_t*)y, (const bf16_t*)x, Tin, Tout, C);
+  else {
+    set_error("pair_rows: dtype");
+    return E_INVALID;
+  }
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+int dvae_argmin(int* codes, const float* dots, const float* esq, int rows, int N, hipStream_t s) {
+  hipLaunchKernelGGL(dvae_argmin_kernel, dim3(rows), dim3(256), 0, s, codes, dots, esq, N);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
 #define K(call)               \
   do {                        \
     if (!dry) ITTS_TRY(call); \
@@ -388,13 +408,7 @@ int Engine::dvae_encode(const void* mel, int B, int T, int32_t* codes_host, hipS
     for (int i = 0; i < c.dv_layers; ++i) {
       const int Tp = (Tn + 1) / 2;
       void* pr = alloc((size_t)B * Tp * 2 * C * es);
-      if (!dry) {
-        if (adt == F32)
-          hipLaunchKernelGGL(pair_rows_kernel<float>, dim3(B * Tp), dim3(256), 0, s, (float*)pr, (const float*)cur, Tn, Tp, C);
-        else
-          hipLaunchKernelGGL(pair_rows_kernel<bf16_t>, dim3(B * Tp), dim3(256), 0, s, (bf16_t*)pr, (const bf16_t*)cur, Tn, Tp, C);
-        ITTS_HIP_CHECK(hipGetLastError());
-      }
+      K(pair_rows(pr, cur, B, Tn, C, adt, s));
       void* o = alloc((size_t)B * Tp * dv.enc[i].N * es);
       ITTS_TRY(conv1d(o, adt, pr, dv.enc[i], Tp, ACT_RELU, nullptr, 1));  // taps (pair t-1, pair t)
       cur = o;
@@ -415,9 +429,8 @@ int Engine::dvae_encode(const void* mel, int B, int T, int32_t* codes_host, hipS
     float* dots = (float*)alloc((size_t)B * Tn * c.dv_tokens * 4);
     ITTS_TRY(conv1d(dots, F32, z, dv.quant, Tn, ACT_NONE, nullptr, 0));
     int* codes_dev = (int*)alloc((size_t)B * Tn * 4);
+    K(dvae_argmin(codes_dev, dots, dv.codebook_sq, B * Tn, c.dv_tokens, s));
     if (!dry) {
-      hipLaunchKernelGGL(dvae_argmin_kernel, dim3(B * Tn), dim3(256), 0, s, codes_dev, dots, dv.codebook_sq, c.dv_tokens);
-      ITTS_HIP_CHECK(hipGetLastError());
       ITTS_HIP_CHECK(hipMemcpyAsync(codes_host, codes_dev, (size_t)B * Tn * 4, hipMemcpyDeviceToHost, s));
     }
     return OK;

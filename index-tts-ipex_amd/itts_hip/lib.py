@@ -54,6 +54,20 @@ class Config(C.Structure):
                 ("max_batch", i32)]
 
 
+# itts_rowop: the op codes (include/itts_hip.h ITTS_ROWOP_*) and the argument block
+ROWOPS = ("layernorm", "rmsnorm_unit", "glu", "geglu", "dwconv", "conv2d_sub2", "cast_copy", "copy_rows", "add_strided", "col_mean",
+          "col_mean_std", "scale_cols_add", "asp_pool", "relpos_pack", "dvae_argmin", "pair_rows")
+ROWOP = {name: i for i, name in enumerate(ROWOPS)}
+
+
+class RowopArgs(C.Structure):
+    _fields_ = [("y", vp), ("y2", vp), ("x", vp), ("x2", vp), ("w", vp), ("b", vp),
+                ("dtype_x", i32), ("dtype_y", i32),
+                ("rows", i32), ("B", i32), ("T", i32), ("D", i32), ("N", i32), ("k", i32),
+                ("ldx", i32), ("ldy", i32), ("ld2", i32),
+                ("act", i32), ("eps", f32)]
+
+
 _lib = None
 _lib_f16 = None
 
@@ -81,6 +95,7 @@ _PROTOS = {
     "itts_retile_weights": (i32, [vp, vp, i32, i32, vp]),
     "itts_ln_rows_bf16": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, vp, i32, vp, i32, vp]),
     "itts_transpose": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "itts_rowop": (i32, [i32, C.POINTER(RowopArgs), vp]),
     "itts_engine_create": (i32, [C.POINTER(Config), C.POINTER(vp)]),
     "itts_engine_destroy": (None, [vp]),
     "itts_engine_bind_tensor": (i32, [vp, C.c_char_p, vp, i32, i32, C.POINTER(i64)]),
