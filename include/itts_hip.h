@@ -381,6 +381,32 @@ int itts_gpt_status(itts_engine* e, int* steps_done_host, int* n_unfinished_host
 /* Copy generated codes (int32 [B, max_gen], pad = stop token) and optionally the last logits fp32 [B, V]. */
 int itts_gpt_fetch(itts_engine* e, int32_t* codes_host, float* logits_host, itts_stream stream);
 
+/* Row retirement of a running batched generation (opt-in; nothing changes for a caller that never calls it).  A finished row
+ * still runs every block and its cache attention each step, although its output is fixed.  itts_gpt_retire_rows synchronises and
+ * compacts the decode state - K/V history, hidden state, logits, ids, forced tokens, repetition bitmap, counters, sampling
+ * uniforms - to the unfinished rows; the following itts_gpt_decode steps run, and are captured, at the smaller row count, which
+ * *rows_now_host receives (itts_gpt_rows answers it too; 0 without an active generation).  The caller still sees the original
+ * batch: itts_gpt_status counts the live rows, itts_gpt_fetch returns all B rows in their ORIGINAL order - retired rows with their
+ * codes followed by the stop token, exactly what an unretired run holds, and with the logits of their LAST STEP BEFORE THE
+ * RETIREMENT (an unretired run would keep computing logits for them; nothing reads those).  It is a no-op that reports the
+ * unchanged row count without an active generation, under beams, under host sampling, while the step runs on the persistent
+ * decode engine or the fused qkv + attention launch, and when no row or every row has finished.  After a retirement the
+ * generation stays on the launch path even at <= 6 rows (itts_gpt_decode_mode answers 0).  The next itts_gpt_prefill resets it. */
+int itts_gpt_retire_rows(itts_engine* e, int* rows_now_host, itts_stream stream);
+int itts_gpt_rows(itts_engine* e);
+
+/* Operator entry of rows_move_kernel on caller memory: for o < n_outer, move i < n_moves, chunk c < n_chunks copy chunk_bytes from
+ * base + o * outer_stride + src[i] * row_stride + c * chunk_stride to the same address with dst[i] in place of src[i].  At most
+ * 128 moves; the source and destination row sets must not intersect (every copy of the launch is then independent).  16-byte
+ * units where base, strides and chunk_bytes are multiples of 16, else 4-byte or single bytes.  n_moves = 0 launches nothing.
+ * ITTS_E_INVALID before any HIP call for: a null base, negative counts, n_moves > 128, intersecting sets, chunk_bytes >
+ * chunk_stride, n_chunks * chunk_stride > row_stride. */
+int itts_rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stride, size_t chunk_stride, int n_chunks, size_t chunk_bytes,
+                   const int* src_host, const int* dst_host, int n_moves, itts_stream stream);
+/* The compaction plan alone (host only): with n live rows of B, the live rows at slots >= n move into the dead slots < n, both
+ * in ascending order; live rows below n keep their slot.  src_host / dst_host hold up to B entries. */
+int itts_retire_plan(const int* unfinished_host, int B, int* n_live, int* src_host, int* dst_host, int* n_moves);
+
 /* G8  UnifiedVoice.forward(return_latent=True) for one sentence (model.py:521-589):
  * text ids host [L], codes host [T] -> latent [T, D] in the engine dtype. */
 int itts_gpt_latent(itts_engine* e, const float* cond, const int32_t* text_ids_host, int L, const int32_t* codes_host,

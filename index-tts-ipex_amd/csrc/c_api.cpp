@@ -163,6 +163,19 @@ int itts_kv_scatter(void* kc, void* vc, const void* qkv, int B, int S, int H, in
   return kv_scatter(kc, vc, qkv, B, S, H, dh, Smax, tq, tc, (hipStream_t)stream);
 }
 
+int itts_rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stride, size_t chunk_stride, int n_chunks, size_t chunk_bytes,
+                   const int* src_host, const int* dst_host, int n_moves, itts_stream stream) {
+  // refused before any HIP call
+  ITTS_TRY(rows_move_check(base, outer_stride, n_outer, row_stride, chunk_stride, n_chunks, chunk_bytes, src_host, dst_host, n_moves));
+  (void)hipGetLastError();
+  return rows_move(base, outer_stride, n_outer, row_stride, chunk_stride, n_chunks, chunk_bytes, src_host, dst_host, n_moves,
+                   (hipStream_t)stream);
+}
+
+int itts_retire_plan(const int* unfinished_host, int B, int* n_live, int* src_host, int* dst_host, int* n_moves) {
+  return retire_plan(unfinished_host, B, n_live, src_host, dst_host, n_moves);
+}
+
 int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
                      int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
                      void* scratch, size_t scratch_bytes, itts_stream stream) {
@@ -529,6 +542,11 @@ int itts_gpt_fetch(itts_engine* e, int32_t* codes, float* logits, itts_stream s)
   ENG(e);
   return e->e.gpt_fetch(codes, logits, (hipStream_t)s);
 }
+int itts_gpt_retire_rows(itts_engine* e, int* rows_now_host, itts_stream s) {
+  ENG(e);
+  return e->e.gpt_retire_rows(rows_now_host, (hipStream_t)s);
+}
+int itts_gpt_rows(itts_engine* e) { return e ? (e->e.ds.active ? e->e.ds.B : 0) : -1; }
 int itts_gpt_latent(itts_engine* e, const float* cond, const int32_t* text_ids_host, int L, const int32_t* codes_host,
                     int T, void* latent_out, itts_stream s) {
   ENG(e);

@@ -121,12 +121,13 @@ struct DvaeW {
 // Whatever SamplerArgs, BeamArgs or EngArgs come to carry by value belongs here (and in Engine::graph_key()).
 struct GraphKey {
   int B = 0, Smax = 0, max_gen = 0, use_forced = 0, input_n = 0, host_sample = 0;
+  int Bcache = 0;  // rows the cache was laid out for (DecodeState::Bcache): the per-layer cache offsets after a row retirement
   int fuse = 0, eng = 0;  // derived: fuse && !fuse_failed, engine_usable()
   int nb = 1, beam_sample = 1, suppress_stop = 0, do_sample = 0, top_k = 0;
   int ct = 0;  // element type of the K/V cache (DecodeState::ct): the attention form and every per-layer cache offset
   float length_penalty = 0.f, typical_mass = 0.f, penalty = 0.f, top_p = 1.f, temperature = 1.f;  // compared as floats: a NaN re-captures
   bool operator==(const GraphKey& o) const {
-    return B == o.B && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
+    return B == o.B && Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
            host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample && ct == o.ct &&
            length_penalty == o.length_penalty && typical_mass == o.typical_mass && penalty == o.penalty &&
            suppress_stop == o.suppress_stop && do_sample == o.do_sample && top_k == o.top_k && top_p == o.top_p &&
@@ -136,6 +137,14 @@ struct GraphKey {
 
 struct DecodeState {
   int B = 0, Smax = 0, prefix = 0, max_gen = 0;
+  // Row retirement (Engine::gpt_retire_rows, opt-in): B is the row count the steps run at, Bcache the one the cache of this
+  // generation was laid out for and B0 the one the caller sees - all three are what the prefill set until a retirement shrinks B.
+  // orig[slot]: the original row a slot holds.  Retired rows live on the host: their codes (stop-padded) and last logits
+  int Bcache = 0, B0 = 0;
+  std::vector<int> orig;
+  std::vector<uint8_t> retired;       // [B0]
+  std::vector<int32_t> ret_codes;     // [B0][max_gen]
+  std::vector<float> ret_logits;      // [B0][V]
   size_t cache_bytes = 0;
   void *kc = nullptr, *vc = nullptr;  // [layers][B][H][Smax][dh], elements of type ct
   // element type of the cache: the engine's own (F32 / BF16) or, opt-in on a 16-bit engine, FP8 = e4m3 bytes (itts_gpt_set_kv_fp8 /
@@ -311,6 +320,8 @@ struct Engine {
   int forced_B = 0, forced_n = 0;
   int gpt_status(int* steps, int* n_unf, hipStream_t s);
   int gpt_fetch(int32_t* codes, float* logits, hipStream_t s);
+  int fetch_retired(int32_t* codes, float* logits, hipStream_t s);  // gpt_fetch after a retirement: original row order
+  int gpt_retire_rows(int* rows_now, hipStream_t s);  // compact a running single-beam generation to its unfinished rows (opt-in)
   int gpt_latent(const float* cond, const int32_t* text_ids, int L, const int32_t* codes, int T, void* latent_out,
                  hipStream_t s);
   int gpt_latent_batch(const float* cond, const int32_t* text_ids, const int* Ls, const int32_t* codes, const int* Ts,

@@ -165,6 +165,21 @@ int double_ln(float* y, const float* x, const float* g1, const float* b1, const 
               int D, float eps, hipStream_t s);
 int kv_scatter(void* kc, void* vc, const void* qkv, int B, int S, int H, int dh, int Smax, int tq, int tc, hipStream_t s);
 
+// decode_rows.hip: rows_move_kernel, the strided row copy behind the row retirement of a running batch (Engine::gpt_retire_rows).
+// The moves travel by value in the argument block: at most ROWS_MOVE_MAX of them (itts_skinny_gemm's row limit), no device upload
+constexpr int ROWS_MOVE_MAX = 128;
+struct RowsMoveArgs {
+  char* base = nullptr;
+  size_t outer_stride = 0, row_stride = 0, chunk_stride = 0, chunk_bytes = 0;
+  int n_outer = 0, n_moves = 0, n_chunks = 0;
+  unsigned short src[ROWS_MOVE_MAX], dst[ROWS_MOVE_MAX];
+};
+int rows_move_check(const void* base, size_t outer_stride, int n_outer, size_t row_stride, size_t chunk_stride, int n_chunks,
+                    size_t chunk_bytes, const int* src, const int* dst, int n_moves);  // host only: no HIP call
+int rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stride, size_t chunk_stride, int n_chunks, size_t chunk_bytes,
+              const int* src, const int* dst, int n_moves, hipStream_t s);
+int retire_plan(const int* unfinished, int B, int* n_live, int* src, int* dst, int* n_moves);  // host only
+
 // second generation, one file per kernel family.  decode_gemv.hip:
 bool gemv2_supported(const GemvArgs& g);
 int gemv2(const GemvArgs& g, int tw, hipStream_t s);

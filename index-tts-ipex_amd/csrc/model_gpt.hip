@@ -94,7 +94,7 @@ int Engine::gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, boo
     ITTS_TRY(ln(xn, adt, h, F32, L.ln1, M, D, s));
     ITTS_TRY(lin(qkv, adt, xn, adt, D, L.attn, M, 3 * D, s));
     if (write_cache) {
-      const size_t lo = (size_t)l * ds.B * H * ds.Smax * dh * ds.ces;  // the cache's element size, not the engine's
+      const size_t lo = (size_t)l * ds.Bcache * H * ds.Smax * dh * ds.ces;  // the cache's element size, not the engine's
       K(kv_scatter((char*)ds.kc + lo, (char*)ds.vc + lo, qkv, B, S, H, dh, ds.Smax, adt, ds.ct, s));
     }
     AttnArgs a;
@@ -194,6 +194,7 @@ bool Engine::engine_usable() const {
   const itts_config& c = cfg;
   if ((env_off && !ds.eng_force) || ds.eng_off || ds.eng_failed || ncu != ENG_NCU) return false;
   if (ds.fuse && !ds.fuse_failed) return false;  // A/B switch of the fused projection + attention launch: a launch-path variant
+  if (ds.B != ds.Bcache) return false;  // rows were retired: the engine computes its layer stride from its row count
   if (ds.ct == FP8) return false;  // the fp8 K/V cache has a launch-path attention form only (decode_attn2_kernel<fp8_t>)
   if (adt != BF16 || ds.B < 1 || ds.B > ENG_MAX_ROWS || ds.nb < 1 || ds.B % ds.nb != 0 || (ds.nb > 1 && !ds.anc)) return false;
   if (c.model_dim != ENG_D || c.heads != ENG_H || c.layers < 1 || c.layers > ENG_MAX_LAYERS || ds.Smax > 2048 || ds.Smax % 256 != 0) return false;
@@ -305,7 +306,11 @@ int Engine::ensure_decode_state(int B, int Smax, int max_gen, hipStream_t s) {
     d.cap_B = cb;
     d.cap_gen = cg;
   }
-  d.B = B;
+  d.B = d.Bcache = d.B0 = B;  // a fresh generation: nothing retired
+  d.orig.clear();
+  d.retired.clear();
+  d.ret_codes.clear();
+  d.ret_logits.clear();
   d.Smax = Smax;
   d.max_gen = max_gen;
   return OK;
@@ -1002,7 +1007,7 @@ int Engine::decode_step_launch(hipStream_t s) {
     g.prologue = 1;
     g.ln_gamma = L.ln1.g;
     g.ln_beta = L.ln1.b;
-    const size_t lo = (size_t)l * B * H * ds.Smax * dh * ds.ces;  // the cache's element size, not the engine's
+    const size_t lo = (size_t)l * ds.Bcache * H * ds.Smax * dh * ds.ces;  // the cache's element size, not the engine's; the rows the cache was laid out for
     // few (row, head) pairs: the keys of each pair go to ATTN_NSPLIT workgroups and the projection merges the partials
     static const bool no_split = getenv("ITTS_ATTN_NOSPLIT") != nullptr;
     static const bool env_fuse = getenv("ITTS_FUSE_QKV_ATTN") != nullptr && atoi(getenv("ITTS_FUSE_QKV_ATTN")) != 0;
@@ -1259,6 +1264,7 @@ GraphKey Engine::graph_key() const {
   const DecodeState& d = ds;
   GraphKey k;
   k.B = d.B;
+  k.Bcache = d.Bcache;
   k.Smax = d.Smax;
   k.max_gen = d.max_gen;
   k.use_forced = d.use_forced;
@@ -1384,6 +1390,7 @@ int Engine::gpt_fetch(int32_t* codes, float* logits, hipStream_t s) {
     return E_STATE;
   }
   ITTS_TRY(engine_check(s));
+  if (ds.B != ds.B0) return fetch_retired(codes, logits, s);
   if (codes && ds.nb > 1)
     ITTS_TRY(beam_finalize(codes, s));  // [B / nb * beam_returns][max_gen]
   else if (codes)
@@ -1391,6 +1398,103 @@ int Engine::gpt_fetch(int32_t* codes, float* logits, hipStream_t s) {
   if (logits)
     ITTS_HIP_CHECK(hipMemcpyAsync(logits, ds.logits, (size_t)ds.B * cfg.number_mel_codes * 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  return OK;
+}
+
+// gpt_fetch after a row retirement: [B0] rows in the ORIGINAL order - live rows from their slot, retired rows from the host store
+// (their codes followed by stop, as an unretired run holds them, and the logits of their last step before the retirement)
+int Engine::fetch_retired(int32_t* codes, float* logits, hipStream_t s) {
+  const DecodeState& d = ds;
+  const size_t mg = (size_t)d.max_gen, V = (size_t)cfg.number_mel_codes;
+  std::vector<int32_t> ids(codes ? (size_t)d.B * mg : 0);
+  std::vector<float> lg(logits ? (size_t)d.B * V : 0);
+  if (codes) ITTS_HIP_CHECK(hipMemcpyAsync(ids.data(), d.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
+  if (logits) ITTS_HIP_CHECK(hipMemcpyAsync(lg.data(), d.logits, lg.size() * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  for (int r = 0; r < d.B0; ++r) {
+    if (!d.retired[r]) continue;
+    if (codes) std::memcpy(codes + (size_t)r * mg, d.ret_codes.data() + (size_t)r * mg, mg * 4);
+    if (logits) std::memcpy(logits + (size_t)r * V, d.ret_logits.data() + (size_t)r * V, V * 4);
+  }
+  for (int slot = 0; slot < d.B; ++slot) {
+    const size_t r = (size_t)d.orig[slot];
+    if (codes) std::memcpy(codes + r * mg, ids.data() + (size_t)slot * mg, mg * 4);
+    if (logits) std::memcpy(logits + r * V, lg.data() + (size_t)slot * V, V * 4);
+  }
+  return OK;
+}
+
+// Row retirement (opt-in): compact the decode state of a running single-beam generation to its unfinished rows, so that the
+// following steps run - and are captured - at the smaller row count.  A finished row's output is fixed (the sampler writes stop
+// for it), a row's results do not depend on its slot, so the caller sees the same generation.  The plan (retire_plan) moves live
+// rows from slots >= n into dead slots < n; rows_move_kernel copies their K/V history (the positions that hold history only:
+// what lies behind stays the dead row's finite bytes, which the attention multiplies by p = 0) and their state arrays.
+// No-op (the row count stays) without an active generation, under beams or host sampling, while the step runs on the persistent
+// engine or the fused qkv + attention launch, and when no row or every row has finished.
+int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
+  DecodeState& d = ds;
+  if (rows_now) *rows_now = d.active ? d.B : 0;
+  if (!d.active) return OK;
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  static const bool env_fuse = getenv("ITTS_FUSE_QKV_ATTN") != nullptr && atoi(getenv("ITTS_FUSE_QKV_ATTN")) != 0;
+  if (d.nb > 1 || d.host_sample || engine_usable() || ((d.fuse || env_fuse) && !d.fuse_failed)) return OK;
+  const itts_config& c = cfg;
+  const int B = d.B, D = c.model_dim, H = c.heads, dh = D / H, V = c.number_mel_codes, mg = d.max_gen;
+  std::vector<int> unf(B), src(B), dst(B);
+  int k = 0, n = 0, nm = 0;
+  ITTS_HIP_CHECK(hipMemcpyAsync(unf.data(), d.unfinished, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(&k, d.len, 4, hipMemcpyDeviceToHost, s));  // every row has run the same steps
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  ITTS_TRY(retire_plan(unf.data(), B, &n, src.data(), dst.data(), &nm));
+  if (n == B || n == 0) return OK;
+  ITTS_REQUIRE(nm <= ROWS_MOVE_MAX && k >= 0 && k <= mg, "gpt_retire_rows: decode state out of range");
+  // 1. the retiring rows' codes and last logits go to the host store, by original row
+  if (d.orig.empty()) {
+    d.orig.resize(B);
+    for (int b = 0; b < B; ++b) d.orig[b] = b;
+    d.retired.assign((size_t)d.B0, 0);
+    d.ret_codes.assign((size_t)d.B0 * mg, c.stop_mel_token);
+    d.ret_logits.assign((size_t)d.B0 * V, 0.f);
+  }
+  {
+    std::vector<int32_t> ids((size_t)B * mg);
+    std::vector<float> lg((size_t)B * V);
+    ITTS_HIP_CHECK(hipMemcpyAsync(ids.data(), d.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
+    ITTS_HIP_CHECK(hipMemcpyAsync(lg.data(), d.logits, lg.size() * 4, hipMemcpyDeviceToHost, s));
+    ITTS_HIP_CHECK(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+      if (unf[b]) continue;
+      const size_t r = (size_t)d.orig[b];
+      d.retired[r] = 1;
+      std::memcpy(d.ret_codes.data() + r * mg, ids.data() + (size_t)b * mg, (size_t)k * 4);  // stop behind them (the fill above)
+      std::memcpy(d.ret_logits.data() + r * V, lg.data() + (size_t)b * V, (size_t)V * 4);
+    }
+  }
+  // 2. the moves: K and V over all layers (heads as chunks, the positions that hold history), then the per-row state arrays
+  const size_t head = (size_t)d.Smax * dh * d.ces, row = (size_t)H * head;
+  const size_t hist = (size_t)std::min(d.Smax, d.prefix + k) * dh * d.ces;
+  for (void* cache : {d.kc, d.vc})
+    ITTS_TRY(rows_move(cache, (size_t)d.Bcache * row, c.layers, row, head, H, hist, src.data(), dst.data(), nm, s));
+  const std::pair<void*, size_t> arrays[] = {{d.h, (size_t)D * 4},      {d.logits, (size_t)V * 4}, {d.ids, (size_t)mg * 4},
+                                             {d.forced, (size_t)mg * 4}, {d.seen, (size_t)V},       {d.len, 4},
+                                             {d.kv_start, 4},            {d.cur_tok, 4},            {d.unfinished, 4}};
+  for (const auto& a : arrays)
+    ITTS_TRY(rows_move(a.first, 0, 1, a.second, a.second, 1, a.second, src.data(), dst.data(), nm, s));
+  for (int i = 0; i < nm; ++i) d.orig[dst[i]] = d.orig[src[i]];
+  d.orig.resize(n);
+  // 3. the sampler reads uniforms[k * B + b]: re-packed to [max_gen][n] by original row
+  std::vector<float> u;
+  if (d.do_sample) {
+    ITTS_REQUIRE(sample_uniforms.size() >= (size_t)mg * d.B0, "gpt_retire_rows: the uniforms of this generation are gone");
+    u.resize((size_t)mg * n);
+    for (int q = 0; q < mg; ++q)
+      for (int b = 0; b < n; ++b) u[(size_t)q * n + b] = sample_uniforms[(size_t)q * d.B0 + d.orig[b]];
+    ITTS_HIP_CHECK(hipMemcpyAsync(d.uniforms, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
+  }
+  d.B = n;
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  d.drop_graphs();  // every later step re-captures at the smaller row count (GraphKey::B / Bcache)
+  if (rows_now) *rows_now = n;
   return OK;
 }
 

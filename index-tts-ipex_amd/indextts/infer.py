@@ -30,6 +30,9 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     lets the 1 - 6 row decode steps stream the fp8 bytes on the persistent decode engine.
   * `kv_fp8=True` (not in the reference; needs `is_fp16=True`, works with both 16-bit engines and together with `gpt_fp8`) keeps
     the K/V cache of the GPT decode steps as fp8-e4m3 bytes: half the cache bytes per step; the decode steps keep the launch path.
+  * `retire_rows=r` (not in the reference; a ratio in (0, 1], None: ITTS_RETIRE_ROWS, else off) lets the batched generations
+    of `infer_fast` / `infer_batch` retire their finished rows: whenever the unfinished rows are <= r * the running rows (and more
+    than 6 rows run), the decode state is compacted and the following steps run at the smaller row count (Engine.generate).
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -54,7 +57,7 @@ from indextts.utils.front import TextNormalizer, TextTokenizer
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
-                 wide_beam_sampler=None, kv_fp8=False):
+                 wide_beam_sampler=None, kv_fp8=False, retire_rows=None):
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -76,6 +79,7 @@ class IndexTTS:
         self.wide_sampler = wide_sampler
         # the same choice for several beams (beam_sample with top_k = 0 / None or > 128): None: ITTS_WIDE_BEAM_SAMPLER, else "host"
         self.wide_beam_sampler = wide_beam_sampler
+        self.retire_rows = retire_rows  # row retirement of the batched generations (Engine.generate); None: ITTS_RETIRE_ROWS, else off
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
         if self.kv_fp8 and not self.is_fp16:
             raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
@@ -175,7 +179,8 @@ class IndexTTS:
             grp = sents[lo:lo + cap]
             ids = infer_core.pad_tokens_cat(grp, self.cfg.gpt.stop_text_token)
             codes = self.engine.generate(cond, ids, g["max_mel_tokens"], repetition_penalty=g["repetition_penalty"],
-                                         wide_sampler=self.wide_sampler, wide_beam_sampler=self.wide_beam_sampler, **sample_kw)
+                                         wide_sampler=self.wide_sampler, wide_beam_sampler=self.wide_beam_sampler,
+                                         retire_rows=self.retire_rows, **sample_kw)
             rows.extend(codes[r] for r in range(len(grp)))
         return rows
 

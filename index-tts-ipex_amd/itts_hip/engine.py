@@ -315,6 +315,20 @@ class Engine:
         self._ck(self.lib.itts_gpt_status(self.h, C.byref(a), C.byref(b), self._s()), "gpt_status")
         return a.value, b.value
 
+    def retire_rows(self) -> int:
+        """Opt-in: compact the running generation to its unfinished rows (itts_gpt_retire_rows; synchronises).  The following
+        decode steps run at the smaller row count, which is returned; status() counts the live rows, fetch() still returns every
+        original row in its original order (retired rows: their codes followed by stop, the logits of their last step before the
+        retirement).  A no-op that returns the unchanged count under beams, host sampling, on the persistent engine (<= 6 rows)
+        and when no row or every row has finished."""
+        n = C.c_int()
+        self._ck(self.lib.itts_gpt_retire_rows(self.h, C.byref(n), self._s()), "gpt_retire_rows")
+        return n.value
+
+    def rows(self) -> int:
+        """Rows the decode steps of the active generation run at (0: no generation)."""
+        return int(self.lib.itts_gpt_rows(self.h))
+
     def fetch(self, logits: bool = False):
         B, mg = self._gen
         codes = np.empty((B * (getattr(self, "_nret", 1) if getattr(self, "_nb", 1) > 1 else 1), mg), dtype=np.int32)
@@ -328,7 +342,7 @@ class Engine:
                  top_p: float = 0.8, temperature: float = 1.0, seed: Optional[int] = None,
                  uniforms: Optional[np.ndarray] = None, num_beams: int = 1, typical_mass: float = 0.0,
                  length_penalty: float = 0.0, num_return_sequences: int = 1, wide_sampler: Optional[str] = None,
-                 wide_beam_sampler: Optional[str] = None) -> np.ndarray:
+                 wide_beam_sampler: Optional[str] = None, retire_rows: Optional[float] = None) -> np.ndarray:
         """Greedy decode (do_sample=False, num_beams=1 of tests/padding_test.py:35-46) or, with do_sample, HF
         GenerationMixin.sample (top-k / top-p / temperature, num_beams=1; draws from `uniforms` or a numpy Generator
         seeded with `seed`).  Returns int64 codes [B, n] with n <= max_gen: HF stops when every row has emitted stop
@@ -344,7 +358,18 @@ class Engine:
         warpers and draws on the host (infer_core.host_beam_step: torch's arithmetic, a logits and beam-state read-back and two
         stream syncs per token); "device": beam_wide_cand_kernel + beam_wide_pick_kernel in front of beam_select_kernel, no
         read-back, graph replay - the same distribution with parallel fp32 sums, top-p boundary and draws within 512 * 2^-24 of
-        the mass of the host's.  None: the environment's ITTS_WIDE_BEAM_SAMPLER, else "host"."""
+        the mass of the host's.  None: the environment's ITTS_WIDE_BEAM_SAMPLER, else "host".
+        retire_rows: opt-in row retirement of a batched single-beam generation - a ratio r in (0, 1]: after a status() the loop
+        calls retire_rows() whenever unfinished <= r * rows() and rows() > 6 (at six rows and below the persistent engine is the
+        better place to be, and it cannot follow a retirement).  Same codes within one projection-kernel family; across families
+        (e.g. 12 -> 3 rows) within the project's cross-family bound.  None: the environment's ITTS_RETIRE_ROWS, else off.
+        Suggested value: 0.5 - measured with tools/bench_row_retire.py (profiles/row_retire.txt): 64 ragged
+        rows decode 1.18 x faster at 0.5 and 1.19 x at 0.75; 20 rows with fp8 weights gain nothing at 0.5 and lose 3 % at 0.75."""
+        if retire_rows is None:
+            retire_rows = float(os.environ.get("ITTS_RETIRE_ROWS") or 0.0)
+        retire_rows = float(retire_rows)
+        if not 0.0 <= retire_rows <= 1.0:
+            raise ValueError(f"retire_rows must be a ratio in (0, 1] (or 0 / None: off), not {retire_rows!r}")
         if wide_sampler is None:
             wide_sampler = os.environ.get("ITTS_WIDE_SAMPLER") or "host"
         if wide_sampler not in ("host", "device"):
@@ -353,7 +378,7 @@ class Engine:
             wide_beam_sampler = os.environ.get("ITTS_WIDE_BEAM_SAMPLER") or "host"
         if wide_beam_sampler not in ("host", "device"):
             raise ValueError(f"wide_beam_sampler must be 'host' or 'device', not {wide_beam_sampler!r}")
-        kw = dict(wide_sampler=wide_sampler, wide_beam_sampler=wide_beam_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
+        kw = dict(retire_rows=retire_rows, wide_sampler=wide_sampler, wide_beam_sampler=wide_beam_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, uniforms=uniforms, num_beams=num_beams,
                   typical_mass=typical_mass, length_penalty=length_penalty, num_return_sequences=num_return_sequences)
         try:
@@ -367,7 +392,7 @@ class Engine:
 
     def _generate_once(self, cond, text_ids, max_gen, repetition_penalty, suppress_stop, check_every, do_sample, top_k, top_p,
                        temperature, seed, uniforms, num_beams, typical_mass, length_penalty, num_return_sequences,
-                       wide_sampler="host", wide_beam_sampler="host") -> np.ndarray:
+                       wide_sampler="host", wide_beam_sampler="host", retire_rows=0.0) -> np.ndarray:
         beams = num_beams > 1
         if num_return_sequences != 1 and not beams:
             raise ValueError("num_return_sequences > 1 without beams: repeat the rows (indextts/gpt/model.py does, as HF does)")
@@ -405,6 +430,10 @@ class Engine:
                     done = step
                     if unf == 0:
                         break
+                    if retire_rows and not beams:
+                        rows = self.rows()
+                        if rows > 6 and unf <= retire_rows * rows:
+                            self.retire_rows()
                 n = min(check_every, max_gen - done)
                 self.decode(n)
                 done += n

@@ -122,6 +122,10 @@ _PROTOS = {
     "itts_gpt_decode": (i32, [vp, i32, vp]),
     "itts_gpt_status": (i32, [vp, C.POINTER(i32), C.POINTER(i32), vp]),
     "itts_gpt_fetch": (i32, [vp, vp, vp, vp]),
+    "itts_gpt_retire_rows": (i32, [vp, C.POINTER(i32), vp]),
+    "itts_gpt_rows": (i32, [vp]),
+    "itts_rows_move": (i32, [vp, C.c_size_t, i32, C.c_size_t, C.c_size_t, i32, C.c_size_t, vp, vp, i32, vp]),
+    "itts_retire_plan": (i32, [vp, i32, C.POINTER(i32), vp, vp, C.POINTER(i32)]),
     "itts_gpt_latent": (i32, [vp, vp, vp, i32, vp, i32, vp, vp]),
     "itts_gpt_latent_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     "itts_bigvgan": (i32, [vp, vp, vp, i32, i32, vp, vp]),
