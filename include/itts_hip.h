@@ -237,6 +237,69 @@ typedef struct {
 } itts_rowop_args;
 int itts_rowop(int op, const itts_rowop_args* args, itts_stream stream);
 
+/* ---- token choice, operator level: one launch (pair) of the beam step, the typical filter and the one-beam samplers on
+ * caller-owned device memory.  Every pointer is a device pointer; the blocks mirror the kernels' own argument blocks (csrc/itts_decode.h
+ * BeamArgs, TypicalArgs, SamplerArgs) and the entries add nothing to them - no scratch, no reset of any state.  Each entry checks
+ * its block on the host and returns ITTS_E_INVALID with a message before any HIP call.  Additions to ABI 4. */
+
+/* One beam step for `items` batch items of nb beams (rows = items * nb).
+ * mode 0: beam_cand_kernel + beam_select_kernel (the narrow pair of the device-sampled generation: do_sample 1 = beam_sample with
+ *         1 <= top_k <= 128, top_p > 0, temperature > 0 and uniforms [max_gen][items][2 nb]; do_sample 0 = beam_search);
+ * mode 1: beam_select_kernel on the caller's 2 nb picks per item IN DRAW ORDER (pick_score with the beam score included, pick_tok,
+ *         pick_beam: [items][2 nb]), what itts_gpt_commit_beams runs.
+ * State, read and advanced as a generation's: len / cur_tok / unfinished / beam_scores [rows]; ids int32 [2][rows][max_gen] and anc
+ * uint8 [2][rows][Smax], ping-pong planes by the parity of len; prefix int32 [1]; the finished hypotheses hyp_tok int32
+ * [items][nb + 1][max_gen], hyp_score / hyp_len / hyp_order [items][nb + 1] (order -1 = free slot), hyp_n / hyp_worst / hyp_counter /
+ * done [items]; mode 0 scratch cand_sc / cand_tok [rows][128], cand_n [rows].  Optional: forced int32 [rows][max_gen] with input_n
+ * (steps below input_n take the given token); h_next fp32 [rows][D] = emb[tok] + pos[min(position, pos_rows - 1)] with emb / pos
+ * fp32 or, emb_bf16 = 1, bf16 tables.
+ * Refused: nb outside 2..10, items < 1, V < 2 or > 15000, max_gen < 1, Smax < 1, stop / start_tok / fake_id outside the vocabulary,
+ * under do_sample in mode 0 top_k outside 1..128, top_p <= 0, temperature <= 0 or no uniforms, h_next without emb, pos, D >= 1 and
+ * pos_rows >= 1, emb_bf16 outside {0, 1}, input_n > 0 without forced, a null state pointer, mode 0 without logits or candidate
+ * scratch, mode 1 without picks. */
+typedef struct {
+  const float* logits; const float* uniforms;
+  int* len; int* cur_tok; int* unfinished; int* ids; void* anc; const int* prefix; float* beam_scores;
+  int* hyp_tok; float* hyp_score; int* hyp_len; int* hyp_order; int* hyp_n; float* hyp_worst; int* hyp_counter; int* done;
+  float* h_next; const void* emb; const void* pos;
+  float* cand_sc; int* cand_tok; int* cand_n;
+  const int* forced;
+  const float* pick_score; const int* pick_tok; const int* pick_beam;
+  int mode, items, nb, V, max_gen, Smax, stop, start_tok, fake_id, suppress_stop, preprocessed, do_sample, top_k, input_n;
+  int D, pos_rows, emb_bf16;
+  float penalty, top_p, temperature, length_penalty;
+} itts_beam_step_args;
+int itts_beam_step(const itts_beam_step_args* args, itts_stream stream);
+
+/* typical_filter_kernel on `rows` rows: logits fp32 [rows][V] -> out fp32 [rows][V], the processed scores (log_softmax first when
+ * log_softmax_first, repetition penalty over the seen set, stop suppression) with everything behind the typical mass at -inf; the
+ * first min_keep ranks always stay.  The seen set is the byte map seen uint8 [rows][V] (may be null: nothing seen), or - beam_ids
+ * given - fake_id, start_tok and the first len[row] ids of beam_ids int32 [2][rows][max_gen], plane len[row] & 1.
+ * Refused: null logits / out, rows < 1, V < 2 or > 16384, mass outside (0, 1), min_keep < 1, penalty <= 0, stop outside the
+ * vocabulary, both seen sources at once, beam_ids without len, max_gen >= 1 and start_tok / fake_id inside the vocabulary. */
+typedef struct {
+  const float* logits; float* out; const void* seen; const int* beam_ids; const int* len;
+  int rows, V, stop, suppress_stop, min_keep, log_softmax_first, max_gen, start_tok, fake_id;
+  float penalty, mass;
+} itts_typical_args;
+int itts_typical_rows(const itts_typical_args* args, itts_stream stream);
+
+/* One sampler launch on a generation's state for B rows: do_sample 0 = sampler2_kernel (greedy), else sampler_sample_kernel
+ * (1 <= top_k <= 128, V <= 15360) or sampler_wide_kernel (any other top_k, V <= 16384; kept int32 [B], may be null, receives the
+ * kept ranks).  State: logits fp32 [B][V], seen uint8 [B][V], ids int32 [B][max_gen], cur_tok / unfinished / step int32 [B];
+ * uniforms fp32 [max_gen][B] (row min(step, max_gen - 1) is read); optional forced int32 [B][max_gen] (>= 0 replaces the choice)
+ * with input_n, and h_next / emb / pos / D / pos_rows / emb_bf16 as in itts_beam_step.  itts_sample_rows is the stateless form.
+ * Refused: a null state pointer, B < 1, V < 1 or above the kernel's limit, max_gen < 1, stop outside the vocabulary, penalty <= 0,
+ * sampling without uniforms, top_p <= 0 or temperature <= 0, h_next without its tables, emb_bf16 outside {0, 1}, input_n > 0 without
+ * forced. */
+typedef struct {
+  const float* logits; void* seen; int* ids; int* cur_tok; int* unfinished; int* step;
+  float* h_next; const void* emb; const void* pos; const float* uniforms; const int* forced; int* kept;
+  int B, V, max_gen, stop, suppress_stop, preprocessed, do_sample, top_k, input_n, D, pos_rows, emb_bf16;
+  float penalty, top_p, temperature;
+} itts_sampler_step_args;
+int itts_sampler_step(const itts_sampler_step_args* args, itts_stream stream);
+
 /* ---- engine level ----------------------------------------------------------------------------------- */
 
 typedef struct {

@@ -160,6 +160,7 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
     }
   }
   __syncthreads();
+  if (s_cnt > BEAM_MAX_CAND) regather_cands_ordered(ssc, V, prefix, cval, cidx, &s_cnt, tid);  // block-uniform: ties with the k-th score
   const int n = min(s_cnt, BEAM_MAX_CAND);
   if (tid < 64) sort_cands_wave<true>(cval, cidx, lane);  // descending score, ascending index on ties
   __syncthreads();

@@ -391,6 +391,113 @@ int itts_rowop(int op, const itts_rowop_args* a, itts_stream stream) {
 #undef ROWOP_REQUIRE
 }
 
+// ---- token choice, operator level: the argument blocks are checked here, on the host, before anything touches the device ----
+#define TOKEN_REQUIRE(name, cond, msg)          \
+  do {                                          \
+    if (!(cond)) {                              \
+      set_error(name ": " msg " (" #cond ")");  \
+      return E_INVALID;                         \
+    }                                           \
+  } while (0)
+
+int itts_beam_step(const itts_beam_step_args* p, itts_stream stream) {
+#define REQ(cond, msg) TOKEN_REQUIRE("itts_beam_step", cond, msg)
+  REQ(p, "null args");
+  REQ(p->mode == 0 || p->mode == 1, "mode 0 (candidates + select) or 1 (select on the caller's picks)");
+  REQ(p->nb >= 2 && p->nb <= 10 && p->items >= 1, "2 <= num_beams <= 10, items >= 1");
+  REQ(p->V >= 2 && p->V <= 15000, "2 <= V <= 15000");
+  REQ(p->max_gen >= 1 && p->Smax >= 1, "max_gen, Smax >= 1");
+  REQ(p->stop >= 0 && p->stop < p->V && p->start_tok >= 0 && p->start_tok < p->V && p->fake_id >= 0 && p->fake_id < p->V,
+      "stop / start_tok / fake_id outside the vocabulary");
+  REQ(p->len && p->cur_tok && p->unfinished && p->ids && p->anc && p->prefix && p->beam_scores && p->done, "null state pointer");
+  REQ(p->hyp_tok && p->hyp_score && p->hyp_len && p->hyp_order && p->hyp_n && p->hyp_worst && p->hyp_counter, "null state pointer (hypotheses)");
+  REQ(p->input_n >= 0 && (p->input_n == 0 || p->forced), "input_n > 0 needs forced");
+  REQ(p->emb_bf16 == 0 || p->emb_bf16 == 1, "emb_bf16 is 0 (fp32 tables) or 1 (bf16 tables)");
+  REQ(!p->h_next || (p->emb && p->pos && p->D >= 1 && p->pos_rows >= 1), "h_next needs emb, pos, D >= 1, pos_rows >= 1");
+  if (p->mode == 0) {
+    REQ(p->logits, "mode 0 needs logits");
+    REQ(p->cand_sc && p->cand_tok && p->cand_n, "mode 0 needs the candidate scratch");
+    REQ(p->do_sample == 0 || p->do_sample == 1, "do_sample 0 or 1");
+    if (p->do_sample) {
+      REQ(p->top_k >= 1 && p->top_k <= BEAM_MAX_CAND, "the narrow pair samples with 1 <= top_k <= 128");
+      REQ(p->top_p > 0.f && p->temperature > 0.f, "top_p > 0, temperature > 0");
+      REQ(p->uniforms, "do_sample needs uniforms");
+    }
+    REQ(p->penalty > 0.f, "penalty > 0");
+  } else {
+    REQ(p->pick_score && p->pick_tok && p->pick_beam, "mode 1 needs the picks");
+  }
+#undef REQ
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  BeamArgs a;
+  a.logits = p->logits; a.V = p->V; a.max_gen = p->max_gen; a.stop = p->stop; a.suppress_stop = p->suppress_stop; a.nb = p->nb;
+  a.B = p->items; a.top_k = p->top_k; a.start_tok = p->start_tok; a.fake_id = p->fake_id; a.Smax = p->Smax; a.penalty = p->penalty;
+  a.top_p = p->top_p; a.temperature = p->temperature; a.uniforms = p->uniforms; a.len = p->len; a.cur_tok = p->cur_tok;
+  a.unfinished = p->unfinished; a.ids = p->ids; a.anc = (uint8_t*)p->anc; a.prefix_dev = p->prefix; a.beam_scores = p->beam_scores;
+  a.hyp_tok = p->hyp_tok; a.hyp_score = p->hyp_score; a.hyp_len = p->hyp_len; a.hyp_order = p->hyp_order; a.hyp_n = p->hyp_n;
+  a.hyp_worst = p->hyp_worst; a.hyp_counter = p->hyp_counter; a.done = p->done; a.h_next = p->h_next; a.emb = p->emb; a.pos = p->pos;
+  a.D = p->D; a.pos_rows = p->pos_rows; a.emb_bf16 = p->emb_bf16; a.preprocessed = p->preprocessed; a.do_sample = p->do_sample;
+  a.length_penalty = p->length_penalty; a.cand_sc = p->cand_sc; a.cand_tok = p->cand_tok; a.cand_n = p->cand_n; a.forced = p->forced;
+  a.input_n = p->input_n;
+  if (p->mode == 0) return beam_sample_step(a, (hipStream_t)stream);
+  a.host_sc = p->pick_score; a.host_tok = p->pick_tok; a.host_beam = p->pick_beam;
+  return beam_commit_step(a, (hipStream_t)stream);
+}
+
+int itts_typical_rows(const itts_typical_args* p, itts_stream stream) {
+#define REQ(cond, msg) TOKEN_REQUIRE("itts_typical_rows", cond, msg)
+  REQ(p, "null args");
+  REQ(p->logits && p->out, "null logits / out");
+  REQ(p->rows >= 1, "rows >= 1");
+  REQ(p->V >= 2 && p->V <= 16384, "2 <= V <= 16384");
+  REQ(p->mass > 0.f && p->mass < 1.f, "0 < mass < 1");
+  REQ(p->min_keep >= 1 && p->penalty > 0.f, "min_keep >= 1, penalty > 0");
+  REQ(p->stop >= 0 && p->stop < p->V, "stop outside the vocabulary");
+  REQ(!(p->seen && p->beam_ids), "one seen source: the byte map or the beam histories");
+  if (p->beam_ids) {
+    REQ(p->len && p->max_gen >= 1, "beam_ids needs len and max_gen >= 1");
+    REQ(p->start_tok >= 0 && p->start_tok < p->V && p->fake_id >= 0 && p->fake_id < p->V, "start_tok / fake_id outside the vocabulary");
+  }
+#undef REQ
+  (void)hipGetLastError();
+  TypicalArgs t;
+  t.logits = p->logits; t.out = p->out; t.V = p->V; t.stop = p->stop; t.suppress_stop = p->suppress_stop; t.min_keep = p->min_keep;
+  t.log_softmax_first = p->log_softmax_first; t.penalty = p->penalty; t.mass = p->mass; t.seen = (const uint8_t*)p->seen;
+  t.beam_ids = p->beam_ids; t.len = p->len; t.max_gen = p->max_gen; t.start_tok = p->start_tok; t.fake_id = p->fake_id;
+  return typical_filter(t, p->rows, (hipStream_t)stream);
+}
+
+int itts_sampler_step(const itts_sampler_step_args* p, itts_stream stream) {
+#define REQ(cond, msg) TOKEN_REQUIRE("itts_sampler_step", cond, msg)
+  REQ(p, "null args");
+  REQ(p->logits && p->seen && p->ids && p->cur_tok && p->unfinished && p->step, "null state pointer");
+  REQ(p->B >= 1 && p->V >= 1 && p->max_gen >= 1, "B, V, max_gen >= 1");
+  REQ(p->stop >= 0 && p->stop < p->V, "stop outside the vocabulary");
+  REQ(p->penalty > 0.f, "penalty > 0");
+  REQ(p->input_n >= 0 && (p->input_n == 0 || p->forced), "input_n > 0 needs forced");
+  REQ(p->emb_bf16 == 0 || p->emb_bf16 == 1, "emb_bf16 is 0 (fp32 tables) or 1 (bf16 tables)");
+  REQ(!p->h_next || (p->emb && p->pos && p->D >= 1 && p->pos_rows >= 1), "h_next needs emb, pos, D >= 1, pos_rows >= 1");
+  REQ(p->do_sample == 0 || p->do_sample == 1, "do_sample 0 or 1");
+  if (p->do_sample) {
+    REQ(p->uniforms, "do_sample needs uniforms");
+    REQ(p->top_p > 0.f && p->temperature > 0.f, "top_p > 0, temperature > 0");
+    if (p->top_k >= 1 && p->top_k <= BEAM_MAX_CAND)
+      REQ(p->V <= 15360, "1 <= top_k <= 128 keeps the vocabulary in LDS: V <= 15360");
+    else
+      REQ(p->V <= 16384, "top_k outside 1..128 sorts the whole vocabulary: V <= 16384");
+  }
+#undef REQ
+  (void)hipGetLastError();
+  SamplerArgs a;
+  a.logits = p->logits; a.seen = (uint8_t*)p->seen; a.ids = p->ids; a.cur_tok = p->cur_tok; a.unfinished = p->unfinished; a.step = p->step;
+  a.V = p->V; a.max_gen = p->max_gen; a.stop = p->stop; a.suppress_stop = p->suppress_stop; a.penalty = p->penalty; a.h_next = p->h_next;
+  a.emb = p->emb; a.pos = p->pos; a.D = p->D; a.pos_rows = p->pos_rows; a.emb_bf16 = p->emb_bf16; a.do_sample = p->do_sample;
+  a.top_k = p->top_k < 1 ? 0 : p->top_k; a.B = p->B; a.top_p = p->top_p; a.temperature = p->temperature; a.uniforms = p->uniforms;
+  a.forced = p->forced; a.input_n = p->input_n; a.preprocessed = p->preprocessed; a.kept = p->kept;
+  return sampler2_step(a, p->B, (hipStream_t)stream);
+}
+#undef TOKEN_REQUIRE
+
 int itts_engine_create(const itts_config* cfg, itts_engine** out) {
   if (!cfg || !out) {
     set_error("itts_engine_create: null argument");

@@ -174,6 +174,7 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
     }
   }
   __syncthreads();
+  if (s_cnt > BEAM_MAX_CAND) regather_cands_ordered(ssc, a.V, prefix, cval, cidx, &s_cnt, tid);  // block-uniform: ties with the k-th score
   if (tid < 64) sort_cands_wave<true>(cval, cidx, lane);  // one wave, no barrier: descending score, ascending index on ties
   __syncthreads();
   if (tid < 64) {

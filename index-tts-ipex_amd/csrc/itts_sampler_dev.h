@@ -3,6 +3,7 @@
 // sampler_sample_kernel (decode_sampler.hip) and beam_cand_kernel (beam.hip) share sort_cands_wave: one order, one tie rule.
 #pragma once
 #include "itts_decode.h"
+#include "itts_wave_dev.h"
 
 namespace itts {
 
@@ -73,6 +74,45 @@ __device__ __forceinline__ void sort_cands_wave(float* cv, int* ci, int lane) {
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
+}
+
+// More than BEAM_MAX_CAND scores reached the k-th largest (ties with it): the atomic gather of sampler_sample_kernel / beam_cand_kernel
+// then kept whichever BEAM_MAX_CAND arrived first, and a strictly larger score could be lost.  Gather again in the order of the
+// restatement (oracle/hf_beam.py warp_row: score descending, id ascending, [:128]): every score strictly above the k-th - fewer than
+// top_k <= BEAM_MAX_CAND of them, in any order, the sort behind this puts them in place - then wave 0 walks the vocabulary upwards
+// and appends the ties in ascending id until the arrays are full.  Every thread of the block calls it, behind the barrier that
+// follows the gather; *cnt is BEAM_MAX_CAND afterwards.  kth_key: order_key of the k-th largest score (the radix select's prefix).
+__device__ __forceinline__ void regather_cands_ordered(const float* sc, int V, unsigned kth_key, float* cv, int* ci, int* cnt, int tid) {
+  __syncthreads();  // every thread has read the overflowing count
+  if (tid == 0) *cnt = 0;
+  __syncthreads();
+  for (int i = tid; i < V; i += 1024) {
+    const float v = sc[i];
+    if (order_key(v) > kth_key) {
+      const int p = atomicAdd(cnt, 1);
+      if (p < BEAM_MAX_CAND) {  // (always: fewer than top_k scores lie above the k-th)
+        cv[p] = v;
+        ci[p] = i;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 64) {
+    int n = *cnt;
+    for (int i0 = 0; i0 < V && n < BEAM_MAX_CAND; i0 += 64) {  // wave-uniform
+      const int i = i0 + tid;
+      const bool tie = i < V && order_key(sc[i]) == kth_key;
+      const unsigned long long m = __ballot(tie);
+      const int p = n + __popcll(m & ((1ull << tid) - 1ull));
+      if (tie && p < BEAM_MAX_CAND) {
+        cv[p] = sc[i];
+        ci[p] = i;
+      }
+      n += __popcll(m);
+    }
+    if (tid == 0) *cnt = BEAM_MAX_CAND;
+  }
+  __syncthreads();
 }
 
 // ---- shared by the whole-vocabulary samplers: sampler_wide_kernel (decode_sampler.hip), beam_wide_cand_kernel /

@@ -68,6 +68,32 @@ class RowopArgs(C.Structure):
                 ("act", i32), ("eps", f32)]
 
 
+# itts_beam_step / itts_typical_rows / itts_sampler_step: the argument blocks of include/itts_hip.h, in the header's order
+class BeamStepArgs(C.Structure):
+    _fields_ = [(n, vp) for n in ("logits", "uniforms", "len", "cur_tok", "unfinished", "ids", "anc", "prefix", "beam_scores",
+                                  "hyp_tok", "hyp_score", "hyp_len", "hyp_order", "hyp_n", "hyp_worst", "hyp_counter", "done",
+                                  "h_next", "emb", "pos", "cand_sc", "cand_tok", "cand_n", "forced",
+                                  "pick_score", "pick_tok", "pick_beam")] + \
+               [(n, i32) for n in ("mode", "items", "nb", "V", "max_gen", "Smax", "stop", "start_tok", "fake_id", "suppress_stop",
+                                   "preprocessed", "do_sample", "top_k", "input_n", "D", "pos_rows", "emb_bf16")] + \
+               [(n, f32) for n in ("penalty", "top_p", "temperature", "length_penalty")]
+
+
+class TypicalArgs(C.Structure):
+    _fields_ = [(n, vp) for n in ("logits", "out", "seen", "beam_ids", "len")] + \
+               [(n, i32) for n in ("rows", "V", "stop", "suppress_stop", "min_keep", "log_softmax_first", "max_gen", "start_tok",
+                                   "fake_id")] + \
+               [(n, f32) for n in ("penalty", "mass")]
+
+
+class SamplerStepArgs(C.Structure):
+    _fields_ = [(n, vp) for n in ("logits", "seen", "ids", "cur_tok", "unfinished", "step", "h_next", "emb", "pos", "uniforms",
+                                  "forced", "kept")] + \
+               [(n, i32) for n in ("B", "V", "max_gen", "stop", "suppress_stop", "preprocessed", "do_sample", "top_k", "input_n", "D",
+                                   "pos_rows", "emb_bf16")] + \
+               [(n, f32) for n in ("penalty", "top_p", "temperature")]
+
+
 _lib = None
 _lib_f16 = None
 
@@ -96,6 +122,9 @@ _PROTOS = {
     "itts_ln_rows_bf16": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, vp, i32, vp, i32, vp]),
     "itts_transpose": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "itts_rowop": (i32, [i32, C.POINTER(RowopArgs), vp]),
+    "itts_beam_step": (i32, [C.POINTER(BeamStepArgs), vp]),
+    "itts_typical_rows": (i32, [C.POINTER(TypicalArgs), vp]),
+    "itts_sampler_step": (i32, [C.POINTER(SamplerStepArgs), vp]),
     "itts_engine_create": (i32, [C.POINTER(Config), C.POINTER(vp)]),
     "itts_engine_destroy": (None, [vp]),
     "itts_engine_bind_tensor": (i32, [vp, C.c_char_p, vp, i32, i32, C.POINTER(i64)]),
