@@ -23,7 +23,11 @@
 //     decode_attn2_kernel<.., 256, 4> on its 16 waves and merges them in LDS: no cross-CU hop for the partials.  Its K/V
 //     rows are requested right after the layer's first gather, one projection ahead of the scores.  This step's own k / v row
 //     stays packed in registers of wave 0 (scored like a cache row) and is appended to the cache BEHIND the publish of the
-//     context, one 16-byte store per lane: no other wave waits for a serial tail of that wave at the merge barrier.
+//     context, one 16-byte store per lane: no other wave waits for a serial tail of that wave at the merge barrier.  Only wave 0
+//     executes that row's score / exp / PV term (the other fifteen branch round it), and the slot reduction of the eight PV
+//     accumulators is a reduce-scatter over lane ^ 16, ^ 32 (one permlane swap of two accumulators per butterfly step): same
+//     addends, same tree, same bits - 0.4207 -> 0.4135 ms per launch at 2 rows (profiles/r11_engine_waves.txt).  c_attn stays on
+//     the eleven compute waves in two rounds: one round on all sixteen waves was measured there and lost.
 //
 // Arithmetic is the launch path's, operation for operation (same lane <-> k mapping and accumulation order of the GEMV
 // dot products, same LayerNorm reduction tree - itts_wave_dev.h, one definition for both paths -, same attention window /
@@ -914,7 +918,9 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           }
         }
         // the row appended by this step, with the cache's rounding (only the `own` lanes' score is kept: slot 0 of split 0)
-        sc[2 * NIT] = (slot == 0 && sp == 0) ? score(ka) : -INFINITY;
+        // (wave-uniform test: the other fifteen waves hold no `own` lane and branch round the score)
+        sc[2 * NIT] = -INFINITY;
+        if (own_wave) sc[2 * NIT] = (slot == 0 && sp == 0) ? score(ka) : -INFINITY;
         float mw = sc[0];
 #pragma unroll
         for (int u = 1; u <= 2 * NIT; ++u) mw = fmaxf(mw, sc[u]);
@@ -928,10 +934,18 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
 #pragma unroll
               for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, vr[u].get(i), acc[i]);
             }
-          const float p = __expf(sc[2 * NIT] - mw);
-          lsum += p;
+          if (own_wave) {
+            const float p = __expf(sc[2 * NIT] - mw);
+            lsum += p;
 #pragma unroll
-          for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, own ? va.get(i) : 0.f, acc[i]);  // (the select stays: p * v could flip the sign of a zero)
+            for (int i = 0; i < VEC; ++i) acc[i] = fmaf(p, own ? va.get(i) : 0.f, acc[i]);  // (the select stays: p * v could flip the sign of a zero)
+          } else {
+            // The other waves' term is p = exp(-inf) = +0: lsum + 0 is lsum (a sum of exps is never -0.f), and fma(+0, +0, acc) is
+            // acc + (+0.f), which turns an acc of -0.f (a product p * v that underflowed below a zero sum) into +0.f - so that
+            // add stays, as what decode_attn2_kernel computes there (hipcc keeps it: four v_pk_add_f32 with 0 in the listing).
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc[i] = acc[i] + 0.f;
+          }
           m = mw;
         }
       }
@@ -956,15 +970,34 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       lsum *= sc0;
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] *= sc0;
+      // Slot reduction over lane ^ 8, ^ 16, ^ 32, the pairwise tree of decode_attn2_kernel.  M, sc0 and lsum are needed in every lane: full
+      // butterflies.  The eight acc[] are needed once per wave: behind the o = 8 step (DPP) the o = 16 / o = 32 steps are a
+      // reduce-scatter - v_permlane16_swap / v_permlane32_swap of TWO accumulators hands every lane both partners' values of one of
+      // them (odd 16-lane rows of the first operand <-> even rows of the second; upper half <-> lower half: tools/probe_permlane.hip),
+      // so one swap and one add do a butterfly step of both: x[lane] + x[lane ^ o], the same two addends as before.  6 swaps for
+      // acc[] instead of 16.  Afterwards the 16-lane row rr holds dimension rr of the lane's slot fragment in a32[0] and 4 + rr in a32[1].
 #pragma unroll
-      for (int o = LPK; o < 64; o <<= 1) {
-        lsum = wave_bfly_sum(lsum, o);
+      for (int o = LPK; o < 64; o <<= 1) lsum = wave_bfly_sum(lsum, o);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = wave_bfly_sum(acc[i], o);
+      for (int i = 0; i < VEC; ++i) acc[i] = wave_bfly_sum(acc[i], LPK);
+      float a16[VEC / 2], a32[VEC / 4];
+#pragma unroll
+      for (int i = 0; i < VEC / 2; ++i) {
+        const u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[2 * i]), __float_as_uint(acc[2 * i + 1]), false, false);
+        a16[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
       }
-      if (ll < LPK)
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) so[wave * DH + ll * VEC + i] = acc[i];
+      for (int i = 0; i < VEC / 4; ++i) {
+        const u32x2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a16[2 * i]), __float_as_uint(a16[2 * i + 1]), false, false);
+        a32[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+      }
+      // Stored by the lanes with bit 3 clear only (the lanes the old store's lanes 0..7 were reduced with): hipcc contracts the
+      // o = 8 step with the rescale into fma(acc, sc0, rotated(acc * sc0)), here and in decode_attn2_kernel, which is not
+      // symmetric in lane and lane ^ 8 - the lanes with bit 3 set hold a sum that may differ in the last bit.
+      if ((ll & LPK) == 0) {
+        so[wave * DH + (ll & (LPK - 1)) * VEC + (ll >> 4)] = a32[0];
+        so[wave * DH + (ll & (LPK - 1)) * VEC + 4 + (ll >> 4)] = a32[1];
+      }
       if (ll == 0) {
         smx[wave] = M;
         slx[wave] = lsum;
