@@ -17,8 +17,12 @@
 // top_k < 1 (HF: TopK warper off) or > BEAM_MAX_CAND: thousands of tokens per beam can survive, so beam_wide_cand_kernel sorts
 // each beam row's whole vocabulary and beam_wide_pick_kernel draws over the flat nb * V scores; beam_select_kernel then takes the
 // picks in draw order exactly as it takes the host's (BeamArgs::host_sc / host_tok / host_beam): three launches per step.
-#include <atomic>
-
+//
+// Shared with each other and with the one-beam samplers of decode_sampler.hip through itts_sampler_dev.h: the block reductions, the
+// row log-sum-exp, the seen bitmap and the processed score (beam_cand_kernel, typical_filter_kernel), the candidate sort and the
+// overflow re-gather, the whole-vocabulary sort and block scan.  The radix select, candidate gather and narrow top-p of
+// beam_cand_kernel and every stage of beam_wide_cand_kernel but its sort and scan are this file's own text (a copy each of what
+// sampler_sample_kernel / sampler_wide_kernel hold): the shared forms measured slower, see the header.
 #include "itts_decode.h"
 #include "itts_sampler_dev.h"
 #include "itts_wave_dev.h"
@@ -27,25 +31,6 @@ namespace itts {
 namespace {
 
 constexpr int MAXB = 10;   // beams per batch item (the reference web UI offers 1..10); kept candidates per beam: BEAM_MAX_CAND
-
-__device__ __forceinline__ float block_max(float v, float* red, int tid) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int i = 1; i < 16; ++i) r = fmaxf(r, red[i]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* red, int tid) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < 16; ++i) r += red[i];
-  __syncthreads();
-  return r;
-}
 
 __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   extern __shared__ float ssc[];  // [V] processed scores of this beam
@@ -65,34 +50,12 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   const int row = bi * nb + r;
   const float* __restrict__ lg = a.logits + (size_t)row * V;
   // ---- log_softmax (a.preprocessed: the typical pre-pass already did this, the penalty and the suppression) ----
-  float lse = 0.f;
-  if (!a.preprocessed) {
-    float mx = -INFINITY;
-    for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, lg[i]);
-    mx = block_max(mx, red, tid);
-    float se = 0.f;
-    for (int i = tid; i < V; i += 1024) se += expf(lg[i] - mx);
-    se = block_sum(se, red, tid);
-    lse = mx + logf(se);
-  }
+  const float lse = a.preprocessed ? 0.f : row_logsumexp(lg, V, red, tid);
   // ---- ids this beam has seen: the fake prompt ids (all 1, then start_mel: model.py:644-653) + its history ----
-  for (int i = tid; i < (V + 31) / 32; i += 1024) seenw[i] = 0u;
-  __syncthreads();
-  if (tid == 0) {
-    atomicOr(&seenw[a.fake_id >> 5], 1u << (a.fake_id & 31));
-    atomicOr(&seenw[a.start_tok >> 5], 1u << (a.start_tok & 31));
-  }
-  for (int i = tid; i < k; i += 1024) {
-    const int t = ids_old[(size_t)row * mg + i];
-    atomicOr(&seenw[t >> 5], 1u << (t & 31));
-  }
-  __syncthreads();
+  beam_seen_bitmap(seenw, V, a.fake_id, a.start_tok, ids_old + (size_t)row * mg, k, tid);
   for (int i = tid; i < V; i += 1024) {
     float v = lg[i] - lse;
-    if (!a.preprocessed) {
-      if (a.penalty != 1.f && ((seenw[i >> 5] >> (i & 31)) & 1u)) v = v < 0.f ? v * a.penalty : v / a.penalty;
-      if (a.suppress_stop && i == a.stop) v = -INFINITY;
-    }
+    if (!a.preprocessed) v = processed_score(v, seen_bit(seenw, i), a.penalty, a.suppress_stop, a.stop, i);
     if (a.do_sample && a.temperature != 1.f) v = v / a.temperature;  // warpers only exist in beam_sample
     ssc[i] = v;
   }
@@ -205,6 +168,7 @@ __global__ __launch_bounds__(1024) void beam_cand_kernel(BeamArgs a) {
   }
 }
 
+// (the scorer: nothing of it is shared but block_max - its draw and bookkeeping exist only here)
 __global__ __launch_bounds__(1024) void beam_select_kernel(BeamArgs a) {
   // the kept candidates of the item's beams in flat (beam-major, token-ascending) order, running beam score included
   __shared__ float fsc[MAXB * BEAM_MAX_CAND];
@@ -522,13 +486,13 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(BeamArgs a) {
 // per beam row, V <= 16384, dynamic LDS NP * 6 bytes with NP = the power of two >= max(V, 1024):
 //   1. scores as beam_cand_kernel computes them (log_softmax unless preprocessed, repetition penalty over the beam's own id
 //      history, stop suppression, / temperature), NaN -> -inf, with their ids into LDS
-//   2. wide_sort_desc: descending score, lower id first on ties; -inf scores and the padding sort last and never count
+//   2. wide_sort<true>: descending score, lower id first on ties; -inf scores and the padding sort last and never count
 //   3. TopK (top_k >= 1 only): kk = min(max(top_k, 2), V); the n ranks whose score is >= the score at rank kk - 1 stay (HF masks
 //      `scores < kth`); without TopK the n finite scores
 //   4. TopP (top_p < 1, min_tokens_to_keep = 2): e_r = expf(s_r - s_0); rank r >= 2 goes iff tail_r = sum_{j >= r} e_j <=
 //      (1 - top_p) * tail_0; R = clamp(last staying rank + 1, 2, n) (n when n < 2)
 //   5. in token order: w.sc[row][t] = score + beam_scores[row] for the R kept tokens, -inf for every other t < V; w.kept[row] = R
-// Sums.  log-sum-exp: <= 16 strided terms per thread, 6 butterfly levels, 16 wave sums in order (beam_cand_kernel's block_sum).
+// Sums.  log-sum-exp: <= 16 strided terms per thread, 6 butterfly levels, 16 wave sums in order (row_logsumexp / block_sum).
 // tail_r: a thread's run of NP / 1024 <= 16 consecutive ranks, wide_scan_excl from the last thread down, finished inside the
 // run.  The longest chain of dependent fp32 additions behind any sum of this kernel is 53: <= 15 for a run's own sum, 6 levels
 // of the wave scan, <= 15 wave sums, 1 to join them with the wave's part, <= 16 along the run.  No fp32 atomics.
@@ -591,7 +555,7 @@ __global__ __launch_bounds__(1024) void beam_wide_cand_kernel(BeamArgs a, BeamWi
     idx[i] = (unsigned short)(i < V ? i : 0xFFFF);  // the padding sorts behind every -inf score
   }
   __syncthreads();
-  wide_sort_desc(keys, idx, NP, tid);
+  wide_sort<true>(keys, idx, NP, tid);
   // ---- TopK: the kept ranks are a prefix [0, n) of the sorted order ----
   const int per = NP >> 10, r0 = tid * per;  // this thread's run of ranks
   const float s0 = keys[0];
@@ -666,6 +630,7 @@ __global__ __launch_bounds__(1024) void beam_wide_cand_kernel(BeamArgs a, BeamWi
 // run's own sum, 6 levels of the wave scan, <= 15 wave sums, 1 to join them with the wave's part, <= L along the run.
 // With no live entry left the pick is (-inf, stop, 0), as in beam_select_kernel.  Picks go to w.pick_* [B][2 * nb] in draw order.
 // ---------------------------------------------------------------------------------------------------------------
+// (shares block_max and wide_scan_excl only: the draw over nb * V scores exists only here)
 __global__ __launch_bounds__(1024) void beam_wide_pick_kernel(BeamArgs a, BeamWide w) {
   __shared__ float red[16], wsum[16];
   __shared__ int s_pick, s_last;
@@ -769,35 +734,14 @@ __global__ __launch_bounds__(1024) void typical_filter_kernel(TypicalArgs a) {
   if (a.beam_ids) {
     const int k = a.len[row], mg = a.max_gen;
     const int* hist = a.beam_ids + ((size_t)(k & 1) * gridDim.x + row) * mg;
-    for (int i = tid; i < (V + 31) / 32; i += 1024) seenw[i] = 0u;
-    __syncthreads();
-    if (tid == 0) {
-      atomicOr(&seenw[a.fake_id >> 5], 1u << (a.fake_id & 31));
-      atomicOr(&seenw[a.start_tok >> 5], 1u << (a.start_tok & 31));
-    }
-    for (int i = tid; i < k; i += 1024) {
-      const int t = hist[i];
-      atomicOr(&seenw[t >> 5], 1u << (t & 31));
-    }
-    __syncthreads();
+    beam_seen_bitmap(seenw, V, a.fake_id, a.start_tok, hist, k, tid);
   }
-  float lse0 = 0.f;
-  if (a.log_softmax_first) {
-    float mx = -INFINITY;
-    for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, lg[i]);
-    mx = block_max(mx, red, tid);
-    float se = 0.f;
-    for (int i = tid; i < V; i += 1024) se += expf(lg[i] - mx);
-    se = block_sum(se, red, tid);
-    lse0 = mx + logf(se);
-  }
+  const float lse0 = a.log_softmax_first ? row_logsumexp(lg, V, red, tid) : 0.f;
   // ---- processed scores -> out; their log-sum-exp ----
   float mx = -INFINITY;
   for (int i = tid; i < V; i += 1024) {
-    float v = lg[i] - lse0;
-    const bool seen = a.beam_ids ? ((seenw[i >> 5] >> (i & 31)) & 1u) != 0 : (a.seen && a.seen[(size_t)row * V + i]);
-    if (a.penalty != 1.f && seen) v = v < 0.f ? v * a.penalty : v / a.penalty;
-    if (a.suppress_stop && i == a.stop) v = -INFINITY;
+    const bool seen = a.beam_ids ? seen_bit(seenw, i) : (a.seen && a.seen[(size_t)row * V + i]);
+    const float v = processed_score(lg[i] - lse0, seen, a.penalty, a.suppress_stop, a.stop, i);
     out[i] = v;
     mx = fmaxf(mx, v);
   }
@@ -823,26 +767,10 @@ __global__ __launch_bounds__(1024) void typical_filter_kernel(TypicalArgs a) {
     idx[i] = (unsigned short)(i < V ? i : 0xFFFF);
   }
   __syncthreads();
-  // ---- bitonic sort, ascending (key, index) ----
-  for (int kk = 2; kk <= NP; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < NP / 2; t += 1024) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-        const bool up = (lo & kk) == 0;
-        const float k0 = keys[lo], k1 = keys[hi];
-        const unsigned short i0 = idx[lo], i1 = idx[hi];
-        const bool gt = k0 > k1 || (k0 == k1 && i0 > i1);
-        if (gt == up) {
-          keys[lo] = k1;
-          keys[hi] = k0;
-          idx[lo] = i1;
-          idx[hi] = i0;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  wide_sort<false>(keys, idx, NP, tid);  // ascending (key, id)
   // ---- running mass in sorted order: per-thread runs of NP / 1024 consecutive entries, block scan of the run sums ----
+  // (NOT wide_scan_excl<false>: the base here is (inc - mine) + wsum[0] + ..., that one gives (wsum[0] + ...) + shfl_up(inc) - other
+  // bits; token_choice_ref.typical_bounds is written against this form)
   const int per = NP / 1024;
   float loc[16];
   float mine = 0.f;
@@ -885,11 +813,8 @@ int typical_filter(const TypicalArgs& a, int rows, hipStream_t s) {
   t.npad = 1024;
   while (t.npad < a.V) t.npad <<= 1;
   const size_t lds = (size_t)t.npad * 6;
-  static bool attr_done = false;
-  if (!attr_done) {
-    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)typical_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    attr_done = true;
-  }
+  static DynLdsLatch latch;
+  ITTS_TRY(allow_dynamic_lds(latch, (const void*)typical_filter_kernel, 128 * 1024));
   hipLaunchKernelGGL(typical_filter_kernel, dim3(rows), dim3(1024), lds, s, t);
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;
@@ -898,13 +823,8 @@ int typical_filter(const TypicalArgs& a, int rows, hipStream_t s) {
 // beam_wide_cand_kernel's 96 KiB of dynamic LDS have to be allowed once on every device ordinal that launches it; gpt_prefill
 // calls this outside the capture of the decode step
 int beam_wide_prepare() {
-  static std::atomic<int> done_on[64];
-  int dev = 0;
-  ITTS_HIP_CHECK(hipGetDevice(&dev));
-  if (done_on[dev & 63].load(std::memory_order_acquire)) return OK;
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)beam_wide_cand_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BEAM_WIDE_MAX_V * 6));
-  done_on[dev & 63].store(1, std::memory_order_release);
-  return OK;
+  static DynLdsLatch latch;
+  return allow_dynamic_lds(latch, (const void*)beam_wide_cand_kernel, BEAM_WIDE_MAX_V * 6);
 }
 
 int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s) {

@@ -281,12 +281,8 @@ int launch(const GemmArgs& g, hipStream_t s) {
   const size_t lds_epi = (size_t)BM * (NP + 4) * 4;
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   const int B = g.M / g.T, tiles = (g.T + BM - 1) / BM;
-  static bool attr_done = false;
-  if (!attr_done) {
-    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)conv_lds_kernel<MT, NT, WAVES_M, WAVES_N, ACT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
+  static DynLdsLatch latch;  // one per instantiation
+  ITTS_TRY(allow_dynamic_lds(latch, (const void*)conv_lds_kernel<MT, NT, WAVES_M, WAVES_N, ACT>, 160 * 1024));
   hipLaunchKernelGGL((conv_lds_kernel<MT, NT, WAVES_M, WAVES_N, ACT>), dim3(B * tiles), dim3(256), lds, s, g, tiles, HR, CP);
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;

@@ -1412,12 +1412,8 @@ int decode_engine_layers(const EngArgs& a, hipStream_t s) {
   const size_t lds = 160 * 1024;  // three weight slots + edge buffers: the whole LDS of a CU, one workgroup per CU
 #define ITTS_ENG_GO(NB, ANC_, W8_)                                                                                              \
   {                                                                                                                             \
-    static bool attr = false;                                                                                                   \
-    if (!attr) {                                                                                                                \
-      ITTS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_engine_kernel<NB, ANC_, W8_>),                   \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                \
-      attr = true;                                                                                                              \
-    }                                                                                                                           \
+    static DynLdsLatch latch;                                                                                                   \
+    ITTS_TRY(allow_dynamic_lds(latch, reinterpret_cast<const void*>(&decode_engine_kernel<NB, ANC_, W8_>), (int)lds));          \
     hipLaunchKernelGGL((decode_engine_kernel<NB, ANC_, W8_>), dim3(ENG_NCU), dim3(1024), lds, s, a);                            \
   }
 #define ITTS_ENG_ROWS(W8_)                                                                                                      \

@@ -2,8 +2,8 @@
 // 1 <= top_k <= 128), sampler_wide_kernel (do_sample=True over the whole vocabulary: top_k < 1 or > 128),
 // each with the token commit and the next step's input embedding fused in (itts_sampler_dev.h), and decode_embed2_kernel, the
 // embedding of a step whose token the host supplies.
-#include <atomic>
-
+// Shared with the beam kernels of beam.hip through itts_sampler_dev.h: the candidate sort and overflow re-gather, the
+// whole-vocabulary sort and block scan, commit and next embedding.  The radix select, gather, top-p and draw are this file's own text.
 #include "itts_decode.h"
 #include "itts_sampler_dev.h"
 #include "itts_wave_dev.h"
@@ -13,7 +13,8 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------
 // sampler2: repetition penalty + argmax + bookkeeping, one 1024-thread block per row; the per-row length
-// counter is advanced by the row's own block (no cross-block step counter, no extra launch).
+// counter is advanced by the row's own block (no cross-block step counter, no extra launch).  (Its vectorised argmax shares
+// sampler_score / sampler_commit / sampler_next_embedding only.)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void sampler2_kernel(SamplerArgs a) {
   __shared__ float sv[16];
@@ -103,11 +104,7 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
   const uint8_t* seen = a.seen + (size_t)b * a.V;
   const int k_pre = a.step[b], unf_pre = a.unfinished[b];
   for (int i = tid; i < a.V; i += 1024) {
-    float v = lg[i];
-    if (!a.preprocessed) {
-      if (a.penalty != 1.f && seen[i]) v = v < 0.f ? v * a.penalty : v / a.penalty;
-      if (a.suppress_stop && i == a.stop) v = -INFINITY;
-    }
+    float v = sampler_score(a, seen, lg[i], i);
     if (a.temperature != 1.f) v = v / a.temperature;  // TemperatureLogitsWarper: scores / temperature
     ssc[i] = v;
   }
@@ -267,7 +264,7 @@ __global__ __launch_bounds__(1024) void sampler_wide_kernel(SamplerArgs a, int N
     idx[i] = (unsigned short)(i < V ? i : 0xFFFF);  // the padding sorts behind every -inf score
   }
   __syncthreads();
-  wide_sort_desc(keys, idx, NP, tid);  // descending score, ascending id on ties
+  wide_sort<true>(keys, idx, NP, tid);  // descending score, ascending id on ties
   // ---- TopK: the kept ranks are a prefix [0, n) of the sorted order ----
   const int per = NP >> 10, r0 = tid * per;  // this thread's run of ranks
   const float s0 = keys[0];
@@ -374,13 +371,8 @@ __global__ void decode_embed2_kernel(float* __restrict__ h, const TW* __restrict
 // sampler_wide_kernel's 96 KiB of dynamic LDS have to be allowed once on every device ordinal that launches it; gpt_prefill
 // calls this outside the capture of the decode step
 int sampler_wide_prepare() {
-  static std::atomic<int> done_on[64];
-  int dev = 0;
-  ITTS_HIP_CHECK(hipGetDevice(&dev));
-  if (done_on[dev & 63].load(std::memory_order_acquire)) return OK;
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)sampler_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_MAX_V * 6));
-  done_on[dev & 63].store(1, std::memory_order_release);
-  return OK;
+  static DynLdsLatch latch;
+  return allow_dynamic_lds(latch, (const void*)sampler_wide_kernel, WIDE_MAX_V * 6);
 }
 
 int sampler2_step(const SamplerArgs& a, int B, hipStream_t s) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <string>
 
 namespace itts {
@@ -55,6 +56,13 @@ const char* last_error();
     int _s = (expr);                \
     if (_s != ::itts::OK) return _s; \
   } while (0)
+
+// A kernel that takes more than 64 KiB of dynamic LDS has to be allowed that size (hipFuncAttributeMaxDynamicSharedMemorySize) once
+// on every device ordinal that launches it.  The latch is the caller's, one static object per kernel; any thread may call.
+struct DynLdsLatch {
+  std::atomic<int> done_on[64];
+};
+int allow_dynamic_lds(DynLdsLatch& latch, const void* kernel, int bytes);
 
 // ---- device helpers ----
 __device__ __forceinline__ float ldf(const float* p) { return *p; }

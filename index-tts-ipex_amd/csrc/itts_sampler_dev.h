@@ -1,19 +1,85 @@
-// Device-side bookkeeping shared by the sampler kernels (decode_sampler.hip) and the persistent decode engine's in-launch greedy
-// sampler (decode_engine.hip): HF greedy search / sample() commit of one token per row + the next step's input embedding.
-// sampler_sample_kernel (decode_sampler.hip) and beam_cand_kernel (beam.hip) share sort_cands_wave: one order, one tie rule.
+// Device code shared by the token-choice kernels, one definition of each stage listed here:
+//   - sampler_commit / sampler_next_embedding: HF greedy search / sample() commit of one token per row + the next step's input
+//     embedding (the sampler kernels of decode_sampler.hip and the persistent decode engine's in-launch greedy sampler)
+//   - block_max / block_sum: every kernel of beam.hip; row_logsumexp, beam_seen_bitmap, processed_score: beam_cand_kernel and
+//     typical_filter_kernel (sampler_score: the form of the one-beam samplers on their byte map)
+//   - sort_cands_wave, regather_cands_ordered: the two narrow kernels (1 <= top_k <= 128), sampler_sample_kernel and beam_cand_kernel
+//   - wide_sort<DESC>: sampler_wide_kernel, beam_wide_cand_kernel (descending), typical_filter_kernel (ascending); wide_scan_excl:
+//     sampler_wide_kernel, beam_wide_cand_kernel, beam_wide_pick_kernel
+// Every helper works on the caller's __shared__ arrays: no kernel's LDS layout depends on this file.  Written out per kernel and
+// kept in step by hand, because every shared form measured slower or took a register more (DESIGN.md section 4a,
+// profiles/token_choice_refactor.txt): the radix select, the candidate gather and the narrow top-p of the two narrow kernels; the
+// fill, top-k count and top-p cut of the two whole-vocabulary kernels; log-sum-exp, bitmap and score inside beam_wide_cand_kernel.
 #pragma once
 #include "itts_decode.h"
 #include "itts_wave_dev.h"
 
 namespace itts {
 
-// repetition penalty (RepetitionPenaltyLogitsProcessor over the row's id history, kept as a byte map) + stop suppression
+// repetition penalty (RepetitionPenaltyLogitsProcessor; seen = the token is in the row's id history) + stop suppression on one
+// score.  Temperature stays with the callers (beam_cand_kernel applies it only under do_sample)
+__device__ __forceinline__ float processed_score(float v, bool seen, float penalty, int suppress_stop, int stop, int i) {
+  if (penalty != 1.f && seen) v = v < 0.f ? v * penalty : v / penalty;
+  if (suppress_stop && i == stop) v = -INFINITY;
+  return v;
+}
+// The same on the byte map of the one-beam samplers: a SECOND copy of the two lines above, to be kept in step with them by hand.
+// It is not a call of processed_score because the persistent engine's in-launch greedy sampler inlines it, and passing a.penalty /
+// a.suppress_stop / a.stop as values (also behind a guard, also with a lazily evaluated `seen`) regroups the scalar argument
+// loads of all 33 decode_engine_kernel instantiations
 __device__ __forceinline__ float sampler_score(const SamplerArgs& a, const uint8_t* seen_row, float v, int i) {
   if (a.preprocessed) return v;
   if (a.penalty != 1.f && seen_row[i]) v = v < 0.f ? v * a.penalty : v / a.penalty;
   if (a.suppress_stop && i == a.stop) v = -INFINITY;
   return v;
 }
+
+// block reductions of 1024 threads: xor butterfly inside every wave, then the 16 wave results in order (red[16])
+__device__ __forceinline__ float block_max(float v, float* red, int tid) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  float r = red[0];
+  for (int i = 1; i < 16; ++i) r = fmaxf(r, red[i]);
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ float block_sum(float v, float* red, int tid) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  float r = 0.f;
+  for (int i = 0; i < 16; ++i) r += red[i];
+  __syncthreads();
+  return r;
+}
+// log-sum-exp of lg[0 .. V): <= 16 strided terms per thread, then block_max / block_sum
+__device__ __forceinline__ float row_logsumexp(const float* __restrict__ lg, int V, float* red, int tid) {
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, lg[i]);
+  mx = block_max(mx, red, tid);
+  float se = 0.f;
+  for (int i = tid; i < V; i += 1024) se += expf(lg[i] - mx);
+  se = block_sum(se, red, tid);
+  return mx + logf(se);
+}
+
+// ids a beam has seen as a bitmap over the vocabulary (seenw[512]: V <= 16384 bits): the fake prompt ids (all fake_id, then
+// start_tok: model.py:644-653) + its history hist[0 .. k).  An id outside the vocabulary has no score to penalise and no bit
+__device__ __forceinline__ void beam_seen_bitmap(unsigned* seenw, int V, int fake_id, int start_tok, const int* hist, int k, int tid) {
+  for (int i = tid; i < (V + 31) / 32; i += 1024) seenw[i] = 0u;
+  __syncthreads();
+  if (tid == 0) {
+    if ((unsigned)fake_id < (unsigned)V) atomicOr(&seenw[fake_id >> 5], 1u << (fake_id & 31));
+    if ((unsigned)start_tok < (unsigned)V) atomicOr(&seenw[start_tok >> 5], 1u << (start_tok & 31));
+  }
+  for (int i = tid; i < k; i += 1024) {
+    const int t = hist[i];
+    if ((unsigned)t < (unsigned)V) atomicOr(&seenw[t >> 5], 1u << (t & 31));
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ bool seen_bit(const unsigned* seenw, int i) { return ((seenw[i >> 5] >> (i & 31)) & 1u) != 0; }
 
 // bookkeeping shared by the greedy and the sampling kernels (thread 0 of the row's block)
 __device__ __forceinline__ void sampler_commit(const SamplerArgs& a, int b, int choice, int* si, int k, int unf) {
@@ -115,8 +181,8 @@ __device__ __forceinline__ void regather_cands_ordered(const float* sc, int V, u
   __syncthreads();
 }
 
-// ---- shared by the whole-vocabulary samplers: sampler_wide_kernel (decode_sampler.hip), beam_wide_cand_kernel /
-//      beam_wide_pick_kernel (beam.hip) - one sort order, one tie rule, one summation structure ----
+// ---- the whole-vocabulary kernels: sampler_wide_kernel (decode_sampler.hip), beam_wide_cand_kernel / beam_wide_pick_kernel
+//      (beam.hip) - one sort order, one tie rule, one summation structure ----
 
 // exclusive block scan of one value per thread in thread order (REV: from the last thread down); one barrier
 template <bool REV>
@@ -140,15 +206,16 @@ __device__ __forceinline__ float wide_scan_excl(float mine, float* wsum, int lan
   return wb + ex;
 }
 
-// block bitonic sort of NP (a power of two >= 1024) (score, u16 id) pairs in LDS by 1024 threads: descending score, ascending
-// id on ties.  The caller has put a barrier behind its writes of keys / idx; the sort ends with one
-__device__ __forceinline__ void wide_sort_desc(float* keys, unsigned short* idx, int NP, int tid) {
+// block bitonic sort of NP (a power of two >= 1024) (key, u16 id) pairs in LDS by 1024 threads: descending (DESC) or ascending
+// key, ascending id on ties.  The caller has put a barrier behind its writes of keys / idx; the sort ends with one
+template <bool DESC>
+__device__ __forceinline__ void wide_sort(float* keys, unsigned short* idx, int NP, int tid) {
   auto compare_swap = [&](int t, int j, int kk) {
     const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
     const bool up = (lo & kk) == 0;
     const float k0 = keys[lo], k1 = keys[hi];
     const unsigned short i0 = idx[lo], i1 = idx[hi];
-    const bool behind = k0 < k1 || (k0 == k1 && i0 > i1);  // entry lo belongs behind entry hi
+    const bool behind = (DESC ? k0 < k1 : k0 > k1) || (k0 == k1 && i0 > i1);  // entry lo belongs behind entry hi
     if (behind == up) {
       keys[lo] = k1;
       keys[hi] = k0;

@@ -243,7 +243,7 @@ def _scan(mine, rev):
 
 
 def _block_sum(per_thread):
-    """beam.hip block_sum: xor butterfly inside every wave, then the 16 wave sums in order."""
+    """itts_sampler_dev.h block_sum: xor butterfly inside every wave, then the 16 wave sums in order."""
     v = per_thread.reshape(16, 64).astype(F32)
     for o in (32, 16, 8, 4, 2, 1):
         v = (v + v[:, np.arange(64) ^ o]).astype(F32)
