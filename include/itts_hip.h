@@ -505,9 +505,18 @@ int itts_gpt_set_engine_fp8(itts_engine* e, int on);
  * environment variable ITTS_KV_FP8 overrides it in both directions (1 / 0; fp32 engines ignore it).  The value is latched by
  * itts_gpt_prefill for the whole generation: a change takes effect at the next prefill, which re-zeroes the cache and re-captures
  * the step.  With an fp8 cache every decode step takes the launch path's whole-form attention (itts_gpt_decode_mode answers 0:
- * no persistent engine, no split form, no fused qkv + attention launch); everything else - fp8 weights, samplers, beams, forced
+ * no persistent engine - unless itts_gpt_set_engine_kv_fp8 below opted in -, no split form, no fused qkv + attention launch); everything else - fp8 weights, samplers, beams, forced
  * and input tokens, host sampling - is unaffected.  Accuracy and speed as measured: INTEGRATION.md, profiles/kv_fp8.txt. */
 int itts_gpt_set_kv_fp8(itts_engine* e, int on);
+
+/* Opt-in, on top of itts_gpt_set_kv_fp8: let a generation with an fp8 K/V cache run its 1 - 6 row decode steps (beam rows included)
+ * on the persistent decode engine, whose attention phase then reads and appends the e4m3 rows itself (itts_gpt_decode_mode
+ * answers 1).  Both libraries; together with itts_gpt_set_engine_fp8 in the bf16 build.  Sticky per engine object, default 0 = an
+ * fp8 cache keeps the launch path at every row count, as before; without an fp8 cache the switch has no effect.  The environment
+ * variable ITTS_ENGINE_KV_FP8, read per call, overrides it in both directions (1: on for every engine, 0: off).  The launch
+ * path's whole-form attention and the engine read the same cache bytes but sum in another order: results agree to a tolerance,
+ * not bit for bit (profiles/engine_kv_fp8.txt). */
+int itts_gpt_set_engine_kv_fp8(itts_engine* e, int on);
 
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);

@@ -707,6 +707,11 @@ int itts_gpt_set_kv_fp8(itts_engine* e, int on) {
   return OK;
 }
 
+int itts_gpt_set_engine_kv_fp8(itts_engine* e, int on) {
+  ENG(e);
+  return e->e.gpt_set_engine_kv_fp8(on);
+}
+
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems) {
   if (!e || !name) return -1;
   auto it = e->e.taps.find(name);

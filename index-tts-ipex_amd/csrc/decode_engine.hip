@@ -44,6 +44,15 @@
 // path at 1 - 4 rows and, because a power-of-two scale commutes with fp32 rounding, to this engine on the dequantised model
 // at 1 - 6 rows (tests/test_gpu_engine_fp8.py).  The bf16 instantiations are instruction for instruction what they were.
 //
+// fp8 K/V cache (decode_engine_kernel<.., KV8>; opt-in on top of the fp8 cache: itts_gpt_set_engine_kv_fp8 / ITTS_ENGINE_KV_FP8, both
+// builds, also together with W8): the attention phase reads and appends rows of OCP e4m3 bytes (fp8_t, itts_common.h).  The same
+// thread <-> (split, slot, sub) mapping, windows and scalar skips; a lane's fragment of a row is CacheVec<fp8_t> - one nontemporal
+// 8-byte load, exact decode -, this step's k / v row is rounded with the cache's conversion (fp8_pack4: clamp to +-448, nearest
+// even) into the u32x2 its score and PV term read, and appended with one 8-byte store per lane; every cache offset counts 1-byte
+// elements.  What decode_attn2_kernel<fp8_t, ..> computes, in the split form's summation order - the launch path has the whole form
+// only for an fp8 cache, so the two agree to a tolerance there (tests/test_gpu_engine_kv_fp8.py).  The KV8 = false instantiations
+// are instruction for instruction what they were.
+//
 // Every spin is bounded (wall clock, s_memrealtime) and also ends on a chip-wide abort word; a workgroup that gave up
 // runs on without waiting, so the grid always drains.  The host reads the abort word at status / fetch.
 //
@@ -596,8 +605,14 @@ __device__ __forceinline__ void ln2_to_sxb(const float* __restrict__ xf, uint32_
 // ancestry names (decode_attn.hip, decode_attn2_kernel<.., ANC>: the same gather, the same arithmetic)
 // W8: every projection (and the head) streams its fp8-e4m3 copy - the bytes and per-row power-of-two scales of
 // gemv_bf16_kernel<.., W8> - through the same slots (half full), the same requests in the same order; y = dot * scale + bias
-template <int NB, bool ANC, bool W8>
+// KV8: the opt-in fp8 (e4m3) K/V cache (EngArgs::kv8) - a.kc / a.vc point at fp8_t bytes, every cache offset counts 1-byte
+// elements, a lane's fragment of a row is CacheVec<fp8_t> (one 8-byte nontemporal load, exact decode), this step's row is rounded
+// with the cache's conversion (fp8_pack4) and appended with one 8-byte store per lane: what decode_attn2_kernel<fp8_t, ..> does.
+// Only phase P2, the cache requests at the head of the block and the append know about it.
+template <int NB, bool ANC, bool W8, bool KV8>
 __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
+  using KVT = std::conditional_t<KV8, fp8_t, bf16_t>;                     // element of the cache
+  using KVF = std::conditional_t<KV8, CacheVec<fp8_t>, V8<bf16_t>>;      // a lane's 8 elements of one cache row
   constexpr int D = ENG_D, H = ENG_H, DH = 64, NCU = ENG_NCU;
   constexpr int GPH = NCU / H;       // workgroups per head group (12)
   constexpr int QO = 3 * DH / GPH;   // c_attn rows per workgroup (16)
@@ -738,7 +753,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     // for c_attn (vmcnt is in-order: a wait of theirs in front of these requests would hold the sweep / the first barrier for
     // an HBM miss).  Same rows, same registers, same arithmetic as before.
     constexpr int NIT_ = 3, NSPLIT_ = 4, SLOTS_ = 32, LPK_ = 8, VEC_ = 8, UNC_ = 2;
-    V8<bf16_t> kr[2 * NIT_], vr[2 * NIT_];
+    KVF kr[2 * NIT_], vr[2 * NIT_];
     const int a_sp = wave >> 2, a_atid = (wave & 3) * 64 + ll, a_slot = a_atid / LPK_, a_sub = a_atid % LPK_;
     const size_t a_lo = ((size_t)l * a.B * H + (size_t)(acu ? gm : 0) * H + gh) * a.Smax * DH;
     const uint8_t* a_arow = nullptr;
@@ -747,13 +762,13 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       a_arow = a.anc + ((size_t)my_par * a.B + (acu ? gm : 0)) * a.Smax;
       a_lbase = ((size_t)l * a.B + (size_t)((acu ? gm : 0) / a.nb) * a.nb) * H;
     }
-    auto krow = [&](int j) -> const bf16_t* {
-      if constexpr (ANC) return a.kc + ((a_lbase + (size_t)min((int)a_arow[j], a.nb - 1) * H + gh) * a.Smax + j) * DH;
-      return a.kc + a_lo + (size_t)j * DH;
+    auto krow = [&](int j) -> const KVT* {
+      if constexpr (ANC) return reinterpret_cast<const KVT*>(a.kc) + ((a_lbase + (size_t)min((int)a_arow[j], a.nb - 1) * H + gh) * a.Smax + j) * DH;
+      return reinterpret_cast<const KVT*>(a.kc) + a_lo + (size_t)j * DH;
     };
-    auto vrow = [&](int j) -> const bf16_t* {
-      if constexpr (ANC) return a.vc + ((a_lbase + (size_t)min((int)a_arow[j], a.nb - 1) * H + gh) * a.Smax + j) * DH;
-      return a.vc + a_lo + (size_t)j * DH;
+    auto vrow = [&](int j) -> const KVT* {
+      if constexpr (ANC) return reinterpret_cast<const KVT*>(a.vc) + ((a_lbase + (size_t)min((int)a_arow[j], a.nb - 1) * H + gh) * a.Smax + j) * DH;
+      return reinterpret_cast<const KVT*>(a.vc) + a_lo + (size_t)j * DH;
     };
     auto kv_issue = [&](auto lo_c, auto hi_c) {  // window pairs [lo, hi)
       constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value;
@@ -783,12 +798,16 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       for (int j = my_ks + c0; j < my_pos; j += NCW * 64) {
         const char* pk = reinterpret_cast<const char*>(krow(j));
         const char* pv = reinterpret_cast<const char*>(vrow(j));
-        asm volatile("global_load_dword %0, %1, off\n\tglobal_load_dword %0, %1, off offset:64\n\t"
-                     "global_load_dword %0, %2, off\n\tglobal_load_dword %0, %2, off offset:64"
-                     : "+v"(pf_sink)  // read-write: ONE live range over all iterations (a fresh "=v" per iteration would let the
-                                      // allocator recycle the previous iteration's register while its load is still in flight)
-                     : "v"(pk), "v"(pv)
-                     : "memory");
+        if constexpr (KV8) {  // a row of e4m3 bytes is 64 bytes: one dword per row (same read-write sink as below)
+          asm volatile("global_load_dword %0, %1, off\n\tglobal_load_dword %0, %2, off" : "+v"(pf_sink) : "v"(pk), "v"(pv) : "memory");
+        } else {
+          asm volatile("global_load_dword %0, %1, off\n\tglobal_load_dword %0, %1, off offset:64\n\t"
+                       "global_load_dword %0, %2, off\n\tglobal_load_dword %0, %2, off offset:64"
+                       : "+v"(pf_sink)  // read-write: ONE live range over all iterations (a fresh "=v" per iteration would let the
+                                        // allocator recycle the previous iteration's register while its load is still in flight)
+                       : "v"(pk), "v"(pv)
+                       : "memory");
+        }
       }
     }
     const bool early_kv = acu && EKV > 0;
@@ -865,8 +884,8 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       // K/V rows of the register window: requested at the head of the block (early_kv) or - the r03 placement - here, before the
       // q / k / v hand-off is polled (all 16 waves; the thread <-> (split, slot, sub) mapping of decode_attn2_kernel<.., 256, 4>)
       const int sp = a_sp, atid = a_atid, slot = a_slot, sub = a_sub;
-      bf16_t* kb = a.kc + a_lo;
-      bf16_t* vb = a.vc + a_lo;
+      KVT* kb = reinterpret_cast<KVT*>(a.kc) + a_lo;
+      KVT* vb = reinterpret_cast<KVT*>(a.vc) + a_lo;
       kv_issue(IcE{}, IcN{});  // what was not requested at the head of the block
       const int pos = my_pos, S = pos + 1, ks = my_ks;
       __builtin_amdgcn_sched_barrier(0);
@@ -894,18 +913,20 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       // This step's k / v fragment of the lane in the packed form of a cache row (two 16-byte LDS reads each, rounded once with the
       // cache's conversion): the score and the PV term of the appended row read it like any other row, and the append behind the
       // publish stores it.  Only wave 0 holds `own` lanes (wave-uniform test: the other fifteen waves branch round the reads).
-      V8<bf16_t> ka, va;
-      ka.raw = va.raw = u32x4{0u, 0u, 0u, 0u};
+      KVF ka, va;
+      if constexpr (KV8) ka.raw = va.raw = u32x2{0u, 0u};
+      else ka.raw = va.raw = u32x4{0u, 0u, 0u, 0u};
       const bool own_wave = wave == 0;
       auto row_frag = [&](const float* __restrict__ src) {
         const f32x4 lo = *reinterpret_cast<const f32x4*>(src + sub * VEC), hi = *reinterpret_cast<const f32x4*>(src + sub * VEC + 4);
-        return u32x4{pack_bf16(lo[0], lo[1]), pack_bf16(lo[2], lo[3]), pack_bf16(hi[0], hi[1]), pack_bf16(hi[2], hi[3])};
+        if constexpr (KV8) return u32x2{fp8_pack4(lo[0], lo[1], lo[2], lo[3]), fp8_pack4(hi[0], hi[1], hi[2], hi[3])};  // clamp, nearest even
+        else return u32x4{pack_bf16(lo[0], lo[1]), pack_bf16(lo[2], lo[3]), pack_bf16(hi[0], hi[1]), pack_bf16(hi[2], hi[3])};
       };
       if (own_wave) ka.raw = row_frag(qkvs + DH);
       float m = -INFINITY, lsum = 0.f, acc[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      auto score = [&](const V8<bf16_t>& kk) { return attn_score<LPK>(qr, kk); };  // itts_attn_dev.h; the lambda stays
+      auto score = [&](const KVF& kk) { return attn_score<LPK>(qr, kk); };  // itts_attn_dev.h; the lambda stays
       {
         float sc[2 * NIT + 1];
 #pragma unroll
@@ -949,11 +970,11 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           m = mw;
         }
       }
-      auto consume = [&](const V8<bf16_t>& kk, const V8<bf16_t>& vv, int j) {
+      auto consume = [&](const KVF& kk, const KVF& vv, int j) {
         attn_consume<LPK>(m, lsum, acc, qr, kk, vv, j < S && j >= ks && j != pos);
       };
       for (int cb = 2 * NIT; (cb * NSPLIT + sp) * SLOTS < S; cb += SD) {
-        V8<bf16_t> k2[SD], v2[SD];
+        KVF k2[SD], v2[SD];
 #pragma unroll
         for (int u = 0; u < SD; ++u) {
           const int j = min(((cb + u) * NSPLIT + sp) * SLOTS + slot, a.Smax - 1);
@@ -1045,8 +1066,8 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       // workgroup works on (row gm, head gh) of block l (beam rows: the ancestry names rows of positions < pos only), its window and
       // streaming loads mask j == pos, and the next reader is the next step's launch, behind a kernel boundary.
       if (own) {
-        *reinterpret_cast<u32x4*>(kb + (size_t)pos * DH + sub * VEC) = ka.raw;
-        *reinterpret_cast<u32x4*>(vb + (size_t)pos * DH + sub * VEC) = va.raw;
+        *reinterpret_cast<decltype(ka.raw)*>(kb + (size_t)pos * DH + sub * VEC) = ka.raw;  // (KV8: 8 bytes per lane, a 64-byte row)
+        *reinterpret_cast<decltype(va.raw)*>(vb + (size_t)pos * DH + sub * VEC) = va.raw;
       }
       ENG_STAMP(3)
     }
@@ -1410,26 +1431,35 @@ size_t eng_gran_count(int layers) { return (size_t)layers * ENG_MAX_ROWS * ENG_D
 int decode_engine_layers(const EngArgs& a, hipStream_t s) {
   ITTS_REQUIRE(a.B >= 1 && a.B <= ENG_MAX_ROWS && a.NL >= 1 && a.NL <= ENG_MAX_LAYERS && a.gran && a.h && a.kc && a.vc && a.ctr, "decode_engine: bad arguments");
   const size_t lds = 160 * 1024;  // three weight slots + edge buffers: the whole LDS of a CU, one workgroup per CU
-#define ITTS_ENG_GO(NB, ANC_, W8_)                                                                                              \
+#define ITTS_ENG_GO(NB, ANC_, W8_, KV8_)                                                                                        \
   {                                                                                                                             \
     static DynLdsLatch latch;                                                                                                   \
-    ITTS_TRY(allow_dynamic_lds(latch, reinterpret_cast<const void*>(&decode_engine_kernel<NB, ANC_, W8_>), (int)lds));          \
-    hipLaunchKernelGGL((decode_engine_kernel<NB, ANC_, W8_>), dim3(ENG_NCU), dim3(1024), lds, s, a);                            \
+    ITTS_TRY(allow_dynamic_lds(latch, reinterpret_cast<const void*>(&decode_engine_kernel<NB, ANC_, W8_, KV8_>), (int)lds));    \
+    hipLaunchKernelGGL((decode_engine_kernel<NB, ANC_, W8_, KV8_>), dim3(ENG_NCU), dim3(1024), lds, s, a);                      \
   }
-#define ITTS_ENG_ROWS(W8_)                                                                                                      \
+#define ITTS_ENG_ROWS_KV(W8_, KV8_)                                                                                             \
   if (a.anc) { /* beam rows (>= 2 rows per batch item) */                                                                       \
-    if (a.B == 2) ITTS_ENG_GO(2, true, W8_)                                                                                     \
-    else if (a.B == 3) ITTS_ENG_GO(3, true, W8_)                                                                                \
-    else if (a.B == 4) ITTS_ENG_GO(4, true, W8_)                                                                                \
-    else if (a.B == 5) ITTS_ENG_GO(5, true, W8_)                                                                                \
-    else ITTS_ENG_GO(6, true, W8_)                                                                                              \
-  } else if (a.B == 1) ITTS_ENG_GO(1, false, W8_)                                                                               \
-  else if (a.B == 2) ITTS_ENG_GO(2, false, W8_)                                                                                 \
-  else if (a.B == 3) ITTS_ENG_GO(3, false, W8_)                                                                                 \
-  else if (a.B == 4) ITTS_ENG_GO(4, false, W8_)                                                                                 \
-  else if (a.B == 5) ITTS_ENG_GO(5, false, W8_)                                                                                 \
-  else ITTS_ENG_GO(6, false, W8_)
+    if (a.B == 2) ITTS_ENG_GO(2, true, W8_, KV8_)                                                                               \
+    else if (a.B == 3) ITTS_ENG_GO(3, true, W8_, KV8_)                                                                          \
+    else if (a.B == 4) ITTS_ENG_GO(4, true, W8_, KV8_)                                                                          \
+    else if (a.B == 5) ITTS_ENG_GO(5, true, W8_, KV8_)                                                                          \
+    else ITTS_ENG_GO(6, true, W8_, KV8_)                                                                                        \
+  } else if (a.B == 1) ITTS_ENG_GO(1, false, W8_, KV8_)                                                                         \
+  else if (a.B == 2) ITTS_ENG_GO(2, false, W8_, KV8_)                                                                           \
+  else if (a.B == 3) ITTS_ENG_GO(3, false, W8_, KV8_)                                                                           \
+  else if (a.B == 4) ITTS_ENG_GO(4, false, W8_, KV8_)                                                                           \
+  else if (a.B == 5) ITTS_ENG_GO(5, false, W8_, KV8_)                                                                           \
+  else ITTS_ENG_GO(6, false, W8_, KV8_)
+#define ITTS_ENG_ROWS(W8_) /* the cache form: 16-bit elements, or (a.kv8) e4m3 bytes */                                         \
+  if (a.kv8) {                                                                                                                  \
+    ITTS_ENG_ROWS_KV(W8_, true)                                                                                                 \
+  } else {                                                                                                                      \
+    ITTS_ENG_ROWS_KV(W8_, false)                                                                                                \
+  }
   if (a.anc) ITTS_REQUIRE(a.nb >= 2 && a.nb <= a.B && a.B % a.nb == 0, "decode_engine: beam ancestry needs B to be a multiple of 2 <= nb <= B");
+  ITTS_REQUIRE(a.kv8 == 0 || a.kv8 == 1, "decode_engine: kv8 is 0 (16-bit K/V cache) or 1 (e4m3 bytes)");
+  ITTS_REQUIRE(!a.kv8 || (((uintptr_t)a.kc | (uintptr_t)a.vc) & 7) == 0, "decode_engine: an fp8 K/V cache is read and appended 8 bytes at a time");
+  ITTS_REQUIRE(a.Smax >= 1, "decode_engine: cache capacity");
   if (a.w8) {  // every projection (and the head, if it is inside the launch) as fp8 bytes + row scales
 #ifdef ITTS_HALF_F16
     ITTS_REQUIRE(false, "decode_engine: fp8 weights need the bf16 build (fp8 expands to bf16 pairs)");
@@ -1443,6 +1473,7 @@ int decode_engine_layers(const EngArgs& a, hipStream_t s) {
     ITTS_ENG_ROWS(false)
   }
 #undef ITTS_ENG_ROWS
+#undef ITTS_ENG_ROWS_KV
 #undef ITTS_ENG_GO
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;

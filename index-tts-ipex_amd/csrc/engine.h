@@ -150,7 +150,8 @@ struct DecodeState {
   // element type of the cache: the engine's own (F32 / BF16) or, opt-in on a 16-bit engine, FP8 = e4m3 bytes (itts_gpt_set_kv_fp8 /
   // ITTS_KV_FP8).  kv_fp8 is the sticky request; ct / ces are what the prefill latched for the whole generation
   // (ensure_decode_state), ct_held the type whose values the allocation last held (-1: fresh).  An fp8 cache keeps the launch
-  // path's whole-form attention at every row count (engine_usable() is false, no split form, no fused qkv + attention launch).
+  // path's whole-form attention at every row count (no split form, no fused qkv + attention launch) unless the engine object
+  // opted into the persistent engine's fp8-cache form (eng_kv8 below; <= 6 rows).
   int kv_fp8 = 0, ct = 0, ct_held = -1;
   size_t ces = 4;
   float *h = nullptr, *qkv = nullptr, *ctx = nullptr, *act = nullptr, *hn = nullptr, *logits = nullptr;
@@ -209,6 +210,7 @@ struct DecodeState {
   int eng_force = 0;                     // debug bit 5: use the engine whatever ITTS_ENGINE / the default says
   int eng_failed = 0;                    // a hand-off timed out: launch path from then on
   int eng_fp8 = 0;                       // itts_gpt_set_engine_fp8: a model with fp8 GPT weights may use the engine (sticky; default: launch path)
+  int eng_kv8 = 0;                       // itts_gpt_set_engine_kv_fp8: a generation with an fp8 K/V cache may use the engine (sticky; default: launch path)
   int graph_mode = 0;                    // last_mode of the captured step
   float typical_mass = 0.f;                        // TypicalLogitsWarper pre-pass (0 = off)
   float* scores2 = nullptr;                        // [cap_B][V] its output
@@ -337,6 +339,7 @@ struct Engine {
   EngArgs engine_args(int& eng_first, bool& fold_head, bool& fold_samp) const;
   bool rows_on_mfma(int B) const;  // the batched decode step: weights streamed once, batch on MFMA
   bool engine_usable() const;
+  int gpt_set_engine_kv_fp8(int on);  // opt-in: the persistent engine reads and appends an fp8 K/V cache (decode_engine_kernel<.., KV8>)
   bool engine_fp8_model() const;  // every projection of every block and the head carry an fp8 copy + row scales
   int ensure_engine_state(hipStream_t s);
   int engine_check(hipStream_t s);

@@ -23,7 +23,7 @@ struct EngArgs {  // passed by value: it must stay inside the 4 KB kernel-argume
                                       // memory latency, and a vmcnt(0) in front of the weight-prefetch issue, in every phase)
   unsigned long long* gran = nullptr; // hand-off granules: eng_gran_count(NL) words, zeroed once at allocation
   float* h = nullptr;                 // residual stream [B][D]: this step's input embedding in, last block's output out
-  bf16_t* kc = nullptr;               // KV cache [NL][B][H][Smax][64]
+  bf16_t* kc = nullptr;               // KV cache [NL][B][H][Smax][64] (kv8: the same layout in fp8_t elements behind these pointers)
   bf16_t* vc = nullptr;
   const int* len = nullptr;           // [B] tokens generated so far
   const int* kv_start = nullptr;      // [B] first valid (not left-padded) cache row
@@ -59,6 +59,8 @@ struct EngArgs {  // passed by value: it must stay inside the 4 KB kernel-argume
   int w8 = 0;                         // the weight pointers carry fp8-e4m3 bytes: decode_engine_kernel<.., W8> (bf16 build only)
   const float* head_s = nullptr;      // [V] w8: row scales of the fp8 mel_head (head_w then holds its fp8 bytes)
   EngLayerS S[ENG_MAX_LAYERS];        // w8: row scales of block l (scalar loads, like L)
+  // fp8 K/V cache (behind everything else again: no offset of an existing field moves)
+  int kv8 = 0;                        // kc / vc point at e4m3 bytes (fp8_t, itts_common.h): decode_engine_kernel<.., KV8>, both builds
 };
 
 static_assert(sizeof(EngArgs) <= 3072, "EngArgs is a kernel argument: keep it well under 4 KB");

@@ -195,7 +195,10 @@ bool Engine::engine_usable() const {
   if ((env_off && !ds.eng_force) || ds.eng_off || ds.eng_failed || ncu != ENG_NCU) return false;
   if (ds.fuse && !ds.fuse_failed) return false;  // A/B switch of the fused projection + attention launch: a launch-path variant
   if (ds.B != ds.Bcache) return false;  // rows were retired: the engine computes its layer stride from its row count
-  if (ds.ct == FP8) return false;  // the fp8 K/V cache has a launch-path attention form only (decode_attn2_kernel<fp8_t>)
+  if (ds.ct == FP8) {  // the fp8 K/V cache keeps the launch path (decode_attn2_kernel<fp8_t>) unless the engine object opted in
+    const char* k8 = getenv("ITTS_ENGINE_KV_FP8");  // read per call, like ITTS_ENGINE_FP8: =1 opts in, =0 overrides the setter
+    if (!(k8 ? atoi(k8) != 0 : ds.eng_kv8 != 0)) return false;  // opted in: decode_engine_kernel<.., KV8>, both builds
+  }
   if (adt != BF16 || ds.B < 1 || ds.B > ENG_MAX_ROWS || ds.nb < 1 || ds.B % ds.nb != 0 || (ds.nb > 1 && !ds.anc)) return false;
   if (c.model_dim != ENG_D || c.heads != ENG_H || c.layers < 1 || c.layers > ENG_MAX_LAYERS || ds.Smax > 2048 || ds.Smax % 256 != 0) return false;
   for (const GptLayerW& L : gpt.layers)
@@ -214,6 +217,13 @@ bool Engine::engine_usable() const {
 #endif
   }
   return true;
+}
+
+// Opt-in (sticky; ITTS_ENGINE_KV_FP8 overrides it per call): a generation whose cache type latched as FP8 may run on the
+// persistent engine.  engine_usable() is part of the graph key, so a change re-captures the step of a running engine object.
+int Engine::gpt_set_engine_kv_fp8(int on) {
+  ds.eng_kv8 = on != 0;
+  return OK;
 }
 
 int Engine::ensure_engine_state(hipStream_t s) {
@@ -821,8 +831,11 @@ EngArgs Engine::engine_args(int& eng_first, bool& fold_head, bool& fold_samp) co
   }
   ea.gran = ds.eng_gran;
   ea.h = ds.h;
-  ea.kc = (bf16_t*)ds.kc;  // engine_usable(): a 16-bit cache (ds.ces == 2) - the kernel's per-layer offsets count bf16_t elements
+  // engine_usable(): a 16-bit cache (ds.ces == 2), or - opted in - e4m3 bytes (ds.ces == 1, kv8); the kernel's per-layer offsets
+  // count elements of the cache's type either way
+  ea.kc = (bf16_t*)ds.kc;
   ea.vc = (bf16_t*)ds.vc;
+  ea.kv8 = ds.ct == FP8;
   ea.len = ds.len;
   ea.kv_start = ds.kv_start;
   ea.prefix = ds.prefix_dev;

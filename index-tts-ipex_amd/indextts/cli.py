@@ -25,6 +25,8 @@ def build_parser():
                    help="store the GPT weights as fp8-e4m3 (bfloat16 engine; the decode steps stream the fp8 bytes)")
     p.add_argument("--kv-fp8", action="store_true", default=False,
                    help="keep the K/V cache of the GPT decode steps as fp8-e4m3 bytes (16-bit engines; half the cache bytes per step)")
+    p.add_argument("--engine-kv-fp8", action="store_true", default=False,
+                   help="with --kv-fp8: keep the 1 - 6 row decode steps on the persistent decode engine, which reads the fp8 cache itself")
     p.add_argument("--retire-rows", type=float, default=None, metavar="R",
                    help="batched generations retire their finished rows whenever unfinished <= R * running rows (0 < R <= 1; more "
                         "than 6 rows); unset: ITTS_RETIRE_ROWS, else off")
@@ -50,7 +52,8 @@ def main():
     from indextts.infer import IndexTTS
 
     tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8, kv_fp8=a.kv_fp8,
-                   wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler, retire_rows=a.retire_rows)
+                   wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler, retire_rows=a.retire_rows,
+                   engine_kv_fp8=a.engine_kv_fp8)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

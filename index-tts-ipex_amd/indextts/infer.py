@@ -30,6 +30,8 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     lets the 1 - 6 row decode steps stream the fp8 bytes on the persistent decode engine.
   * `kv_fp8=True` (not in the reference; needs `is_fp16=True`, works with both 16-bit engines and together with `gpt_fp8`) keeps
     the K/V cache of the GPT decode steps as fp8-e4m3 bytes: half the cache bytes per step; the decode steps keep the launch path.
+  * `engine_kv_fp8=True` (not in the reference; needs `kv_fp8=True`, ValueError otherwise) keeps the 1 - 6 row decode steps of an
+    fp8-cache generation on the persistent decode engine, which reads and appends the e4m3 rows itself.
   * `retire_rows=r` (not in the reference; a ratio in (0, 1], None: ITTS_RETIRE_ROWS, else off) lets the batched generations
     of `infer_fast` / `infer_batch` retire their finished rows: whenever the unfinished rows are <= r * the running rows (and more
     than 6 rows run), the decode state is compacted and the following steps run at the smaller row count (Engine.generate).
@@ -57,7 +59,12 @@ from indextts.utils.front import TextNormalizer, TextTokenizer
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
-                 wide_beam_sampler=None, kv_fp8=False, retire_rows=None):
+                 wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False):
+        # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
+        self.engine_kv_fp8 = bool(engine_kv_fp8)
+        if self.engine_kv_fp8 and not kv_fp8:
+            raise ValueError("engine_kv_fp8=True needs kv_fp8=True: it keeps the fp8 K/V cache's small-batch decode steps on the "
+                             "persistent decode engine and has no effect on the 16-bit cache")
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -111,7 +118,9 @@ class IndexTTS:
             self.engine.set_engine_fp8(True)
         if self.kv_fp8:
             self.engine.set_kv_fp8(True)
-        self.gpt = UnifiedVoice(self.engine, self.cfg.gpt)
+        if self.engine_kv_fp8:
+            self.engine.set_engine_kv_fp8(True)
+        self.gpt =UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])
         self.normalizer = TextNormalizer()  # infer.py:69-71

@@ -303,9 +303,16 @@ class Engine:
     def set_kv_fp8(self, on: bool = True):
         """Opt-in: the K/V cache of the GPT decode steps as fp8-e4m3 bytes (no scale) instead of the engine's 16-bit type - half
         the cache bytes a decode step streams and half the cache allocation.  16-bit engines only (bf16 and IEEE half; an fp32
-        engine raises).  Takes effect at the next prefill; the decode steps then keep the launch path (decode_mode() == 0).
-        ITTS_KV_FP8=0 / 1 in the environment overrides this setting."""
+        engine raises).  Takes effect at the next prefill; the decode steps then keep the launch path (decode_mode() == 0)
+        unless set_engine_kv_fp8 opted the engine object in.  ITTS_KV_FP8=0 / 1 in the environment overrides this setting."""
         self._ck(self.lib.itts_gpt_set_kv_fp8(self.h, int(bool(on))), "gpt_set_kv_fp8")
+
+    def set_engine_kv_fp8(self, on: bool = True):
+        """Opt-in, on top of set_kv_fp8: a generation with an fp8 K/V cache runs its 1 - 6 row decode steps (beam rows included) on
+        the persistent decode engine, whose attention phase reads and appends the e4m3 rows (decode_mode() == 1); off (the
+        default) an fp8 cache keeps the launch path at every row count.  No effect without an fp8 cache.  Both 16-bit engines,
+        also together with set_engine_fp8.  ITTS_ENGINE_KV_FP8=0 / 1 in the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_engine_kv_fp8(self.h, int(bool(on))), "gpt_set_engine_kv_fp8")
 
     def decode(self, nsteps: int):
         self._ck(self.lib.itts_gpt_decode(self.h, nsteps, self._s()), "gpt_decode")
@@ -650,12 +657,13 @@ def _dvae_code_len(T: int, layers: int) -> int:
 
 def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1234, parts=("gpt", "bigvgan", "dvae"),
                  state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False,
-                 kv_fp8: bool = False) -> Engine:
+                 kv_fp8: bool = False, engine_kv_fp8: bool = False) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
     "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
     engine_fp8: Engine.set_engine_fp8(True) - the fp8 model's small-batch decode steps on the persistent decode engine.
-    kv_fp8: Engine.set_kv_fp8(True) - the decode steps' K/V cache as fp8-e4m3 bytes (16-bit engines)."""
+    kv_fp8: Engine.set_kv_fp8(True) - the decode steps' K/V cache as fp8-e4m3 bytes (16-bit engines).
+    engine_kv_fp8: Engine.set_engine_kv_fp8(True) - with an fp8 cache the small-batch decode steps stay on the persistent engine."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -674,4 +682,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
         eng.set_engine_fp8(True)
     if kv_fp8:
         eng.set_kv_fp8(True)
+    if engine_kv_fp8:
+        eng.set_engine_kv_fp8(True)
     return eng

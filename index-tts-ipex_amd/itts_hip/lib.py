@@ -139,6 +139,7 @@ _PROTOS = {
     "itts_gpt_decode_mode": (i32, [vp]),
     "itts_gpt_set_engine_fp8": (i32, [vp, i32]),
     "itts_gpt_set_kv_fp8": (i32, [vp, i32]),
+    "itts_gpt_set_engine_kv_fp8": (i32, [vp, i32]),
     "itts_gpt_set_host_sampling": (i32, [vp, i32]),
     "itts_gpt_set_cond_per_row": (i32, [vp, i32]),
     "itts_gpt_commit": (i32, [vp, vp, vp]),
