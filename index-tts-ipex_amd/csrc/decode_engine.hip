@@ -53,6 +53,17 @@
 // only for an fp8 cache, so the two agree to a tolerance there (tests/test_gpu_engine_kv_fp8.py).  The KV8 = false instantiations
 // are instruction for instruction what they were.
 //
+// Around the 24 blocks a launch spends 13.4 us at 2 rows (profiles/r12_engine_tail.txt; 15 us before): 3.2 us from the first
+// workgroup's start to the first block's E1 (one wave issues the 54 KB of c_proj(0) / c_attn(0), 2.2 us from the first request to
+// the last, then they have to land), 6.2 us of head on every workgroup (gather 2.8, ln_f -> final_norm 1.1, 32 - 33 dot products
+// from registers 0.56 - they do not wait for their weights -, score + candidate publish 1.7) and 4 us more on the workgroups that
+// finish a row (candidate hop 1.7, commit 0.8, next input embedding 1.7).  A workgroup's 33 candidates of a row are reduced by one
+// wave with a DPP arg-max (wave_argmax, also the reduction of the 256 candidates behind the hop): one thread walking them was 33
+// dependent LDS round trips, 2 us of every launch.  Measured there and NOT taken: touching the mel_head rows into L2 during the
+// last block, ln_f gamma / beta through LDS or loaded early, the `seen` byte and the sampler's kernel arguments loaded before the
+// gather, one 16-byte load per candidate, the first weight requests in front of the launch's scalars, the loader's wait for
+// c_attn moved into the first LayerNorm - each slower or inside the run-to-run spread.
+//
 // Every spin is bounded (wall clock, s_memrealtime) and also ends on a chip-wide abort word; a workgroup that gave up
 // runs on without waiting, so the grid always drains.  The host reads the abort word at status / fetch.
 //
@@ -101,11 +112,17 @@ struct Rt {
 #define ENG_STAMP(i)                                                                                              \
   if (a.stamp && (tl & 63) == 0 && (i < 8 ? tl == 0 : tl == 320))                                                \
     a.stamp[((size_t)cu * a.NL + l) * 16 + (i)] = (unsigned)__builtin_amdgcn_s_memrealtime();
+// ... and stamp j of the launch's prologue / head / sampler tail, taken by thread `thr` (slot 15 of block 3 + j; blocks 0..2 hold the
+// shader clock and the workgroup's start / end there): 0 scalars resolved, 1 first weights requested (both the loader), 2 h gathered,
+// 3 ln_f + final_norm done, 4 dots and wave sums done, 5 candidates published, 6 candidates gathered, 7 token committed (cu < NB)
+#define ENG_HSTAMP(j, thr) \
+  if (a.stamp && a.NL > 3 + (j) && t == (thr)) a.stamp[((size_t)cu * a.NL + 3 + (j)) * 16 + 15] = (unsigned)__builtin_amdgcn_s_memrealtime();
 #define ENG_TAP(off, val) \
   if (a.dbg && l == a.dbg_layer) a.dbg[off] = (val);
 #define ENG_FAKE_DIV(n) ((n) / a.fake_div)
 #else
 #define ENG_STAMP(i)
+#define ENG_HSTAMP(j, thr)
 #define ENG_TAP(off, val)
 #define ENG_FAKE_DIV(n) (n)
 #endif
@@ -600,6 +617,35 @@ __device__ __forceinline__ void ln2_to_sxb(const float* __restrict__ xf, uint32_
   __syncthreads();
 }
 
+// arg-max of (score, id) over the 64 lanes of a wave: larger score, lower id on ties (the rule of sampler2_kernel - a total order, so
+// the result does not depend on the order of the merges); every lane ends with the wave's result
+__device__ __forceinline__ void wave_argmax(float& best, int& bi) {
+  auto merge = [&](float ov, int oi) {
+    if (ov > best || (ov == best && oi < bi)) {
+      best = ov;
+      bi = oi;
+    }
+  };
+#define ENG_ARGMAX_DPP(CTRL)                                                                          \
+  merge(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best), CTRL, 0xf, 0xf, true)),  \
+        __builtin_amdgcn_update_dpp(0, bi, CTRL, 0xf, 0xf, true))
+  ENG_ARGMAX_DPP(0xB1);
+  ENG_ARGMAX_DPP(0x4E);
+  ENG_ARGMAX_DPP(0x141);
+  ENG_ARGMAX_DPP(0x140);
+#undef ENG_ARGMAX_DPP
+  const u32x2 v16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(best), __float_as_uint(best), false, false);
+  const u32x2 i16 = __builtin_amdgcn_permlane16_swap((unsigned)bi, (unsigned)bi, false, false);
+  best = __uint_as_float(v16[0]);
+  bi = (int)i16[0];
+  merge(__uint_as_float(v16[1]), (int)i16[1]);
+  const u32x2 v32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(best), __float_as_uint(best), false, false);
+  const u32x2 i32 = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
+  best = __uint_as_float(v32[0]);
+  bi = (int)i32[0];
+  merge(__uint_as_float(v32[1]), (int)i32[1]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // ANC: beam rows - the cache is never re-ordered when the beams are; key j of beam row b lives in the physical row its
 // ancestry names (decode_attn.hip, decode_attn2_kernel<.., ANC>: the same gather, the same arithmetic)
@@ -704,6 +750,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
   const int my_ks = acu ? __builtin_amdgcn_readfirstlane(a.kv_start[acu ? gm : 0]) : 0;
   const int my_par = (ANC && acu) ? __builtin_amdgcn_readfirstlane(a.len[acu ? gm : 0] & 1) : 0;  // ancestry ping-pong half
 
+  ENG_HSTAMP(0, 256)
   if (t == 0) *own = 0;
   unsigned phase = 0;  // compute phases finished so far (every wave counts alike)
   auto phase_done = [&](int ln_) {  // a compute wave is through a phase: its publishes are issued
@@ -730,6 +777,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       dma_rows<QO, D, W8>(a.L[0].wa, a.L[0].ba, a.S[0].sa, an0, S0, lane);
     }
   }
+  ENG_HSTAMP(1, 256)
   if (t < NB * HO) hown[(t / HO) * 8 + t % HO] = a.h[(size_t)(t / HO) * D + cu * HO + t % HO];
 
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing the compiler counts is pending at the head of the layer loop
@@ -1253,8 +1301,10 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       sweep2<(NB * D / 2 + 255) / 256, false>(a.gran + (size_t)(a.NL - 1) * LSTRIDE + OH2, NB * D / 2, tl, rt,
                                               [&](int i, uint32_t v) { xf[i] = __uint_as_float(v); }, rt.first_delay);
     }
+    ENG_HSTAMP(2, 0)
     __syncthreads();
     ln2_to_sxb<NB, D>(xf, xn, red, tl, a.eps, a.lnf_g, a.lnf_b);
+    ENG_HSTAMP(3, 320)
     if (cwv) {
       const int klast = 2 * 512 + ll * 8;
       const bool kok = klast < D;
@@ -1290,6 +1340,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           const float x = wave_sum_rl(acc[r][b]);
           mine = ll == r * NB + b ? x : mine;
         }
+      ENG_HSTAMP(4, 320)
       if (ll < 3 * NB) {
         const int r = ll / NB, b = ll % NB;
         const int n = r == 0 ? hn_[0] : (r == 1 ? hn_[1] : hn_[2]);
@@ -1314,20 +1365,27 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       const float* cv = so;
       const int* ci = reinterpret_cast<const int*>(so + ENG_MAX_ROWS * 36);
       __syncthreads();
-      if (tl < NB) {
+      // Wave b takes row b's 33 candidates, one per lane, and reduces them with the DPP arg-max below instead of one thread walking
+      // the 33 entries (33 dependent LDS round trips and branches: 2 us of every workgroup's path on the r12 timeline).  A NaN score
+      // never wins, as in a scan that starts from -inf.
+      if (wave < NB) {
         float best = -INFINITY;
         int bi = 0x7fffffff;
-        for (int q = 0; q < 3 * NCW; ++q) {
-          const float v = cv[tl * 36 + q];
-          const int i = ci[tl * 36 + q];
-          if (v > best || (v == best && i < bi)) {
+        if (ll < 3 * NCW) {
+          const float v = cv[wave * 36 + ll];
+          const int i = ci[wave * 36 + ll];
+          if (v >= -INFINITY) {
             best = v;
             bi = i;
           }
         }
-        st_gran(a.cand + ((size_t)tl * NCU + cu) * 2, rt.tag, __float_as_uint(best));
-        st_gran(a.cand + ((size_t)tl * NCU + cu) * 2 + 1, rt.tag, (uint32_t)bi);
+        wave_argmax(best, bi);
+        if (ll == 0) {
+          st_gran(a.cand + ((size_t)wave * NCU + cu) * 2, rt.tag, __float_as_uint(best));
+          st_gran(a.cand + ((size_t)wave * NCU + cu) * 2 + 1, rt.tag, (uint32_t)bi);
+        }
       }
+      ENG_HSTAMP(5, 0)
       if (cu < NB) {  // workgroup b finishes row b
         const int b = cu;
         const int k_pre = a.samp.step[b], unf_pre = a.samp.unfinished[b];
@@ -1357,35 +1415,13 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
             best = -INFINITY;
             bi = 0x7fffffff;
           }
-          auto merge = [&](float ov, int oi) {
-            if (ov > best || (ov == best && oi < bi)) {
-              best = ov;
-              bi = oi;
-            }
-          };
-#define ENG_ARGMAX_DPP(CTRL)                                                                          \
-  merge(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best), CTRL, 0xf, 0xf, true)),  \
-        __builtin_amdgcn_update_dpp(0, bi, CTRL, 0xf, 0xf, true))
-          ENG_ARGMAX_DPP(0xB1);
-          ENG_ARGMAX_DPP(0x4E);
-          ENG_ARGMAX_DPP(0x141);
-          ENG_ARGMAX_DPP(0x140);
-#undef ENG_ARGMAX_DPP
-          const u32x2 v16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(best), __float_as_uint(best), false, false);
-          const u32x2 i16 = __builtin_amdgcn_permlane16_swap((unsigned)bi, (unsigned)bi, false, false);
-          best = __uint_as_float(v16[0]);
-          bi = (int)i16[0];
-          merge(__uint_as_float(v16[1]), (int)i16[1]);
-          const u32x2 v32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(best), __float_as_uint(best), false, false);
-          const u32x2 i32 = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
-          best = __uint_as_float(v32[0]);
-          bi = (int)i32[0];
-          merge(__uint_as_float(v32[1]), (int)i32[1]);
+          wave_argmax(best, bi);
           if (ll == 0) {
             sv[wave] = best;
             si[wave] = bi;
           }
         }
+        ENG_HSTAMP(6, 0)
         __syncthreads();
         if (t == 0) {
           for (int w = 1; w < 4; ++w)
@@ -1403,6 +1439,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           } else {
             sampler_commit(a.samp, b, bi, si, k_pre, unf_pre);
           }
+          ENG_HSTAMP(7, 0)
         }
         __syncthreads();
         sampler_next_embedding(a.samp, b, si, t);

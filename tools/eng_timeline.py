@@ -1,7 +1,9 @@
 """Debugging aid: phase timeline of the persistent decode engine (ITTS_ENGINE_STAMPS=1), one decode step.
 Stamps per workgroup and block (100 MHz wall clock): 0 E1 gathered, 1 after B1, 2 q/k/v polled (attention WGs), 3 context
 published, 4 E3 gathered, 5 E4 gathered, 6 E5 gathered, 7 after B5; compute side: 8 q/k/v published, 9 c_proj published,
-10 c_fc published, 11 mlp.c_proj published.
+10 c_fc published, 11 mlp.c_proj published.  Around the blocks (slot 15 of blocks 3 .. 10): scalars resolved, first weights
+requested, h gathered, ln_f + final_norm done, dots done, candidates published and, on the workgroups that finish a row, candidates
+gathered and token committed - printed as the split of the launch's fixed cost into prologue, head and sampler tail.
 Needs the probes library (`make -C index-tts-ipex_amd/csrc probes`): the product library compiles the engine's stamps, block taps and
 gather divisor out and ignores their switches.  Select it through the usual override:
 ITTS_HIP_LIB=index-tts-ipex_amd/csrc/libitts_hip_probes.so python tools/eng_timeline.py ..."""
@@ -56,6 +58,21 @@ base = us[:, 2:NL - 1, 0].min(axis=0, keepdims=True)
 rel = us[:, 2:NL - 1, :] - base[:, :, None]
 print("-- attention workgroups vs the others (mean us since the block's first E1): " +
       ", ".join(f"{names[i]} {rel[acu][:, :, i].mean():.2f} / {rel[~acu][:, :, i].mean():.2f}" for i in (4, 9, 5, 10, 6, 11)))
+if NL >= 11:  # prologue / head / sampler tail: slot 15 of blocks 3.. (ENG_HSTAMP in decode_engine.hip), median over workgroups
+    hs = (st[:, 3:11, 15] - t0) / 100.0  # [256][8]
+    h2 = us[:, -1, 11].max()
+    wg_end = np.median(k1[rows:]) if rows < 256 else np.median(k1)
+    print(f"-- prologue (us since the workgroup's start, median / max over workgroups): scalars resolved {np.median(hs[:, 0] - k0):.2f} / {(hs[:, 0] - k0).max():.2f}, "
+          f"first weights requested {np.median(hs[:, 1] - k0):.2f} / {(hs[:, 1] - k0).max():.2f}, block 0 E1 gathered {np.median(us[:, 0, 0] - k0):.2f} / {(us[:, 0, 0] - k0).max():.2f}, "
+          f"after B1 {np.median(us[:, 0, 1] - k0):.2f} / {(us[:, 0, 1] - k0).max():.2f}; first start -> last after B1 {us[:, 0, 1].max() - k0.min():.2f}")
+    print(f"-- head (us since the last h2 publish, median / max over workgroups): h gathered {np.median(hs[:, 2]) - h2:.2f} / {hs[:, 2].max() - h2:.2f}, "
+          f"ln_f + final_norm done {np.median(hs[:, 3]) - h2:.2f} / {hs[:, 3].max() - h2:.2f}, dots + wave sums done {np.median(hs[:, 4]) - h2:.2f} / {hs[:, 4].max() - h2:.2f}, "
+          f"candidates published {np.median(hs[:, 5]) - h2:.2f} / {hs[:, 5].max() - h2:.2f}, workgroup end (cu >= rows) {wg_end - h2:.2f}")
+    print(f"-- sampler tail (workgroups cu < rows, us since the last h2 publish): candidates gathered {hs[:rows, 6].max() - h2:.2f}, token committed {hs[:rows, 7].max() - h2:.2f}, "
+          f"embedding stored / end {k1[:rows].max() - h2:.2f}")
+    print(f"-- fixed cost: launch {k1.max() - k0.min():.2f} - {NL} x block {(us[:, -1, 11].max() - us[:, 0, 0].min()) / NL:.2f} = "
+          f"{k1.max() - k0.min() - (us[:, -1, 11].max() - us[:, 0, 0].min()):.2f} us: prologue (first start -> first E1) {us[:, 0, 0].min() - k0.min():.2f}, "
+          f"head (last h2 -> median end) {wg_end - h2:.2f}, sampler tail (-> last end) {k1.max() - wg_end:.2f}")
 clk = st[:, 0, 15]
 print(f"shader clock over the launch: {np.median(clk) / 10.0:.0f} MHz (min {clk.min() / 10.0:.0f}, max {clk.max() / 10.0:.0f})")
 d = us[:, 2:NL - 1, :]
