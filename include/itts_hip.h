@@ -74,6 +74,16 @@ int itts_gemm(const itts_gemm_args* args, itts_stream stream);
 /* Which kernel family itts_gemm takes for these arguments (no launch): 0 vector ALU, 1 register-staged MFMA, 2 LDS-DMA staged
  * 128-wide tiles, 3 the 256 x 256 eight-phase kernel, 4 the LDS-tiled narrow conv.  Tests and tools/bench_gemm.py use it. */
 int itts_gemm_which(const itts_gemm_args* args);
+/* conv (itts_gemm semantics) whose input A is Activation1d(A) applied inside the kernel (conv_lds.hip ACT): the anti-aliased
+ * SnakeBeta of itts_snake_aa_fwd (log_alpha / log_beta fp32 [Cin], filt12 the 12-tap filter, up = down) runs while the input tile
+ * is staged, and the convolution sees exactly the 16-bit values itts_snake_aa_fwd (layout 1) would have written - the a -> conv of
+ * the narrow BigVGAN stages as the engine issues it.  A is the PRE-activation tensor and is not modified.
+ * Refuses (ITTS_E_INVALID, before any HIP call) whatever it cannot run FUSED - it never runs the conv without the activation:
+ * null args or pointers, force_simple, a dtype that is not the 16-bit one, lda != Cin, every shape itts_gemm_which does not answer
+ * 4 for (T < 256, Cin > 96 or < 16, N % 8, reflect padding, taps < 3, (taps - 1) * dil > 64, nphase / in_up != 1,
+ * ITTS_NO_CONV_LDS set) and ITTS_NO_CONV_ACT set (both switches are read per call).  itts_act_conv_supported: 1 / 0, no launch. */
+int itts_act_conv(const itts_gemm_args* args, const float* log_alpha, const float* log_beta, const float* filt12, itts_stream stream);
+int itts_act_conv_supported(const itts_gemm_args* args);
 /* Which instantiation the bf16 decode GEMV of the launch path (1-4 rows) takes for a call (no launch): -1 = it does not take the
  * call, else nb | rpw << 4 | nch << 8 | waves << 16 (batch rows compiled in, weight rows per wave, 512-column chunks per lane, waves
  * per workgroup).  w5 = the ITTS_GEMV_W5 rows.  tests/test_gemv_selector.py uses it. */

@@ -87,6 +87,38 @@ int itts_gemm_which(const itts_gemm_args* a) {
   return a->force_simple ? 0 : gemm_which(g, a->dtype_a, a->dtype_w, a->dtype_c);
 }
 
+// Why itts_act_conv cannot run a call FUSED (null = it can).  The early answers only name the reason; the decision is gemm_act_fused.
+static const char* act_conv_refusal(const itts_gemm_args* a, const float* log_alpha, const float* log_beta, const float* filt12) {
+  if (!a) return "null args";
+  if (!a->A || !a->W || !a->C || !log_alpha || !log_beta || !filt12) return "null pointer";
+  if (a->force_simple) return "force_simple: the vector-ALU kernel has no fused activation";
+  if (a->dtype_a != BF16 || a->dtype_w != BF16 || a->dtype_c != BF16) return "dtype: A, W and C must be the 16-bit type of the library";
+  if (a->lda != a->Cin) return "lda != Cin: the fused form stages whole dense rows";
+  GemmArgs g;
+  to_gemm_args(a, g);
+  g.pre_alpha = log_alpha, g.pre_beta = log_beta, g.pre_filt = filt12;
+  if (gemm_which(g, BF16, BF16, BF16) != 4) return "shape: not the LDS-tiled narrow conv (itts_gemm_which != 4)";
+  if (!gemm_act_fused(g, BF16, BF16, BF16)) return "the fused activation is switched off (ITTS_NO_CONV_ACT)";
+  return nullptr;
+}
+
+int itts_act_conv(const itts_gemm_args* a, const float* log_alpha, const float* log_beta, const float* filt12, itts_stream stream) {
+  if (const char* why = act_conv_refusal(a, log_alpha, log_beta, filt12)) {  // before any HIP call
+    set_error(std::string("itts_act_conv: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  GemmArgs g;
+  to_gemm_args(a, g);
+  g.pre_alpha = log_alpha, g.pre_beta = log_beta, g.pre_filt = filt12;
+  return gemm(g, BF16, BF16, BF16, (hipStream_t)stream);  // (gemm() itself refuses a pre_* call it would not run fused)
+}
+
+int itts_act_conv_supported(const itts_gemm_args* a) {
+  static const float dummy = 0.f;  // a real call has its three parameter vectors; the rule only asks whether they are there
+  return act_conv_refusal(a, &dummy, &dummy, &dummy) ? 0 : 1;
+}
+
 int itts_gemv_which(int B, int N, int K, int prologue, int x_bf16, int y_bf16, int w5) {
   static const float partials = 0.f;  // prologue 3: a real call has its two partial buffers; the selector only asks whether they are there
   GemvArgs g;

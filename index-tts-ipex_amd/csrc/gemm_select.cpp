@@ -71,7 +71,16 @@ int gemm_which(const GemmArgs& g, int ta, int tw, int tc) {
   return 0;
 }
 
+// Does a call that carries g.pre_* run with Activation1d applied INSIDE the convolution?  Only family 4 has that form.  The one rule
+// behind the engine's a -> conv (model_vocoder.hip act_conv), itts_act_conv / itts_act_conv_supported and the guard in gemm() below.
+bool gemm_act_fused(const GemmArgs& g, int ta, int tw, int tc) {
+  return gemm_which(g, ta, tw, tc) == 4 && conv_lds_act_supported(g, ta, tw, tc);
+}
+
 int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
+  // the other families do not read pre_*: they would convolve the raw input without a word
+  ITTS_REQUIRE(!(g.pre_alpha || g.pre_beta || g.pre_filt) || gemm_act_fused(g, ta, tw, tc),
+               "gemm: pre_alpha / pre_beta / pre_filt set on a call that does not run the fused Activation1d kernel");
   switch (gemm_which(g, ta, tw, tc)) {
     case 4: return conv_lds(g, s);
     case 3: return gemm_p8(g, ta, tw, tc, s);

@@ -22,6 +22,7 @@ bool conv_lds_act_supported(const GemmArgs& g, int ta, int tw, int tc);  // ... 
 int conv_lds(const GemmArgs& g, hipStream_t s);
 int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);  // dispatcher
 int gemm_which(const GemmArgs& g, int ta, int tw, int tc);           // the kernel family the dispatcher takes: 0 VALU, 1 mfma, 2 glds, 3 p8, 4 conv_lds
+bool gemm_act_fused(const GemmArgs& g, int ta, int tw, int tc);      // a call with g.pre_* runs Activation1d inside the conv: family 4 and conv_lds_act_supported
 
 // ---- anti-aliased SnakeBeta (snake.hip); x,y [B,T,C] ----
 int snake_aa(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12,

@@ -266,7 +266,7 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
         q.pre_alpha = la;
         q.pre_beta = lb;
         q.pre_filt = bv.filter;
-        if (!force_simple && gemm_which(q, adt, wdt, adt) == 4 && conv_lds_act_supported(q, adt, wdt, adt)) return conv(q, adt, wdt, adt, s);
+        if (!force_simple && gemm_act_fused(q, adt, wdt, adt)) return conv(q, adt, wdt, adt, s);
         q.pre_alpha = q.pre_beta = q.pre_filt = nullptr;
         K(snake_aa(tact, xraw, la, lb, bv.filter, bv.filter, B, Tc, ch, adt, s));
         q.A = tact;

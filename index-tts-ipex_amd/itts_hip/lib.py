@@ -105,6 +105,8 @@ _PROTOS = {
     "itts_snake_aa_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "itts_gemm": (i32, [C.POINTER(GemmArgs), vp]),
     "itts_gemm_which": (i32, [C.POINTER(GemmArgs)]),
+    "itts_act_conv": (i32, [C.POINTER(GemmArgs), vp, vp, vp, vp]),
+    "itts_act_conv_supported": (i32, [C.POINTER(GemmArgs)]),
     "itts_gemv_which": (i32, [i32] * 7),
     "itts_gemm_ws": (i32, [C.POINTER(GemmArgs), vp, C.c_size_t, vp]),
     "itts_gemm_ksplit": (i32, [C.POINTER(GemmArgs), C.c_size_t]),
