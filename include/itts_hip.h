@@ -84,6 +84,25 @@ int itts_gemm_which(const itts_gemm_args* args);
  * ITTS_NO_CONV_LDS set) and ITTS_NO_CONV_ACT set (both switches are read per call).  itts_act_conv_supported: 1 / 0, no launch. */
 int itts_act_conv(const itts_gemm_args* args, const float* log_alpha, const float* log_beta, const float* filt12, itts_stream stream);
 int itts_act_conv_supported(const itts_gemm_args* args);
+
+/* ---- padded ragged batches (the vocoder over latents of unequal length) ----
+ * A [B, T, C] tensor holds B signals of lens_dev[b] * mul rows each (lens_dev: device int32 [B]; mul >= 1, the up-sampling between
+ * the unit of the lengths and this tensor's rows; a product outside [0, T] is clamped to it; the fused convolution
+ * clamps to [1, T]).  All three refuse null pointers,
+ * B < 1, T < 1, C < 1 and mul < 1 with ITTS_E_INVALID before any HIP call; the lengths are device memory and are not read on the host.
+ *
+ * itts_snake_aa_fwd_len: itts_snake_aa_fwd, layout 1 ([B, T, C]) only, with the signal of item b ending at row lens_dev[b] * mul - its
+ * replicate padding is taken there, not at the end of the buffer.  The first lens_dev[b] * mul rows of dst have the bits of
+ * itts_snake_aa_fwd on the item cut to that length, the rows behind them are written as zeros.  dtype 0 / 1 / 5 as there.
+ * itts_act_conv_len: itts_act_conv with the same per-item signal length inside the fused Activation1d (args->T stays the row count of
+ * the buffers): the convolution reads zeros behind an item's end - the zero "same" padding the item would see alone.  Every output row
+ * is stored; rows < lens_dev[b] * mul have the bits of itts_snake_aa_fwd_len followed by itts_gemm.  The refusals of itts_act_conv.
+ * itts_zero_tail_rows: rows [lens_dev[b] * mul, T) of item b of x become zeros, nothing else is written.  dtype 0 / 1; B <= 65535. */
+int itts_snake_aa_fwd_len(void* dst, const void* src, const float* up12, const float* down12, const float* log_alpha,
+                          const float* log_beta, int B, int C, int T, const int* lens_dev, int mul, int dtype, itts_stream stream);
+int itts_act_conv_len(const itts_gemm_args* args, const float* log_alpha, const float* log_beta, const float* filt12,
+                      const int* lens_dev, int mul, itts_stream stream);
+int itts_zero_tail_rows(void* x, int B, int T, int C, const int* lens_dev, int mul, int dtype, itts_stream stream);
 /* Which instantiation the bf16 decode GEMV of the launch path (1-4 rows) takes for a call (no launch): -1 = it does not take the
  * call, else nb | rpw << 4 | nch << 8 | waves << 16 (batch rows compiled in, weight rows per wave, 512-column chunks per lane, waves
  * per workgroup).  w5 = the ITTS_GEMV_W5 rows.  tests/test_gemv_selector.py uses it. */
@@ -494,6 +513,15 @@ int itts_gpt_latent_batch(itts_engine* e, const float* cond, const int32_t* text
 /* V1-V5  BigVGAN.forward given the speaker embedding (BigVGAN/models.py:201-250):
  * latent [B, T, gpt_dim] (engine dtype), spk fp32 [B, spk_dim] -> wav fp32 [B, T * prod(up_rates)] */
 int itts_bigvgan(itts_engine* e, const void* latent, const float* spk, int B, int T, float* wav_out, itts_stream stream);
+
+/* The same over a padded ragged batch (opt-in): item b is a latent of lens_host[b] frames (host int32 [B], each in
+ * [1, T]) at the head of its T rows, whatever the rows behind them hold (they are not read as signal; latent is not modified).
+ * wav_out fp32 [B][T * prod(up_rates)]: the first lens_host[b] * prod(up_rates) samples of row b are the waveform of that latent run
+ * alone (the same kernels on the same values; a K-split or tile choice that depends on the row count may reorder fp32 sums), the
+ * samples behind them are zero.  Refused with ITTS_E_INVALID before any HIP call: null pointers, B outside [1, max_batch], T < 1,
+ * a length outside [1, T].  lens_host is consumed before the call returns. */
+int itts_bigvgan_ragged(itts_engine* e, const void* latent, const float* spk, int B, int T, const int32_t* lens_host, float* wav_out,
+                        itts_stream stream);
 
 /* Q1  DiscreteVAE.decode (vqvae/xtts_dvae.py:332-351): codes host int32 [B, T] -> mel [B, 4T, channels] engine dtype */
 int itts_dvae_decode(itts_engine* e, const int32_t* codes_host, int B, int T, void* mel_out, itts_stream stream);

@@ -114,6 +114,53 @@ int itts_act_conv(const itts_gemm_args* a, const float* log_alpha, const float* 
   return gemm(g, BF16, BF16, BF16, (hipStream_t)stream);  // (gemm() itself refuses a pre_* call it would not run fused)
 }
 
+// ---- padded ragged batches: every block is judged on the host before any HIP call ----
+static const char* ragged_refusal(const void* lens_dev, int mul) {
+  if (!lens_dev) return "null pointer";
+  if (mul < 1) return "mul < 1";
+  return nullptr;
+}
+
+int itts_snake_aa_fwd_len(void* dst, const void* src, const float* up12, const float* down12, const float* log_alpha,
+                          const float* log_beta, int B, int C, int T, const int* lens_dev, int mul, int dtype, itts_stream stream) {
+  const char* why = (!dst || !src || !up12 || !down12 || !log_alpha || !log_beta) ? "null pointer" : ragged_refusal(lens_dev, mul);
+  if (!why && (B < 1 || C < 1 || T < 1)) why = "B, C and T must be >= 1";
+  if (!why && dtype != F32 && dtype != BF16 && dtype != F16) why = "unsupported dtype";
+  if (why) {
+    set_error(std::string("itts_snake_aa_fwd_len: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  return snake_aa_len(dst, src, log_alpha, log_beta, up12, down12, B, T, C, lens_dev, mul, dtype, (hipStream_t)stream);
+}
+
+int itts_act_conv_len(const itts_gemm_args* a, const float* log_alpha, const float* log_beta, const float* filt12, const int* lens_dev,
+                      int mul, itts_stream stream) {
+  const char* why = act_conv_refusal(a, log_alpha, log_beta, filt12);
+  if (!why) why = ragged_refusal(lens_dev, mul);
+  if (why) {
+    set_error(std::string("itts_act_conv_len: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  GemmArgs g;
+  to_gemm_args(a, g);
+  g.pre_alpha = log_alpha, g.pre_beta = log_beta, g.pre_filt = filt12;
+  return gemm(g, BF16, BF16, BF16, (hipStream_t)stream, lens_dev, mul);
+}
+
+int itts_zero_tail_rows(void* x, int B, int T, int C, const int* lens_dev, int mul, int dtype, itts_stream stream) {
+  const char* why = !x ? "null pointer" : ragged_refusal(lens_dev, mul);
+  if (!why && (B < 1 || B > 65535 || C < 1 || T < 1)) why = "B in [1, 65535], C and T >= 1";
+  if (!why && dtype != F32 && dtype != BF16) why = "unsupported dtype";
+  if (why) {
+    set_error(std::string("itts_zero_tail_rows: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  return zero_tail_rows(x, B, T, C, lens_dev, mul, dtype, (hipStream_t)stream);
+}
+
 int itts_act_conv_supported(const itts_gemm_args* a) {
   static const float dummy = 0.f;  // a real call has its three parameter vectors; the rule only asks whether they are there
   return act_conv_refusal(a, &dummy, &dummy, &dummy) ? 0 : 1;
@@ -701,6 +748,21 @@ int itts_gpt_latent_batch(itts_engine* e, const float* cond, const int32_t* text
 int itts_bigvgan(itts_engine* e, const void* latent, const float* spk, int B, int T, float* wav_out, itts_stream s) {
   ENG(e);
   return e->e.bigvgan(latent, spk, B, T, wav_out, (hipStream_t)s);
+}
+int itts_bigvgan_ragged(itts_engine* e, const void* latent, const float* spk, int B, int T, const int32_t* lens_host, float* wav_out,
+                        itts_stream s) {
+  // refused before any HIP call
+  const char* why = !e ? "null engine" : (!latent || !spk || !lens_host || !wav_out) ? "null pointer" : nullptr;
+  if (!why && (B < 1 || B > e->e.cfg.max_batch)) why = "B outside [1, max_batch]";
+  if (!why && T < 1) why = "T < 1";
+  for (int b = 0; !why && b < B; ++b)
+    if (lens_host[b] < 1 || lens_host[b] > T) why = "a length outside [1, T]";
+  if (why) {
+    set_error(std::string("itts_bigvgan_ragged: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  return e->e.bigvgan(latent, spk, B, T, wav_out, (hipStream_t)s, lens_host);
 }
 int itts_dvae_decode(itts_engine* e, const int32_t* codes_host, int B, int T, void* mel_out, itts_stream s) {
   ENG(e);

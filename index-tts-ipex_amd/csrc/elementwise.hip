@@ -1,5 +1,7 @@
 // Row-wise / elementwise kernels of the conditioning encoder, ECAPA-TDNN and the GPT glue.
 // All HBM-bound; lanes always walk the contiguous (channel) axis.
+#include <algorithm>
+
 #include "itts_kernels.h"
 
 namespace itts {
@@ -483,6 +485,44 @@ int relpos_pack(void* qc, void* kc, const void* qkv, const void* p, const float*
 
 int tanh_rows(void* y, const void* x, long n, int dt, hipStream_t s) {
   DISPATCH_T(dt, T, hipLaunchKernelGGL(tanh_kernel<T>, dim3(nblk(n)), dim3(256), 0, s, (T*)y, (const T*)x, n));
+  CHECK_LAUNCH();
+}
+
+// ---- padding of a ragged batch: rows [lens[b] * mul, T) of item b (blockIdx.y) of x [B, T, C] become zeros -------------------------
+// U is the store unit (16 bytes where a row is a whole number of them, else one element), row_units / item_units a row and an item
+// in units.  The tail of an item is one contiguous span; workgroups count from its first unit and those behind its end leave at once,
+// so the traffic is the padding and nothing else.
+namespace {
+template <typename U>
+__global__ __launch_bounds__(256) void zero_tail_rows_kernel(U* __restrict__ x, long item_units, long row_units,
+                                                             const int* __restrict__ lens, int mul, int T_) {
+  const int b = blockIdx.y;
+  const long v = (long)lens[b] * mul;
+  const long start = (v < 0 ? 0 : (v > T_ ? (long)T_ : v)) * row_units;
+  U* __restrict__ xb = x + (size_t)b * item_units + start;
+  const long n = item_units - start;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) xb[i] = U{};
+}
+}  // namespace
+
+int zero_tail_rows(void* x, int B, int T_, int C, const int* lens, int mul, int dt, hipStream_t s) {
+  ITTS_REQUIRE(x && lens, "zero_tail_rows: null pointer");
+  ITTS_REQUIRE(B > 0 && B <= 65535 && T_ > 0 && C > 0 && mul >= 1, "zero_tail_rows: bad dims");
+  ITTS_REQUIRE(dt == F32 || dt == BF16, "zero_tail_rows: dtype");
+  const long es = dt == F32 ? 4 : 2, row_bytes = (long)C * es;
+  // the longest tail the grid has to reach: every row of an item but the first mul (lens >= 1); shorter tails end their loop early
+  const long tail_rows = T_ > mul ? T_ - mul : 1;
+  if (row_bytes % 16 == 0 && !((uintptr_t)x & 15)) {
+    const long units = row_bytes / 16;
+    hipLaunchKernelGGL(zero_tail_rows_kernel<uint4>, dim3((unsigned)std::min<long>(nblk(tail_rows * units), 65535), B), dim3(256), 0, s,
+                       (uint4*)x, (long)T_ * units, units, lens, mul, T_);
+  } else if (dt == F32) {
+    hipLaunchKernelGGL(zero_tail_rows_kernel<uint32_t>, dim3((unsigned)std::min<long>(nblk(tail_rows * C), 65535), B), dim3(256), 0, s,
+                       (uint32_t*)x, (long)T_ * C, (long)C, lens, mul, T_);
+  } else {
+    hipLaunchKernelGGL(zero_tail_rows_kernel<uint16_t>, dim3((unsigned)std::min<long>(nblk(tail_rows * C), 65535), B), dim3(256), 0, s,
+                       (uint16_t*)x, (long)T_ * C, (long)C, lens, mul, T_);
+  }
   CHECK_LAUNCH();
 }
 

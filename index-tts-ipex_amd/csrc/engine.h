@@ -281,7 +281,7 @@ struct Engine {
   // op wrappers (skip launches in dry mode)
   int lin(void* C, int tc, const void* A, int ta, int lda, const Lin& w, int M, int ldc, hipStream_t s, int act = ACT_NONE,
           const void* R = nullptr, int ldr = 0, float alpha = 1.f);
-  int conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
+  int conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* lens = nullptr, int mul = 1);  // lens / mul: gemm()
   int ln(void* y, int ty, const void* x, int tx, const Norm& n, int rows, int D, hipStream_t s, int act = ACT_NONE,
          float eps = 1e-5f);
 
@@ -328,7 +328,9 @@ struct Engine {
                  hipStream_t s);
   int gpt_latent_batch(const float* cond, const int32_t* text_ids, const int* Ls, const int32_t* codes, const int* Ts,
                        int nseq, void* latent_out, hipStream_t s);
-  int bigvgan(const void* latent, const float* spk, int B, int T, float* wav, hipStream_t s);
+  // lens_host (optional, [B], each in [1, T]): a padded ragged batch - item b is a latent of lens_host[b] frames, whatever its rows
+  // behind them hold; its waveform is that of the item alone, zeros from sample lens_host[b] * up on
+  int bigvgan(const void* latent, const float* spk, int B, int T, float* wav, hipStream_t s, const int* lens_host = nullptr);
   int dvae_decode(const int32_t* codes, int B, int T, void* mel_out, hipStream_t s);
   int dvae_encode(const void* mel, int B, int T, int32_t* codes_host, hipStream_t s);
 

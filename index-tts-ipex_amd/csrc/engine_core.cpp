@@ -92,9 +92,12 @@ int Engine::lin(void* C, int tc, const void* A, int ta, int lda, const Lin& w, i
   return conv(g, ta, w.dt, tc, s);
 }
 
-int Engine::conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
+int Engine::conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* lens, int mul) {
   if (dry) return OK;
-  if (force_simple) return gemm_simple(g, ta, tw, tc, s);
+  if (force_simple) {
+    ITTS_REQUIRE(!lens, "conv: per-item lengths on the vector-ALU kernel");
+    return gemm_simple(g, ta, tw, tc, s);
+  }
   // few-tile deep-K shapes split K over workgroups (this engine's own fp32 workspace: engines on other streams have theirs)
   const int S = ksplit_off ? 1 : gemm_ksplit_plan(g, ta, tw, tc, KSPLIT_WS_BYTES);
   if (S > 1) {
@@ -109,7 +112,7 @@ int Engine::conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
     g.ws = ksplit_ws;
     g.ksplit = S;
   }
-  return gemm(g, ta, tw, tc, s);
+  return gemm(g, ta, tw, tc, s, lens, mul);
 }
 
 int Engine::ln(void* y, int ty, const void* x, int tx, const Norm& n, int rows, int D, hipStream_t s, int act, float eps) {

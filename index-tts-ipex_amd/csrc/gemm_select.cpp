@@ -77,12 +77,14 @@ bool gemm_act_fused(const GemmArgs& g, int ta, int tw, int tc) {
   return gemm_which(g, ta, tw, tc) == 4 && conv_lds_act_supported(g, ta, tw, tc);
 }
 
-int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
+int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* lens, int mul) {
   // the other families do not read pre_*: they would convolve the raw input without a word
   ITTS_REQUIRE(!(g.pre_alpha || g.pre_beta || g.pre_filt) || gemm_act_fused(g, ta, tw, tc),
                "gemm: pre_alpha / pre_beta / pre_filt set on a call that does not run the fused Activation1d kernel");
+  // ... and only the fused activation knows a per-item signal length
+  ITTS_REQUIRE(!lens || (g.pre_alpha && mul >= 1), "gemm: per-item lengths on a call that does not run the fused Activation1d kernel");
   switch (gemm_which(g, ta, tw, tc)) {
-    case 4: return conv_lds(g, s);
+    case 4: return conv_lds(g, s, lens, mul);
     case 3: return gemm_p8(g, ta, tw, tc, s);
     case 2: return gemm_glds(g, ta, tw, tc, s);
     case 1: return gemm_mfma(g, ta, tw, tc, s);

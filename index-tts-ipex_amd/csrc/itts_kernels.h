@@ -19,14 +19,20 @@ int gemm_p8(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);  // 256 x
 int gemm_ksplit_plan(const GemmArgs& g, int ta, int tw, int tc, size_t ws_bytes);  // K split of the few-tile deep-K shapes; 1 = none
 bool conv_lds_supported(const GemmArgs& g, int ta, int tw, int tc);
 bool conv_lds_act_supported(const GemmArgs& g, int ta, int tw, int tc);  // ... with Activation1d fused into the tile load (g.pre_*)
-int conv_lds(const GemmArgs& g, hipStream_t s);
-int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);  // dispatcher
+// lens / mul (ragged batches, next to the args so that GemmArgs - a by-value argument of every GEMM kernel - does not grow): item b of
+// a fused-activation call is the signal of its first lens[b] * mul rows (device ints, one per batch item); null = all T rows
+int conv_lds(const GemmArgs& g, hipStream_t s, const int* lens = nullptr, int mul = 1);
+int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* lens = nullptr, int mul = 1);  // dispatcher
 int gemm_which(const GemmArgs& g, int ta, int tw, int tc);           // the kernel family the dispatcher takes: 0 VALU, 1 mfma, 2 glds, 3 p8, 4 conv_lds
 bool gemm_act_fused(const GemmArgs& g, int ta, int tw, int tc);      // a call with g.pre_* runs Activation1d inside the conv: family 4 and conv_lds_act_supported
 
 // ---- anti-aliased SnakeBeta (snake.hip); x,y [B,T,C] ----
 int snake_aa(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12,
              const float* down12, int B, int T, int C, int dt, hipStream_t s);
+// ... on a padded ragged batch: item b is the signal of its first lens[b] * mul rows (clamped to [0, T]; replicate clamp at its own
+// end), the rows behind it are written as zeros; lens: device ints [B]
+int snake_aa_len(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12, const float* down12,
+                 int B, int T, int C, const int* lens, int mul, int dt, hipStream_t s);
 // same op on the reference's [B,C,T] layout (drop-in for anti_alias_activation_cuda.forward)
 int snake_aa_bct(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12,
                  const float* down12, int B, int C, int T, int dt, hipStream_t s);
@@ -55,6 +61,8 @@ int asp_pool(float* out, const void* logits, const void* x, const float* bn_scal
 int relpos_pack(void* qc, void* kc, const void* qkv, const void* p, const float* bu, const float* bv, int T, int H,
                 int dk, int dt, hipStream_t s);
 int tanh_rows(void* y, const void* x, long n, int dt, hipStream_t s);
+// x [B, T, C]: rows [lens[b] * mul, T) of item b become zeros (the padding of a ragged batch and nothing else is written)
+int zero_tail_rows(void* x, int B, int T, int C, const int* lens, int mul, int dt, hipStream_t s);
 
 // ---- the DVAE encoder's small kernels (model_vocoder.hip) ----
 // y[B][(Tin + 1) / 2][2 C] = x[B][2t][:] | x[B][2t + 1][:], zero past Tin (the row pairs of a stride-2 convolution)

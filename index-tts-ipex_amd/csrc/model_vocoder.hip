@@ -2,6 +2,7 @@
 // Reference: BigVGAN.forward / AMPBlock1.forward (indextts/BigVGAN/models.py:65-74,201-250), Activation1d
 // (alias_free_torch/act.py, resample.py, filter.py), ECAPA_TDNN.forward (BigVGAN/ECAPA_TDNN.py:545-581),
 // DiscreteVAE.decode (vqvae/xtts_dvae.py:332-351).
+#include <algorithm>
 #include <cmath>
 
 #include "engine.h"
@@ -15,6 +16,15 @@ __global__ void add_vec_rows_kernel(float* __restrict__ out, const float* __rest
                                     int B, int N) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B * N) out[i] = a[i] + v[i % N];
+}
+
+// a few host ints to device memory as a kernel ARGUMENT: nothing of the caller's has to outlive the launch (capture-safe)
+struct IntPack {
+  int v[256];
+};
+__global__ void store_ints_kernel(int* __restrict__ dst, IntPack p, int n) {
+  const int i = threadIdx.x;
+  if (i < n) dst[i] = p.v[i];
 }
 
 template <typename T>
@@ -199,15 +209,38 @@ int Engine::ecapa(const void* mel, int B, int F, float* spk_out, hipStream_t s) 
 // ------------------------------------------------------------------------------------------------
 // BigVGAN generator
 // ------------------------------------------------------------------------------------------------
-int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* wav, hipStream_t s) {
+int Engine::bigvgan(const void* latent_in, const float* spk, int B, int T, float* wav, hipStream_t s, const int* lens_host) {
   if (!finalized || !bv.ok) {
     set_error("bigvgan: generator weights not bound");
     return E_STATE;
   }
   const itts_config& c = cfg;
-  ITTS_REQUIRE(latent && spk && wav && B > 0 && T > 0, "bigvgan: bad arguments");
+  ITTS_REQUIRE(latent_in && spk && wav && B > 0 && T > 0, "bigvgan: bad arguments");
+  if (lens_host)
+    for (int b = 0; b < B; ++b) ITTS_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "bigvgan: a row length outside [1, T]");
   const int C0 = c.bv_init_ch, E = c.bv_spk_dim, nk = c.bv_num_res, nd = c.bv_num_dil;
   auto body = [&]() -> int {
+    // Ragged batch (lens_host): every tensor a convolution reads is zero behind its item's len * U rows (U the up-sampling so far) -
+    // the zero "same" padding the item would see alone - and every Activation1d takes len * U as its signal length; residual and
+    // accumulate tensors keep whatever their tails hold, nothing reads them but a length-aware activation or the next mask.
+    const void* latent = latent_in;
+    int* lens = nullptr;
+    if (lens_host) {
+      lens = (int*)alloc((size_t)B * 4);
+      void* lat = alloc((size_t)B * T * c.bv_gpt_dim * es);
+      if (!dry) {
+        for (int o = 0; o < B; o += 256) {
+          IntPack p;
+          const int n = std::min(256, B - o);
+          for (int i = 0; i < n; ++i) p.v[i] = lens_host[o + i];
+          hipLaunchKernelGGL(store_ints_kernel, dim3(1), dim3(256), 0, s, lens + o, p, n);
+          ITTS_HIP_CHECK(hipGetLastError());
+        }
+        ITTS_HIP_CHECK(hipMemcpyAsync(lat, latent_in, (size_t)B * T * c.bv_gpt_dim * es, hipMemcpyDeviceToDevice, s));
+      }
+      K(zero_tail_rows(lat, B, T, c.bv_gpt_dim, lens, 1, adt, s));  // the caller's tail rows are not read as signal
+      latent = lat;
+    }
     // speaker conditioning -> per-batch biases (cond_layer / conds[i] are 1x1 convs of a length-1 signal)
     float* cb = (float*)alloc((size_t)B * C0 * 4);
     float* cbias = (float*)alloc((size_t)B * C0 * 4);
@@ -225,6 +258,7 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
       g.bias_bstride = C0;
       ITTS_TRY(conv(g, adt, bv.conv_pre.dt, adt, s));
     }
+    if (lens) K(zero_tail_rows(x, B, T, C0, lens, 1, adt, s));
     ITTS_TRY(tap("bv_pre", x, adt, (int64_t)B * T * C0, s));
     int Tc = T, ch = C0;
     for (int i = 0; i < c.bv_num_up; ++i) {
@@ -266,9 +300,12 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
         q.pre_alpha = la;
         q.pre_beta = lb;
         q.pre_filt = bv.filter;
-        if (!force_simple && gemm_act_fused(q, adt, wdt, adt)) return conv(q, adt, wdt, adt, s);
+        if (!force_simple && gemm_act_fused(q, adt, wdt, adt)) return conv(q, adt, wdt, adt, s, lens, Tc / T);
         q.pre_alpha = q.pre_beta = q.pre_filt = nullptr;
-        K(snake_aa(tact, xraw, la, lb, bv.filter, bv.filter, B, Tc, ch, adt, s));
+        if (lens)
+          K(snake_aa_len(tact, xraw, la, lb, bv.filter, bv.filter, B, Tc, ch, lens, Tc / T, adt, s));
+        else
+          K(snake_aa(tact, xraw, la, lb, bv.filter, bv.filter, B, Tc, ch, adt, s));
         q.A = tact;
         return conv(q, adt, wdt, adt, s);
       };
@@ -304,17 +341,22 @@ int Engine::bigvgan(const void* latent, const float* spk, int B, int T, float* w
           if (i == 0 && j == 0 && l == nd - 1 && nk == 1) ITTS_TRY(tap("bv_amp0", xs, adt, (int64_t)nel, s));
         }
       }
+      if (lens && i + 1 < c.bv_num_up) K(zero_tail_rows(xs, B, Tc, ch, lens, Tc / T, adt, s));  // what the next ups[] reads
       ITTS_TRY(tap(("bv_stage" + std::to_string(i)).c_str(), xs, adt, (int64_t)nel, s));
       x = xs;
     }
     void* t1 = alloc((size_t)B * Tc * ch * es);
-    K(snake_aa(t1, x, bv.post_alpha, bv.post_beta, bv.filter, bv.filter, B, Tc, ch, adt, s));
+    if (lens)
+      K(snake_aa_len(t1, x, bv.post_alpha, bv.post_beta, bv.filter, bv.filter, B, Tc, ch, lens, Tc / T, adt, s));
+    else
+      K(snake_aa(t1, x, bv.post_alpha, bv.post_beta, bv.filter, bv.filter, B, Tc, ch, adt, s));
     {
       GemmArgs g = conv_args(t1, ch, bv.conv_post, wav, 1, B * Tc, Tc);
       g.pad_left = 3;
       g.act = ACT_TANH;
       ITTS_TRY(conv(g, adt, bv.conv_post.dt, F32, s));
     }
+    if (lens) K(zero_tail_rows(wav, B, Tc, 1, lens, Tc / T, F32, s));
     return OK;
   };
   return two_pass(body, s);

@@ -35,6 +35,9 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `retire_rows=r` (not in the reference; a ratio in (0, 1], None: ITTS_RETIRE_ROWS, else off) lets the batched generations
     of `infer_fast` / `infer_batch` retire their finished rows: whenever the unfinished rows are <= r * the running rows (and more
     than 6 rows run), the decode state is compacted and the following steps run at the smaller row count (Engine.generate).
+  * `ragged_vocoder=True` (not in the reference; default off; ITTS_RAGGED_VOCODER=1 / 0 overrides it in both directions) lets the
+    sentences of `infer_batch` share vocoder passes although their lengths differ (Engine.bigvgan_grouped(ragged=True)); without
+    it only sentences of equal length do.  `infer` / `infer_fast` are not affected.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -59,7 +62,7 @@ from indextts.utils.front import TextNormalizer, TextTokenizer
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
-                 wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False):
+                 wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -87,6 +90,7 @@ class IndexTTS:
         # the same choice for several beams (beam_sample with top_k = 0 / None or > 128): None: ITTS_WIDE_BEAM_SAMPLER, else "host"
         self.wide_beam_sampler = wide_beam_sampler
         self.retire_rows = retire_rows  # row retirement of the batched generations (Engine.generate); None: ITTS_RETIRE_ROWS, else off
+        self.ragged_vocoder = bool(ragged_vocoder)  # infer_batch: sentences of unequal length share vocoder passes (ITTS_RAGGED_VOCODER overrides)
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
         if self.kv_fp8 and not self.is_fp16:
             raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
@@ -306,7 +310,9 @@ class IndexTTS:
                     code_rows[i] = r
                 lats = self._clean_and_latents(cond, [f[2] for f in flat], code_rows, g["max_mel_tokens"])
                 wav_parts = {u: [] for u in us}
-                for (u, k, _), wav in zip(flat, self.engine.bigvgan_grouped(lats, spk)):  # equal lengths share a launch
+                ragged = {"1": True, "0": False}.get(os.environ.get("ITTS_RAGGED_VOCODER", ""), self.ragged_vocoder)
+                # equal lengths share a launch sequence; with ragged, unequal ones too
+                for (u, k, _), wav in zip(flat, self.engine.bigvgan_grouped(lats, spk, ragged=ragged)):
                     wav_parts[u].append(self._to_int16_range(wav))
                 for u in us:
                     if wav_parts[u]:

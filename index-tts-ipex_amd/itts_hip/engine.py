@@ -609,15 +609,61 @@ class Engine:
         self._exit()
         return codes.astype(np.int64)
 
-    def bigvgan_grouped(self, lats: List[torch.Tensor], spk: torch.Tensor) -> List[torch.Tensor]:
+    def bigvgan_ragged(self, lats: List[torch.Tensor], spk: torch.Tensor) -> List[torch.Tensor]:
+        """One vocoder pass over latents [1, T_i, D] of unequal length (itts_bigvgan_ragged): they are packed into a zero-padded
+        [B, Tmax, D] batch with their lengths beside it; every tensor a convolution reads is kept zero behind a row's own end
+        and every Activation1d ends its signal there, so each row is the waveform of its latent run alone.  spk [E], [1, E]
+        (shared) or [B, E].  -> wavs fp32 [1, 1, T_i * up], in the order of lats."""
+        B = len(lats)
+        lens = np.asarray([int(l.shape[1]) for l in lats], dtype=np.int32)
+        T = int(lens.max())
+        D = int(lats[0].shape[2])
+        lat = torch.zeros(B, T, D, dtype=self.tdt, device=self.device)
+        for b, l in enumerate(lats):
+            lat[b, :int(lens[b])] = l[0].to(device=self.device, dtype=self.tdt)
+        spk = spk.to(device=self.device, dtype=torch.float32).reshape(-1, spk.shape[-1])
+        spk = (spk.expand(B, -1) if spk.shape[0] == 1 else spk).contiguous()
+        assert spk.shape[0] == B, (spk.shape, B)
+        out = torch.empty(B, 1, T * self.up_total, dtype=torch.float32, device=self.device)
+        self._enter()
+        self._join_side()
+        self._ck(self.lib.itts_bigvgan_ragged(self.h, lat.data_ptr(), spk.data_ptr(), B, T, lens.ctypes.data_as(C.c_void_p),
+                                              out.data_ptr(), self._s()), "bigvgan_ragged")
+        self._exit()
+        lat.record_stream(self.stream)
+        spk.record_stream(self.stream)
+        return [out[b:b + 1, :, :int(lens[b]) * self.up_total] for b in range(B)]
+
+    def bigvgan_grouped(self, lats: List[torch.Tensor], spk: torch.Tensor, ragged: bool = False,
+                        max_pad: float = 0.1) -> List[torch.Tensor]:
         """Vocoder over several sentences: latents [1, T_i, D] of EQUAL length share one batched launch sequence (rows of
         a batch are independent, so each result equals its batch-1 run); ragged lengths cannot be padded - the convs
-        would see conv_pre(0) = bias instead of zero "same" padding - and go in groups of their own."""
+        would see conv_pre(0) = bias instead of zero "same" padding - and go in groups of their own.
+        ragged=True (opt-in): rows of unequal length share a pass too (bigvgan_ragged, which masks what plain padding gets
+        wrong), grouped by infer_core.ragged_groups so that at most max_pad of a batch's frames are padding; a group of one or
+        of equal lengths runs as above.  Same shapes in the same order either way.  max_pad = 0.1 is the best of the three
+        values tools/bench_ragged_vocoder.py measured (64 latents of 275 .. 544 frames, bf16, profiles/ragged_vocoder.txt: 1.81 x
+        the 64 batch-1 runs at 0.1, 1.64 x at 0.25, 1.65 x at 0.5 - more padding is more frames computed)."""
+        cap = max(1, int(self.ccfg.max_batch))
+        if ragged:
+            from . import infer_core
+
+            res: List[Optional[torch.Tensor]] = [None] * len(lats)
+            lens = [int(l.shape[1]) for l in lats]
+            for sel in infer_core.ragged_groups(lens, max_pad, cap):
+                sub = [lats[i] for i in sel]
+                if len({lens[i] for i in sel}) == 1:
+                    wav = self.bigvgan(torch.cat(sub, 0), spk.view(1, -1).expand(len(sel), -1).contiguous())
+                    wavs = [wav[j:j + 1] for j in range(len(sel))]
+                else:
+                    wavs = self.bigvgan_ragged(sub, spk.view(1, -1))
+                for i, w in zip(sel, wavs):
+                    res[i] = w
+            return res
         groups: Dict[int, List[int]] = {}
         for i, l in enumerate(lats):
             groups.setdefault(int(l.shape[1]), []).append(i)
         out: List[Optional[torch.Tensor]] = [None] * len(lats)
-        cap = max(1, int(self.ccfg.max_batch))
         for T, idx in groups.items():
             for lo in range(0, len(idx), cap):
                 sel = idx[lo:lo + cap]

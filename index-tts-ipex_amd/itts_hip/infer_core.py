@@ -73,6 +73,31 @@ def pad_tokens_cat(tokens: Sequence[np.ndarray], stop_text_token: int) -> np.nda
     return out
 
 
+def ragged_groups(lengths: Sequence[int], max_pad: float, cap: int) -> List[List[int]]:
+    """Vocoder batches over latents of unequal length (Engine.bigvgan_grouped(ragged=True)): indices sorted by length, longest
+    first (ties: lower index first); a group opens with the longest remaining row and takes the following rows while the share of
+    padded frames of the [n, Tmax] batch, 1 - sum(len) / (n * Tmax), stays <= max_pad and n <= cap.  Rows only get shorter, so the
+    first row that does not fit closes the group.  max_pad = 0: groups of equal length, at most cap rows each."""
+    if cap < 1 or not 0.0 <= max_pad < 1.0:
+        raise ValueError(f"ragged_groups: cap >= 1 and 0 <= max_pad < 1 expected, not cap={cap!r}, max_pad={max_pad!r}")
+    order = sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i))
+    groups: List[List[int]] = []
+    tmax = total = 0
+    for i in order:
+        n = int(lengths[i])
+        if n < 1:
+            raise ValueError(f"ragged_groups: length {n} of row {i}")
+        g = groups[-1] if groups else None
+        # (integers: padded = cells - frames <= max_pad * cells, compared without a division)
+        if g is not None and len(g) < cap and (len(g) + 1) * tmax - (total + n) <= max_pad * (len(g) + 1) * tmax:
+            g.append(i)
+            total += n
+        else:
+            groups.append([i])
+            tmax, total = n, n
+    return groups
+
+
 def sampling_kwargs(do_sample, num_beams, top_k, top_p, temperature, typical_sampling=False, typical_mass=0.9,
                     length_penalty=0.0) -> dict:
     """HF `generate` kwargs (infer.py:116-124) -> Engine.generate keywords; every mode runs on the device:

@@ -107,6 +107,9 @@ _PROTOS = {
     "itts_gemm_which": (i32, [C.POINTER(GemmArgs)]),
     "itts_act_conv": (i32, [C.POINTER(GemmArgs), vp, vp, vp, vp]),
     "itts_act_conv_supported": (i32, [C.POINTER(GemmArgs)]),
+    "itts_snake_aa_fwd_len": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]),
+    "itts_act_conv_len": (i32, [C.POINTER(GemmArgs), vp, vp, vp, vp, i32, vp]),
+    "itts_zero_tail_rows": (i32, [vp, i32, i32, i32, vp, i32, i32, vp]),
     "itts_gemv_which": (i32, [i32] * 7),
     "itts_gemm_ws": (i32, [C.POINTER(GemmArgs), vp, C.c_size_t, vp]),
     "itts_gemm_ksplit": (i32, [C.POINTER(GemmArgs), C.c_size_t]),
@@ -161,6 +164,7 @@ _PROTOS = {
     "itts_gpt_latent": (i32, [vp, vp, vp, i32, vp, i32, vp, vp]),
     "itts_gpt_latent_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     "itts_bigvgan": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "itts_bigvgan_ragged": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "itts_dvae_decode": (i32, [vp, vp, i32, i32, vp, vp]),
     "itts_dvae_encode": (i32, [vp, vp, i32, i32, vp, vp]),
     "itts_debug_fetch": (i64, [vp, C.c_char_p, vp, i64]),
