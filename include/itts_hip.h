@@ -74,6 +74,19 @@ int itts_gemm(const itts_gemm_args* args, itts_stream stream);
 /* Which kernel family itts_gemm takes for these arguments (no launch): 0 vector ALU, 1 register-staged MFMA, 2 LDS-DMA staged
  * 128-wide tiles, 3 the 256 x 256 eight-phase kernel, 4 the LDS-tiled narrow conv.  Tests and tools/bench_gemm.py use it. */
 int itts_gemm_which(const itts_gemm_args* args);
+/* itts_gemm on ONE kernel family named by the caller, whatever itts_gemm_which would answer: family 0 - 3 as above (family 4 runs
+ * through itts_gemm / itts_act_conv).  The families' own launchers, i.e. the production code path, below the tile counts at which the
+ * selector sends a shape to them - the operator tests (tests/test_gpu_gemm_family.py) run every kernel at the smallest shapes that
+ * reach its paths.  variant: 0 = whatever that family's launcher picks; family 1 only: tile | depth << 4 | nbuf << 8 with tile
+ * 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 128x32, depth 1 / 2 / 4 chunk pairs in flight, nbuf 1 / 2 LDS buffers (tiles 1 - 3 need
+ * N >= 64).  ksplit: 1 = none; > 1, family 3 only: that many K splits into ws (16-byte aligned, ws_bytes >= ksplit * M * N * 4,
+ * nphase == 1, (ksplit - 1) * ceil(nk / ksplit) < nk for nk = taps * Cin / 64 K-tiles).  Never falls back to another family:
+ * whatever the family's launcher would refuse is refused here with ITTS_E_INVALID and a message before any HIP call - null args or
+ * pointers, an unknown family or variant, dtype, lda / ldc, M % T, force_simple on a family other than 0, and every shape outside the
+ * family's structural rule (1: Cin % 8, M >= 16; 2: Cin % 64, in_up == 1, nphase == 1, N >= 64, M >= 256; 3: Cin % 64, in_up == 1,
+ * N >= 192, N % 64, taps * Cin >= 256).  itts_gemm_family_supported: 1 / 0, no launch (the workspace by its size alone). */
+int itts_gemm_family(const itts_gemm_args* args, int family, int variant, int ksplit, void* ws, size_t ws_bytes, itts_stream stream);
+int itts_gemm_family_supported(const itts_gemm_args* args, int family, int variant, int ksplit, size_t ws_bytes);
 /* conv (itts_gemm semantics) whose input A is Activation1d(A) applied inside the kernel (conv_lds.hip ACT): the anti-aliased
  * SnakeBeta of itts_snake_aa_fwd (log_alpha / log_beta fp32 [Cin], filt12 the 12-tap filter, up = down) runs while the input tile
  * is staged, and the convolution sees exactly the 16-bit values itts_snake_aa_fwd (layout 1) would have written - the a -> conv of

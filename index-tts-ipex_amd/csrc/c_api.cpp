@@ -87,6 +87,39 @@ int itts_gemm_which(const itts_gemm_args* a) {
   return a->force_simple ? 0 : gemm_which(g, a->dtype_a, a->dtype_w, a->dtype_c);
 }
 
+// Why itts_gemm_family cannot run a call (null = it can): the entry's own questions, then the family's rule (gemm_family_refusal).
+// have_ws: the launch (its workspace pointer is judged) or itts_gemm_family_supported (only ws_bytes is known).
+static const char* gemm_family_entry_refusal(const itts_gemm_args* a, int family, int variant, int ksplit, const void* ws, bool have_ws,
+                                             size_t ws_bytes, GemmArgs& g) {
+  static const float dummy_ws[4] __attribute__((aligned(16))) = {0.f, 0.f, 0.f, 0.f};  // stands for a workspace the rule only asks the presence of
+  if (!a) return "null args";
+  if (a->force_simple && family != 0) return "force_simple: that is family 0";
+  to_gemm_args(a, g);
+  if (ksplit > 1 && family == 3) {
+    if (have_ws && !ws) return "ksplit: a K split needs a workspace";
+    if (have_ws && ((uintptr_t)ws & 15)) return "ksplit: the workspace must be 16-byte aligned";
+    if (a->M >= 1 && a->N >= 1 && ws_bytes < (size_t)ksplit * a->M * a->N * 4) return "ksplit: the workspace is shorter than ksplit * M * N * 4 bytes";
+    g.ws = have_ws ? (float*)ws : const_cast<float*>(dummy_ws);
+  }
+  g.ksplit = ksplit;
+  return gemm_family_refusal(g, a->dtype_a, a->dtype_w, a->dtype_c, family, variant);
+}
+
+int itts_gemm_family(const itts_gemm_args* a, int family, int variant, int ksplit, void* ws, size_t ws_bytes, itts_stream stream) {
+  GemmArgs g;
+  if (const char* why = gemm_family_entry_refusal(a, family, variant, ksplit, ws, true, ws_bytes, g)) {  // before any HIP call
+    set_error(std::string("itts_gemm_family: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  return gemm_family(g, a->dtype_a, a->dtype_w, a->dtype_c, family, variant, (hipStream_t)stream);
+}
+
+int itts_gemm_family_supported(const itts_gemm_args* a, int family, int variant, int ksplit, size_t ws_bytes) {
+  GemmArgs g;
+  return gemm_family_entry_refusal(a, family, variant, ksplit, nullptr, false, ws_bytes, g) ? 0 : 1;
+}
+
 // Why itts_act_conv cannot run a call FUSED (null = it can).  The early answers only name the reason; the decision is gemm_act_fused.
 static const char* act_conv_refusal(const itts_gemm_args* a, const float* log_alpha, const float* log_beta, const float* filt12) {
   if (!a) return "null args";

@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmArgs g, int tiles
   const int wm = wave >> 1, wn = wave & 1;
   const int wgid = xcd_remap(blockIdx.x, gridDim.x);
   const int per_phase = tiles_m * tiles_n;
+  // (gemm_glds_can_run keeps nphase == 1, so phase is 0 on every launch there is: the polyphase arithmetic below has never run)
   const int phase = wgid / per_phase, rem = wgid - phase * per_phase;
   const int tm = rem / tiles_n, tn = rem - tm * tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -189,18 +190,23 @@ int launch(const GemmArgs& g, hipStream_t s) {
 
 }  // namespace
 
+// What the kernel needs to run a shape at all (the launcher's own condition; itts_gemm_family runs it on nothing more): 64-channel
+// stages, no upsampled source rows, one phase, at least one 64-wide column tile and two row tiles.
+bool gemm_glds_can_run(const GemmArgs& g, int ta, int tw, int tc) {
+  if (!gemm_operands_ok(g, ta, tw, tc)) return false;
+  if (g.Cin % 64 != 0 || g.in_up != 1 || g.nphase != 1) return false;
+  return g.N >= 64 && g.M >= 256;
+}
+
 // Shapes this kernel takes from gemm_mfma, from the A/B of tools/bench_gemm.py (profiles/r02_gemm_ab_*.txt): with two
 // stages per workgroup the DMA pipeline is shallower than gemm_mfma's register ring, so it wins where the K loop is
 // long (K = taps * Cin >= 4096: BigVGAN k = 7 / 11 convs at C >= 384, conv_pre; 1.1-1.3x) and on the 64-wide tile
 // (N = 192, BigVGAN stage 3: 1.1-1.5x), and loses on short K (k = 3, the 1280-deep GPT projections) and on the
 // polyphase transposed convs - those stay on the register-staged kernel.
 bool gemm_glds_supported(const GemmArgs& g, int ta, int tw, int tc) {
-  if (!gemm_operands_ok(g, ta, tw, tc)) return false;
-  if (g.Cin % 64 != 0 || g.in_up != 1 || g.nphase < 1 || g.nphase > 8) return false;
-  if (g.N < 64 || g.M < 256) return false;
+  if (!gemm_glds_can_run(g, ta, tw, tc)) return false;
   const int bn = gemm_ragged128(g) ? 64 : 128;
-  const long tiles = (long)((g.M + BM - 1) / BM) * ((g.N + bn - 1) / bn) * g.nphase;
-  if (g.nphase != 1) return false;
+  const long tiles = (long)((g.M + BM - 1) / BM) * ((g.N + bn - 1) / bn);
   // enough tiles to fill the chip twice over on the K-deep or 64-wide shapes; the narrow convolutions (N <= 512: the weight panel
   // stays in L2) already pay from one tile per CU and K >= 1024 (measured: tools/bench_gemm.py --batch 1, profiles/r04_gemm_ab_b1.txt)
   if (tiles >= 384 && (bn == 64 || (long)g.taps * g.Cin >= 4096)) return true;
@@ -209,7 +215,7 @@ bool gemm_glds_supported(const GemmArgs& g, int ta, int tw, int tc) {
 
 int gemm_glds(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
   ITTS_REQUIRE(g.A && g.W && g.C, "gemm_glds: null pointer");
-  ITTS_REQUIRE(gemm_glds_supported(g, ta, tw, tc), "gemm_glds: unsupported shape/dtype");
+  ITTS_REQUIRE(gemm_glds_can_run(g, ta, tw, tc), "gemm_glds: unsupported shape/dtype");  // (whether it is the RIGHT kernel: gemm_which)
   const int T = g.T > 0 ? g.T : g.M;
   ITTS_REQUIRE(g.M % T == 0 && g.lda >= g.Cin && g.ldc >= g.N * g.nphase, "gemm_glds: bad dims");
   const bool bn64 = gemm_ragged128(g);

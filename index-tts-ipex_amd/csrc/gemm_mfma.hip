@@ -216,46 +216,54 @@ static int g_nbuf = 1;  // 1 = single LDS buffer (more workgroups per CU; measur
 
 static int g_depth = 0;  // 0 = per-tile default; ITTS_GEMM_DEPTH=1/2/4 to A/B
 
+// An explicit choice of instantiation (gemm_mfma's internal overload: itts_gemm_family and the operator tests); a zero field leaves
+// that choice to the code below and to the A/B statics above
+struct Pick {
+  int tile = 0, depth = 0, nbuf = 0;  // tile 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 128x32; depth 1 / 2 / 4; nbuf 1 / 2
+};
+
 template <int BM, int BN, typename TC, int DEPTH>
-int launch_d(const GemmArgs& g, hipStream_t s) {
+int launch_d(const GemmArgs& g, hipStream_t s, const Pick& pk) {
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.nphase);
-  if (g_nbuf == 1) hipLaunchKernelGGL((gemm_mfma_kernel<BM, BN, TC, 1, DEPTH>), grid, dim3(256), 0, s, g);
+  if ((pk.nbuf ? pk.nbuf : g_nbuf) == 1) hipLaunchKernelGGL((gemm_mfma_kernel<BM, BN, TC, 1, DEPTH>), grid, dim3(256), 0, s, g);
   else hipLaunchKernelGGL((gemm_mfma_kernel<BM, BN, TC, 2, DEPTH>), grid, dim3(256), 0, s, g);
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;
 }
 
 template <int BM, int BN, typename TC, int DDEF>
-int launch(const GemmArgs& g, hipStream_t s) {
-  const int d = g_depth ? g_depth : DDEF;
-  if (d <= 1) return launch_d<BM, BN, TC, 1>(g, s);
-  if (d == 2) return launch_d<BM, BN, TC, 2>(g, s);
-  return launch_d<BM, BN, TC, 4>(g, s);
+int launch(const GemmArgs& g, hipStream_t s, const Pick& pk) {
+  const int d = pk.depth ? pk.depth : g_depth ? g_depth : DDEF;
+  if (d <= 1) return launch_d<BM, BN, TC, 1>(g, s, pk);
+  if (d == 2) return launch_d<BM, BN, TC, 2>(g, s, pk);
+  return launch_d<BM, BN, TC, 4>(g, s, pk);
 }
 
 template <typename TC>
-int dispatch(const GemmArgs& g, hipStream_t s) {
+int dispatch(const GemmArgs& g, hipStream_t s, const Pick& pk) {
   // tile choice: the K loop of one workgroup is latency-bound (register-staged), so what matters first is having several
   // workgroups per CU (256 CUs); among shapes that do, prefer the larger tile (fewer LDS bytes per MFMA).  Small tiles
   // carry a deeper register ring (their stages are cheap: 16 VGPRs per pair at 64x64).
   auto tiles = [&](int bm, int bn) { return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * g.nphase; };
   // ring depth: deep where a CU holds 1-2 workgroups (nothing else hides the refill latency), 1 where there are many
   // tiles per CU (the extra registers would cost more occupancy than the ring buys)
-  static const int force = [] {  // ITTS_GEMM_TILE=1 (128x128) / 2 (128x64) / 3 (64x64): experiments only
+  static const int env_force = [] {  // ITTS_GEMM_TILE=1 (128x128) / 2 (128x64) / 3 (64x64): experiments only
     const char* e = getenv("ITTS_GEMM_TILE");
     return e ? atoi(e) : 0;
   }();
-  if (force == 1 && g.N >= 64) return launch<128, 128, TC, 2>(g, s);
-  if (force == 2 && g.N >= 64) return launch<128, 64, TC, 2>(g, s);
-  if (force == 3 && g.N >= 64) return launch<64, 64, TC, 4>(g, s);
-  if (g.N <= 32) return launch<128, 32, TC, 1>(g, s);
+  const int force = pk.tile ? pk.tile : env_force;
+  if (force == 1 && g.N >= 64) return launch<128, 128, TC, 2>(g, s, pk);
+  if (force == 2 && g.N >= 64) return launch<128, 64, TC, 2>(g, s, pk);
+  if (force == 3 && g.N >= 64) return launch<64, 64, TC, 4>(g, s, pk);
+  if (pk.tile == 4) return launch<128, 32, TC, 1>(g, s, pk);  // (by override only: gemm_mfma_variant_ok has judged it)
+  if (g.N <= 32) return launch<128, 32, TC, 1>(g, s, pk);
   if (g.N >= 128 && tiles(128, 128) >= 768 && !gemm_ragged128(g))
-    return tiles(128, 128) >= 1536 ? launch<128, 128, TC, 1>(g, s) : launch<128, 128, TC, 2>(g, s);
+    return tiles(128, 128) >= 1536 ? launch<128, 128, TC, 1>(g, s, pk) : launch<128, 128, TC, 2>(g, s, pk);
   if (tiles(128, 64) >= 512 || g.M <= 64) {
-    if (g.M <= 64) return launch<64, 64, TC, 4>(g, s);
-    return tiles(128, 64) >= 768 ? launch<128, 64, TC, 1>(g, s) : launch<128, 64, TC, 2>(g, s);
+    if (g.M <= 64) return launch<64, 64, TC, 4>(g, s, pk);
+    return tiles(128, 64) >= 768 ? launch<128, 64, TC, 1>(g, s, pk) : launch<128, 64, TC, 2>(g, s, pk);
   }
-  return launch<64, 64, TC, 4>(g, s);
+  return launch<64, 64, TC, 4>(g, s, pk);
 }
 
 }  // namespace
@@ -266,7 +274,16 @@ bool gemm_mfma_supported(const GemmArgs& g, int ta, int tw, int tc) {
   return true;
 }
 
-int gemm_mfma(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
+// variant = tile | depth << 4 | nbuf << 8 with every field given, or 0 = what dispatch() picks.  A forced 128x128, 128x64 or 64x64
+// tile keeps dispatch()'s own N >= 64 condition: below it the override would fall through to another tile.
+bool gemm_mfma_variant_ok(const GemmArgs& g, int variant) {
+  if (variant == 0) return true;
+  const int tile = variant & 15, depth = (variant >> 4) & 15, nbuf = variant >> 8;
+  if (variant < 0 || tile < 1 || tile > 4 || (depth != 1 && depth != 2 && depth != 4) || (nbuf != 1 && nbuf != 2)) return false;
+  return tile == 4 || g.N >= 64;
+}
+
+int gemm_mfma(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, int variant) {
   static const bool once = [] {
     const char* e = getenv("ITTS_GEMM_NBUF");
     if (e) g_nbuf = atoi(e) == 2 ? 2 : 1;
@@ -281,7 +298,12 @@ int gemm_mfma(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
   ITTS_REQUIRE(g.lda >= g.Cin && g.ldc >= g.N * g.nphase, "gemm_mfma: bad leading dims");
   const int T = g.T > 0 ? g.T : g.M;
   ITTS_REQUIRE(g.M % T == 0 && T % g.in_up == 0, "gemm_mfma: M must be a multiple of T");
-  return tc == BF16 ? dispatch<bf16_t>(g, s) : dispatch<float>(g, s);
+  ITTS_REQUIRE(gemm_mfma_variant_ok(g, variant), "gemm_mfma: unknown variant, or a 128x128 / 128x64 / 64x64 tile forced on N < 64");
+  Pick pk;
+  if (variant) pk.tile = variant & 15, pk.depth = (variant >> 4) & 15, pk.nbuf = variant >> 8;
+  return tc == BF16 ? dispatch<bf16_t>(g, s, pk) : dispatch<float>(g, s, pk);
 }
+
+int gemm_mfma(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) { return gemm_mfma(g, ta, tw, tc, s, 0); }
 
 }  // namespace itts

@@ -26,7 +26,7 @@
 // Conv addressing, zero page for padded rows and XCD-aware tile order as gemm_glds.hip; the polyphase transposed convs (nphase > 1)
 // run as extra column tiles with their own tap shift and weight slab.
 // Two geometries, same per-wave work (128 x 64 outputs): 2 x 4 waves = 256 x 256 tile (N a multiple of 256) and 4 x 2 waves =
-// 512 x 128 tile (N a multiple of 128 only: 384-wide convs would leave a quarter of a 256-wide column tile empty); the second one
+// 512 x 128 tile (every other N the gate admits, N % 64 == 0: 384-wide convs would leave a quarter of a 256-wide column tile empty); the second one
 // stages 80 KB per K-tile (4 + 4 + 1 + 1 DMA instructions per thread) and fills the 160 KB of LDS exactly.
 #include <cstdlib>
 
@@ -408,8 +408,9 @@ int launch_p8(const GemmArgs& g, hipStream_t s) {
 
 }  // namespace
 
-// Large regular shapes only: >= 4 K-tiles, enough tiles to fill the 256 CUs at least once and a half; N a multiple of 256 takes the
-// 256 x 256 tile, a multiple of 128 the 512 x 128 tile.
+// Large regular shapes only: >= 4 K-tiles; WHEN they are large enough is the selector's business.  N a multiple of 256 takes the
+// 256 x 256 tile, every other admitted N (a multiple of 64 from 192 up) the 512 x 128 tile: where N % 128 == 64 (N = 192, 320) the
+// last column tile is half empty - its second wave column clamps its W rows and stores nothing.
 static bool p8_wide(const GemmArgs& g) { return g.N % 256 == 0; }
 // Number of tiles the launch would have, 0 where the kernel cannot run the shape at all.  WHEN it is the right kernel is the
 // selector's business (gemm_select.cpp gemm_which): >= 200 tiles always; 64..199 where the 128-wide LDS-DMA kernel has no better claim.
@@ -421,14 +422,19 @@ long gemm_p8_tiles(const GemmArgs& g, int ta, int tw, int tc) {
   return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * g.nphase;
 }
 
+// g.ksplit / g.ws as the kernel can run them: no split, or a 16-byte aligned workspace, one phase, and split ksplit - 1 still starts
+// inside the K range (kper = ceil(nk / ksplit) K-tiles per split)
+bool gemm_p8_ksplit_ok(const GemmArgs& g) {
+  return g.ksplit >= 1 && (g.ksplit == 1 || (g.ws && g.nphase == 1 && !((uintptr_t)g.ws & 15) &&
+                                            (long)(g.ksplit - 1) * ((g.taps * (g.Cin / PBK) + g.ksplit - 1) / g.ksplit) < (long)g.taps * (g.Cin / PBK)));
+}
+
 int gemm_p8(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
   ITTS_REQUIRE(g.A && g.W && g.C, "gemm_p8: null pointer");
   ITTS_REQUIRE(gemm_p8_tiles(g, ta, tw, tc) > 0, "gemm_p8: unsupported shape/dtype");  // (whether it is the RIGHT kernel: gemm_which)
   const int T = g.T > 0 ? g.T : g.M;
   ITTS_REQUIRE(g.M % T == 0 && g.lda >= g.Cin && g.ldc >= g.N * g.nphase, "gemm_p8: bad dims");
-  ITTS_REQUIRE(g.ksplit >= 1 && (g.ksplit == 1 || (g.ws && g.nphase == 1 && !((uintptr_t)g.ws & 15) &&
-                                                  (long)(g.ksplit - 1) * ((g.taps * (g.Cin / PBK) + g.ksplit - 1) / g.ksplit) < (long)g.taps * (g.Cin / PBK))),
-               "gemm_p8: K split needs a workspace, one phase and a K-tile for every split");
+  ITTS_REQUIRE(gemm_p8_ksplit_ok(g), "gemm_p8: K split needs a workspace, one phase and a K-tile for every split");
   if (p8_wide(g)) return tc == BF16 ? launch_p8<2, 4, bf16_t>(g, s) : launch_p8<2, 4, float>(g, s);
   return tc == BF16 ? launch_p8<4, 2, bf16_t>(g, s) : launch_p8<4, 2, float>(g, s);
 }

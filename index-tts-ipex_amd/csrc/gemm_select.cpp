@@ -2,6 +2,7 @@
 // of the few-tile deep-K shapes (gemm_ksplit_plan).  Pure host code: no HIP call before the launch itself.
 #include <algorithm>
 #include <cstdlib>
+#include <string>
 
 #include "itts_kernels.h"
 
@@ -88,6 +89,49 @@ int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* le
     case 3: return gemm_p8(g, ta, tw, tc, s);
     case 2: return gemm_glds(g, ta, tw, tc, s);
     case 1: return gemm_mfma(g, ta, tw, tc, s);
+    default: return gemm_simple(g, ta, tw, tc, s);
+  }
+}
+
+// ---- one family by name (itts_gemm_family: the operator tests run each kernel at the smallest shapes that reach its paths, far below
+//      the performance gates of gemm_which).  The refusal repeats, in words, every condition of that family's launcher, so that the
+//      entry answers on the host before any HIP call; the launchers keep their own ITTS_REQUIREs behind it. ----
+const char* gemm_family_refusal(const GemmArgs& g, int ta, int tw, int tc, int family, int variant) {
+  if (!g.A || !g.W || !g.C) return "null pointer";
+  if (g.pre_alpha || g.pre_beta || g.pre_filt) return "pre_alpha / pre_beta / pre_filt: only family 4 (itts_act_conv) has the fused activation";
+  if (family < 0 || family > 3) return "unknown family (0 vector ALU, 1 gemm_mfma, 2 gemm_glds, 3 gemm_p8; family 4 runs through itts_gemm / itts_act_conv)";
+  if (variant != 0 && family != 1) return "unknown variant: only family 1 has variants";
+  if (g.ksplit < 1) return "ksplit < 1";
+  if (g.ksplit > 1 && family != 3) return "ksplit > 1: only family 3 splits K";
+  if (g.M < 1 || g.N < 1 || g.Cin < 1 || g.taps < 1) return "bad dims: M, N, Cin and taps must be >= 1";
+  if (g.nphase < 1 || g.nphase > 8 || g.in_up < 1) return "bad phase/upsample: 1 <= nphase <= 8, in_up >= 1";
+  if (g.lda < g.Cin || (long)g.ldc < (long)g.N * g.nphase) return "bad leading dims: lda >= Cin and ldc >= N * nphase";
+  const int T = g.T > 0 ? g.T : g.M;
+  if (g.M % T != 0 || T % g.in_up != 0) return "M must be a multiple of T (and T of in_up)";
+  if (family == 0) {
+    const bool combo = (ta == F32 && (tw == F32 || tw == BF16)) || (ta == BF16 && tw == BF16);  // gemm_simple's six instantiations
+    return combo && (tc == F32 || tc == BF16) ? nullptr : "dtype: not a combination the vector-ALU kernel is built for";
+  }
+  if (ta != BF16 || tw != BF16 || (tc != BF16 && tc != F32)) return "dtype: A and W must be the 16-bit type of the library, C that or fp32";
+  if (!gemm_operands_ok(g, ta, tw, tc)) return "operands: lda % 8 == 0, A and W 16-byte aligned";
+  if (family == 1) {
+    if (!gemm_mfma_supported(g, ta, tw, tc)) return "shape: gemm_mfma needs Cin % 8 == 0 and M >= 16";
+    if (!gemm_mfma_variant_ok(g, variant)) return "unknown variant: tile 1 - 4 | depth 1, 2 or 4 << 4 | nbuf 1 or 2 << 8; tiles 1 - 3 need N >= 64";
+    return nullptr;
+  }
+  if (family == 2) return gemm_glds_can_run(g, ta, tw, tc) ? nullptr : "shape: gemm_glds needs Cin % 64 == 0, in_up == 1, nphase == 1, N >= 64 and M >= 256";
+  if (gemm_p8_tiles(g, ta, tw, tc) <= 0) return "shape: gemm_p8 needs Cin % 64 == 0, in_up == 1, N >= 192, N % 64 == 0 and taps * Cin >= 256";
+  if (!gemm_p8_ksplit_ok(g)) return "ksplit: a K split needs a 16-byte aligned workspace, one phase and a K-tile for every split";
+  return nullptr;
+}
+
+int gemm_family(const GemmArgs& g, int ta, int tw, int tc, int family, int variant, hipStream_t s) {
+  const char* why = gemm_family_refusal(g, ta, tw, tc, family, variant);
+  ITTS_REQUIRE(!why, (std::string("gemm_family: ") + why).c_str());
+  switch (family) {
+    case 3: return gemm_p8(g, ta, tw, tc, s);
+    case 2: return gemm_glds(g, ta, tw, tc, s);
+    case 1: return gemm_mfma(g, ta, tw, tc, s, variant);
     default: return gemm_simple(g, ta, tw, tc, s);
   }
 }

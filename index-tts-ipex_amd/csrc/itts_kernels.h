@@ -12,10 +12,16 @@ bool gemm_operands_ok(const GemmArgs& g, int ta, int tw, int tc);  // the operan
 bool gemm_ragged128(const GemmArgs& g);                             // N = 192-like shapes: 64-wide column tiles instead of 128-wide
 bool gemm_mfma_supported(const GemmArgs& g, int ta, int tw, int tc);
 int gemm_mfma(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
-bool gemm_glds_supported(const GemmArgs& g, int ta, int tw, int tc);  // LDS-DMA staged 128 x 128 / 128 x 64 tiles (gemm_glds.hip)
+// ... with the instantiation named: variant = tile | depth << 4 | nbuf << 8 (tile 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 128x32; depth 1 / 2 / 4;
+// nbuf 1 / 2), 0 = the launcher's own pick.  Tiles 1 - 3 need N >= 64.  For gemm_family and the operator tests; production passes 0.
+bool gemm_mfma_variant_ok(const GemmArgs& g, int variant);
+int gemm_mfma(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, int variant);
+bool gemm_glds_can_run(const GemmArgs& g, int ta, int tw, int tc);    // what gemm_glds needs of a shape (structural) ...
+bool gemm_glds_supported(const GemmArgs& g, int ta, int tw, int tc);  // ... and where it pays: LDS-DMA staged 128 x 128 / 128 x 64 tiles (gemm_glds.hip)
 int gemm_glds(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
 long gemm_p8_tiles(const GemmArgs& g, int ta, int tw, int tc);      // 0 = cannot run the shape
 int gemm_p8(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);  // 256 x 256 tile, 8-phase LDS-DMA pipeline (gemm_p8.hip)
+bool gemm_p8_ksplit_ok(const GemmArgs& g);                          // g.ksplit / g.ws as gemm_p8 can run them (1 = no split)
 int gemm_ksplit_plan(const GemmArgs& g, int ta, int tw, int tc, size_t ws_bytes);  // K split of the few-tile deep-K shapes; 1 = none
 bool conv_lds_supported(const GemmArgs& g, int ta, int tw, int tc);
 bool conv_lds_act_supported(const GemmArgs& g, int ta, int tw, int tc);  // ... with Activation1d fused into the tile load (g.pre_*)
@@ -24,6 +30,10 @@ bool conv_lds_act_supported(const GemmArgs& g, int ta, int tw, int tc);  // ... 
 int conv_lds(const GemmArgs& g, hipStream_t s, const int* lens = nullptr, int mul = 1);
 int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* lens = nullptr, int mul = 1);  // dispatcher
 int gemm_which(const GemmArgs& g, int ta, int tw, int tc);           // the kernel family the dispatcher takes: 0 VALU, 1 mfma, 2 glds, 3 p8, 4 conv_lds
+// One family (0 - 3) by name, whatever the selector would take: why it cannot run the call (null = it can; no HIP call), and the
+// launch.  g.ksplit / g.ws as the caller set them (family 3 only).  Never another family.  itts_gemm_family, the operator tests.
+const char* gemm_family_refusal(const GemmArgs& g, int ta, int tw, int tc, int family, int variant);
+int gemm_family(const GemmArgs& g, int ta, int tw, int tc, int family, int variant, hipStream_t s);
 bool gemm_act_fused(const GemmArgs& g, int ta, int tw, int tc);      // a call with g.pre_* runs Activation1d inside the conv: family 4 and conv_lds_act_supported
 
 // ---- anti-aliased SnakeBeta (snake.hip); x,y [B,T,C] ----

@@ -105,6 +105,8 @@ _PROTOS = {
     "itts_snake_aa_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "itts_gemm": (i32, [C.POINTER(GemmArgs), vp]),
     "itts_gemm_which": (i32, [C.POINTER(GemmArgs)]),
+    "itts_gemm_family": (i32, [C.POINTER(GemmArgs), i32, i32, i32, vp, C.c_size_t, vp]),
+    "itts_gemm_family_supported": (i32, [C.POINTER(GemmArgs), i32, i32, i32, C.c_size_t]),
     "itts_act_conv": (i32, [C.POINTER(GemmArgs), vp, vp, vp, vp]),
     "itts_act_conv_supported": (i32, [C.POINTER(GemmArgs)]),
     "itts_snake_aa_fwd_len": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]),

@@ -593,6 +593,9 @@ def test_gemm_full_epilogue_chain(lib, case, out_f32, acts):
 
 
 def test_gemm_glds_transposed_conv(lib):
+    """A transposed conv of the size the LDS-DMA kernels were written for.  Despite its name it runs gemm_p8: gemm_glds keeps
+    nphase == 1 (gemm_glds_can_run), and the selector table (tests/test_gemm_selector.py, convT(2, 4096, 768, 384, 8, 4)) pins
+    family 3 for this shape - asserted below."""
     B, T, Cin, Cout, k, u = 2, 4096, 768, 384, 8, 4
     p = (k - u) // 2
     x = rnd("glt.x", (B, Cin, T)).to(torch.bfloat16)
@@ -604,6 +607,7 @@ def test_gemm_glds_transposed_conv(lib):
     out = run_gemm(lib, A, W, (B, T * u, Cout), L.BF16, L.BF16, L.BF16, 0, M=B * T, N=Cout, Cin=Cin, taps=k // u, lda=Cin,
                    ldc=u * Cout, T=T, dil=-1, pad_left=0, nphase=u, phase_shift=[(ph + p) // u for ph in range(u)],
                    bias=bias.to(DEV), bias_bstride=Cout)
+    assert run_gemm.which == 3
     assert relerr(out.float().transpose(1, 2), ref) < 2e-2
 
 
