@@ -134,6 +134,20 @@ int itts_layernorm(void* y, int dtype_y, const void* x, int dtype_x, const float
 int itts_attention(void* o, const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv,
                    int ldq, int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype,
                    itts_stream stream);
+/* itts_attention on ONE kernel named by the caller: kernel 0 = the dispatcher (exactly itts_attention), 1 = attention_simple
+ * (csrc/attention.hip: vector ALU, fp32 or 16-bit, dqk <= 128, dv <= 64), 2 = attention_mfma (csrc/attention_mfma.hip: matrix cores,
+ * 16-bit, dqk 64 or 128, dv 64, Sq >= 16, ldq / ldk / ldv % 8 == 0, q / k / v 16-byte aligned).  The named kernel runs or nothing
+ * does - never the other one.  The operator tests (tests/test_gpu_attention.py) run each kernel at every shape this way.
+ * itts_attention_which: 1 or 2, the kernel the dispatcher takes for the call (ITTS_ATTN_SIMPLE, read once per process, makes it 1),
+ * without a launch; -1 for a call the entries refuse.  All three entries share one host-side check, made before any HIP call, that
+ * answers ITTS_E_INVALID with a message that begins with the entry's name: a null q / k / v / o; B, H, Sq or Sk <= 0; B or H > 65535;
+ * a dtype other than ITTS_F32 / ITTS_BF16 (the library's 16-bit type); dqk outside 1..128 or dv outside 1..64; ldq or ldk < H * dqk,
+ * ldv or ldo < H * dv; a kernel other than 0, 1, 2; and for kernel 2 whatever the matrix-core kernel's rule above rejects. */
+int itts_attention_kernel(void* o, const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv,
+                          int ldq, int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype, int kernel,
+                          itts_stream stream);
+int itts_attention_which(const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv, int ldq,
+                         int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype);
 
 /* Decode-step batched GEMV (GPT2 Conv1D on one token per row, HF GPT2Attention/GPT2MLP):
  * Y[b, n] (+)= act(prologue(X)[b, :] . W[n, :] + bias[n]); X, Y fp32; prologue 0 none, 1 LayerNorm, 2 LN o LN.

@@ -177,10 +177,30 @@ int attention_mfma(const AttnArgs& a, int dt, hipStream_t s) {
   return OK;
 }
 
-int attention(const AttnArgs& a, int dt, hipStream_t s) {
+static bool attn_simple_forced() {
   static const bool no_mfma = getenv("ITTS_ATTN_SIMPLE") != nullptr;
-  if (!no_mfma && attention_mfma_supported(a, dt)) return attention_mfma(a, dt, s);
+  return no_mfma;
+}
+
+int attention_which(const AttnArgs& a, int dt) { return !attn_simple_forced() && attention_mfma_supported(a, dt) ? 2 : 1; }
+
+int attention(const AttnArgs& a, int dt, hipStream_t s) {
+  if (attention_which(a, dt) == 2) return attention_mfma(a, dt, s);
   return attention_simple(a, dt, s);
+}
+
+const char* attention_refusal(const AttnArgs& a, int dt, int kernel) {
+  if (!a.q || !a.k || !a.v || !a.o) return "null pointer (q, k, v, o)";
+  if (a.B <= 0 || a.H <= 0 || a.Sq <= 0 || a.Sk <= 0) return "bad dims (B, H, Sq, Sk >= 1)";
+  if (a.B > 65535 || a.H > 65535) return "B and H are grid dimensions (at most 65535)";
+  if (dt != F32 && dt != BF16) return "dtype must be ITTS_F32 or ITTS_BF16 (the library's 16-bit type)";
+  if (a.dqk < 1 || a.dqk > 128 || a.dv < 1 || a.dv > 64) return "head dims out of range (1 <= dqk <= 128, 1 <= dv <= 64)";
+  if (a.ldq < a.H * a.dqk || a.ldk < a.H * a.dqk || a.ldv < a.H * a.dv || a.ldo < a.H * a.dv)
+    return "bad leading dims (ldq, ldk >= H * dqk; ldv, ldo >= H * dv)";
+  if (kernel < 0 || kernel > 2) return "unknown kernel (0 dispatcher, 1 attention_simple, 2 attention_mfma)";
+  if (kernel == 2 && !attention_mfma_supported(a, dt))
+    return "attention_mfma needs the 16-bit type, dqk 64 or 128, dv 64, Sq >= 16, ldq / ldk / ldv % 8 == 0 and 16-byte aligned q, k, v";
+  return nullptr;
 }
 
 }  // namespace itts

@@ -214,14 +214,48 @@ int itts_layernorm(void* y, int dtype_y, const void* x, int dtype_x, const float
   return layernorm(y, dtype_y, x, dtype_x, gamma, beta, rows, D, D, D, eps, ACT_NONE, (hipStream_t)stream);
 }
 
-int itts_attention(void* o, const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv,
-                   int ldq, int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype,
-                   itts_stream stream) {
-  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+static AttnArgs to_attn_args(void* o, const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv, int ldq,
+                             int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start) {
   AttnArgs a;
   a.q = q; a.k = k; a.v = v; a.o = o; a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.dqk = dqk; a.dv = dv;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale; a.causal = causal; a.kv_start = kv_start;
+  return a;
+}
+
+// itts_attention (kernel 0) and itts_attention_kernel: one host-side check (attention_refusal) before any HIP call, then the
+// dispatcher or the named kernel's own launcher - a named kernel is never replaced by the other one.
+static int attention_entry(const char* entry, void* o, const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk,
+                           int dv, int ldq, int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype, int kernel,
+                           itts_stream stream) {
+  const AttnArgs a = to_attn_args(o, q, k, v, B, H, Sq, Sk, dqk, dv, ldq, ldk, ldv, ldo, scale, causal, kv_start);
+  if (const char* why = attention_refusal(a, dtype, kernel)) {
+    set_error(std::string(entry) + ": " + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  if (kernel == 1) return attention_simple(a, dtype, (hipStream_t)stream);
+  if (kernel == 2) return attention_mfma(a, dtype, (hipStream_t)stream);
   return attention(a, dtype, (hipStream_t)stream);
+}
+
+int itts_attention(void* o, const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv,
+                   int ldq, int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype,
+                   itts_stream stream) {
+  return attention_entry("itts_attention", o, q, k, v, B, H, Sq, Sk, dqk, dv, ldq, ldk, ldv, ldo, scale, causal, kv_start, dtype, 0, stream);
+}
+
+int itts_attention_kernel(void* o, const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv,
+                          int ldq, int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype, int kernel,
+                          itts_stream stream) {
+  return attention_entry("itts_attention_kernel", o, q, k, v, B, H, Sq, Sk, dqk, dv, ldq, ldk, ldv, ldo, scale, causal, kv_start, dtype, kernel,
+                         stream);
+}
+
+int itts_attention_which(const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv, int ldq, int ldk,
+                         int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype) {
+  static const float dummy_o = 0.f;  // a real call has its output; the rule only asks whether it is there
+  const AttnArgs a = to_attn_args(const_cast<float*>(&dummy_o), q, k, v, B, H, Sq, Sk, dqk, dv, ldq, ldk, ldv, ldo, scale, causal, kv_start);
+  return attention_refusal(a, dtype, 0) ? E_INVALID : attention_which(a, dtype);
 }
 
 int itts_gemv(float* Y, const float* X, const void* W, const float* bias, int B, int N, int K, int act, int accumulate,

@@ -96,5 +96,9 @@ int attention_simple(const AttnArgs& a, int dt, hipStream_t s);
 bool attention_mfma_supported(const AttnArgs& a, int dt);
 int attention_mfma(const AttnArgs& a, int dt, hipStream_t s);
 int attention(const AttnArgs& a, int dt, hipStream_t s);  // dispatcher
+// The host-side check of the C ABI entries (itts_attention, itts_attention_kernel, itts_attention_which): why the call cannot run
+// (null = it can), no HIP call.  kernel 0 = the dispatcher, 1 = attention_simple, 2 = attention_mfma (then also its own rule).
+const char* attention_refusal(const AttnArgs& a, int dt, int kernel);
+int attention_which(const AttnArgs& a, int dt);  // 1 / 2: the kernel attention() takes (ITTS_ATTN_SIMPLE honoured), no launch
 
 }  // namespace itts
