@@ -234,17 +234,38 @@ int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_be
  * ((k/32) * ceil(B/16) + b/16) * 512 + ((k%32)/8 * 16 + b%16) * 8 + k%8 (csrc/itts_decode.h tile_off).
  * layout bit 2: W is the fragment-tiled copy made by itts_retile_weights (same bits out, 1.3x faster weight stream).
  * B <= 16 only - bit 3: X is the fp32 residual stream and LayerNorm (eps 1e-5, affine folded into W) runs in the
- * prologue (K <= 1280, ksplit 1); bit 4: 8 features per workgroup (narrow residual projections, ksplit 1). */
+ * prologue (K <= 1280, ksplit 1); bit 4: 8 features per workgroup (narrow residual projections, ksplit 1).
+ * A tiled bf16 Y needs N % 32 == 0 (the tiles are 32 columns wide).  Null X / W (Y unless ksplit > 1; partial when ksplit > 1),
+ * non-positive B / N / K / ksplit and every shape itts_skinny_gemm_supported says 0 for are refused with ITTS_E_INVALID and a
+ * message that begins with the entry's name, before any HIP call. */
 int itts_skinny_gemm(void* Y, int y_bf16, const void* X, const void* W, const float* bias, int B, int N, int K, int act,
                      int accumulate, int ksplit, float* partial, int layout, itts_stream stream);
+
+/* The same projection from fp8 weights (BASELINE config 5): W8 [N, K] OCP e4m3 bytes, wscale fp32 [N] one scale per output
+ * row (y = wscale[n] * (x . W8[n]) + bias[n]); W8t null, or the fragment-tiled copy of W8 made by itts_retile_weights_fp8, which
+ * the kernel then streams instead (W8 still has to be given).  No bf16 weights are read.  layout bits 0, 1, 3, 4 as above; bit 2
+ * is refused (W8t says that the weights are tiled).  W8 and W8t 8-byte aligned. */
+int itts_skinny_gemm_fp8(void* Y, int y_bf16, const void* X, const void* W8, const void* W8t, const float* wscale, const float* bias,
+                         int B, int N, int K, int act, int accumulate, int ksplit, float* partial, int layout, itts_stream stream);
+
+/* Host only, no HIP call: 1 when the two entries above take this shape (fp8 != 0: itts_skinny_gemm_fp8), 0 when they refuse it -
+ * the rule the launcher itself enforces: 1 <= B <= 128, N >= 1, K a positive multiple of 32, 1 <= ksplit <= K / 32, no activation
+ * with ksplit > 1, no accumulate into bf16 Y, bits 3 and 4 at B <= 16 with ksplit 1 and not together, bit 3 at K <= 1280, a tiled
+ * bf16 Y at N % 32 == 0, no layout bit past 4.  Pointer alignment is checked at the launch. */
+int itts_skinny_gemm_supported(int y_bf16, int B, int N, int K, int act, int accumulate, int ksplit, int layout, int fp8);
 
 /* dst[16*ceil(N/16)*K] <- bf16 W[N, K] in MFMA-fragment tiles: element (n, k) at
  * ((n/16) * (K/32) + k/32) * 512 + ((k%32)/8 * 16 + n%16) * 8 + k%8, rows past N zero (csrc/itts_decode.h wtile_off).
  * The engine makes these copies of the GPT projections itself on the first batched generation. */
 int itts_retile_weights(void* dst, const void* src, int N, int K, itts_stream stream);
 
+/* The same order for fp8 weights, one byte per element: dst[16*ceil(N/16)*K] bytes <- W8[N, K]; both 8-byte aligned. */
+int itts_retile_weights_fp8(void* dst, const void* src, int N, int K, itts_stream stream);
+
 /* y (bf16) = LayerNorm(x fp32) [passes == 2: LayerNorm again without affine], GPT-2 ln_1 / ln_2 / ln_f o final_norm.
- * nsplit > 0: first x += partial_bias + sum_s partial[s] (the residual add of a split-K projection), written back. */
+ * nsplit > 0: first x += partial_bias + sum_s partial[s] (the residual add of a split-K projection), written back.
+ * gamma and beta come together or not at all; rows >= 1, 1 <= D <= 2048, passes 1 or 2, nsplit 0 .. 8 (partial[nsplit][rows][D]
+ * with them, partial_bias may be null), tiled y at D % 32 == 0: anything else is refused with ITTS_E_INVALID before any HIP call. */
 int itts_ln_rows_bf16(void* y, float* x, const float* gamma, const float* beta, int rows, int D, float eps, int passes,
                       const float* partial, int nsplit, const float* partial_bias, int y_tiled, itts_stream stream);
 

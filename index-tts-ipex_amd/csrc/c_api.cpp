@@ -396,22 +396,62 @@ int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_be
   return beam_wide_pair(a, w, s);
 }
 
-int itts_skinny_gemm(void* Y, int y_bf16, const void* X, const void* W, const float* bias, int B, int N, int K, int act,
-                     int accumulate, int ksplit, float* partial, int layout, itts_stream stream) {
-  (void)hipGetLastError();
-  GemvArgs g;
-  g.X = (const float*)X; g.x_bf16 = 1; g.W = W; g.Y = (float*)Y; g.y_bf16 = y_bf16; g.bias = bias; g.B = B; g.N = N; g.K = K;
-  g.ldy = N; g.act = act; g.accumulate = accumulate; g.ksplit = ksplit; g.partial = partial;
+// The argument block of the two skinny entries, without pointers: what itts_skinny_gemm_supported judges and the entries launch.
+static bool skinny_args(GemvArgs& g, int y_bf16, int B, int N, int K, int act, int accumulate, int ksplit, int layout, int fp8) {
+  if ((layout & ~31) || (fp8 && (layout & 4))) return false;  // fp8: tiling is said by W8t
+  g.x_bf16 = 1; g.y_bf16 = y_bf16 ? 1 : 0; g.B = B; g.N = N; g.K = K; g.ldy = N; g.act = act; g.accumulate = accumulate ? 1 : 0;
+  g.ksplit = ksplit;
   g.x_tiled = layout & 1; g.y_tiled = (layout >> 1) & 1;
-  if (layout & 4) {
-    g.Wt = W;
-    g.W = nullptr;
-  }
   if (layout & 8) {  // X is fp32 [B, K]: LayerNorm (eps 1e-5, no affine) in the prologue, B <= 16
     g.x_bf16 = 0;
     g.prologue = 1;
   }
   g.half_tiles = (layout >> 4) & 1;
+  return skinny_mfma_shape_ok(g);
+}
+
+int itts_skinny_gemm_supported(int y_bf16, int B, int N, int K, int act, int accumulate, int ksplit, int layout, int fp8) {
+  GemvArgs g;
+  return skinny_args(g, y_bf16, B, N, K, act, accumulate, ksplit, layout, fp8) ? 1 : 0;
+}
+
+#define SKINNY_REQUIRE(name, cond, msg)                 \
+  do {                                                  \
+    if (!(cond)) {                                      \
+      set_error(std::string(name) + ": " msg " (" #cond ")"); \
+      return E_INVALID;                                 \
+    }                                                   \
+  } while (0)
+
+int itts_skinny_gemm(void* Y, int y_bf16, const void* X, const void* W, const float* bias, int B, int N, int K, int act,
+                     int accumulate, int ksplit, float* partial, int layout, itts_stream stream) {
+  (void)hipGetLastError();
+  const char* me = "itts_skinny_gemm";
+  SKINNY_REQUIRE(me, X && W && (Y || ksplit > 1), "null pointer (X, W; Y unless ksplit > 1)");
+  SKINNY_REQUIRE(me, B > 0 && N > 0 && K > 0 && ksplit > 0, "non-positive B, N, K or ksplit");
+  SKINNY_REQUIRE(me, ksplit == 1 || partial, "ksplit > 1 needs partial[ksplit][B][N]");
+  GemvArgs g;
+  SKINNY_REQUIRE(me, skinny_args(g, y_bf16, B, N, K, act, accumulate, ksplit, layout, 0), "unsupported shape (itts_skinny_gemm_supported)");
+  g.X = (const float*)X; g.Y = (float*)Y; g.bias = bias; g.partial = partial;
+  if (layout & 4)
+    g.Wt = W;
+  else
+    g.W = W;
+  return skinny_mfma(g, (hipStream_t)stream);
+}
+
+int itts_skinny_gemm_fp8(void* Y, int y_bf16, const void* X, const void* W8, const void* W8t, const float* wscale, const float* bias,
+                         int B, int N, int K, int act, int accumulate, int ksplit, float* partial, int layout, itts_stream stream) {
+  (void)hipGetLastError();
+  const char* me = "itts_skinny_gemm_fp8";
+  SKINNY_REQUIRE(me, X && W8 && wscale && (Y || ksplit > 1), "null pointer (X, W8, wscale; Y unless ksplit > 1)");
+  SKINNY_REQUIRE(me, B > 0 && N > 0 && K > 0 && ksplit > 0, "non-positive B, N, K or ksplit");
+  SKINNY_REQUIRE(me, ksplit == 1 || partial, "ksplit > 1 needs partial[ksplit][B][N]");
+  SKINNY_REQUIRE(me, !(layout & 4), "layout bit 2 is the bf16 entry's: W8t says that the weights are tiled");
+  GemvArgs g;
+  SKINNY_REQUIRE(me, skinny_args(g, y_bf16, B, N, K, act, accumulate, ksplit, layout, 1), "unsupported shape (itts_skinny_gemm_supported)");
+  g.X = (const float*)X; g.Y = (float*)Y; g.bias = bias; g.partial = partial;
+  g.W8 = W8; g.W8t = W8t; g.wscale = wscale;  // g.W stays null: the fp8 instantiations read no bf16 weights
   return skinny_mfma(g, (hipStream_t)stream);
 }
 
@@ -420,15 +460,24 @@ int itts_retile_weights(void* dst, const void* src, int N, int K, itts_stream st
   return retile_weights_bf16(dst, src, N, K, (hipStream_t)stream);
 }
 
+int itts_retile_weights_fp8(void* dst, const void* src, int N, int K, itts_stream stream) {
+  (void)hipGetLastError();
+  return retile_weights_fp8(dst, src, N, K, (hipStream_t)stream);
+}
+
 int itts_ln_rows_bf16(void* y, float* x, const float* gamma, const float* beta, int rows, int D, float eps, int passes,
                       const float* partial, int nsplit, const float* partial_bias, int y_tiled, itts_stream stream) {
   (void)hipGetLastError();
-  if (!y || !x || rows <= 0) {
-    set_error("itts_ln_rows_bf16: bad arguments");
-    return E_INVALID;
-  }
+  const char* me = "itts_ln_rows_bf16";
+  SKINNY_REQUIRE(me, y && x, "null pointer");
+  SKINNY_REQUIRE(me, rows > 0 && D >= 1 && D <= 2048, "rows >= 1, 1 <= D <= 2048");
+  SKINNY_REQUIRE(me, (gamma == nullptr) == (beta == nullptr), "one of gamma / beta alone");
+  SKINNY_REQUIRE(me, passes >= 1 && passes <= 2, "1 or 2 passes");
+  SKINNY_REQUIRE(me, nsplit >= 0 && nsplit <= 8 && (nsplit == 0 || partial), "0 .. 8 splits, partial[nsplit][rows][D] with them");
+  SKINNY_REQUIRE(me, !y_tiled || D % 32 == 0, "tiled output needs D % 32 == 0");
   return ln_rows_bf16(y, x, gamma, beta, rows, D, eps, passes, partial, nsplit, partial_bias, y_tiled, (hipStream_t)stream);
 }
+#undef SKINNY_REQUIRE
 
 int itts_transpose(void* y, const void* x, int B, int R, int C, int dtype, itts_stream stream) {
   (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)

@@ -19,7 +19,8 @@ constexpr int SW = 8;  // waves per workgroup (K split inside the workgroup)
 // (ksplit > 1: raw partial sums go to g.partial[split][b][n]; bias / residual are applied by ln_rows_bf16).
 // W8: the weights are OCP fp8 e4m3 bytes with one power-of-two scale per output row (BASELINE config 5: half the weight
 // stream); a lane's 8 bytes become the same half8_bits MFMA operand through v_cvt_scalef32_pk_bf16_fp8, the row scale
-// multiplies the fp32 sum in the epilogue - bit-identical to running the bf16 dequantisation of the same weights.
+// multiplies the fp32 sum in the epilogue - bit-identical to running the bf16 dequantisation of the same weights
+// (tests/test_gpu_skinny.py holds that in every form: 0 ulp).
 
 // LNP (B <= 16 only, BT = 1): X is the fp32 residual stream [B][K]; LayerNorm without affine (folded into W) runs in the
 // prologue - wave w owns rows 2w and 2w + 1, moments by DPP wave sums, the normalised bf16 rows go to LDS and every wave
@@ -182,9 +183,12 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(GemvArgs g) {
         }
       }
     }
+    // the guard has to be a scalar branch: v_mfma ignores EXEC, and the compiler drops the skip branch around a masked block that
+    // holds nothing but the MFMA (SU = 20 with fewer than 20 k-steps in a wave ran them all, on registers never loaded)
+    const int k0s = __builtin_amdgcn_readfirstlane(k0);
 #pragma unroll
     for (int u = 0; u < SU; ++u) {
-      if (k0 + u * SW < nks) {
+      if (k0s + u * SW < nks) {
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -352,16 +356,27 @@ int retile_weights_bf16(void* dst, const void* src, int N, int K, hipStream_t s)
   return OK;
 }
 
-bool skinny_mfma_supported(const GemvArgs& g) {
+// The whole shape rule of skinny_mfma, pointers aside (itts_skinny_gemm_supported asks it without any): what the kernels index
+// relies on every line of it.
+bool skinny_mfma_shape_ok(const GemvArgs& g) {
+  if (!(g.B >= 1 && g.B <= 128 && g.N >= 1 && g.K >= 32 && g.K % 32 == 0)) return false;
+  if (!(g.ksplit >= 1 && g.ksplit <= (g.K >> 5))) return false;
+  if (g.accumulate && g.y_bf16) return false;
+  if (g.ksplit > 1 && g.act != ACT_NONE) return false;  // raw partial sums: bias / act / Y belong to ln_rows_bf16
   if (g.prologue == 1) {
     if (!(g.B <= 16 && !g.x_bf16 && !g.half_tiles && g.K <= 1280 && g.ksplit == 1)) return false;
   } else if (!(g.x_bf16 && g.prologue == 0)) {
     return false;
   }
   if (g.half_tiles && !(g.B <= 16 && g.ksplit == 1)) return false;
-  return g.B >= 1 && g.B <= 128 && g.K % 32 == 0 && !(g.accumulate && g.y_bf16) &&
-         !(((uintptr_t)g.W | (uintptr_t)g.X) & 15) && !((uintptr_t)g.W8 & 7) && (!g.W8 || g.wscale) && g.ksplit >= 1 &&
-         (g.ksplit == 1 || (g.partial && g.act == ACT_NONE));
+  // tile_off(b, n, ..) walks 32-wide column groups: a tiled bf16 Y of ceil(B/16) * 16 * N elements holds them only at N % 32 == 0
+  if (g.y_bf16 && g.y_tiled && g.N % 32 != 0) return false;
+  return true;
+}
+
+bool skinny_mfma_supported(const GemvArgs& g) {
+  return skinny_mfma_shape_ok(g) && !(((uintptr_t)g.W | (uintptr_t)g.X) & 15) && !((uintptr_t)g.W8 & 7) && (!g.W8 || g.wscale) &&
+         (g.ksplit == 1 || g.partial);
 }
 
 // <= 16 rows: LayerNorm prologue (prologue == 1, X = fp32 residual stream) or half-tile residual projection (half_tiles)
@@ -425,21 +440,13 @@ static int launch_skinny(const GemvArgs& g, hipStream_t s) {
 }
 
 int skinny_mfma(const GemvArgs& g, hipStream_t s) {
-  ITTS_REQUIRE(g.X && (g.W || g.W8 || g.Wt) && (g.Y || g.ksplit > 1) && g.N > 0, "skinny_mfma: bad args");
+  ITTS_REQUIRE(g.X && (g.W || g.W8 || g.Wt) && (g.Y || g.ksplit > 1), "skinny_mfma: bad args");
   ITTS_REQUIRE(!g.Wt || !((uintptr_t)g.Wt & 15), "skinny_mfma: tiled weights must be 16-byte aligned");
   ITTS_REQUIRE(!g.W8t || (g.W8 && !((uintptr_t)g.W8t & 7)), "skinny_mfma: tiled fp8 weights come with the row-major ones, 8-byte aligned");
   ITTS_REQUIRE(skinny_mfma_supported(g), "skinny_mfma: unsupported shape");
-  ITTS_REQUIRE(g.ksplit <= (g.K >> 5), "skinny_mfma: ksplit larger than the number of k-steps");
   const int bt = (g.B + 15) / 16;
-  if (g.prologue == 1 || g.half_tiles) {
-    ITTS_REQUIRE(bt == 1 && g.ksplit == 1, "skinny_mfma: LayerNorm prologue / half tiles are for <= 16 rows, no K split");
-    if (g.prologue == 1) {
-      ITTS_REQUIRE(!g.x_bf16 && !g.half_tiles && g.K <= 1280 && !((uintptr_t)g.X & 15),
-                   "skinny_mfma: LayerNorm prologue needs fp32 X [B, K], K <= 1280");
-      return launch_skinny16<true, false>(g, s);
-    }
-    return launch_skinny16<false, true>(g, s);
-  }
+  if (g.prologue == 1) return launch_skinny16<true, false>(g, s);  // (<= 16 rows, no K split: skinny_mfma_shape_ok)
+  if (g.half_tiles) return launch_skinny16<false, true>(g, s);
   if (bt <= 1) return launch_skinny<1>(g, s);
   if (bt <= 2) return launch_skinny<2>(g, s);
   if (bt <= 4) return launch_skinny<4>(g, s);
@@ -448,7 +455,10 @@ int skinny_mfma(const GemvArgs& g, hipStream_t s) {
 
 int ln_rows_bf16(void* y, float* x, const float* g1, const float* b1, int rows, int D, float eps, int passes,
                  const float* partial, int nsplit, const float* pbias, int y_tiled, hipStream_t s) {
-  ITTS_REQUIRE(D <= 2048 && passes >= 1 && passes <= 2, "ln_rows_bf16: D > 2048 or bad pass count");
+  ITTS_REQUIRE(y && x && rows >= 1 && D >= 1 && D <= 2048 && passes >= 1 && passes <= 2,
+               "ln_rows_bf16: null pointer, rows < 1, D outside 1 .. 2048 or bad pass count");
+  ITTS_REQUIRE((g1 == nullptr) == (b1 == nullptr), "ln_rows_bf16: one of gamma / beta alone");
+  ITTS_REQUIRE(nsplit >= 0, "ln_rows_bf16: negative split count");
   ITTS_REQUIRE(nsplit == 0 || (partial && nsplit <= 8), "ln_rows_bf16: partial sums missing or more than 8 splits");
   ITTS_REQUIRE(!y_tiled || D % 32 == 0, "ln_rows_bf16: tiled output needs D % 32 == 0");
   if (D <= 1280)

@@ -206,7 +206,8 @@ int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, co
                   hipStream_t s);
 
 // larger decode batches (decode_mfma.hip): X bf16 [B,K], W bf16 [N,K]; Y fp32 (store / accumulate) or bf16
-bool skinny_mfma_supported(const GemvArgs& g);
+bool skinny_mfma_shape_ok(const GemvArgs& g);   // the shape rule alone, no pointer is looked at
+bool skinny_mfma_supported(const GemvArgs& g);  // the shape rule and what the pointers have to satisfy
 int skinny_mfma(const GemvArgs& g, hipStream_t s);
 int ln_rows_bf16(void* y, float* x, const float* g1, const float* b1, int rows, int D, float eps, int passes,
                  const float* partial, int nsplit, const float* pbias, int y_tiled, hipStream_t s);

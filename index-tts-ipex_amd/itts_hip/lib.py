@@ -127,7 +127,10 @@ _PROTOS = {
     "itts_beam_sample_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, f32, f32, vp,
                                     vp, C.c_size_t, vp]),
     "itts_skinny_gemm": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "itts_skinny_gemm_fp8": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "itts_skinny_gemm_supported": (i32, [i32] * 9),
     "itts_retile_weights": (i32, [vp, vp, i32, i32, vp]),
+    "itts_retile_weights_fp8": (i32, [vp, vp, i32, i32, vp]),
     "itts_ln_rows_bf16": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, vp, i32, vp, i32, vp]),
     "itts_transpose": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "itts_rowop": (i32, [i32, C.POINTER(RowopArgs), vp]),
