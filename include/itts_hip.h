@@ -377,6 +377,24 @@ typedef struct {
 } itts_sampler_step_args;
 int itts_sampler_step(const itts_sampler_step_args* args, itts_stream stream);
 
+/* One row of a mixed decode batch: its own token choice.  mode 0 = greedy (top_k / top_p / temperature unread), 1 = sample.
+ * top_k <= 0 switches the TopK warper off.  0 < top_p <= 1, temperature > 0, penalty > 0 (the row's repetition penalty). */
+typedef struct {
+  int mode, top_k;
+  float top_p, temperature, penalty;
+} itts_row_sampling;
+
+/* itts_sampler_step with one setting per row: rows_host is a HOST table of args->B entries, and the scalar sampling fields of
+ * args (do_sample, top_k, top_p, temperature, penalty) are ignored.  rows_dev_scratch: args->B * sizeof(itts_row_sampling) bytes
+ * of caller device memory, 4-byte aligned, which the call fills on the stream (the host table is the caller's again on return).
+ * Every row gets the bits of itts_sampler_step with its entry as the scalar setting: a greedy row runs in sampler2_kernel, a row
+ * with 1 <= top_k <= 128 in sampler_sample_kernel, any other sampled row in sampler_wide_kernel - one launch per class present,
+ * each over all rows, a row's block returning at once in the kernels of the other classes.  Refused with ITTS_E_INVALID before
+ * any device call: what itts_sampler_step refuses, null rows_host / rows_dev_scratch, a mode outside {0, 1}, top_p outside
+ * (0, 1], temperature <= 0, penalty <= 0, a sampled row without uniforms, V > 15360 with a narrow row, V > 16384 with a wide row. */
+int itts_sampler_step_rows(const itts_sampler_step_args* args, const itts_row_sampling* rows_host, void* rows_dev_scratch,
+                           itts_stream stream);
+
 /* ---- engine level ----------------------------------------------------------------------------------- */
 
 typedef struct {
@@ -422,6 +440,20 @@ int itts_ecapa(itts_engine* e, const void* mel_bfc, int B, int F, float* spk_out
  * top-p boundary within 64 * 2^-24 of it).  0 < top_p <= 1, temperature > 0. */
 int itts_gpt_set_sampling(itts_engine* e, int do_sample, int top_k, float top_p, float temperature, const float* uniforms_host,
                           int64_t n_uniforms);
+
+/* Mixed batches (opt-in): one setting per row for the following single-beam generations.  rows_host: HOST table of B entries,
+ * row b of a batch of B; uniforms_host [max_gen][B] as in itts_gpt_set_sampling, needed when any row samples.  B = 0 clears the
+ * table (the scalar setting then is what itts_gpt_set_sampling last said, or greedy after a table that was not uniform).
+ * itts_gpt_prefill latches the table and refuses when B is not its batch, when beams, typical filtering or host sampling are on.
+ * Every row's `penalty` replaces the prefill's repetition_penalty argument.
+ * A table whose rows are all equal IS the scalar setting with those values - the same code path, the persistent engine's in-launch
+ * greedy sampler included, the same bits.  With any other table the step (the persistent engine's blocks and head at <= 6 rows,
+ * the launch path above) is followed by one sampler launch per class present (itts_sampler_step_rows), and every row's codes and
+ * logits are the bits of a generation of the same rows with that row's entry as the scalar setting and the same uniforms.
+ * A sampled row with top_k outside 1..128 always runs on the device's whole-vocabulary sampler (number_mel_codes <= 16384).
+ * itts_gpt_retire_rows carries the entries with their rows. */
+int itts_gpt_set_sampling_rows(itts_engine* e, const itts_row_sampling* rows_host, int B, const float* uniforms_host,
+                               int64_t n_uniforms);
 
 /* Beam-sample mode of the next generations: HF 4.36.2 GenerationMixin.beam_sample + BeamSearchScorer, the generate() mode
  * the reference's DEFAULT kwargs select (infer.py:116-124: do_sample=True, num_beams=3, top_k=30, top_p=0.8,
@@ -557,6 +589,11 @@ int itts_gpt_latent(itts_engine* e, const float* cond, const int32_t* text_ids_h
 int itts_gpt_latent_batch(itts_engine* e, const float* cond, const int32_t* text_ids_host, const int32_t* text_lens_host,
                           const int32_t* codes_host, const int32_t* code_lens_host, int nseq, void* latent_out,
                           itts_stream stream);
+/* The same with one voice per sentence: cond = [n_cond][latents, D] fp32 on the device, sentence i reads block
+ * cond_index_host[i] (host, [nseq], each in [0, n_cond)).  itts_gpt_latent_batch is the all-zero index. */
+int itts_gpt_latent_batch_cond(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond,
+                               const int32_t* text_ids_host, const int32_t* text_lens_host, const int32_t* codes_host,
+                               const int32_t* code_lens_host, int nseq, void* latent_out, itts_stream stream);
 
 /* V1-V5  BigVGAN.forward given the speaker embedding (BigVGAN/models.py:201-250):
  * latent [B, T, gpt_dim] (engine dtype), spk fp32 [B, spk_dim] -> wav fp32 [B, T * prod(up_rates)] */

@@ -662,16 +662,29 @@ int itts_typical_rows(const itts_typical_args* p, itts_stream stream) {
   return typical_filter(t, p->rows, (hipStream_t)stream);
 }
 
+// what both sampler entries ask of the state and the embedding tables (REQ: the caller's TOKEN_REQUIRE with its own name)
+#define SAMPLER_STATE_CHECKS                                                                                                     \
+  REQ(p, "null args");                                                                                                           \
+  REQ(p->logits && p->seen && p->ids && p->cur_tok && p->unfinished && p->step, "null state pointer");                           \
+  REQ(p->B >= 1 && p->V >= 1 && p->max_gen >= 1, "B, V, max_gen >= 1");                                                          \
+  REQ(p->stop >= 0 && p->stop < p->V, "stop outside the vocabulary");                                                            \
+  REQ(p->input_n >= 0 && (p->input_n == 0 || p->forced), "input_n > 0 needs forced");                                            \
+  REQ(p->emb_bf16 == 0 || p->emb_bf16 == 1, "emb_bf16 is 0 (fp32 tables) or 1 (bf16 tables)");                                   \
+  REQ(!p->h_next || (p->emb && p->pos && p->D >= 1 && p->pos_rows >= 1), "h_next needs emb, pos, D >= 1, pos_rows >= 1")
+
+static SamplerArgs sampler_state_args(const itts_sampler_step_args* p) {  // everything but the sampling settings
+  SamplerArgs a;
+  a.logits = p->logits; a.seen = (uint8_t*)p->seen; a.ids = p->ids; a.cur_tok = p->cur_tok; a.unfinished = p->unfinished; a.step = p->step;
+  a.V = p->V; a.max_gen = p->max_gen; a.stop = p->stop; a.suppress_stop = p->suppress_stop; a.h_next = p->h_next;
+  a.emb = p->emb; a.pos = p->pos; a.D = p->D; a.pos_rows = p->pos_rows; a.emb_bf16 = p->emb_bf16; a.B = p->B; a.uniforms = p->uniforms;
+  a.forced = p->forced; a.input_n = p->input_n; a.preprocessed = p->preprocessed; a.kept = p->kept;
+  return a;
+}
+
 int itts_sampler_step(const itts_sampler_step_args* p, itts_stream stream) {
 #define REQ(cond, msg) TOKEN_REQUIRE("itts_sampler_step", cond, msg)
-  REQ(p, "null args");
-  REQ(p->logits && p->seen && p->ids && p->cur_tok && p->unfinished && p->step, "null state pointer");
-  REQ(p->B >= 1 && p->V >= 1 && p->max_gen >= 1, "B, V, max_gen >= 1");
-  REQ(p->stop >= 0 && p->stop < p->V, "stop outside the vocabulary");
+  SAMPLER_STATE_CHECKS;
   REQ(p->penalty > 0.f, "penalty > 0");
-  REQ(p->input_n >= 0 && (p->input_n == 0 || p->forced), "input_n > 0 needs forced");
-  REQ(p->emb_bf16 == 0 || p->emb_bf16 == 1, "emb_bf16 is 0 (fp32 tables) or 1 (bf16 tables)");
-  REQ(!p->h_next || (p->emb && p->pos && p->D >= 1 && p->pos_rows >= 1), "h_next needs emb, pos, D >= 1, pos_rows >= 1");
   REQ(p->do_sample == 0 || p->do_sample == 1, "do_sample 0 or 1");
   if (p->do_sample) {
     REQ(p->uniforms, "do_sample needs uniforms");
@@ -683,14 +696,52 @@ int itts_sampler_step(const itts_sampler_step_args* p, itts_stream stream) {
   }
 #undef REQ
   (void)hipGetLastError();
-  SamplerArgs a;
-  a.logits = p->logits; a.seen = (uint8_t*)p->seen; a.ids = p->ids; a.cur_tok = p->cur_tok; a.unfinished = p->unfinished; a.step = p->step;
-  a.V = p->V; a.max_gen = p->max_gen; a.stop = p->stop; a.suppress_stop = p->suppress_stop; a.penalty = p->penalty; a.h_next = p->h_next;
-  a.emb = p->emb; a.pos = p->pos; a.D = p->D; a.pos_rows = p->pos_rows; a.emb_bf16 = p->emb_bf16; a.do_sample = p->do_sample;
-  a.top_k = p->top_k < 1 ? 0 : p->top_k; a.B = p->B; a.top_p = p->top_p; a.temperature = p->temperature; a.uniforms = p->uniforms;
-  a.forced = p->forced; a.input_n = p->input_n; a.preprocessed = p->preprocessed; a.kept = p->kept;
+  SamplerArgs a = sampler_state_args(p);
+  a.penalty = p->penalty; a.do_sample = p->do_sample; a.top_k = p->top_k < 1 ? 0 : p->top_k; a.top_p = p->top_p; a.temperature = p->temperature;
   return sampler2_step(a, p->B, (hipStream_t)stream);
 }
+
+// every entry of a host row table, and the classes it holds (bit ROWCLS_*); 0 with *why set = refused.  No HIP call
+static int row_table_classes(const itts_row_sampling* rows, int B, const char** why) {
+  int classes = 0;
+  for (int b = 0; b < B; ++b) {
+    const itts_row_sampling& r = rows[b];
+    if (r.mode != 0 && r.mode != 1) return *why = "mode is 0 (greedy) or 1 (sample)", 0;
+    if (!(r.top_p > 0.f && r.top_p <= 1.f)) return *why = "0 < top_p <= 1", 0;
+    if (!(r.temperature > 0.f)) return *why = "temperature > 0", 0;
+    if (!(r.penalty > 0.f)) return *why = "penalty > 0", 0;
+    classes |= 1 << row_class(r.mode, r.top_k);
+  }
+  return classes;
+}
+
+int itts_sampler_step_rows(const itts_sampler_step_args* p, const itts_row_sampling* rows_host, void* rows_dev_scratch, itts_stream stream) {
+  static_assert(sizeof(itts_row_sampling) == sizeof(RowSampling) && sizeof(RowSampling) == 20, "the public row entry is the kernels' own");
+#define REQ(cond, msg) TOKEN_REQUIRE("itts_sampler_step_rows", cond, msg)
+  SAMPLER_STATE_CHECKS;
+  REQ(rows_host && rows_dev_scratch && !((uintptr_t)rows_dev_scratch & 3), "null row table / device scratch (4-byte aligned)");
+  const char* why = nullptr;
+  const int classes = row_table_classes(rows_host, p->B, &why);
+  if (!classes) {
+    set_error(std::string("itts_sampler_step_rows: bad row entry: ") + why);
+    return E_INVALID;
+  }
+  REQ(!(classes & ~(1 << ROWCLS_GREEDY)) || p->uniforms, "a sampled row needs uniforms");
+  REQ(!(classes >> ROWCLS_NARROW & 1) || p->V <= 15360, "1 <= top_k <= 128 keeps the vocabulary in LDS: V <= 15360");
+  REQ(!(classes >> ROWCLS_WIDE & 1) || p->V <= 16384, "top_k outside 1..128 sorts the whole vocabulary: V <= 16384");
+#undef REQ
+  (void)hipGetLastError();
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<RowSampling> tab((size_t)p->B);
+  for (int b = 0; b < p->B; ++b)
+    tab[b] = {rows_host[b].mode, rows_host[b].top_k < 1 ? 0 : rows_host[b].top_k, rows_host[b].top_p, rows_host[b].temperature, rows_host[b].penalty};
+  ITTS_HIP_CHECK(hipMemcpyAsync(rows_dev_scratch, tab.data(), tab.size() * sizeof(RowSampling), hipMemcpyHostToDevice, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));  // tab is a host buffer of this call
+  SamplerArgs a = sampler_state_args(p);
+  a.rows = (const RowSampling*)rows_dev_scratch;
+  return sampler_rows_step(a, p->B, classes, s);
+}
+#undef SAMPLER_STATE_CHECKS
 #undef TOKEN_REQUIRE
 
 int itts_engine_create(const itts_config* cfg, itts_engine** out) {
@@ -779,6 +830,14 @@ int itts_gpt_set_sampling(itts_engine* e, int do_sample, int top_k, float top_p,
   ENG(e);
   return e->e.gpt_set_sampling(do_sample, top_k, top_p, temperature, uniforms_host, (long)n_uniforms);
 }
+int itts_gpt_set_sampling_rows(itts_engine* e, const itts_row_sampling* rows_host, int B, const float* uniforms_host, int64_t n_uniforms) {
+  ENG(e);
+  if (B < 0 || (B > 0 && !rows_host)) {
+    set_error("itts_gpt_set_sampling_rows: B >= 0, and a row table for B > 0");
+    return E_INVALID;
+  }
+  return e->e.gpt_set_sampling_rows((const RowSampling*)rows_host, B, uniforms_host, (long)n_uniforms);
+}
 int itts_gpt_set_beam_sample(itts_engine* e, int num_beams, int top_k, float top_p, float temperature, const float* uniforms_host,
                              int64_t n_uniforms) {
   ENG(e);
@@ -860,6 +919,17 @@ int itts_gpt_latent_batch(itts_engine* e, const float* cond, const int32_t* text
   ENG(e);
   return e->e.gpt_latent_batch(cond, text_ids_host, text_lens_host, codes_host, code_lens_host, nseq, latent_out,
                                (hipStream_t)s);
+}
+int itts_gpt_latent_batch_cond(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond, const int32_t* text_ids_host,
+                               const int32_t* text_lens_host, const int32_t* codes_host, const int32_t* code_lens_host, int nseq,
+                               void* latent_out, itts_stream s) {
+  ENG(e);
+  if (!cond_index_host || n_cond < 1) {
+    set_error("itts_gpt_latent_batch_cond: needs cond_index_host and n_cond >= 1");
+    return E_INVALID;
+  }
+  return e->e.gpt_latent_batch(cond, text_ids_host, text_lens_host, codes_host, code_lens_host, nseq, latent_out, (hipStream_t)s,
+                               cond_index_host, n_cond);
 }
 int itts_bigvgan(itts_engine* e, const void* latent, const float* spk, int B, int T, float* wav_out, itts_stream s) {
   ENG(e);

@@ -11,12 +11,32 @@
 namespace itts {
 namespace {
 
+// Mixed batches (ROWS, sampler_rows_step): row b's entry of a.rows replaces the scalar settings in this block's own copy of the
+// argument block; false = a kernel of another class owns the row.  The entry goes through readfirstlane: its values are the same
+// for every thread of the block, so they stay in scalar registers like the kernel arguments they replace, and the early return on
+// them is taken by whole blocks - no barrier is passed by part of a block.  !ROWS: nothing is read, the kernel is what it was.
+template <bool ROWS, int CLS>
+__device__ __forceinline__ bool sampler_take_row(SamplerArgs& a, int b) {
+  if constexpr (ROWS) {
+    const int* r = reinterpret_cast<const int*>(a.rows + b);
+    const int mode = __builtin_amdgcn_readfirstlane(r[0]), top_k = __builtin_amdgcn_readfirstlane(r[1]);
+    if (row_class(mode, top_k) != CLS) return false;
+    a.top_k = top_k;
+    a.top_p = __int_as_float(__builtin_amdgcn_readfirstlane(r[2]));
+    a.temperature = __int_as_float(__builtin_amdgcn_readfirstlane(r[3]));
+    a.penalty = __int_as_float(__builtin_amdgcn_readfirstlane(r[4]));
+  }
+  return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // sampler2: repetition penalty + argmax + bookkeeping, one 1024-thread block per row; the per-row length
 // counter is advanced by the row's own block (no cross-block step counter, no extra launch).  (Its vectorised argmax shares
 // sampler_score / sampler_commit / sampler_next_embedding only.)
 // ---------------------------------------------------------------------------------------------
+template <bool ROWS>
 __global__ __launch_bounds__(1024) void sampler2_kernel(SamplerArgs a) {
+  if (!sampler_take_row<ROWS, ROWCLS_GREEDY>(a, blockIdx.x)) return;
   __shared__ float sv[16];
   __shared__ int si[16];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -92,7 +112,9 @@ __global__ __launch_bounds__(1024) void sampler2_kernel(SamplerArgs a) {
 // radix select on order-preserving keys (no sort of the vocabulary), the <= 128 survivors are bitonic-sorted by one
 // wave, top-p and the draw run serially over them in the order torch.cumsum uses.
 // ---------------------------------------------------------------------------------------------
+template <bool ROWS>
 __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
+  if (!sampler_take_row<ROWS, ROWCLS_NARROW>(a, blockIdx.x)) return;
   extern __shared__ float ssc[];  // [V] processed scores
   __shared__ unsigned hist[256];
   __shared__ int s_bin, s_k, s_cnt;
@@ -235,7 +257,9 @@ __global__ __launch_bounds__(1024) void sampler_sample_kernel(SamplerArgs a) {
 // ---------------------------------------------------------------------------------------------
 constexpr int WIDE_MAX_V = 16384;  // NP * 6 bytes of LDS: 96 KiB
 
+template <bool ROWS>
 __global__ __launch_bounds__(1024) void sampler_wide_kernel(SamplerArgs a, int NP) {
+  if (!sampler_take_row<ROWS, ROWCLS_WIDE>(a, blockIdx.x)) return;
   extern __shared__ unsigned char wsm[];
   float* keys = reinterpret_cast<float*>(wsm);                                     // [NP] scores, sorted in place
   unsigned short* idx = reinterpret_cast<unsigned short*>(wsm + (size_t)NP * 4);  // [NP] their token ids
@@ -371,28 +395,52 @@ __global__ void decode_embed2_kernel(float* __restrict__ h, const TW* __restrict
 // sampler_wide_kernel's 96 KiB of dynamic LDS have to be allowed once on every device ordinal that launches it; gpt_prefill
 // calls this outside the capture of the decode step
 int sampler_wide_prepare() {
-  static DynLdsLatch latch;
-  return allow_dynamic_lds(latch, (const void*)sampler_wide_kernel, WIDE_MAX_V * 6);
+  static DynLdsLatch latch, latch_rows;  // both instantiations: the scalar form and the one of mixed batches
+  ITTS_TRY(allow_dynamic_lds(latch, (const void*)sampler_wide_kernel<false>, WIDE_MAX_V * 6));
+  return allow_dynamic_lds(latch_rows, (const void*)sampler_wide_kernel<true>, WIDE_MAX_V * 6);
 }
 
 int sampler2_step(const SamplerArgs& a, int B, hipStream_t s) {
+  ITTS_REQUIRE(!a.rows, "sampler: a row table runs through sampler_rows_step");
   if (a.do_sample) {
     ITTS_REQUIRE(a.uniforms && a.temperature > 0.f && a.top_p > 0.f && a.B == B,
                  "sampler: sampling needs uniforms, temperature > 0, top_p > 0");
     if (a.top_k >= 1 && a.top_k <= BEAM_MAX_CAND) {
       ITTS_REQUIRE((size_t)a.V * 4 <= 60 * 1024, "sampler: vocabulary too large for the LDS-resident sampler");
-      hipLaunchKernelGGL(sampler_sample_kernel, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
+      hipLaunchKernelGGL(sampler_sample_kernel<false>, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
     } else {  // TopK off or wider than the narrow kernel's candidates: the whole vocabulary
       ITTS_REQUIRE(a.V >= 1 && a.V <= WIDE_MAX_V, "sampler: top_k outside [1, 128] needs a vocabulary of at most 16384");
       ITTS_TRY(sampler_wide_prepare());
       int np = 1024;
       while (np < a.V) np <<= 1;
-      hipLaunchKernelGGL(sampler_wide_kernel, dim3(B), dim3(1024), (size_t)np * 6, s, a, np);
+      hipLaunchKernelGGL(sampler_wide_kernel<false>, dim3(B), dim3(1024), (size_t)np * 6, s, a, np);
     }
     ITTS_HIP_CHECK(hipGetLastError());
     return OK;
   }
-  hipLaunchKernelGGL(sampler2_kernel, dim3(B), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(sampler2_kernel<false>, dim3(B), dim3(1024), 0, s, a);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+// Mixed batch: every class present gets its kernel over the whole grid; row b's block does its work in the kernel of rows[b]'s
+// class and returns at once in the others, so the commit and the next-step embedding of every row run exactly once.  The
+// launches follow one another on the stream and touch disjoint rows.  `classes`: what the caller's host copy of the table holds
+// (bit ROWCLS_*); the entries themselves were checked where the table was built (c_api.cpp, Engine::gpt_set_sampling_rows).
+int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s) {
+  ITTS_REQUIRE(a.rows && a.B == B && classes > 0 && classes < 8, "sampler: a mixed batch needs its row table and the classes present");
+  const bool narrow = classes >> ROWCLS_NARROW & 1, wide = classes >> ROWCLS_WIDE & 1;
+  ITTS_REQUIRE(!(narrow || wide) || a.uniforms, "sampler: sampled rows need uniforms");
+  ITTS_REQUIRE(!narrow || (size_t)a.V * 4 <= 60 * 1024, "sampler: vocabulary too large for the LDS-resident sampler");
+  ITTS_REQUIRE(!wide || (a.V >= 1 && a.V <= WIDE_MAX_V), "sampler: top_k outside [1, 128] needs a vocabulary of at most 16384");
+  if (wide) ITTS_TRY(sampler_wide_prepare());
+  if (classes >> ROWCLS_GREEDY & 1) hipLaunchKernelGGL(sampler2_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+  if (narrow) hipLaunchKernelGGL(sampler_sample_kernel<true>, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
+  if (wide) {
+    int np = 1024;
+    while (np < a.V) np <<= 1;
+    hipLaunchKernelGGL(sampler_wide_kernel<true>, dim3(B), dim3(1024), (size_t)np * 6, s, a, np);
+  }
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;
 }

@@ -126,8 +126,11 @@ struct GraphKey {
   int nb = 1, beam_sample = 1, suppress_stop = 0, do_sample = 0, top_k = 0;
   int ct = 0;  // element type of the K/V cache (DecodeState::ct): the attention form and every per-layer cache offset
   float length_penalty = 0.f, typical_mass = 0.f, penalty = 0.f, top_p = 1.f, temperature = 1.f;  // compared as floats: a NaN re-captures
+  // mixed batch (DecodeState::rows_active): the step launches one sampler kernel per class present (bits ROWCLS_*).  The entries
+  // themselves live in device memory behind a pointer that only changes together with dropped graphs
+  int rows_active = 0, rows_classes = 0;
   bool operator==(const GraphKey& o) const {
-    return B == o.B && Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
+    return rows_active == o.rows_active && rows_classes == o.rows_classes && B == o.B &&Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
            host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample && ct == o.ct &&
            length_penalty == o.length_penalty && typical_mass == o.typical_mass && penalty == o.penalty &&
            suppress_stop == o.suppress_stop && do_sample == o.do_sample && top_k == o.top_k && top_p == o.top_p &&
@@ -179,6 +182,10 @@ struct DecodeState {
   float top_p = 1.f, temperature = 1.f;
   float* uniforms = nullptr;
   size_t uniforms_cap = 0;
+  // mixed batch (itts_gpt_set_sampling_rows, a table that is not uniform): what the prefill latched for this generation.
+  // rows [B] on the device, in slot order; rows_classes: the classes its live rows hold (bits ROWCLS_*, sampler_rows_step)
+  RowSampling* rows = nullptr;
+  int rows_cap = 0, rows_active = 0, rows_classes = 0;
   // beam-sample (itts_gpt_set_beam_sample): B = batch items * nb rows; state of beam.hip
   int nb = 1;                         // beams per batch item (1 = off)
   int beam_sample = 1;                // 1: beam_sample (draws), 0: beam_search (deterministic top-2nb)
@@ -295,6 +302,12 @@ struct Engine {
   int gpt_decode_steps(int nsteps, hipStream_t s);
   int gpt_set_sampling(int do_sample, int top_k, float top_p, float temperature, const float* uniforms_host, long n);
   std::vector<float> sample_uniforms;  // host copy, uploaded by the next prefill
+  // per-row settings of the following generations (B = 0 clears); uniforms as gpt_set_sampling.  A table whose rows are all
+  // equal IS the scalar setting (gpt_set_sampling is called with it) and only its penalty and row count are kept here
+  int gpt_set_sampling_rows(const RowSampling* rows_host, int B, const float* uniforms_host, long n);
+  std::vector<RowSampling> row_table;  // [B] by original row; empty = no table
+  bool row_table_uniform = false;
+  int upload_row_table(hipStream_t s);  // ds.rows / ds.rows_classes from row_table by ds.orig (or the identity)
   int gpt_set_forced(const int32_t* ids_host, int B, int n);
   int gpt_set_input_tokens(const int32_t* ids_host, int B, int n);
   int gpt_set_host_sampling(int on);
@@ -327,7 +340,7 @@ struct Engine {
   int gpt_latent(const float* cond, const int32_t* text_ids, int L, const int32_t* codes, int T, void* latent_out,
                  hipStream_t s);
   int gpt_latent_batch(const float* cond, const int32_t* text_ids, const int* Ls, const int32_t* codes, const int* Ts,
-                       int nseq, void* latent_out, hipStream_t s);
+                       int nseq, void* latent_out, hipStream_t s, const int32_t* cond_index = nullptr, int n_cond = 1);
   // lens_host (optional, [B], each in [1, T]): a padded ragged batch - item b is a latent of lens_host[b] frames, whatever its rows
   // behind them hold; its waveform is that of the item alone, zeros from sample lens_host[b] * up on
   int bigvgan(const void* latent, const float* spk, int B, int T, float* wav, hipStream_t s, const int* lens_host = nullptr);

@@ -55,6 +55,18 @@ __host__ __device__ inline size_t wtile_off(int n, int k, int K) {
 int retile_weights_bf16(void* dst, const void* src, int N, int K, hipStream_t s);
 int retile_weights_fp8(void* dst, const void* src, int N, int K, hipStream_t s);  // same order, one byte per element
 
+// one row of a mixed decode batch (SamplerArgs::rows; the layout of itts_row_sampling, include/itts_hip.h)
+struct RowSampling {
+  int mode;   // 0 greedy, 1 sample
+  int top_k;  // <= 0: TopK warper off
+  float top_p, temperature, penalty;
+};
+// the kernel that owns a row: 0 greedy (sampler2_kernel), 1 narrow (sampler_sample_kernel), 2 wide (sampler_wide_kernel)
+enum { ROWCLS_GREEDY = 0, ROWCLS_NARROW = 1, ROWCLS_WIDE = 2 };
+__host__ __device__ inline int row_class(int mode, int top_k) {
+  return mode == 0 ? ROWCLS_GREEDY : (top_k >= 1 && top_k <= 128 ? ROWCLS_NARROW : ROWCLS_WIDE);
+}
+
 struct SamplerArgs {
   const float* logits = nullptr;  // [B, V]
   uint8_t* seen = nullptr;        // [B, V]
@@ -80,6 +92,9 @@ struct SamplerArgs {
   int input_n = 0;  // the first input_n forced tokens are HF `input_tokens`: token k is fed at mel position k + 1, not k + 2
   int preprocessed = 0;  // logits already went through typical_filter (penalty, stop suppression done)
   int* kept = nullptr;   // [B] sampler_wide_kernel writes the number of kept ranks here (the operator entry point sets it)
+  // mixed batches (sampler_rows_step): row b takes rows[b] in place of do_sample / top_k / top_p / temperature / penalty above.
+  // nullptr = the scalars.  Last, so that no offset of an existing field moves
+  const RowSampling* rows = nullptr;  // [B]
 };
 
 // one beam-sample step for every batch item (beam.hip): HF 4.36.2 beam_sample + BeamSearchScorer.process on the device
@@ -202,6 +217,8 @@ int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* 
 // decode_sampler.hip
 int sampler2_step(const SamplerArgs& a, int B, hipStream_t s);
 int sampler_wide_prepare();  // once per device ordinal, outside graph capture: sampler_wide_kernel's dynamic LDS limit
+// a.rows set: one launch per class in `classes` (bit ROWCLS_*), grid B each; a block whose row another class owns returns at once
+int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s);
 int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, const int* len, int B, int D, int tw,
                   hipStream_t s);
 

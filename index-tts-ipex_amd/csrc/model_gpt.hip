@@ -518,7 +518,17 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
   const int Smax = (S0 + max_gen + 255) / 256 * 256;  // coarse, so one captured graph serves many L
   ITTS_REQUIRE(Smax <= 2048, "gpt_prefill: sequence too long for the decode attention kernel");
   ITTS_REQUIRE(max_gen < 4095, "gpt_prefill: max_gen must stay below 4095 (12-bit step field of the fused hand-off tags)");
+  // per-row settings (gpt_set_sampling_rows): single-beam device modes only, and for exactly this batch
+  if (!row_table.empty()) {
+    ITTS_REQUIRE((int)row_table.size() == B_items, "gpt_prefill: the per-row sampling table was set for another batch size");
+    ITTS_REQUIRE(nbeam == 1, "gpt_prefill: per-row sampling settings do not run under beams");
+    ITTS_REQUIRE(!(ds.typical_mass > 0.f), "gpt_prefill: per-row sampling settings do not run with typical filtering");
+    ITTS_REQUIRE(!ds.host_sample, "gpt_prefill: per-row sampling settings do not run with host sampling");
+    penalty = row_table[0].penalty;  // a uniform table: the scalar path with its values; else every row reads its own
+  }
   ITTS_TRY(ensure_decode_state(B, Smax, max_gen, s));
+  ds.rows_active = !row_table.empty() && !row_table_uniform;
+  ds.rows_classes = 0;
   ds.prefix = sp;
   ds.penalty = penalty;
   ds.suppress_stop = suppress;
@@ -539,6 +549,16 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
   }
   if (engine_usable()) ITTS_TRY(ensure_engine_state(s));  // allocations must not happen inside the graph capture of the step
   if (ds.do_sample && nbeam == 1 && (ds.top_k < 1 || ds.top_k > BEAM_MAX_CAND)) ITTS_TRY(sampler_wide_prepare());  // nor this
+  if (ds.rows_active) {
+    ITTS_TRY(upload_row_table(s));  // (may allocate)
+    if (ds.rows_classes >> ROWCLS_NARROW & 1)
+      ITTS_REQUIRE((size_t)V * 4 <= 60 * 1024, "gpt_prefill: a row with 1 <= top_k <= 128 needs number_mel_codes <= 15360");
+    if (ds.rows_classes >> ROWCLS_WIDE & 1) {
+      ITTS_REQUIRE(V <= 16384, "gpt_prefill: a sampled row with top_k outside [1, 128] needs number_mel_codes <= 16384");
+      ITTS_TRY(sampler_wide_prepare());
+    }
+  }
+  const bool rows_sample = ds.rows_active && (ds.rows_classes & ~(1 << ROWCLS_GREEDY));
   ds.wide_valid = 0;
   if (nbeam > 1 && beam_do_sample && !ds.host_sample && (ds.top_k < 1 || ds.top_k > BEAM_MAX_CAND)) {  // nor these two
     ITTS_REQUIRE(cfg.number_mel_codes <= BEAM_WIDE_MAX_V, "gpt_prefill: beam_sample with top_k outside [1, 128] needs number_mel_codes <= 16384");
@@ -546,7 +566,7 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
     ITTS_TRY(ensure_beam_wide_state(B, nbeam, cfg.number_mel_codes, s));
     ds.wide_valid = 1;  // this generation's steps leave their picks in ds.wide (gpt_beam_picks)
   }
-  if (ds.do_sample || (nbeam > 1 && beam_do_sample && !ds.host_sample)) {
+  if (ds.do_sample || rows_sample || (nbeam > 1 && beam_do_sample && !ds.host_sample)) {
     const size_t need_u = nbeam > 1 ? (size_t)max_gen * B_items * 2 * nbeam : (size_t)max_gen * B;
     ITTS_REQUIRE(sample_uniforms.size() >= need_u,
                  "gpt_prefill: sampling enabled but fewer uniforms than max_gen * B (* 2 * num_beams) were supplied");
@@ -773,6 +793,10 @@ int Engine::sample_from_logits(hipStream_t s, bool sampled) {
     return beam_sample_step(ba, s, wide ? &ds.wide : nullptr);
   }
   SamplerArgs sa = greedy_sampler_args(lg_in, typical);
+  if (ds.rows_active) {  // a mixed batch: one launch per class present, every row in its own class's kernel
+    sa.rows = ds.rows;
+    return sampler_rows_step(sa, B, ds.rows_classes, s);
+  }
   return sampler2_step(sa, B, s);
 }
 
@@ -889,7 +913,7 @@ EngArgs Engine::engine_args(int& eng_first, bool& fold_head, bool& fold_samp) co
   // ... and the greedy sampler behind it (ITTS_ENGINE_SAMPLER=0: own launch): plain greedy search only - sampling, beams,
   // typical filtering and host-side sampling keep their kernels
   static const bool e_samp = !(getenv("ITTS_ENGINE_SAMPLER") && atoi(getenv("ITTS_ENGINE_SAMPLER")) == 0);
-  fold_samp = fold_head && e_samp && !ds.do_sample && ds.nb == 1 && !ds.host_sample && !(ds.typical_mass > 0.f);
+  fold_samp = fold_head && e_samp && !ds.do_sample && !ds.rows_active && ds.nb == 1 && !ds.host_sample && !(ds.typical_mass > 0.f);
   if (fold_samp) {
     ea.fold_sampler = 1;
     ea.samp = greedy_sampler_args(ds.logits, false);
@@ -1102,6 +1126,68 @@ int Engine::gpt_set_sampling(int do_sample, int top_k, float top_p, float temper
   return OK;
 }
 
+// Per-row settings of the following single-beam generations: row b of a batch of B takes rows_host[b] (B = 0 clears the table;
+// the scalar setting then is whatever gpt_set_sampling last said, or greedy after a table that was not uniform).  The prefill
+// latches it.  A table whose rows are all equal is the scalar setting with those values: gpt_set_sampling is called with it here
+// and the steps take the scalar path, the persistent engine's in-launch greedy sampler included.  Any other table makes the step
+// choose its tokens with sampler_rows_step; uniforms_host [max_gen][B] as in gpt_set_sampling, needed when any row samples.
+int Engine::gpt_set_sampling_rows(const RowSampling* rows_host, int B, const float* uniforms_host, long n) {
+  if (B == 0) {
+    row_table.clear();
+    row_table_uniform = false;
+    return OK;
+  }
+  ITTS_REQUIRE(rows_host && B > 0, "gpt_set_sampling_rows: row table missing");
+  bool uniform = true, samples = false;
+  for (int b = 0; b < B; ++b) {
+    const RowSampling& r = rows_host[b];
+    ITTS_REQUIRE(r.mode == 0 || r.mode == 1, "gpt_set_sampling_rows: mode is 0 (greedy) or 1 (sample)");
+    ITTS_REQUIRE(r.top_p > 0.f && r.top_p <= 1.f && r.temperature > 0.f && r.penalty > 0.f,
+                 "gpt_set_sampling_rows: need 0 < top_p <= 1, temperature > 0 and penalty > 0");
+    samples = samples || r.mode == 1;
+    const RowSampling& r0 = rows_host[0];
+    uniform = uniform && r.mode == r0.mode && r.penalty == r0.penalty &&
+              (r.mode == 0 || ((r.top_k < 1 ? 0 : r.top_k) == (r0.top_k < 1 ? 0 : r0.top_k) && r.top_p == r0.top_p && r.temperature == r0.temperature));
+  }
+  ITTS_REQUIRE(!samples || (uniforms_host && n > 0), "gpt_set_sampling_rows: a sampled row needs uniforms");
+  if (uniform) {
+    ITTS_TRY(gpt_set_sampling(rows_host[0].mode, rows_host[0].top_k, rows_host[0].top_p, rows_host[0].temperature, uniforms_host, n));
+  } else {
+    ds.do_sample = 0;  // no scalar sampling beside the table
+    if (samples)
+      sample_uniforms.assign(uniforms_host, uniforms_host + n);
+    else
+      sample_uniforms.clear();
+  }
+  row_table.assign(rows_host, rows_host + B);
+  for (RowSampling& r : row_table) r.top_k = r.top_k < 1 ? 0 : r.top_k;
+  row_table_uniform = uniform;
+  return OK;
+}
+
+// ds.rows [ds.B] <- row_table by the original row of every slot; ds.rows_classes <- the classes those rows hold
+int Engine::upload_row_table(hipStream_t s) {
+  DecodeState& d = ds;
+  ITTS_REQUIRE((int)row_table.size() == d.B0 && d.B >= 1 && d.B <= d.B0 && (d.orig.empty() ? d.B == d.B0 : (int)d.orig.size() == d.B),
+               "per-row sampling table: it does not belong to this generation");
+  if (d.B0 > d.rows_cap) {
+    ITTS_HIP_CHECK(hipStreamSynchronize(s));
+    d.drop_graphs();  // the captured samplers hold the old pointer
+    ITTS_TRY(dev_alloc((void**)&d.rows, (size_t)d.B0 * sizeof(RowSampling)));
+    d.rows_cap = d.B0;
+  }
+  std::vector<RowSampling> tab((size_t)d.B);
+  int classes = 0;
+  for (int b = 0; b < d.B; ++b) {
+    tab[b] = row_table[d.orig.empty() ? b : d.orig[b]];
+    classes |= 1 << row_class(tab[b].mode, tab[b].top_k);
+  }
+  ITTS_HIP_CHECK(hipMemcpyAsync(d.rows, tab.data(), tab.size() * sizeof(RowSampling), hipMemcpyHostToDevice, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));  // tab is a host buffer of this call
+  d.rows_classes = classes;
+  return OK;
+}
+
 // TypicalLogitsWarper(mass) in front of the warpers of the sampling modes (typical_sampling=True, model.py:690-697); 0 = off
 int Engine::gpt_set_typical(float mass) {
   ITTS_REQUIRE(mass == 0.f || (mass > 0.f && mass < 1.f), "gpt_set_typical: `typical_mass` has to be a float > 0 and < 1");
@@ -1296,6 +1382,8 @@ GraphKey Engine::graph_key() const {
   k.top_k = d.top_k;
   k.top_p = d.top_p;
   k.temperature = d.temperature;
+  k.rows_active = d.rows_active;
+  k.rows_classes = d.rows_classes;
   return k;
 }
 
@@ -1497,7 +1585,7 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
   d.orig.resize(n);
   // 3. the sampler reads uniforms[k * B + b]: re-packed to [max_gen][n] by original row
   std::vector<float> u;
-  if (d.do_sample) {
+  if (d.do_sample || (d.rows_active && (d.rows_classes & ~(1 << ROWCLS_GREEDY)))) {
     ITTS_REQUIRE(sample_uniforms.size() >= (size_t)mg * d.B0, "gpt_retire_rows: the uniforms of this generation are gone");
     u.resize((size_t)mg * n);
     for (int q = 0; q < mg; ++q)
@@ -1505,6 +1593,8 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
     ITTS_HIP_CHECK(hipMemcpyAsync(d.uniforms, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
   }
   d.B = n;
+  // 4. the per-row settings travel with their rows, and the classes are those of the rows that are left (GraphKey::rows_classes)
+  if (d.rows_active) ITTS_TRY(upload_row_table(s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   d.drop_graphs();  // every later step re-captures at the smaller row count (GraphKey::B / Bcache)
   if (rows_now) *rows_now = n;
@@ -1516,7 +1606,7 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
 // ([pad.., cond, text, mel] with the pad keys masked exactly like prepare_gpt_inputs' left padding), which fills the
 // MFMA tiles better without changing any row's result.  out = concatenated [sum T_i, D] latents in the engine dtype.
 int Engine::gpt_latent_batch(const float* cond_dev, const int32_t* text_ids, const int* Ls, const int32_t* codes,
-                             const int* Ts, int nseq, void* latent_out, hipStream_t s) {
+                             const int* Ts, int nseq, void* latent_out, hipStream_t s, const int32_t* cond_index, int n_cond) {
   if (!finalized || !gpt.ok) {
     set_error("gpt_latent: GPT weights not bound");
     return E_STATE;
@@ -1542,7 +1632,10 @@ int Engine::gpt_latent_batch(const float* cond_dev, const int32_t* text_ids, con
     RowDesc* r = rd.data() + (size_t)b * Smax;
     int k = 0;
     for (int i = 0; i < pad; ++i) r[k++] = {0, 0, 0, 0};
-    for (int i = 0; i < nl; ++i) r[k++] = {1, i, 0, 0};
+    // conditioning latents: one block for every sentence, or block cond_index[b] of cond [n_cond][nl, D] (several voices in one pass)
+    const int cb = cond_index ? cond_index[b] : 0;
+    ITTS_REQUIRE(cb >= 0 && cb < n_cond, "gpt_latent: conditioning index outside [0, n_cond)");
+    for (int i = 0; i < nl; ++i) r[k++] = {1, cb * nl + i, 0, 0};
     r[k++] = {2, c.start_text_token, 0, 0};
     for (int i = 0; i < L; ++i) {
       const int t = text_ids[to + i];

@@ -38,6 +38,11 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `ragged_vocoder=True` (not in the reference; default off; ITTS_RAGGED_VOCODER=1 / 0 overrides it in both directions) lets the
     sentences of `infer_batch` share vocoder passes although their lengths differ (Engine.bigvgan_grouped(ragged=True)); without
     it only sentences of equal length do.  `infer` / `infer_fast` are not affected.
+  * `mixed_batch=True` (not in the reference; default off; ITTS_MIXED_BATCH=1 / 0 overrides it in both directions) lets the
+    utterances of one `infer_batch` call share decode batches across voices and - with one beam and no typical filter - across
+    sampling settings (`per_utterance`): conditioning and the speaker encoder run once per distinct prompt, every decode row
+    carries its own conditioning latents and its own do_sample / top_k / top_p / temperature / repetition_penalty / seed, the
+    latent pass and the vocoder take one voice per sentence.  `infer` / `infer_fast` are not affected.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -62,7 +67,8 @@ from indextts.utils.front import TextNormalizer, TextTokenizer
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
-                 wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False):
+                 wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
+                 mixed_batch=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -91,6 +97,7 @@ class IndexTTS:
         self.wide_beam_sampler = wide_beam_sampler
         self.retire_rows = retire_rows  # row retirement of the batched generations (Engine.generate); None: ITTS_RETIRE_ROWS, else off
         self.ragged_vocoder = bool(ragged_vocoder)  # infer_batch: sentences of unequal length share vocoder passes (ITTS_RAGGED_VOCODER overrides)
+        self.mixed_batch = bool(mixed_batch)  # infer_batch: one decode batch across voices and sampling settings (ITTS_MIXED_BATCH overrides)
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
         if self.kv_fp8 and not self.is_fp16:
             raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
@@ -186,6 +193,8 @@ class IndexTTS:
         batch, so a group is exactly one `inference_speech` call of the reference)."""
         sample_kw = infer_core.sampling_kwargs(g["do_sample"], g["num_beams"], g["top_k"], g["top_p"], g["temperature"],
                                                g["typical_sampling"], g["typical_mass"], g["length_penalty"])
+        if g.get("seed") is not None and "seed" in sample_kw:
+            sample_kw["seed"] = int(g["seed"])  # infer_batch(per_utterance=[{"seed": ..}]): the caller's seed instead of a drawn one
         cap = max(1, self.engine.ccfg.max_batch // max(1, sample_kw.get("num_beams", 1)))
         rows = []
         for lo in range(0, len(sents), cap):
@@ -279,24 +288,39 @@ class IndexTTS:
 
     @torch.no_grad()
     def infer_batch(self, prompt_mels, texts, output_paths=None, max_text_tokens_per_sentence=120, verbose=False,
-                    **generation_kwargs):
+                    per_utterance=None, **generation_kwargs):
         """Several utterances in one call (the multi-utterance / data-parallel entry point): the sentences of
         all utterances that share a prompt are decoded together in length-sorted batches of up to `max_batch` rows,
         the latent pass is stacked, the vocoder runs per sentence.  Under torch.distributed (one process per GPU) each
         rank should pass its own shard - see itts_hip.dp.run_sharded.  prompt_mels: one tensor for all utterances or a
-        list with one per utterance.  Returns a list of (24000, int16 [n, 1]) or of written paths."""
+        list with one per utterance.  Returns a list of (24000, int16 [n, 1]) or of written paths.
+        per_utterance (optional): a list with one dict of generation kwargs per utterance, on top of **generation_kwargs
+        (plus `seed`: the seed of that utterance's draws instead of one drawn from torch's global RNG).  Utterances then run in
+        groups of equal settings per prompt - or, with mixed_batch on, share decode batches across prompts and settings
+        (_infer_batch_mixed)."""
         n = len(texts)
         prompts = [prompt_mels] * n if isinstance(prompt_mels, torch.Tensor) else list(prompt_mels)
         assert len(prompts) == n and (output_paths is None or len(output_paths) == n)
-        g = self._gen_kwargs(generation_kwargs)
+        assert per_utterance is None or len(per_utterance) == n
+        settings = []
+        for u in range(n):
+            over = dict(per_utterance[u] or {}) if per_utterance is not None else {}
+            seed = over.pop("seed", None)
+            settings.append(dict(self._gen_kwargs(dict(generation_kwargs, **over)), seed=seed))
         start = time.perf_counter()
         utt_sents = [self._sentences_to_ids(t, max_text_tokens_per_sentence) for t in texts]
         results = [None] * n
-        groups = {}
-        for u, p in enumerate(prompts):
-            groups.setdefault(id(p), []).append(u)
+        if {"1": True, "0": False}.get(os.environ.get("ITTS_MIXED_BATCH", ""), self.mixed_batch):
+            with self.engine.lock:
+                self._infer_batch_mixed(prompts, utt_sents, settings, results)
+            groups = {}
+        else:
+            groups = {}  # utterances of one prompt and one setting, in the order of their first utterance
+            for u, p in enumerate(prompts):
+                groups.setdefault((id(p), tuple(sorted(settings[u].items(), key=lambda kv: kv[0]))), []).append(u)
         with self.engine.lock:
             for us in groups.values():
+                g = settings[us[0]]
                 mel = self._prompt(prompts[us[0]], None)
                 spk = self.engine.ecapa(mel.transpose(1, 2), overlap=True)
                 cond = self.gpt.get_conditioning(mel)
@@ -323,6 +347,85 @@ class IndexTTS:
                 raise RuntimeError(f"IndexTTS.infer_batch: utterance {u} produced no sentences (empty input)")
             out.append(self._finish(results[u], output_paths[u] if output_paths else None, start, (0, 0, 0), False, "batch "))
         return out
+
+    def _infer_batch_mixed(self, prompts, utt_sents, settings, results):
+        """infer_batch with mixed_batch on: utterances share decode batches whatever their voice, and - with one beam and no
+        typical filter - whatever their sampling settings (infer_core.mixed_groups).  Conditioning and the speaker encoder run
+        once per distinct prompt object; a decode row carries its prompt's conditioning latents (per-row cond of the prefill) and
+        its utterance's entry of the per-row table (Engine.generate with sequences); the latent pass reads its voice through
+        cond_index, the vocoder takes one speaker embedding per sentence.  A row's codes, latent and waveform are those of a
+        call in which every utterance carries that row's prompt and settings.  results[u] <- the int16-range wave parts."""
+        voice, conds, spks = {}, [], []  # id(prompt) -> index; conditioning [1, latents, D] and speaker embedding [1, E] per voice
+        for p in prompts:
+            if id(p) not in voice:
+                voice[id(p)] = len(conds)
+                mel = self._prompt(p, None)
+                spks.append(self.engine.ecapa(mel.transpose(1, 2)))
+                conds.append(self.gpt.get_conditioning(mel))
+        nl, D = self.engine.ccfg.cond_latents, self.engine.ccfg.model_dim
+        cond_all = torch.cat([c.reshape(1, nl, D).float() for c in conds], 0)  # [voices, latents, D]
+        spk_all = torch.cat([s.reshape(1, -1) for s in spks], 0)
+        ragged = {"1": True, "0": False}.get(os.environ.get("ITTS_RAGGED_VOCODER", ""), self.ragged_vocoder)
+        for us in infer_core.mixed_groups(settings):
+            flat = [(u, k, s) for u in us for k, s in enumerate(utt_sents[u])]
+            if not flat:
+                continue
+            g0 = settings[us[0]]
+            kws = {}  # Engine.generate keywords of every utterance of the group (its seed drawn here, in utterance order)
+            for u in us:
+                g = settings[u]
+                kw = infer_core.sampling_kwargs(g["do_sample"], g["num_beams"], g["top_k"], g["top_p"], g["temperature"],
+                                                g["typical_sampling"], g["typical_mass"], g["length_penalty"])
+                if g.get("seed") is not None:
+                    kw["seed"] = int(g["seed"])
+                kws[u] = kw
+            shared = {k: v for k, v in kws[us[0]].items() if k in ("num_beams", "typical_mass", "length_penalty")}
+            per_row = shared.get("num_beams", 1) == 1 and not shared.get("typical_mass")
+            order = sorted(range(len(flat)), key=lambda i: (len(flat[i][2]), i))  # length-sorted decode batches
+            cap = max(1, self.engine.ccfg.max_batch // max(1, shared.get("num_beams", 1)))
+            code_rows = [None] * len(flat)
+            for lo in range(0, len(order), cap):
+                sel = order[lo:lo + cap]
+                ids = infer_core.pad_tokens_cat([flat[i][2] for i in sel], self.cfg.gpt.stop_text_token)
+                vs = [voice[id(prompts[flat[i][0]])] for i in sel]
+                cond = cond_all[vs[0]] if len(set(vs)) == 1 else cond_all[vs]  # one voice: the shared-cond prefill, as without the switch
+                if per_row:
+                    row = lambda name, default: [kws[flat[i][0]].get(name, default) for i in sel]  # noqa: E731
+                    # a sentence's draws: its utterance's seed and its own index in the utterance, whoever shares the batch
+                    seeds = [(int(kws[flat[i][0]].get("seed", 0)) * 1000003 + flat[i][1]) % (2 ** 63) for i in sel]
+                    kw = dict(do_sample=row("do_sample", False), top_k=row("top_k", 0), top_p=row("top_p", 1.0),
+                              temperature=row("temperature", 1.0), seed=seeds,
+                              repetition_penalty=[settings[flat[i][0]]["repetition_penalty"] for i in sel])
+                else:  # beams / typical filtering: the group shares every setting (mixed_groups), the voices still differ per row
+                    kw = dict(kws[us[0]], repetition_penalty=g0["repetition_penalty"])
+                codes = self.engine.generate(cond, ids, g0["max_mel_tokens"], wide_sampler=self.wide_sampler,
+                                             wide_beam_sampler=self.wide_beam_sampler, retire_rows=self.retire_rows, **kw)
+                for j, i in enumerate(sel):
+                    code_rows[i] = codes[j]
+            if any(r[-1] != self.stop_mel_token for r in code_rows):
+                warnings.warn(f"WARN: generation stopped due to exceeding `max_mel_tokens` ({g0['max_mel_tokens']}). "
+                              "Consider reducing `max_text_tokens_per_sentence` or increasing `max_mel_tokens`.", RuntimeWarning)
+            clean = []
+            for r in code_rows:
+                c, m = infer_core.remove_long_silence(np.asarray(r)[None], self.stop_mel_token)
+                clean.append(c[0, : int(m[0])])
+            # Latent pass and vocoder: one batch per UTTERANCE (its sentences, its voice through cond_index / per-row spk).  A decode
+            # row has the same bits whoever shares its batch; these two stages do not - the latent pass left-pads a batch to its
+            # longest sequence, which moves the key tiles of the prefill attention, and the vocoder's few-tile GEMMs choose their
+            # tiles by the row count (INTEGRATION.md) - so batches across utterances would make a request's waveform depend, in
+            # its last bits, on the requests it happened to be served with (measured on the micro checkpoint: latents 1e-6,
+            # 2.5 % of the int16 samples one unit apart).  The decode steps are where the rows pay; these passes run once.
+            cap = self.engine.ccfg.max_batch
+            for u in us:
+                idx = [i for i, f in enumerate(flat) if f[0] == u]
+                if not idx:
+                    continue
+                v = [voice[id(prompts[u])]] * len(idx)
+                lats = []
+                for lo in range(0, len(idx), cap):
+                    sel = idx[lo:lo + cap]
+                    lats.extend(self.engine.latent_batch(cond_all, [flat[i][2] for i in sel], [clean[i] for i in sel], cond_index=v[:len(sel)]))
+                results[u] = [self._to_int16_range(w) for w in self.engine.bigvgan_grouped(lats, spk_all[v], ragged=ragged)]
 
     def _prompt(self, prompt_mel, audio_prompt):
         if prompt_mel is None and audio_prompt is None:

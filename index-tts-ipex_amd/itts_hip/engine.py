@@ -252,6 +252,19 @@ class Engine:
         self._ck(self.lib.itts_gpt_set_sampling(self.h, 1, int(top_k), float(top_p), float(temperature),
                                                u.ctypes.data_as(C.c_void_p), u.size), "gpt_set_sampling")
 
+    def set_sampling_rows(self, table, uniforms: Optional[np.ndarray] = None):
+        """Mixed batch: one (mode, top_k, top_p, temperature, penalty) entry per row for the following single-beam generations
+        (itts_gpt_set_sampling_rows; infer_core.row_sampling_table builds the table); uniforms [max_gen, B] are needed when any
+        row samples.  Every row's penalty replaces prefill's repetition_penalty.  A table whose rows are all equal is the scalar
+        setting (set_sampling) with those values.  None / empty clears the table."""
+        if not table:
+            self._ck(self.lib.itts_gpt_set_sampling_rows(self.h, None, 0, None, 0), "gpt_set_sampling_rows")
+            return
+        tab = (L.RowSampling * len(table))(*[L.RowSampling(int(m), int(k), float(p), float(t), float(pen)) for m, k, p, t, pen in table])
+        u = None if uniforms is None else np.ascontiguousarray(uniforms, dtype=np.float32)
+        self._ck(self.lib.itts_gpt_set_sampling_rows(self.h, tab, len(table), None if u is None else u.ctypes.data_as(C.c_void_p),
+                                                    0 if u is None else u.size), "gpt_set_sampling_rows")
+
     def set_beam_sample(self, num_beams: int, top_k: int = 30, top_p: float = 0.8, temperature: float = 1.0,
                         uniforms: Optional[np.ndarray] = None, do_sample: bool = True, length_penalty: float = 0.0,
                         num_return_sequences: int = 1, host: bool = False):
@@ -371,7 +384,37 @@ class Engine:
         better place to be, and it cannot follow a retirement).  Same codes within one projection-kernel family; across families
         (e.g. 12 -> 3 rows) within the project's cross-family bound.  None: the environment's ITTS_RETIRE_ROWS, else off.
         Suggested value: 0.5 - measured with tools/bench_row_retire.py (profiles/row_retire.txt): 64 ragged
-        rows decode 1.18 x faster at 0.5 and 1.19 x at 0.75; 20 rows with fp8 weights gain nothing at 0.5 and lose 3 % at 0.75."""
+        rows decode 1.18 x faster at 0.5 and 1.19 x at 0.75; 20 rows with fp8 weights gain nothing at 0.5 and lose 3 % at 0.75.
+        Mixed batches: do_sample, top_k, top_p, temperature, repetition_penalty and seed also take a sequence of length B, one
+        entry per row (single beam, no typical filter: ValueError otherwise).  Entries that are all equal - with one seed - are the
+        scalar request, on today's path.  Otherwise every row chooses its tokens with its own entry (infer_core.row_sampling_table,
+        itts_gpt_set_sampling_rows) and gets the codes of a generation of the same rows in which every row carries that entry.
+        With per-row seeds column b of the draws is np.random.default_rng(seed[b]).random(max_gen, dtype=float32): a row's draws
+        do not depend on who shares its batch.  In a table that is not uniform a row with top_k outside 1 .. 128 always runs on
+        the device's whole-vocabulary sampler - the host path cannot mix - whatever wide_sampler says."""
+        rows = None
+        per_row = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty)
+        if any(isinstance(v, (list, tuple, np.ndarray)) for v in list(per_row.values()) + [seed]):
+            from . import infer_core
+
+            if num_beams > 1 or typical_mass:
+                raise ValueError("per-row sampling settings run with one beam and without typical filtering only")
+            nrow = np.asarray(text_ids).shape[0]
+            table = infer_core.row_sampling_table(nrow, **per_row)
+            seeds = list(seed) if isinstance(seed, (list, tuple, np.ndarray)) else [seed] * nrow
+            if len(seeds) != nrow:
+                raise ValueError(f"seed has {len(seeds)} entries for {nrow} rows")
+            one_seed = all(s == seeds[0] for s in seeds)
+            if uniforms is None and not one_seed and any(r[0] for r in table):
+                uniforms = infer_core.row_uniforms(seeds, max_gen)
+            seed = seeds[0]
+            if all(r == table[0] for r in table):  # the scalar request
+                mode, top_k, top_p, temperature, repetition_penalty = table[0]
+                do_sample = bool(mode)
+            else:
+                if uniforms is None and any(r[0] for r in table):
+                    uniforms = np.random.default_rng(seed).random((max_gen, nrow), dtype=np.float32)
+                rows, do_sample, repetition_penalty = table, False, table[0][4]
         if retire_rows is None:
             retire_rows = float(os.environ.get("ITTS_RETIRE_ROWS") or 0.0)
         retire_rows = float(retire_rows)
@@ -387,7 +430,7 @@ class Engine:
             raise ValueError(f"wide_beam_sampler must be 'host' or 'device', not {wide_beam_sampler!r}")
         kw = dict(retire_rows=retire_rows, wide_sampler=wide_sampler, wide_beam_sampler=wide_beam_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, uniforms=uniforms, num_beams=num_beams,
-                  typical_mass=typical_mass, length_penalty=length_penalty, num_return_sequences=num_return_sequences)
+                  typical_mass=typical_mass, length_penalty=length_penalty, num_return_sequences=num_return_sequences, rows=rows)
         try:
             return self._generate_once(cond, text_ids, max_gen, **kw)
         except L.HandoffTimeout as e:
@@ -399,7 +442,8 @@ class Engine:
 
     def _generate_once(self, cond, text_ids, max_gen, repetition_penalty, suppress_stop, check_every, do_sample, top_k, top_p,
                        temperature, seed, uniforms, num_beams, typical_mass, length_penalty, num_return_sequences,
-                       wide_sampler="host", wide_beam_sampler="host", retire_rows=0.0) -> np.ndarray:
+                       wide_sampler="host", wide_beam_sampler="host", retire_rows=0.0, rows=None) -> np.ndarray:
+        """rows: the per-row table of a mixed batch (generate; do_sample is False then and the scalar settings are not read)."""
         beams = num_beams > 1
         if num_return_sequences != 1 and not beams:
             raise ValueError("num_return_sequences > 1 without beams: repeat the rows (indextts/gpt/model.py does, as HF does)")
@@ -429,6 +473,8 @@ class Engine:
                 uniforms = np.random.default_rng(seed).random((max_gen, nrow), dtype=np.float32)
             self.set_sampling(True, top_k, top_p, temperature, uniforms)
         try:
+            if rows is not None:
+                self.set_sampling_rows(rows, uniforms)
             self.prefill(cond, text_ids, max_gen, repetition_penalty, suppress_stop)
             done = 1
             while done < max_gen:
@@ -454,6 +500,8 @@ class Engine:
                 self.set_beam_sample(1)
             elif do_sample:
                 self.set_sampling(False)
+            if rows is not None:
+                self.set_sampling_rows(None)
         # HF stops right after the step in which the last running row emitted stop: trim the look-ahead steps
         stop = self.ccfg.stop_mel_token
         n = 0
@@ -563,8 +611,10 @@ class Engine:
         self._exit()
         return out
 
-    def latent_batch(self, cond: torch.Tensor, texts, codes) -> List[torch.Tensor]:
-        """Several sentences in one pass -> list of latents [1, T_i, D] (views of one buffer)."""
+    def latent_batch(self, cond: torch.Tensor, texts, codes, cond_index=None) -> List[torch.Tensor]:
+        """Several sentences in one pass -> list of latents [1, T_i, D] (views of one buffer).  cond_index (optional, one int per
+        sentence): cond holds several conditioning blocks [n_cond, latents, D] and sentence i reads block cond_index[i] - several
+        voices in one pass, each sentence with the bits of the pass over its own voice alone."""
         ts = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in texts]
         cs = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in codes]
         tl = np.asarray([t.shape[0] for t in ts], dtype=np.int32)
@@ -573,10 +623,20 @@ class Engine:
         cond = cond.to(device=self.device, dtype=torch.float32).contiguous().view(-1, self.ccfg.model_dim)
         out = torch.empty(int(cl.sum()), self.ccfg.model_dim, dtype=self.tdt, device=self.device)
         self._enter()
-        self._ck(self.lib.itts_gpt_latent_batch(self.h, cond.data_ptr(), tcat.ctypes.data_as(C.c_void_p),
-                                               tl.ctypes.data_as(C.c_void_p), ccat.ctypes.data_as(C.c_void_p),
-                                               cl.ctypes.data_as(C.c_void_p), len(ts), out.data_ptr(), self._s()),
-                "gpt_latent_batch")
+        if cond_index is None:
+            self._ck(self.lib.itts_gpt_latent_batch(self.h, cond.data_ptr(), tcat.ctypes.data_as(C.c_void_p),
+                                                   tl.ctypes.data_as(C.c_void_p), ccat.ctypes.data_as(C.c_void_p),
+                                                   cl.ctypes.data_as(C.c_void_p), len(ts), out.data_ptr(), self._s()),
+                    "gpt_latent_batch")
+        else:
+            ci = np.ascontiguousarray(cond_index, dtype=np.int32).reshape(-1)
+            n_cond, rem = divmod(cond.shape[0], self.ccfg.cond_latents)
+            if rem or ci.shape[0] != len(ts):
+                raise ValueError(f"latent_batch: cond {tuple(cond.shape)} / {ci.shape[0]} indices for {len(ts)} sentences")
+            self._ck(self.lib.itts_gpt_latent_batch_cond(self.h, cond.data_ptr(), ci.ctypes.data_as(C.c_void_p), n_cond,
+                                                        tcat.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                        ccat.ctypes.data_as(C.c_void_p), cl.ctypes.data_as(C.c_void_p), len(ts),
+                                                        out.data_ptr(), self._s()), "gpt_latent_batch_cond")
         self._exit()
         res, o = [], 0
         for n in cl:
@@ -637,7 +697,8 @@ class Engine:
     def bigvgan_grouped(self, lats: List[torch.Tensor], spk: torch.Tensor, ragged: bool = False,
                         max_pad: float = 0.1) -> List[torch.Tensor]:
         """Vocoder over several sentences: latents [1, T_i, D] of EQUAL length share one batched launch sequence (rows of
-        a batch are independent, so each result equals its batch-1 run); ragged lengths cannot be padded - the convs
+        a batch are independent, so each result equals its batch-1 run).  spk: one embedding [E] / [1, E] for all of them, or
+        [n, E], one per latent (several voices in one pass); ragged lengths cannot be padded - the convs
         would see conv_pre(0) = bias instead of zero "same" padding - and go in groups of their own.
         ragged=True (opt-in): rows of unequal length share a pass too (bigvgan_ragged, which masks what plain padding gets
         wrong), grouped by infer_core.ragged_groups so that at most max_pad of a batch's frames are padding; a group of one or
@@ -645,6 +706,13 @@ class Engine:
         values tools/bench_ragged_vocoder.py measured (64 latents of 275 .. 544 frames, bf16, profiles/ragged_vocoder.txt: 1.81 x
         the 64 batch-1 runs at 0.1, 1.64 x at 0.25, 1.65 x at 0.5 - more padding is more frames computed)."""
         cap = max(1, int(self.ccfg.max_batch))
+        spk = spk.reshape(-1, spk.shape[-1])
+        if spk.shape[0] not in (1, len(lats)):
+            raise ValueError(f"bigvgan_grouped: {spk.shape[0]} speaker embeddings for {len(lats)} latents (one, or one per latent)")
+
+        def spk_of(sel):  # [len(sel), E]: the one embedding for every row, or each latent's own
+            return (spk.expand(len(sel), -1) if spk.shape[0] == 1 else spk[list(sel)]).contiguous()
+
         if ragged:
             from . import infer_core
 
@@ -653,10 +721,10 @@ class Engine:
             for sel in infer_core.ragged_groups(lens, max_pad, cap):
                 sub = [lats[i] for i in sel]
                 if len({lens[i] for i in sel}) == 1:
-                    wav = self.bigvgan(torch.cat(sub, 0), spk.view(1, -1).expand(len(sel), -1).contiguous())
+                    wav = self.bigvgan(torch.cat(sub, 0), spk_of(sel))
                     wavs = [wav[j:j + 1] for j in range(len(sel))]
                 else:
-                    wavs = self.bigvgan_ragged(sub, spk.view(1, -1))
+                    wavs = self.bigvgan_ragged(sub, spk_of(sel))
                 for i, w in zip(sel, wavs):
                     res[i] = w
             return res
@@ -667,7 +735,7 @@ class Engine:
         for T, idx in groups.items():
             for lo in range(0, len(idx), cap):
                 sel = idx[lo:lo + cap]
-                wav = self.bigvgan(torch.cat([lats[i] for i in sel], 0), spk.view(1, -1).expand(len(sel), -1).contiguous())
+                wav = self.bigvgan(torch.cat([lats[i] for i in sel], 0), spk_of(sel))
                 for j, i in enumerate(sel):
                     out[i] = wav[j:j + 1]
         return out

@@ -141,6 +141,65 @@ def sampling_kwargs(do_sample, num_beams, top_k, top_p, temperature, typical_sam
                 seed=int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
 
 
+# ---- mixed decode batches: which utterances may share a generation, and the per-row table of one ----
+MIXED_SHARED = ("num_beams", "typical_sampling", "typical_mass", "length_penalty", "max_mel_tokens")
+MIXED_PER_ROW = ("do_sample", "top_k", "top_p", "temperature", "repetition_penalty")
+
+
+def _is_seq(x) -> bool:
+    return isinstance(x, (list, tuple, np.ndarray))
+
+
+def mixed_groups(settings: Sequence[dict]) -> List[List[int]]:
+    """Index lists of the utterances that may share one generation (IndexTTS.infer_batch, mixed_batch): settings[u] holds the
+    generation kwargs of utterance u (IndexTTS._gen_kwargs).  A generation has one num_beams, one typical filter, one
+    length_penalty and one max_mel_tokens, so those are the key; do_sample / top_k / top_p / temperature / repetition_penalty
+    are per row - except under beams or typical filtering, which have no per-row form: there the key holds them as well.
+    The voice never is part of the key.  Groups in the order of their first utterance, indices ascending."""
+    groups: Dict[tuple, List[int]] = {}
+    for u, g in enumerate(settings):
+        nb = max(1, int(g.get("num_beams") or 1))
+        typical = bool(g.get("typical_sampling", False))
+        key = (nb, typical, float(g.get("typical_mass", 0.9)) if typical else 0.0, float(g.get("length_penalty") or 0.0),
+               int(g.get("max_mel_tokens", 600)))
+        if nb > 1 or typical:
+            key += row_sampling_table(1, *(g.get(k, d) for k, d in zip(MIXED_PER_ROW, (True, 30, 0.8, 1.0, 10.0))))[0]
+        groups.setdefault(key, []).append(u)
+    return list(groups.values())
+
+
+def row_sampling_table(B: int, do_sample, top_k, top_p, temperature, repetition_penalty) -> List[tuple]:
+    """The per-row table of a mixed batch of B rows: every argument a scalar (all rows) or a sequence of length B.
+    -> [(mode, top_k, top_p, temperature, penalty)] * B in the form of itts_row_sampling, normalised as sampling_kwargs does it:
+    mode 1 = sample, 0 = greedy; top_k None / < 1 -> 0 (TopK warper off); top_p None -> 1, clipped to [1e-6, 1]; temperature
+    None / 0 -> 1.  A greedy row reads none of the three, so it carries (0, 1.0, 1.0): equal rows compare equal."""
+    cols = []
+    for name, v in zip(MIXED_PER_ROW, (do_sample, top_k, top_p, temperature, repetition_penalty)):
+        v = list(v) if _is_seq(v) else [v] * B
+        if len(v) != B:
+            raise ValueError(f"row_sampling_table: {name} has {len(v)} entries for {B} rows")
+        cols.append(v)
+    table = []
+    for ds, k, p, t, pen in zip(*cols):
+        pen = float(pen)
+        t = float(t or 1.0)
+        if not pen > 0.0 or not t > 0.0:
+            raise ValueError(f"row_sampling_table: temperature and repetition_penalty have to be > 0, not {t!r}, {pen!r}")
+        if not ds:
+            table.append((0, 0, 1.0, 1.0, pen))
+            continue
+        k = int(k) if k else 0
+        p = 1.0 if p is None else float(p)
+        table.append((1, k if k >= 1 else 0, min(max(p, 1e-6), 1.0), t, pen))
+    return table
+
+
+def row_uniforms(seeds: Sequence, max_gen: int) -> np.ndarray:
+    """Draws [max_gen, B] of a batch whose row b has its own seed: column b is default_rng(seeds[b]).random(max_gen) - what the
+    request would draw alone, whoever shares its batch and whichever row it sits in."""
+    return np.stack([np.random.default_rng(s).random(max_gen, dtype=np.float32) for s in seeds], axis=1)
+
+
 # ---- host-side token choice (HF GenerationMixin.sample over the whole vocabulary) ----
 def host_distribution(scores: np.ndarray, seen_ids, penalty: float, temperature: float, top_k: int, top_p: float,
                       typical_mass: float, stop: int, suppress_stop: bool, min_keep: int = 1, log_softmax_first: bool = False,

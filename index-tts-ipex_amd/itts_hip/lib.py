@@ -94,6 +94,11 @@ class SamplerStepArgs(C.Structure):
                [(n, f32) for n in ("penalty", "top_p", "temperature")]
 
 
+class RowSampling(C.Structure):
+    """itts_row_sampling: one row of a mixed decode batch (mode 0 greedy / 1 sample)."""
+    _fields_ = [("mode", i32), ("top_k", i32), ("top_p", f32), ("temperature", f32), ("penalty", f32)]
+
+
 _lib = None
 _lib_f16 = None
 
@@ -137,6 +142,9 @@ _PROTOS = {
     "itts_beam_step": (i32, [C.POINTER(BeamStepArgs), vp]),
     "itts_typical_rows": (i32, [C.POINTER(TypicalArgs), vp]),
     "itts_sampler_step": (i32, [C.POINTER(SamplerStepArgs), vp]),
+    "itts_sampler_step_rows": (i32, [C.POINTER(SamplerStepArgs), C.POINTER(RowSampling), vp, vp]),
+    "itts_gpt_set_sampling_rows": (i32, [vp, C.POINTER(RowSampling), i32, vp, i64]),
+    "itts_gpt_latent_batch_cond": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
     "itts_engine_create": (i32, [C.POINTER(Config), C.POINTER(vp)]),
     "itts_engine_destroy": (None, [vp]),
     "itts_engine_bind_tensor": (i32, [vp, C.c_char_p, vp, i32, i32, C.POINTER(i64)]),
