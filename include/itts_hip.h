@@ -579,6 +579,65 @@ int itts_rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stri
  * in ascending order; live rows below n keep their slot.  src_host / dst_host hold up to B entries. */
 int itts_retire_plan(const int* unfinished_host, int B, int* n_live, int* src_host, int* dst_host, int* n_moves);
 
+/* Row admission into a running batched generation (opt-in; nothing changes for a caller that never calls it).  A token step costs
+ * almost the same at every row count, so a slot whose row has finished is better given to the next waiting request than carried
+ * to the end of the slowest row.  itts_gpt_admit_rows synchronises, takes the n lowest finished slots (finished: unfinished == 0 or
+ * len >= max_gen; itts_admit_plan), keeps their rows' codes and last logits on the host, prefills the n new requests in scratch
+ * with the prefill's kernels, writes their K/V into the slots (itts_kv_admit), resets the slots' state (itts_rows_admit) and
+ * chooses their first token - the running rows are neither stepped nor touched.  The following itts_gpt_decode steps carry the
+ * new rows with len = 0; within one projection-kernel family a row's codes and logits are those of a fresh generation.
+ *   cond fp32 [cond_rows][latents, D] on the device, cond_rows = 1 (shared) or n; text_ids_host int32 [n][L], L the running
+ *   generation's own (a shorter text is padded with stop ids and left-padded as in the prefill);
+ *   rows_host [n] or null: in a table generation (itts_gpt_set_sampling_rows, see itts_gpt_keep_row_table) each row's own
+ *   settings (null: greedy with the generation's penalty) - a class that was not present re-captures the step, any other
+ *   admission keeps the captured step; a scalar generation admits only rows with its own settings (null: those);
+ *   uniforms_host [n][max_gen]: the draws of the sampled rows (row-major per new row);
+ *   forced_host int32 [n][n_forced] or null (-1 = free): needs a generation that was started with forced tokens;
+ *   slots_host [n] (optional) receives the slots.
+ * The new rows become original rows B0, B0 + 1, ..: itts_gpt_fetch then returns all B0 rows (itts_gpt_rows_total) in that order,
+ * a replaced row with its codes followed by the stop token and its last logits.  itts_gpt_status still counts slots;
+ * itts_gpt_row_status answers per slot.  Refused with a message before anything is changed: no active generation, beams,
+ * typical filtering, host sampling, `input_tokens`, the fused qkv + attention launch, a step on the persistent engine (<= 6
+ * rows), after a retirement, fewer finished slots than n, n > 128, a text id out of range, L not the generation's, an entry the
+ * prefill would refuse, uniforms missing for a sampled row, a sampled row in a generation without room for draws.
+ * Additions to ABI 4 (the version stays): itts_gpt_admit_rows, itts_gpt_row_status, itts_gpt_rows_total, itts_gpt_graph_captures,
+ * itts_gpt_keep_row_table, itts_kv_admit, itts_rows_admit, itts_admit_plan. */
+int itts_gpt_admit_rows(itts_engine* e, const float* cond, int cond_rows, const int32_t* text_ids_host, int n, int L,
+                        const itts_row_sampling* rows_host, const float* uniforms_host, const int32_t* forced_host, int n_forced,
+                        int32_t* slots_host, itts_stream stream);
+/* Per slot of the active generation (host int32 [itts_gpt_rows] each, any may be null): the original row it holds, its tokens so
+ * far, whether it is unfinished.  Synchronises. */
+int itts_gpt_row_status(itts_engine* e, int32_t* orig_host, int32_t* len_host, int32_t* unfinished_host, itts_stream stream);
+/* Rows itts_gpt_fetch returns: the prefill's batch plus every admitted row (0 without an active generation). */
+int itts_gpt_rows_total(itts_engine* e);
+/* Times this engine object has captured its decode step so far (a replayed step does not count): what tells an admission that
+ * kept the captured step from one that re-captured. */
+int itts_gpt_graph_captures(itts_engine* e);
+/* on = 1: the following prefills keep a per-row table that is uniform as a table generation (one sampler launch per class, room
+ * for draws) instead of the scalar path, so that it can admit rows of other settings.  itts_gpt_set_sampling_rows is unchanged. */
+int itts_gpt_keep_row_table(itts_engine* e, int on);
+
+/* Operator entry of kv_admit_kernel on caller memory: the k and v thirds of qkv [n][S][3 * H * dh] (type tq) -> positions 0 .. S - 1
+ * of rows slots_host[i] of kc / vc [Bcache][H][Smax][dh] (type tc), the bytes itts_kv_scatter writes for the same rows; nothing else
+ * is written.  16 bytes per lane (8 into an e4m3 cache).  ITTS_E_INVALID before any HIP call for: null pointers, n outside
+ * [1, 128], S / H / dh / Smax / Bcache < 1, S > Smax, a type pair itts_kv_scatter refuses, dh no multiple of 8 (4: fp32 cache),
+ * qkv not 16-byte aligned, a cache not 16-byte (e4m3: 8-byte) aligned, a slot outside [0, Bcache), a slot twice. */
+int itts_kv_admit(void* kc, void* vc, const void* qkv, int n, int S, int H, int dh, int Smax, int Bcache, int tq, int tc,
+                  const int* slots_host, itts_stream stream);
+/* Operator entry of rows_admit_kernel on caller memory: the state of a fresh generation for n slots of B - seen [B][V] bytes
+ * (1 at fake_id and start_tok), unfinished = 1, cur_tok = start_tok, len = 0, kv_start = kv_start_host[i], the ids row filled with
+ * stop, the forced row (forced null: skipped; forced_src [n][max_gen] device or null: -1) and, uniforms_src [n][max_gen] given,
+ * column slot of uniforms [max_gen][B].  No other slot is written. */
+typedef struct {
+  void *seen, *unfinished, *cur_tok, *len, *kv_start, *ids, *forced, *uniforms;
+  const void *forced_src, *uniforms_src;
+  const int *slots_host, *kv_start_host; /* [n] */
+  int n, B, V, max_gen, fake_id, start_tok, stop;
+} itts_rows_admit_args;
+int itts_rows_admit(const itts_rows_admit_args* args, itts_stream stream);
+/* The slot choice alone (host only): the min(n, *n_free) lowest finished slots in ascending order, *n_free = all finished slots. */
+int itts_admit_plan(const int* unfinished_host, const int* len_host, int B, int max_gen, int n, int* slots_host, int* n_free);
+
 /* G8  UnifiedVoice.forward(return_latent=True) for one sentence (model.py:521-589):
  * text ids host [L], codes host [T] -> latent [T, D] in the engine dtype. */
 int itts_gpt_latent(itts_engine* e, const float* cond, const int32_t* text_ids_host, int L, const int32_t* codes_host,

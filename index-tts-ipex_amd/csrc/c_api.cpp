@@ -322,6 +322,43 @@ int itts_retire_plan(const int* unfinished_host, int B, int* n_live, int* src_ho
   return retire_plan(unfinished_host, B, n_live, src_host, dst_host, n_moves);
 }
 
+int itts_kv_admit(void* kc, void* vc, const void* qkv, int n, int S, int H, int dh, int Smax, int Bcache, int tq, int tc,
+                  const int* slots_host, itts_stream stream) {
+  // refused before any HIP call
+  ITTS_TRY(kv_admit_check(kc, vc, qkv, n, S, H, dh, Smax, Bcache, tq, tc, slots_host));
+  (void)hipGetLastError();
+  return kv_admit(kc, vc, qkv, n, S, H, dh, Smax, Bcache, tq, tc, slots_host, (hipStream_t)stream);
+}
+
+int itts_rows_admit(const itts_rows_admit_args* p, itts_stream stream) {
+  ITTS_REQUIRE(p, "itts_rows_admit: null argument block");
+  RowsAdmitArgs a;
+  a.seen = (uint8_t*)p->seen;
+  a.unfinished = (int*)p->unfinished;
+  a.cur_tok = (int*)p->cur_tok;
+  a.len = (int*)p->len;
+  a.kv_start = (int*)p->kv_start;
+  a.ids = (int*)p->ids;
+  a.forced = (int*)p->forced;
+  a.uniforms = (float*)p->uniforms;
+  a.forced_src = (const int*)p->forced_src;
+  a.uniforms_src = (const float*)p->uniforms_src;
+  a.n = p->n;
+  a.B = p->B;
+  a.V = p->V;
+  a.max_gen = p->max_gen;
+  a.fake_id = p->fake_id;
+  a.start_tok = p->start_tok;
+  a.stop = p->stop;
+  ITTS_TRY(rows_admit_check(a, p->slots_host, p->kv_start_host));  // refused before any HIP call
+  (void)hipGetLastError();
+  return rows_admit(a, p->slots_host, p->kv_start_host, (hipStream_t)stream);
+}
+
+int itts_admit_plan(const int* unfinished_host, const int* len_host, int B, int max_gen, int n, int* slots_host, int* n_free) {
+  return admit_plan(unfinished_host, len_host, B, max_gen, n, slots_host, n_free);
+}
+
 int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
                      int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
                      void* scratch, size_t scratch_bytes, itts_stream stream) {
@@ -908,6 +945,23 @@ int itts_gpt_retire_rows(itts_engine* e, int* rows_now_host, itts_stream s) {
   return e->e.gpt_retire_rows(rows_now_host, (hipStream_t)s);
 }
 int itts_gpt_rows(itts_engine* e) { return e ? (e->e.ds.active ? e->e.ds.B : 0) : -1; }
+int itts_gpt_admit_rows(itts_engine* e, const float* cond, int cond_rows, const int32_t* text_ids_host, int n, int L,
+                        const itts_row_sampling* rows_host, const float* uniforms_host, const int32_t* forced_host, int n_forced,
+                        int32_t* slots_host, itts_stream s) {
+  ENG(e);
+  return e->e.gpt_admit_rows(cond, cond_rows, text_ids_host, n, L, (const RowSampling*)rows_host, uniforms_host, forced_host, n_forced,
+                             slots_host, (hipStream_t)s);
+}
+int itts_gpt_row_status(itts_engine* e, int32_t* orig_host, int32_t* len_host, int32_t* unfinished_host, itts_stream s) {
+  ENG(e);
+  return e->e.gpt_row_status(orig_host, len_host, unfinished_host, (hipStream_t)s);
+}
+int itts_gpt_graph_captures(itts_engine* e) { return e ? e->e.ds.graph_captures : -1; }
+int itts_gpt_rows_total(itts_engine* e) { return e ? (e->e.ds.active ? e->e.ds.B0 : 0) : -1; }
+int itts_gpt_keep_row_table(itts_engine* e, int on) {
+  ENG(e);
+  return e->e.gpt_keep_row_table(on);
+}
 int itts_gpt_latent(itts_engine* e, const float* cond, const int32_t* text_ids_host, int L, const int32_t* codes_host,
                     int T, void* latent_out, itts_stream s) {
   ENG(e);

@@ -445,6 +445,46 @@ int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s) {
   return OK;
 }
 
+// One row's token choice (row admission, Engine::gpt_admit_rows): the same kernels with a grid of one block on an argument block
+// whose per-row pointers start at the slot, so block 0 is that row.  uniforms[k * a.B + 0] of the advanced base is
+// uniforms[k * B + slot] of the batch.  a.rows set: the <true> instantiations, which read the slot's own entry.
+int sampler_slot_step(const SamplerArgs& a0, int slot, int cls, hipStream_t s) {
+  ITTS_REQUIRE(slot >= 0 && slot < a0.B && cls >= ROWCLS_GREEDY && cls <= ROWCLS_WIDE, "sampler: slot outside the batch, or no such class");
+  SamplerArgs a = a0;
+  a.logits += (size_t)slot * a.V;
+  a.seen += (size_t)slot * a.V;
+  a.ids += (size_t)slot * a.max_gen;
+  a.cur_tok += slot;
+  a.unfinished += slot;
+  a.step += slot;
+  if (a.h_next) a.h_next += (size_t)slot * a.D;
+  if (a.forced) a.forced += (size_t)slot * a.max_gen;
+  if (a.uniforms) a.uniforms += slot;
+  if (a.kept) a.kept += slot;
+  if (a.rows) a.rows += slot;
+  const bool rows = a.rows != nullptr;
+  if (cls == ROWCLS_GREEDY) {
+    if (rows) hipLaunchKernelGGL(sampler2_kernel<true>, dim3(1), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL(sampler2_kernel<false>, dim3(1), dim3(1024), 0, s, a);
+  } else {
+    ITTS_REQUIRE(a.uniforms, "sampler: a sampled row needs uniforms");
+    if (cls == ROWCLS_NARROW) {
+      ITTS_REQUIRE((size_t)a.V * 4 <= 60 * 1024, "sampler: vocabulary too large for the LDS-resident sampler");
+      if (rows) hipLaunchKernelGGL(sampler_sample_kernel<true>, dim3(1), dim3(1024), (size_t)a.V * 4, s, a);
+      else hipLaunchKernelGGL(sampler_sample_kernel<false>, dim3(1), dim3(1024), (size_t)a.V * 4, s, a);
+    } else {
+      ITTS_REQUIRE(a.V >= 1 && a.V <= WIDE_MAX_V, "sampler: top_k outside [1, 128] needs a vocabulary of at most 16384");
+      ITTS_TRY(sampler_wide_prepare());
+      int np = 1024;
+      while (np < a.V) np <<= 1;
+      if (rows) hipLaunchKernelGGL(sampler_wide_kernel<true>, dim3(1), dim3(1024), (size_t)np * 6, s, a, np);
+      else hipLaunchKernelGGL(sampler_wide_kernel<false>, dim3(1), dim3(1024), (size_t)np * 6, s, a, np);
+    }
+  }
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
 int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, const int* len, int B, int D, int tw,
                   hipStream_t s) {
   if (tw == F32)

@@ -148,6 +148,12 @@ struct DecodeState {
   std::vector<uint8_t> retired;       // [B0]
   std::vector<int32_t> ret_codes;     // [B0][max_gen]
   std::vector<float> ret_logits;      // [B0][V]
+  // Row admission (Engine::gpt_admit_rows, opt-in): finished slots take new requests, which get the original rows B0, B0 + 1, ..
+  // - so B0 grows while B and Bcache stay.  What the generation then owns by ORIGINAL row: the per-row settings (a table
+  // generation; row_table is the caller's setting for the next prefill and keeps its size) and the draws [B0][max_gen]
+  int admitted = 0;                   // rows admitted so far (0: everything as before)
+  std::vector<RowSampling> adm_rows;  // [B0], empty in a scalar generation
+  std::vector<float> adm_uniforms;    // [B0][max_gen], empty when no row of the generation draws
   size_t cache_bytes = 0;
   void *kc = nullptr, *vc = nullptr;  // [layers][B][H][Smax][dh], elements of type ct
   // element type of the cache: the engine's own (F32 / BF16) or, opt-in on a 16-bit engine, FP8 = e4m3 bytes (itts_gpt_set_kv_fp8 /
@@ -170,6 +176,7 @@ struct DecodeState {
   int suppress_stop = 0;
   hipGraphExec_t graph = nullptr, graphK = nullptr;  // one decode step / ITTS_GRAPH_STEPS (8) steps per launch
   GraphKey graph_key;                                // what they were captured with
+  int graph_captures = 0;                            // times the step was captured (itts_gpt_graph_captures: tests)
   void drop_graphs() {                               // (the caller synchronises the stream first where a replay may be in flight)
     for (hipGraphExec_t* ge : {&graph, &graphK})
       if (*ge) {
@@ -182,6 +189,7 @@ struct DecodeState {
   float top_p = 1.f, temperature = 1.f;
   float* uniforms = nullptr;
   size_t uniforms_cap = 0;
+  int have_uniforms = 0;  // this generation's prefill set the buffer up for its own [max_gen][B] draws (else it may be an earlier one's)
   // mixed batch (itts_gpt_set_sampling_rows, a table that is not uniform): what the prefill latched for this generation.
   // rows [B] on the device, in slot order; rows_classes: the classes its live rows hold (bits ROWCLS_*, sampler_rows_step)
   RowSampling* rows = nullptr;
@@ -307,6 +315,8 @@ struct Engine {
   int gpt_set_sampling_rows(const RowSampling* rows_host, int B, const float* uniforms_host, long n);
   std::vector<RowSampling> row_table;  // [B] by original row; empty = no table
   bool row_table_uniform = false;
+  bool row_table_keep = false;  // gpt_keep_row_table: a uniform table stays a table generation (so that it can admit rows of other settings)
+  int gpt_keep_row_table(int on);
   int upload_row_table(hipStream_t s);  // ds.rows / ds.rows_classes from row_table by ds.orig (or the identity)
   int gpt_set_forced(const int32_t* ids_host, int B, int n);
   int gpt_set_input_tokens(const int32_t* ids_host, int B, int n);
@@ -337,6 +347,10 @@ struct Engine {
   int gpt_fetch(int32_t* codes, float* logits, hipStream_t s);
   int fetch_retired(int32_t* codes, float* logits, hipStream_t s);  // gpt_fetch after a retirement: original row order
   int gpt_retire_rows(int* rows_now, hipStream_t s);  // compact a running single-beam generation to its unfinished rows (opt-in)
+  // refill n finished slots of the running generation with new requests (opt-in); slots_out [n]: the slots they took
+  int gpt_admit_rows(const float* cond, int cond_rows, const int32_t* text_ids, int n, int L, const RowSampling* rows_host,
+                     const float* uniforms_host, const int32_t* forced_host, int n_forced, int32_t* slots_out, hipStream_t s);
+  int gpt_row_status(int32_t* orig_host, int32_t* len_host, int32_t* unf_host, hipStream_t s);  // per slot, [B] each
   int gpt_latent(const float* cond, const int32_t* text_ids, int L, const int32_t* codes, int T, void* latent_out,
                  hipStream_t s);
   int gpt_latent_batch(const float* cond, const int32_t* text_ids, const int* Ls, const int32_t* codes, const int* Ts,
@@ -348,7 +362,8 @@ struct Engine {
   int dvae_encode(const void* mel, int B, int T, int32_t* codes_host, hipStream_t s);
 
   // internals
-  int gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, bool write_cache, hipStream_t s);
+  // admit_slots (host, [B]): the cache rows the B rows of this pass go to (kv_admit); nullptr: rows 0 .. B - 1 (kv_scatter)
+  int gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, bool write_cache, hipStream_t s, const int* admit_slots = nullptr);
   int decode_step_launch(hipStream_t s);
   GraphKey graph_key() const;
   EngArgs engine_args(int& eng_first, bool& fold_head, bool& fold_samp) const;
@@ -359,6 +374,7 @@ struct Engine {
   int ensure_engine_state(hipStream_t s);
   int engine_check(hipStream_t s);
   int head_and_sample(hipStream_t s, bool have_logits = false, bool sampled = false);
+  int head_rows(float* h, float* hn, float* logits, int B, hipStream_t s);  // ln_f -> final_norm -> mel_head of B rows
   int sample_from_logits(hipStream_t s, bool sampled = false);
   SamplerArgs greedy_sampler_args(const float* lg_in, bool typical) const;
   int ensure_decode_state(int B, int Smax, int max_gen, hipStream_t s);

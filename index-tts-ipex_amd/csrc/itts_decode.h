@@ -195,6 +195,33 @@ int rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stride, s
               const int* src, const int* dst, int n_moves, hipStream_t s);
 int retire_plan(const int* unfinished, int B, int* n_live, int* src, int* dst, int* n_moves);  // host only
 
+// decode_admit.hip: the two kernels behind the row admission into a running batch (Engine::gpt_admit_rows).  The slots travel by
+// value in the argument blocks, at most ROWS_MOVE_MAX of them, as the moves of rows_move_kernel do
+struct KvAdmitArgs {
+  void *kc = nullptr, *vc = nullptr;  // [Bcache][H][Smax][dh] of one layer
+  const void* qkv = nullptr;          // [n][S][3 * H * dh]
+  int n = 0, S = 0, H = 0, dh = 0, Smax = 0;
+  unsigned short slot[ROWS_MOVE_MAX];
+};
+int kv_admit_check(const void* kc, const void* vc, const void* qkv, int n, int S, int H, int dh, int Smax, int Bcache, int tq, int tc,
+                   const int* slots);  // host only: no HIP call
+int kv_admit(void* kc, void* vc, const void* qkv, int n, int S, int H, int dh, int Smax, int Bcache, int tq, int tc, const int* slots,
+             hipStream_t s);
+struct RowsAdmitArgs {
+  uint8_t* seen = nullptr;                                                   // [B][V]
+  int *unfinished = nullptr, *cur_tok = nullptr, *len = nullptr, *kv_start = nullptr;  // [B]
+  int* ids = nullptr;                                                        // [B][max_gen]
+  int* forced = nullptr;                                                     // [B][max_gen] or null
+  float* uniforms = nullptr;                                                 // [max_gen][B] or null
+  const int* forced_src = nullptr;                                           // [n][max_gen] device, or null: -1
+  const float* uniforms_src = nullptr;                                       // [n][max_gen] device, or null: the column stays
+  int n = 0, B = 0, V = 0, max_gen = 0, fake_id = 1, start_tok = 0, stop = 0;
+  unsigned short slot[ROWS_MOVE_MAX], kvs[ROWS_MOVE_MAX];                    // filled by rows_admit from its host lists
+};
+int rows_admit_check(const RowsAdmitArgs& a, const int* slots, const int* kvs);  // host only
+int rows_admit(RowsAdmitArgs a, const int* slots, const int* kvs, hipStream_t s);
+int admit_plan(const int* unfinished, const int* len, int B, int max_gen, int n, int* slots, int* n_free);  // host only
+
 // second generation, one file per kernel family.  decode_gemv.hip:
 bool gemv2_supported(const GemvArgs& g);
 int gemv2(const GemvArgs& g, int tw, hipStream_t s);
@@ -219,6 +246,9 @@ int sampler2_step(const SamplerArgs& a, int B, hipStream_t s);
 int sampler_wide_prepare();  // once per device ordinal, outside graph capture: sampler_wide_kernel's dynamic LDS limit
 // a.rows set: one launch per class in `classes` (bit ROWCLS_*), grid B each; a block whose row another class owns returns at once
 int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s);
+// the token choice of ONE row of a batch (row admission): the per-row pointers of `a` are advanced to `slot` - uniforms by slot
+// with the stride a.B kept - and the kernel of class `cls` runs with a grid of one block; no other row is read or written
+int sampler_slot_step(const SamplerArgs& a, int slot, int cls, hipStream_t s);
 int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, const int* len, int B, int D, int tw,
                   hipStream_t s);
 

@@ -82,7 +82,7 @@ __global__ void beam_init_kernel(uint8_t* anc, float* beam_scores, int* hyp_orde
   } while (0)
 
 // full-sequence pass of the 24 blocks over h fp32 [B*S, D] (in place); optional KV-cache fill
-int Engine::gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, bool write_cache, hipStream_t s) {
+int Engine::gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, bool write_cache, hipStream_t s, const int* admit_slots) {
   const itts_config& c = cfg;
   const int D = c.model_dim, H = c.heads, dh = D / H, M = B * S;
   void* xn = alloc((size_t)M * D * es);
@@ -95,7 +95,10 @@ int Engine::gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, boo
     ITTS_TRY(lin(qkv, adt, xn, adt, D, L.attn, M, 3 * D, s));
     if (write_cache) {
       const size_t lo = (size_t)l * ds.Bcache * H * ds.Smax * dh * ds.ces;  // the cache's element size, not the engine's
-      K(kv_scatter((char*)ds.kc + lo, (char*)ds.vc + lo, qkv, B, S, H, dh, ds.Smax, adt, ds.ct, s));
+      if (admit_slots)  // a row admission: the B rows of this pass go to chosen rows of the running generation's cache
+        K(kv_admit((char*)ds.kc + lo, (char*)ds.vc + lo, qkv, B, S, H, dh, ds.Smax, ds.Bcache, adt, ds.ct, admit_slots, s));
+      else
+        K(kv_scatter((char*)ds.kc + lo, (char*)ds.vc + lo, qkv, B, S, H, dh, ds.Smax, adt, ds.ct, s));
     }
     AttnArgs a;
     a.q = qkv;
@@ -321,6 +324,9 @@ int Engine::ensure_decode_state(int B, int Smax, int max_gen, hipStream_t s) {
   d.retired.clear();
   d.ret_codes.clear();
   d.ret_logits.clear();
+  d.admitted = 0;
+  d.adm_rows.clear();
+  d.adm_uniforms.clear();
   d.Smax = Smax;
   d.max_gen = max_gen;
   return OK;
@@ -527,7 +533,7 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
     penalty = row_table[0].penalty;  // a uniform table: the scalar path with its values; else every row reads its own
   }
   ITTS_TRY(ensure_decode_state(B, Smax, max_gen, s));
-  ds.rows_active = !row_table.empty() && !row_table_uniform;
+  ds.rows_active = !row_table.empty() && (!row_table_uniform || row_table_keep);  // (kept: a generation that will admit other settings)
   ds.rows_classes = 0;
   ds.prefix = sp;
   ds.penalty = penalty;
@@ -566,9 +572,12 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
     ITTS_TRY(ensure_beam_wide_state(B, nbeam, cfg.number_mel_codes, s));
     ds.wide_valid = 1;  // this generation's steps leave their picks in ds.wide (gpt_beam_picks)
   }
-  if (ds.do_sample || rows_sample || (nbeam > 1 && beam_do_sample && !ds.host_sample)) {
+  // a kept table whose rows are all greedy: room for the draws of sampled rows it may admit (gpt_admit_rows fills their columns)
+  const bool keep_u = ds.rows_active && row_table_keep && !ds.do_sample && !rows_sample;
+  ds.have_uniforms = 0;
+  if (ds.do_sample || rows_sample || (nbeam > 1 && beam_do_sample && !ds.host_sample) || keep_u) {
     const size_t need_u = nbeam > 1 ? (size_t)max_gen * B_items * 2 * nbeam : (size_t)max_gen * B;
-    ITTS_REQUIRE(sample_uniforms.size() >= need_u,
+    ITTS_REQUIRE(keep_u || sample_uniforms.size() >= need_u,
                  "gpt_prefill: sampling enabled but fewer uniforms than max_gen * B (* 2 * num_beams) were supplied");
     if (need_u > ds.uniforms_cap) {
       ITTS_HIP_CHECK(hipStreamSynchronize(s));
@@ -576,8 +585,12 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
       ITTS_TRY(dev_alloc((void**)&ds.uniforms, need_u * 4));
       ds.uniforms_cap = need_u;
     }
-    ITTS_HIP_CHECK(hipMemcpyAsync(ds.uniforms, sample_uniforms.data(), need_u * 4, hipMemcpyHostToDevice, s));
+    if (keep_u)
+      ITTS_HIP_CHECK(hipMemsetAsync(ds.uniforms, 0, need_u * 4, s));
+    else
+      ITTS_HIP_CHECK(hipMemcpyAsync(ds.uniforms, sample_uniforms.data(), need_u * 4, hipMemcpyHostToDevice, s));
     ITTS_HIP_CHECK(hipStreamSynchronize(s));
+    ds.have_uniforms = nbeam == 1;
   }
   ds.use_forced = forced_n > 0;
   ds.input_n = forced_input ? forced_n : 0;
@@ -654,18 +667,25 @@ int Engine::gpt_prefill(const float* cond_dev, const int32_t* text_ids_in, int B
 
 // ln_f -> final_norm -> mel_head -> repetition penalty / argmax / bookkeeping (lm_head, model.py:48,180)
 int Engine::head_and_sample(hipStream_t s, bool have_logits, bool sampled) {
-  const itts_config& c = cfg;
-  const int D = c.model_dim, V = c.number_mel_codes, B = ds.B;
   if (have_logits) return sample_from_logits(s, sampled);  // the persistent engine ran ln_f / final_norm / mel_head itself
+  ITTS_TRY(head_rows(ds.h, ds.hn, ds.logits, ds.B, s));
+  return sample_from_logits(s);
+}
+
+// the head of B rows: h [B][D] fp32 -> logits [B][V]; hn: [ceil(B / 16) * 16][D] floats of scratch (the decode step's own buffers,
+// or those of a row admission)
+int Engine::head_rows(float* h, float* hn, float* logits, int B, hipStream_t s) {
+  const itts_config& c = cfg;
+  const int D = c.model_dim, V = c.number_mel_codes;
   GemvArgs g;
   g.W = gpt.head.w;
-  g.Y = ds.logits;
+  g.Y = logits;
   g.bias = gpt.head.b;
   g.B = B;
   g.N = V;
   g.K = D;
   g.ldy = V;
-  g.X = ds.h;
+  g.X = h;
   g.prologue = 2;
   g.ln_gamma = gpt.ln_f.g;
   g.ln_beta = gpt.ln_f.b;
@@ -673,9 +693,9 @@ int Engine::head_and_sample(hipStream_t s, bool have_logits, bool sampled) {
   g.ln2_beta = nullptr;
   if (rows_on_mfma(B)) {
     // batched decode: ln_f -> final_norm as a row kernel (bf16), head on the matrix cores
-    ITTS_TRY(ln_rows_bf16(ds.hn, ds.h, gpt.ln_f.g, gpt.ln_f.b, B, D, 1e-5f, 2, ds.partial, ds.pend_split, ds.pend_bias, 1, s));
+    ITTS_TRY(ln_rows_bf16(hn, h, gpt.ln_f.g, gpt.ln_f.b, B, D, 1e-5f, 2, ds.partial, ds.pend_split, ds.pend_bias, 1, s));
     ds.pend_split = 0;
-    g.X = ds.hn;
+    g.X = hn;
     g.x_bf16 = 1;
     g.x_tiled = 1;
     g.prologue = 0;
@@ -693,12 +713,12 @@ int Engine::head_and_sample(hipStream_t s, bool have_logits, bool sampled) {
   } else {
     // (also the bf16 engine at a width the bf16 GEMV refuses: gemv2 hands the elements of its LayerNorm rows to the threads by
     // their position in the batch, so identical rows would differ in the last ulp; these two kernels treat every row alike)
-    ITTS_TRY(double_ln(ds.hn, ds.h, gpt.ln_f.g, gpt.ln_f.b, nullptr, nullptr, B, D, 1e-5f, s));
-    g.X = ds.hn;
+    ITTS_TRY(double_ln(hn, h, gpt.ln_f.g, gpt.ln_f.b, nullptr, nullptr, B, D, 1e-5f, s));
+    g.X = hn;
     g.prologue = 0;
     ITTS_TRY(gemv(g, gpt.head.dt, s));
   }
-  return sample_from_logits(s);
+  return OK;
 }
 
 // arguments of the beam kernels (beam_sample_step / beam_commit_step) from the decode state
@@ -1168,13 +1188,16 @@ int Engine::gpt_set_sampling_rows(const RowSampling* rows_host, int B, const flo
 // ds.rows [ds.B] <- row_table by the original row of every slot; ds.rows_classes <- the classes those rows hold
 int Engine::upload_row_table(hipStream_t s) {
   DecodeState& d = ds;
+  // after an admission the generation owns its table (adm_rows, by original row; B0 has grown, the slots have not)
+  const std::vector<RowSampling>& row_table = d.admitted ? d.adm_rows : this->row_table;
   ITTS_REQUIRE((int)row_table.size() == d.B0 && d.B >= 1 && d.B <= d.B0 && (d.orig.empty() ? d.B == d.B0 : (int)d.orig.size() == d.B),
                "per-row sampling table: it does not belong to this generation");
-  if (d.B0 > d.rows_cap) {
+  const int room = d.admitted ? d.Bcache : d.B0;  // entries: one per slot
+  if (room > d.rows_cap) {
     ITTS_HIP_CHECK(hipStreamSynchronize(s));
     d.drop_graphs();  // the captured samplers hold the old pointer
-    ITTS_TRY(dev_alloc((void**)&d.rows, (size_t)d.B0 * sizeof(RowSampling)));
-    d.rows_cap = d.B0;
+    ITTS_TRY(dev_alloc((void**)&d.rows, (size_t)room * sizeof(RowSampling)));
+    d.rows_cap = room;
   }
   std::vector<RowSampling> tab((size_t)d.B);
   int classes = 0;
@@ -1418,6 +1441,7 @@ int Engine::gpt_decode_steps(int nsteps, hipStream_t s) {
       }
       d.graph_key = key;
       d.graph_mode = d.last_mode;  // what the captured step runs on
+      ++d.graph_captures;
     }
     d.last_mode = d.graph_mode;  // a replayed graph: the mode it was captured with
     int left = nsteps;
@@ -1541,14 +1565,18 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
   if (d.nb > 1 || d.host_sample || engine_usable() || ((d.fuse || env_fuse) && !d.fuse_failed)) return OK;
   const itts_config& c = cfg;
   const int B = d.B, D = c.model_dim, H = c.heads, dh = D / H, V = c.number_mel_codes, mg = d.max_gen;
-  std::vector<int> unf(B), src(B), dst(B);
+  std::vector<int> unf(B), lens(B), src(B), dst(B);
   int k = 0, n = 0, nm = 0;
   ITTS_HIP_CHECK(hipMemcpyAsync(unf.data(), d.unfinished, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-  ITTS_HIP_CHECK(hipMemcpyAsync(&k, d.len, 4, hipMemcpyDeviceToHost, s));  // every row has run the same steps
+  ITTS_HIP_CHECK(hipMemcpyAsync(lens.data(), d.len, (size_t)B * 4, hipMemcpyDeviceToHost, s));  // (admitted rows started later)
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   ITTS_TRY(retire_plan(unf.data(), B, &n, src.data(), dst.data(), &nm));
   if (n == B || n == 0) return OK;
-  ITTS_REQUIRE(nm <= ROWS_MOVE_MAX && k >= 0 && k <= mg, "gpt_retire_rows: decode state out of range");
+  for (int b = 0; b < B; ++b) {
+    ITTS_REQUIRE(lens[b] >= 0 && lens[b] <= mg, "gpt_retire_rows: decode state out of range");
+    k = std::max(k, lens[b]);  // the longest history: what the K/V moves copy
+  }
+  ITTS_REQUIRE(nm <= ROWS_MOVE_MAX, "gpt_retire_rows: decode state out of range");
   // 1. the retiring rows' codes and last logits go to the host store, by original row
   if (d.orig.empty()) {
     d.orig.resize(B);
@@ -1567,7 +1595,7 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
       if (unf[b]) continue;
       const size_t r = (size_t)d.orig[b];
       d.retired[r] = 1;
-      std::memcpy(d.ret_codes.data() + r * mg, ids.data() + (size_t)b * mg, (size_t)k * 4);  // stop behind them (the fill above)
+      std::memcpy(d.ret_codes.data() + r * mg, ids.data() + (size_t)b * mg, (size_t)lens[b] * 4);  // stop behind them (the fill above)
       std::memcpy(d.ret_logits.data() + r * V, lg.data() + (size_t)b * V, (size_t)V * 4);
     }
   }
@@ -1586,10 +1614,12 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
   // 3. the sampler reads uniforms[k * B + b]: re-packed to [max_gen][n] by original row
   std::vector<float> u;
   if (d.do_sample || (d.rows_active && (d.rows_classes & ~(1 << ROWCLS_GREEDY)))) {
-    ITTS_REQUIRE(sample_uniforms.size() >= (size_t)mg * d.B0, "gpt_retire_rows: the uniforms of this generation are gone");
+    ITTS_REQUIRE(d.admitted ? d.adm_uniforms.size() == (size_t)mg * d.B0 : sample_uniforms.size() >= (size_t)mg * d.B0,
+                 "gpt_retire_rows: the uniforms of this generation are gone");
     u.resize((size_t)mg * n);
     for (int q = 0; q < mg; ++q)
-      for (int b = 0; b < n; ++b) u[(size_t)q * n + b] = sample_uniforms[(size_t)q * d.B0 + d.orig[b]];
+      for (int b = 0; b < n; ++b)
+        u[(size_t)q * n + b] = d.admitted ? d.adm_uniforms[(size_t)d.orig[b] * mg + q] : sample_uniforms[(size_t)q * d.B0 + d.orig[b]];
     ITTS_HIP_CHECK(hipMemcpyAsync(d.uniforms, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
   }
   d.B = n;
@@ -1598,6 +1628,251 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   d.drop_graphs();  // every later step re-captures at the smaller row count (GraphKey::B / Bcache)
   if (rows_now) *rows_now = n;
+  return OK;
+}
+
+// A uniform per-row table normally IS the scalar setting (gpt_set_sampling_rows).  With on = 1 the following prefills keep any
+// table as a table generation - one sampler launch per class, room for draws - so that it can admit rows of other settings later.
+int Engine::gpt_keep_row_table(int on) {
+  row_table_keep = on != 0;
+  return OK;
+}
+
+int Engine::gpt_row_status(int32_t* orig_host, int32_t* len_host, int32_t* unf_host, hipStream_t s) {
+  if (!ds.active) {
+    set_error("gpt_row_status: no active generation");
+    return E_STATE;
+  }
+  if (len_host) ITTS_HIP_CHECK(hipMemcpyAsync(len_host, ds.len, (size_t)ds.B * 4, hipMemcpyDeviceToHost, s));
+  if (unf_host) ITTS_HIP_CHECK(hipMemcpyAsync(unf_host, ds.unfinished, (size_t)ds.B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  ITTS_TRY(engine_check(s));
+  if (orig_host)
+    for (int b = 0; b < ds.B; ++b) orig_host[b] = ds.orig.empty() ? b : ds.orig[b];
+  return OK;
+}
+
+// Row admission (opt-in): n finished slots of the running generation take n new requests.  A batched token step costs almost the
+// same at every row count, so a slot that a finished row holds is better spent on the next waiting sentence than carried to the
+// end of the slowest row.  Every kernel of the step reads a row's position from its own len / kv_start, so an admitted row is a row
+// with len = 0 whose prefix sits in positions [kv_start, prefix] of its slot: the steps that follow are the steps of a fresh
+// generation for it, and the running rows are neither stepped nor touched here.
+//   1. synchronise; the n lowest finished slots (admit_plan); their codes and last logits go to the host store by original row
+//   2. the new rows become original rows B0 .. B0 + n - 1 (gpt_fetch returns all of them, in that order)
+//   3. embedding + the 24 blocks over the n rows in scratch (the prefill's kernels at n rows), K/V into the slots (kv_admit)
+//   4. rows_admit_kernel: the slots' state of a fresh generation
+//   5. the head on the n rows' last position in scratch, logits to the slots, one sampler launch (grid 1) per admitted row
+//   6. a table generation: the row table for the new occupancy (a class that was not present re-captures the step)
+// text_ids [n][L] with L the generation's own text length (stop ids pad a shorter text, which is left-padded as in the prefill).
+// cond [cond_rows][latents, D], cond_rows 1 (shared) or n.  rows_host [n] (optional): in a table generation the rows' settings
+// (missing: greedy with the generation's penalty); in a scalar generation only its own settings are accepted.  uniforms_host
+// [n][max_gen]: the draws of a sampled row.  forced_host [n][n_forced] (optional, -1 free): needs a generation started with forced
+// tokens.  Everything is refused before anything is changed.
+int Engine::gpt_admit_rows(const float* cond_dev, int cond_rows, const int32_t* text_ids, int n, int L, const RowSampling* rows_host,
+                           const float* uniforms_host, const int32_t* forced_host, int n_forced, int32_t* slots_out, hipStream_t s) {
+  DecodeState& d = ds;
+  if (!d.active) {
+    set_error("gpt_admit_rows: no active generation");
+    return E_STATE;
+  }
+  const itts_config& c = cfg;
+  const int D = c.model_dim, nl = c.cond_latents, V = c.number_mel_codes, B = d.B, mg = d.max_gen;
+  ITTS_REQUIRE(cond_dev && text_ids && n >= 1 && L >= 1 && (cond_rows == 1 || cond_rows == n), "gpt_admit_rows: bad arguments");
+  ITTS_REQUIRE(n <= ROWS_MOVE_MAX, "gpt_admit_rows: more than 128 rows in one admission");
+  ITTS_REQUIRE(d.nb == 1, "gpt_admit_rows: rows cannot be admitted under beams");
+  ITTS_REQUIRE(!(d.typical_mass > 0.f), "gpt_admit_rows: rows cannot be admitted with typical filtering");
+  ITTS_REQUIRE(!d.host_sample, "gpt_admit_rows: rows cannot be admitted with host sampling");
+  static const bool env_fuse = getenv("ITTS_FUSE_QKV_ATTN") != nullptr && atoi(getenv("ITTS_FUSE_QKV_ATTN")) != 0;
+  ITTS_REQUIRE(!((d.fuse || env_fuse) && !d.fuse_failed), "gpt_admit_rows: rows cannot be admitted with the fused qkv + attention launch");
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  ITTS_REQUIRE(!engine_usable(), "gpt_admit_rows: rows cannot be admitted while the step runs on the persistent engine (<= 6 rows)");
+  ITTS_REQUIRE(d.B == d.Bcache, "gpt_admit_rows: rows cannot be admitted after a retirement");
+  ITTS_REQUIRE(d.input_n == 0, "gpt_admit_rows: rows cannot be admitted into a generation with `input_tokens`");
+  ITTS_REQUIRE(L == d.prefix - nl - 2, "gpt_admit_rows: L must be the text length of the running generation");
+  // what kv_admit would refuse inside the launch sequence, asked here - before anything is changed (its slots come from admit_plan:
+  // distinct, inside [0, B); the scratch and the per-layer cache offsets are 256-byte aligned)
+  ITTS_REQUIRE((D / c.heads) % (d.ct == F32 ? 4 : 8) == 0 && d.Bcache <= 65536 && ((uintptr_t)d.kc | (uintptr_t)d.vc) % 16 == 0,
+               "gpt_admit_rows: the cache write needs a head dim that is a multiple of 8 (4: fp32 cache) and at most 65536 cache rows");
+  ITTS_REQUIRE(!forced_host || (d.use_forced && n_forced >= 1 && n_forced <= mg),
+               "gpt_admit_rows: forced tokens need a generation started with forced tokens, and 1 <= n_forced <= max_gen");
+  // the text rows, stripped and left-padded as gpt_prefill does
+  const int sp = d.prefix, S0 = sp + 1;
+  std::vector<RowDesc> rd((size_t)n * S0);
+  std::vector<int> kvs(n);
+  for (int b = 0; b < n; ++b) {
+    std::vector<int> ids;
+    for (int i = 0; i < L; ++i) {
+      const int t = text_ids[(size_t)b * L + i];
+      if (t != c.start_text_token && t != c.stop_text_token) {
+        ITTS_REQUIRE(t >= 0 && t <= c.number_text_tokens, "gpt_admit_rows: text id out of range");
+        ids.push_back(t);
+      }
+    }
+    const int nt = (int)ids.size(), pad = L - nt;
+    kvs[b] = pad;
+    RowDesc* r = rd.data() + (size_t)b * S0;
+    int k = 0;
+    for (int i = 0; i < pad; ++i) r[k++] = {0, 0, 0, 0};
+    for (int i = 0; i < nl; ++i) r[k++] = {1, (cond_rows == n && n > 1 ? b * nl : 0) + i, 0, 0};
+    r[k++] = {2, c.start_text_token, 0, 0};
+    for (int i = 0; i < nt; ++i) r[k++] = {2, ids[i], i + 1, 0};
+    r[k++] = {2, c.stop_text_token, nt + 1, 0};
+    r[k++] = {3, c.start_mel_token, 0, 0};
+  }
+  // the rows' settings and classes
+  std::vector<RowSampling> rs(n);
+  std::vector<int> cls(n);
+  bool draws = false;
+  for (int b = 0; b < n; ++b) {
+    RowSampling r = rows_host ? rows_host[b] : RowSampling{d.rows_active ? 0 : d.do_sample, d.top_k, d.top_p, d.temperature, d.penalty};
+    ITTS_REQUIRE(r.mode == 0 || r.mode == 1, "gpt_admit_rows: mode is 0 (greedy) or 1 (sample)");
+    ITTS_REQUIRE(r.top_p > 0.f && r.top_p <= 1.f && r.temperature > 0.f && r.penalty > 0.f,
+                 "gpt_admit_rows: need 0 < top_p <= 1, temperature > 0 and penalty > 0");
+    r.top_k = r.top_k < 1 ? 0 : r.top_k;
+    if (!d.rows_active)
+      ITTS_REQUIRE(r.mode == d.do_sample && r.penalty == d.penalty &&
+                       (r.mode == 0 || (r.top_k == d.top_k && r.top_p == d.top_p && r.temperature == d.temperature)),
+                   "gpt_admit_rows: a scalar generation admits only rows that carry its own settings (start a table generation: itts_gpt_keep_row_table)");
+    cls[b] = row_class(r.mode, r.top_k);
+    if (cls[b] == ROWCLS_NARROW) ITTS_REQUIRE((size_t)V * 4 <= 60 * 1024, "gpt_admit_rows: a row with 1 <= top_k <= 128 needs number_mel_codes <= 15360");
+    if (cls[b] == ROWCLS_WIDE) ITTS_REQUIRE(V <= 16384, "gpt_admit_rows: a sampled row with top_k outside [1, 128] needs number_mel_codes <= 16384");
+    draws = draws || r.mode == 1;
+    rs[b] = r;
+  }
+  ITTS_REQUIRE(!draws || uniforms_host, "gpt_admit_rows: uniforms missing for a sampled row");
+  ITTS_REQUIRE(!draws || (d.have_uniforms && d.uniforms && d.uniforms_cap >= (size_t)mg * B),
+               "gpt_admit_rows: this generation has no room for draws (start it with the row table kept: itts_gpt_keep_row_table)");
+  if (forced_host)
+    for (long i = 0; i < (long)n * n_forced; ++i)
+      ITTS_REQUIRE(forced_host[i] >= -1 && forced_host[i] < V, "gpt_admit_rows: forced token id out of range");
+  // 1. the slots
+  std::vector<int> unf(B), lens(B), slots(n);
+  ITTS_HIP_CHECK(hipMemcpyAsync(unf.data(), d.unfinished, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(lens.data(), d.len, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  int n_free = 0;
+  ITTS_TRY(admit_plan(unf.data(), lens.data(), B, mg, n, slots.data(), &n_free));
+  ITTS_REQUIRE(n_free >= n, "gpt_admit_rows: fewer finished slots than rows to admit");
+  for (int i = 0; i < n; ++i) ITTS_REQUIRE(lens[slots[i]] >= 0 && lens[slots[i]] <= mg, "gpt_admit_rows: decode state out of range");
+  if (std::find(cls.begin(), cls.end(), (int)ROWCLS_WIDE) != cls.end()) ITTS_TRY(sampler_wide_prepare());  // (outside any capture)
+  // ---- nothing was changed up to here ----
+  {  // the leaving rows' codes and last logits, by original row
+    std::vector<int32_t> ids((size_t)n * mg);
+    std::vector<float> lg((size_t)n * V);
+    for (int i = 0; i < n; ++i) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(ids.data() + (size_t)i * mg, d.ids + (size_t)slots[i] * mg, (size_t)mg * 4, hipMemcpyDeviceToHost, s));
+      ITTS_HIP_CHECK(hipMemcpyAsync(lg.data() + (size_t)i * V, d.logits + (size_t)slots[i] * V, (size_t)V * 4, hipMemcpyDeviceToHost, s));
+    }
+    ITTS_HIP_CHECK(hipStreamSynchronize(s));
+    if (d.orig.empty()) {
+      d.orig.resize(B);
+      for (int b = 0; b < B; ++b) d.orig[b] = b;
+      d.retired.assign((size_t)d.B0, 0);
+      d.ret_codes.assign((size_t)d.B0 * mg, c.stop_mel_token);
+      d.ret_logits.assign((size_t)d.B0 * V, 0.f);
+    }
+    if (!d.admitted) {  // the generation takes its own copy of the per-row settings and the draws, by original row
+      if (d.rows_active) d.adm_rows = row_table;
+      if (d.do_sample || d.rows_active) {
+        d.adm_uniforms.assign((size_t)d.B0 * mg, 0.f);
+        if (sample_uniforms.size() >= (size_t)mg * d.B0)
+          for (int q = 0; q < mg; ++q)
+            for (int b = 0; b < d.B0; ++b) d.adm_uniforms[(size_t)b * mg + q] = sample_uniforms[(size_t)q * d.B0 + b];
+      }
+    }
+    for (int i = 0; i < n; ++i) {
+      const size_t r = (size_t)d.orig[slots[i]];
+      d.retired[r] = 1;
+      std::fill(d.ret_codes.begin() + r * mg, d.ret_codes.begin() + (r + 1) * mg, c.stop_mel_token);
+      std::memcpy(d.ret_codes.data() + r * mg, ids.data() + (size_t)i * mg, (size_t)lens[slots[i]] * 4);  // stop behind them
+      std::memcpy(d.ret_logits.data() + r * V, lg.data() + (size_t)i * V, (size_t)V * 4);
+    }
+  }
+  // 2. the new original rows
+  const int first = d.B0;
+  d.B0 += n;
+  d.admitted += n;
+  d.retired.resize((size_t)d.B0, 0);
+  d.ret_codes.resize((size_t)d.B0 * mg, c.stop_mel_token);
+  d.ret_logits.resize((size_t)d.B0 * V, 0.f);
+  for (int i = 0; i < n; ++i) d.orig[slots[i]] = first + i;
+  if (d.rows_active) d.adm_rows.insert(d.adm_rows.end(), rs.begin(), rs.end());
+  if (d.do_sample || d.rows_active) {
+    d.adm_uniforms.resize((size_t)d.B0 * mg, 0.f);
+    for (int i = 0; i < n; ++i)
+      if (rs[i].mode == 1) std::memcpy(d.adm_uniforms.data() + (size_t)(first + i) * mg, uniforms_host + (size_t)i * mg, (size_t)mg * 4);
+  }
+  std::vector<int32_t> ftab;
+  if (forced_host) {
+    ftab.assign((size_t)n * mg, -1);
+    for (int i = 0; i < n; ++i) std::memcpy(ftab.data() + (size_t)i * mg, forced_host + (size_t)i * n_forced, (size_t)n_forced * 4);
+  }
+  // 6 (first: the samplers of step 5 read the slot's own entry)
+  if (d.rows_active) ITTS_TRY(upload_row_table(s));
+  d.pend_split = 0;
+  const int nr = (n + 15) / 16 * 16;  // the batched head keeps its bf16 rows in 16-row tiles
+  auto body = [&]() -> int {
+    RowDesc* rd_dev = (RowDesc*)alloc(rd.size() * sizeof(RowDesc));
+    int* kvs_dev = (int*)alloc((size_t)n * 4);
+    float* h = (float*)alloc((size_t)n * S0 * D * 4);
+    float* h_last = (float*)alloc((size_t)nr * D * 4);
+    float* hn = (float*)alloc((size_t)nr * D * 4);
+    float* lg = (float*)alloc((size_t)nr * V * 4);
+    int* f_dev = forced_host ? (int*)alloc(ftab.size() * 4) : nullptr;
+    float* u_dev = draws ? (float*)alloc((size_t)n * mg * 4) : nullptr;
+    if (!dry) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(rd_dev, rd.data(), rd.size() * sizeof(RowDesc), hipMemcpyHostToDevice, s));
+      ITTS_HIP_CHECK(hipMemcpyAsync(kvs_dev, kvs.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+      if (f_dev) ITTS_HIP_CHECK(hipMemcpyAsync(f_dev, ftab.data(), ftab.size() * 4, hipMemcpyHostToDevice, s));
+      if (u_dev) ITTS_HIP_CHECK(hipMemcpyAsync(u_dev, d.adm_uniforms.data() + (size_t)first * mg, (size_t)n * mg * 4, hipMemcpyHostToDevice, s));
+      if (adt == F32)
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<float>, dim3(n * S0), dim3(256), 0, s, h, rd_dev, cond_dev,
+                           (const float*)gpt.text_emb, (const float*)gpt.text_pos, (const float*)gpt.mel_emb,
+                           (const float*)gpt.mel_pos, D);
+      else
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<bf16_t>, dim3(n * S0), dim3(256), 0, s, h, rd_dev, cond_dev,
+                           (const bf16_t*)gpt.text_emb, (const bf16_t*)gpt.text_pos, (const bf16_t*)gpt.mel_emb,
+                           (const bf16_t*)gpt.mel_pos, D);
+      ITTS_HIP_CHECK(hipGetLastError());
+    }
+    // 3.
+    ITTS_TRY(gpt_layers_full(h, n, S0, kvs_dev, true, s, slots.data()));
+    if (dry) return OK;
+    // 4.
+    RowsAdmitArgs ra;
+    ra.seen = d.seen;
+    ra.unfinished = d.unfinished;
+    ra.cur_tok = d.cur_tok;
+    ra.len = d.len;
+    ra.kv_start = d.kv_start;
+    ra.ids = d.ids;
+    ra.forced = d.forced;
+    ra.uniforms = u_dev ? d.uniforms : nullptr;
+    ra.forced_src = f_dev;
+    ra.uniforms_src = u_dev;
+    ra.n = n;
+    ra.B = B;
+    ra.V = V;
+    ra.max_gen = mg;
+    ra.fake_id = 1;
+    ra.start_tok = c.start_mel_token;
+    ra.stop = c.stop_mel_token;
+    ITTS_TRY(rows_admit(ra, slots.data(), kvs.data(), s));
+    // 5. (the sampler writes the next step's input row h[slot] itself)
+    ITTS_TRY(copy_rows(h_last, D, h + (size_t)(S0 - 1) * D, S0 * D, n, D, F32, s));
+    ITTS_TRY(head_rows(h_last, hn, lg, n, s));
+    SamplerArgs sa = greedy_sampler_args(d.logits, false);
+    if (d.rows_active) sa.rows = d.rows;
+    for (int i = 0; i < n; ++i) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(d.logits + (size_t)slots[i] * V, lg + (size_t)i * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
+      ITTS_TRY(sampler_slot_step(sa, slots[i], cls[i], s));
+    }
+    return OK;
+  };
+  ITTS_TRY(two_pass(body, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));  // rd / kvs / the tables are host buffers of this call
+  if (slots_out)
+    for (int i = 0; i < n; ++i) slots_out[i] = slots[i];
   return OK;
 }
 

@@ -33,6 +33,9 @@ def build_parser():
     p.add_argument("--ragged-vocoder", action="store_true", default=False,
                    help="batched synthesis (IndexTTS.infer_batch): sentences of unequal length share vocoder passes; "
                         "ITTS_RAGGED_VOCODER=0 / 1 overrides")
+    p.add_argument("--admit-rows", action="store_true", default=False,
+                   help="batched synthesis (IndexTTS.infer_batch with mixed batches, ITTS_MIXED_BATCH=1): finished decode rows are "
+                        "refilled from the waiting sentences; ITTS_ADMIT_ROWS=0 / 1 overrides")
     return p
 
 
@@ -56,7 +59,7 @@ def main():
 
     tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8, kv_fp8=a.kv_fp8,
                    wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler, retire_rows=a.retire_rows,
-                   engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder)
+                   engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder, admit_rows=a.admit_rows)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

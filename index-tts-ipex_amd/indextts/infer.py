@@ -43,6 +43,11 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     sampling settings (`per_utterance`): conditioning and the speaker encoder run once per distinct prompt, every decode row
     carries its own conditioning latents and its own do_sample / top_k / top_p / temperature / repetition_penalty / seed, the
     latent pass and the vocoder take one voice per sentence.  `infer` / `infer_fast` are not affected.
+  * `admit_rows=True` (not in the reference; default off; ITTS_ADMIT_ROWS=1 / 0 overrides it in both directions; needs
+    `mixed_batch`, without which it does nothing and says so once) lets a group of `infer_batch` with more sentences than
+    `max_batch` decode as ONE generation of `max_batch` rows: a finished row's slot takes the next waiting sentence
+    (Engine.generate(slots=..)) instead of every `max_batch`-sized generation draining to its slowest row.  Single beam, no
+    typical filter, more than 6 rows.  `infer` / `infer_fast` are not affected.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -68,7 +73,7 @@ class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
-                 mixed_batch=False):
+                 mixed_batch=False, admit_rows=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -98,6 +103,8 @@ class IndexTTS:
         self.retire_rows = retire_rows  # row retirement of the batched generations (Engine.generate); None: ITTS_RETIRE_ROWS, else off
         self.ragged_vocoder = bool(ragged_vocoder)  # infer_batch: sentences of unequal length share vocoder passes (ITTS_RAGGED_VOCODER overrides)
         self.mixed_batch = bool(mixed_batch)  # infer_batch: one decode batch across voices and sampling settings (ITTS_MIXED_BATCH overrides)
+        self.admit_rows = bool(admit_rows)  # infer_batch with mixed_batch: finished decode rows are refilled from the waiting sentences (ITTS_ADMIT_ROWS overrides)
+        self._admit_told = False
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
         if self.kv_fp8 and not self.is_fp16:
             raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
@@ -310,11 +317,16 @@ class IndexTTS:
         start = time.perf_counter()
         utt_sents = [self._sentences_to_ids(t, max_text_tokens_per_sentence) for t in texts]
         results = [None] * n
+        admit = {"1": True, "0": False}.get(os.environ.get("ITTS_ADMIT_ROWS", ""), self.admit_rows)
         if {"1": True, "0": False}.get(os.environ.get("ITTS_MIXED_BATCH", ""), self.mixed_batch):
             with self.engine.lock:
-                self._infer_batch_mixed(prompts, utt_sents, settings, results)
+                self._infer_batch_mixed(prompts, utt_sents, settings, results, admit)
             groups = {}
         else:
+            if admit and not self._admit_told:
+                self._admit_told = True
+                warnings.warn("admit_rows / ITTS_ADMIT_ROWS does nothing without mixed_batch / ITTS_MIXED_BATCH: row admission runs "
+                              "on the per-row path of infer_batch only", RuntimeWarning)
             groups = {}  # utterances of one prompt and one setting, in the order of their first utterance
             for u, p in enumerate(prompts):
                 groups.setdefault((id(p), tuple(sorted(settings[u].items(), key=lambda kv: kv[0]))), []).append(u)
@@ -348,13 +360,15 @@ class IndexTTS:
             out.append(self._finish(results[u], output_paths[u] if output_paths else None, start, (0, 0, 0), False, "batch "))
         return out
 
-    def _infer_batch_mixed(self, prompts, utt_sents, settings, results):
+    def _infer_batch_mixed(self, prompts, utt_sents, settings, results, admit=False):
         """infer_batch with mixed_batch on: utterances share decode batches whatever their voice, and - with one beam and no
         typical filter - whatever their sampling settings (infer_core.mixed_groups).  Conditioning and the speaker encoder run
         once per distinct prompt object; a decode row carries its prompt's conditioning latents (per-row cond of the prefill) and
         its utterance's entry of the per-row table (Engine.generate with sequences); the latent pass reads its voice through
         cond_index, the vocoder takes one speaker embedding per sentence.  A row's codes, latent and waveform are those of a
-        call in which every utterance carries that row's prompt and settings.  results[u] <- the int16-range wave parts."""
+        call in which every utterance carries that row's prompt and settings.  results[u] <- the int16-range wave parts.
+        admit: a per-row group with more sentences than max_batch (> 6) is ONE generation of max_batch rows whose finished rows
+        are refilled from the waiting sentences (Engine.generate(slots=..)) instead of max_batch-sized generations."""
         voice, conds, spks = {}, [], []  # id(prompt) -> index; conditioning [1, latents, D] and speaker embedding [1, E] per voice
         for p in prompts:
             if id(p) not in voice:
@@ -384,8 +398,16 @@ class IndexTTS:
             order = sorted(range(len(flat)), key=lambda i: (len(flat[i][2]), i))  # length-sorted decode batches
             cap = max(1, self.engine.ccfg.max_batch // max(1, shared.get("num_beams", 1)))
             code_rows = [None] * len(flat)
-            for lo in range(0, len(order), cap):
-                sel = order[lo:lo + cap]
+            one = admit and per_row and cap > 6 and len(order) > cap  # row admission: the whole group in one generation of cap rows
+            if one and (self.wide_sampler or os.environ.get("ITTS_WIDE_SAMPLER") or "host") != "device":
+                # one whole-vocabulary setting for every row is the scalar request, which takes the host-side token choice here:
+                # that path cannot admit rows, so such a group keeps its cap-sized generations
+                ents = {infer_core.row_sampling_table(1, kws[u].get("do_sample", False), kws[u].get("top_k", 0), kws[u].get("top_p", 1.0),
+                                                      kws[u].get("temperature", 1.0), settings[u]["repetition_penalty"])[0] for u in us}
+                e0 = next(iter(ents))
+                one = not (len(ents) == 1 and e0[0] == 1 and not 1 <= e0[1] <= 128)
+            for lo in range(0, len(order), len(order) if one else cap):
+                sel = order if one else order[lo:lo + cap]
                 ids = infer_core.pad_tokens_cat([flat[i][2] for i in sel], self.cfg.gpt.stop_text_token)
                 vs = [voice[id(prompts[flat[i][0]])] for i in sel]
                 cond = cond_all[vs[0]] if len(set(vs)) == 1 else cond_all[vs]  # one voice: the shared-cond prefill, as without the switch
@@ -398,6 +420,8 @@ class IndexTTS:
                               repetition_penalty=[settings[flat[i][0]]["repetition_penalty"] for i in sel])
                 else:  # beams / typical filtering: the group shares every setting (mixed_groups), the voices still differ per row
                     kw = dict(kws[us[0]], repetition_penalty=g0["repetition_penalty"])
+                if one:
+                    kw["slots"] = cap
                 codes = self.engine.generate(cond, ids, g0["max_mel_tokens"], wide_sampler=self.wide_sampler,
                                              wide_beam_sampler=self.wide_beam_sampler, retire_rows=self.retire_rows, **kw)
                 for j, i in enumerate(sel):

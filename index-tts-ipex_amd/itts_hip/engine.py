@@ -290,16 +290,20 @@ class Engine:
         """Forced tokens [B or 1, n] (int, -1 = free) for the first n steps of the following generations; None clears."""
         if ids is None or np.asarray(ids).size == 0:
             self._ck(self.lib.itts_gpt_set_forced(self.h, None, 0, 0), "gpt_set_forced")
+            self._forced = None
             return
         a = np.ascontiguousarray(np.atleast_2d(ids), dtype=np.int32)
         self._ck(self.lib.itts_gpt_set_forced(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1]), "gpt_set_forced")
+        self._forced = a  # (generate(slots=) hands every request its own rows of it)
 
     def set_input_tokens(self, ids: Optional[np.ndarray]):
         """HF `input_tokens` [B or 1, n] (inference_speech, model.py:672-686) for the following generations: forced like
         set_forced, at the reference's positions (token k at mel position k + 1); None clears."""
         if ids is None or np.asarray(ids).size == 0:
             self._ck(self.lib.itts_gpt_set_input_tokens(self.h, None, 0, 0), "gpt_set_input_tokens")
+            self._forced = None
             return
+        self._forced = None  # (the library's forced table now holds input tokens: nothing for generate(slots=) to hand out)
         a = np.ascontiguousarray(np.atleast_2d(ids), dtype=np.int32)
         self._ck(self.lib.itts_gpt_set_input_tokens(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1]), "gpt_set_input_tokens")
 
@@ -349,6 +353,56 @@ class Engine:
         """Rows the decode steps of the active generation run at (0: no generation)."""
         return int(self.lib.itts_gpt_rows(self.h))
 
+    def keep_row_table(self, on: bool = True):
+        """on: the following prefills keep a per-row table that is uniform as a table generation (itts_gpt_keep_row_table), so
+        that it can admit rows of other settings (admit_rows)."""
+        self._ck(self.lib.itts_gpt_keep_row_table(self.h, int(bool(on))), "gpt_keep_row_table")
+
+    def row_status(self):
+        """Per slot of the running generation: (original row, tokens so far, unfinished) as int32 arrays [rows()]."""
+        n = self.rows()
+        orig, ln, unf = (np.empty(n, dtype=np.int32) for _ in range(3))
+        self._ck(self.lib.itts_gpt_row_status(self.h, orig.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p),
+                                             unf.ctypes.data_as(C.c_void_p), self._s()), "gpt_row_status")
+        return orig, ln, unf
+
+    def admit_rows(self, cond: torch.Tensor, text_ids: np.ndarray, rows=None, uniforms: Optional[np.ndarray] = None,
+                   forced: Optional[np.ndarray] = None) -> np.ndarray:
+        """Opt-in: refill finished slots of the running generation with new requests (itts_gpt_admit_rows; synchronises).
+        text_ids [n, L] with L the text length the generation was prefilled with (pad a shorter text with stop ids); cond one
+        [latents, D] block for all n rows or n of them; rows: one (mode, top_k, top_p, temperature, penalty) entry per new row
+        (a table generation; None: the generation's own settings); uniforms [n, max_gen]: the draws of sampled rows; forced
+        [n, k] (-1 free): only in a generation that was started with forced tokens.  The new rows become original rows
+        B0, B0 + 1, ..: fetch() then returns them behind the earlier ones.  The running rows are not stepped.  -> the slots taken.
+        Raises (nothing changed) under beams, typical filtering, host sampling, at <= 6 rows on the persistent engine, after a
+        retirement, and when fewer than n slots are finished (a row at max_gen counts as finished)."""
+        ids = np.ascontiguousarray(text_ids, dtype=np.int32)
+        assert ids.ndim == 2
+        n, Lt = ids.shape
+        cond = cond.to(device=self.device, dtype=torch.float32).contiguous().view(-1, self.ccfg.model_dim)
+        cond_rows, rem = divmod(cond.shape[0], self.ccfg.cond_latents)
+        if rem or cond_rows not in (1, n):
+            raise ValueError(f"admit_rows: cond {tuple(cond.shape)} for {n} rows")
+        tab = None
+        if rows is not None:
+            if len(rows) != n:
+                raise ValueError(f"admit_rows: {len(rows)} settings for {n} rows")
+            tab = (L.RowSampling * n)(*[L.RowSampling(int(m), int(k), float(p), float(t), float(pen)) for m, k, p, t, pen in rows])
+        u = None if uniforms is None else np.ascontiguousarray(uniforms, dtype=np.float32)
+        if u is not None and u.shape != (n, self._gen[1]):
+            raise ValueError(f"admit_rows: uniforms {u.shape}, expected {(n, self._gen[1])}")
+        f = None if forced is None else np.ascontiguousarray(np.atleast_2d(forced), dtype=np.int32)
+        if f is not None and f.shape[0] != n:
+            raise ValueError(f"admit_rows: forced tokens {f.shape} for {n} rows")
+        slots = np.empty(n, dtype=np.int32)
+        self._enter()
+        self._ck(self.lib.itts_gpt_admit_rows(self.h, cond.data_ptr(), cond_rows, ids.ctypes.data_as(C.c_void_p), n, Lt, tab,
+                                             None if u is None else u.ctypes.data_as(C.c_void_p),
+                                             None if f is None else f.ctypes.data_as(C.c_void_p), 0 if f is None else f.shape[1],
+                                             slots.ctypes.data_as(C.c_void_p), self._s()), "gpt_admit_rows")
+        self._gen = (int(self.lib.itts_gpt_rows_total(self.h)), self._gen[1])
+        return slots
+
     def fetch(self, logits: bool = False):
         B, mg = self._gen
         codes = np.empty((B * (getattr(self, "_nret", 1) if getattr(self, "_nb", 1) > 1 else 1), mg), dtype=np.int32)
@@ -362,7 +416,8 @@ class Engine:
                  top_p: float = 0.8, temperature: float = 1.0, seed: Optional[int] = None,
                  uniforms: Optional[np.ndarray] = None, num_beams: int = 1, typical_mass: float = 0.0,
                  length_penalty: float = 0.0, num_return_sequences: int = 1, wide_sampler: Optional[str] = None,
-                 wide_beam_sampler: Optional[str] = None, retire_rows: Optional[float] = None) -> np.ndarray:
+                 wide_beam_sampler: Optional[str] = None, retire_rows: Optional[float] = None, slots: Optional[int] = None,
+                 admit_min: float = 0.125, return_log: bool = False) -> np.ndarray:
         """Greedy decode (do_sample=False, num_beams=1 of tests/padding_test.py:35-46) or, with do_sample, HF
         GenerationMixin.sample (top-k / top-p / temperature, num_beams=1; draws from `uniforms` or a numpy Generator
         seeded with `seed`).  Returns int64 codes [B, n] with n <= max_gen: HF stops when every row has emitted stop
@@ -391,7 +446,20 @@ class Engine:
         itts_gpt_set_sampling_rows) and gets the codes of a generation of the same rows in which every row carries that entry.
         With per-row seeds column b of the draws is np.random.default_rng(seed[b]).random(max_gen, dtype=float32): a row's draws
         do not depend on who shares its batch.  In a table that is not uniform a row with top_k outside 1 .. 128 always runs on
-        the device's whole-vocabulary sampler - the host path cannot mix - whatever wide_sampler says."""
+        the device's whole-vocabulary sampler - the host path cannot mix - whatever wide_sampler says.
+        Row admission (opt-in): slots=S with more than S rows in text_ids (and in the per-row sequences; cond shared or one block
+        per row) decodes them as ONE generation of S rows - the S longest texts start, and after each status check rows from the
+        waiting list take the slots of finished rows (admit_rows) whenever at least ceil(admit_min * S) slots are finished or
+        the rest of the list fits; once the list is empty retire_rows applies as above.  The loop ends when the list is empty
+        and no row is live (a row at max_gen counts as finished).  Codes come back in the caller's order; return_log=True also
+        returns the admissions as (tokens decoded so far, slots, request indices).  Single beam, no typical filter, more than 6
+        slots.  Device samplers only: one sampled setting for every request with top_k outside 1 .. 128 needs
+        wide_sampler="device" (ValueError otherwise: the host path cannot admit); in a table that is not uniform such rows run
+        on the device as above.  Forced tokens given to set_forced for all N requests (or one row for all) follow their requests.
+        Suggested admit_min: 0.125, the default - measured with tools/bench_admit_rows.py (profiles/admit_rows.txt, DESIGN.md
+        section 5i): 192 ragged requests through 64 slots take 1708 ms at 1/8, 1746 ms at 1/4 and 1932 ms at 1/2 against 2149 ms
+        as three 64-row generations (1900 ms with retire_rows=0.5): an admission of 8 rows costs 5 ms, about three token steps, so
+        small groups do not lose."""
         rows = None
         per_row = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty)
         if any(isinstance(v, (list, tuple, np.ndarray)) for v in list(per_row.values()) + [seed]):
@@ -428,6 +496,23 @@ class Engine:
             wide_beam_sampler = os.environ.get("ITTS_WIDE_BEAM_SAMPLER") or "host"
         if wide_beam_sampler not in ("host", "device"):
             raise ValueError(f"wide_beam_sampler must be 'host' or 'device', not {wide_beam_sampler!r}")
+        if slots is not None and np.asarray(text_ids).shape[0] > int(slots):
+            if num_beams > 1 or typical_mass:
+                raise ValueError("row admission (slots=) runs with one beam and without typical filtering only")
+            nrow = np.asarray(text_ids).shape[0]
+            scalar = None
+            if rows is None:  # one setting for every request
+                scalar = (int(bool(do_sample)), int(top_k or 0) if do_sample else 0, float(top_p), float(temperature), float(repetition_penalty))
+                if do_sample and not 1 <= scalar[1] <= 128 and wide_sampler != "device":
+                    raise ValueError("row admission (slots=) with top_k outside 1 .. 128 runs on the device's whole-vocabulary sampler "
+                                     "only: pass wide_sampler='device' (the host-side token choice cannot admit rows)")
+                if do_sample and uniforms is None:
+                    uniforms = np.random.default_rng(seed).random((max_gen, nrow), dtype=np.float32)
+            out = self._generate_admit(cond, text_ids, max_gen, rows, scalar, uniforms, int(slots), float(admit_min), suppress_stop,
+                                       check_every, retire_rows)
+            return out if return_log else out[0]
+        if return_log:
+            raise ValueError("return_log needs slots= and more rows than slots")
         kw = dict(retire_rows=retire_rows, wide_sampler=wide_sampler, wide_beam_sampler=wide_beam_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, uniforms=uniforms, num_beams=num_beams,
                   typical_mass=typical_mass, length_penalty=length_penalty, num_return_sequences=num_return_sequences, rows=rows)
@@ -509,6 +594,88 @@ class Engine:
             hit = np.nonzero(row == stop)[0]
             n = max(n, int(hit[0]) + 1 if len(hit) else step)
         return codes[:, :n]
+
+    def _generate_admit(self, cond, text_ids, max_gen, table, scalar, uniforms, slots, admit_min, suppress_stop, check_every,
+                        retire_rows):
+        """generate(slots=..): one generation of `slots` rows over all N requests (infer_core.AdmitScheduler says who starts and
+        who takes which finished slot).  table: the N per-row entries, or None with `scalar` = the one entry of every request;
+        uniforms [max_gen, N] by request (None: nobody draws).  -> (codes int64 [N, n] in the caller's order, the admission log)"""
+        from . import infer_core
+
+        ids = np.ascontiguousarray(text_ids, dtype=np.int32)
+        N = ids.shape[0]
+        cc = self.ccfg
+        lengths = [int(np.count_nonzero((r != cc.start_text_token) & (r != cc.stop_text_token))) for r in ids]
+        sched = infer_core.AdmitScheduler(lengths, slots, admit_min)
+        cond = cond.to(device=self.device, dtype=torch.float32).contiguous().view(-1, cc.cond_latents, cc.model_dim)
+        if cond.shape[0] not in (1, N):
+            raise ValueError(f"generate(slots=): cond holds {cond.shape[0]} blocks for {N} rows")
+        cond_of = (lambda req: cond[0]) if cond.shape[0] == 1 else (lambda req: cond[list(req)])
+        u = None if uniforms is None else np.ascontiguousarray(uniforms, dtype=np.float32).reshape(max_gen, N)
+        entry = (lambda r: table[r]) if table is not None else (lambda r: scalar)
+        log, stop = [], cc.stop_mel_token
+        first = sched.first
+        held = getattr(self, "_forced", None)  # what set_forced holds: one row for all, or one per request
+        if held is not None and held.shape[0] not in (1, N):
+            raise ValueError(f"generate(slots=): forced tokens were set for {held.shape[0]} rows, not for 1 or {N}")
+        fo = None if held is None else np.ascontiguousarray(np.broadcast_to(held, (N, held.shape[1])))
+        try:
+            if fo is not None:
+                self.set_forced(fo[first])
+            if table is not None:
+                self.keep_row_table(True)
+                self.set_sampling_rows([table[r] for r in first], None if u is None else u[:, first])
+            elif scalar[0]:
+                self.set_sampling(True, scalar[1], scalar[2], scalar[3], u[:, first])
+            self.prefill(cond_of(first), ids[first], max_gen, entry(first[0])[4], suppress_stop)
+            steps, retired = 1, False
+            while True:
+                orig, ln, unf = self.row_status()
+                live = (unf != 0) & (ln < max_gen)
+                if sched.waiting and not retired:
+                    sl, req = sched.take(np.nonzero(~live)[0].tolist())
+                    if req:
+                        draws = u is not None and any(entry(r)[0] for r in req)
+                        took = self.admit_rows(cond_of(req), ids[req], rows=None if table is None else [table[r] for r in req],
+                                               uniforms=np.ascontiguousarray(u[:, req].T) if draws else None,
+                                               forced=None if fo is None else fo[req])
+                        assert took.tolist() == sl, (took, sl)
+                        log.append((steps, sl, req))
+                        ln[sl], live[sl] = 1, True  # (a forced first stop shows at the next status)
+                if not sched.waiting:
+                    if not live.any():
+                        break
+                    rows_now = self.rows()
+                    if retire_rows and rows_now > 6 and int(live.sum()) <= retire_rows * rows_now and int(live.sum()) < rows_now:
+                        if self.retire_rows() != rows_now:  # the slots are another set now; only the live rows' counts are read below
+                            retired = True
+                            ln, live = ln[live], live[live]
+                n = min(check_every, max_gen - int(ln[live].min())) if live.any() else check_every
+                self.decode(n)
+                steps += n
+            orig, ln, unf = self.row_status()
+            codes = self.fetch().astype(np.int64)
+            for s, j in enumerate(orig):
+                codes[j, ln[s]:] = stop  # behind a row's own tokens the slot holds what an earlier row left
+            self._exit()
+        finally:
+            if fo is not None:
+                self.set_forced(held)  # the caller's setting, as it was
+            if table is not None:
+                self.set_sampling_rows(None)
+                self.keep_row_table(False)
+            # a table whose FIRST rows are all equal is the scalar setting to the library (it sets do_sample and keeps the draws):
+            # nothing of this call may stay behind for the next generation
+            self.set_sampling(False)
+        order = sched.order()
+        assert sorted(order) == list(range(N)) and codes.shape[0] == N, (order, codes.shape)
+        out = np.empty_like(codes)
+        out[order] = codes
+        n = 0
+        for row in out:
+            hit = np.nonzero(row == stop)[0]
+            n = max(n, int(hit[0]) + 1 if len(hit) else max_gen)
+        return out[:, :n], log
 
     def _generate_host_sampled(self, cond, text_ids, max_gen, repetition_penalty, suppress_stop, top_k, top_p, temperature, seed,
                                uniforms, typical_mass) -> np.ndarray:

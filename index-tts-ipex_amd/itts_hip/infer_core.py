@@ -200,6 +200,42 @@ def row_uniforms(seeds: Sequence, max_gen: int) -> np.ndarray:
     return np.stack([np.random.default_rng(s).random(max_gen, dtype=np.float32) for s in seeds], axis=1)
 
 
+class AdmitScheduler:
+    """Which requests of one call start a generation of `slots` rows and which wait for a finished row's slot (row admission,
+    Engine.generate(slots=..)).  Pure bookkeeping, no engine: the longest `slots` texts start - so every later text fits the
+    generation's text length - in the caller's order; the others wait in the caller's order.  take(finished) hands the head
+    of the waiting list to the lowest finished slots once at least ceil(admit_min * slots) slots are finished, or as soon as the
+    rest of the list fits into the finished ones.  slot_req[s]: the request slot s holds; log: (slots, requests) per admission."""
+
+    def __init__(self, lengths: Sequence[int], slots: int, admit_min: float):
+        n, slots = len(lengths), int(slots)
+        if slots < 1 or not 0.0 < float(admit_min) <= 1.0:
+            raise ValueError(f"AdmitScheduler: slots >= 1 and 0 < admit_min <= 1, not {slots!r}, {admit_min!r}")
+        order = sorted(range(n), key=lambda i: (-int(lengths[i]), i))
+        self.first = sorted(order[:slots])
+        self.waiting = sorted(order[slots:])
+        self.need = max(1, int(np.ceil(float(admit_min) * slots - 1e-9)))
+        self.slot_req = list(self.first)
+        self.log: List[tuple] = []
+
+    def take(self, finished: Sequence[int]):
+        """finished: the slots whose row has finished, ascending.  -> (slots, requests) to admit now (both empty: not yet)."""
+        f = len(finished)
+        if not self.waiting or f == 0 or (f < self.need and len(self.waiting) > f):
+            return [], []
+        k = min(f, len(self.waiting))
+        req, self.waiting = self.waiting[:k], self.waiting[k:]
+        sl = [int(s) for s in finished[:k]]
+        for s, r in zip(sl, req):
+            self.slot_req[s] = r
+        self.log.append((sl, req))
+        return sl, req
+
+    def order(self) -> List[int]:
+        """The request of every original row of the generation: the first rows, then the admitted ones in admission order."""
+        return self.first + [r for _, req in self.log for r in req]
+
+
 # ---- host-side token choice (HF GenerationMixin.sample over the whole vocabulary) ----
 def host_distribution(scores: np.ndarray, seen_ids, penalty: float, temperature: float, top_k: int, top_p: float,
                       typical_mass: float, stop: int, suppress_stop: bool, min_keep: int = 1, log_softmax_first: bool = False,

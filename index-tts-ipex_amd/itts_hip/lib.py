@@ -99,6 +99,13 @@ class RowSampling(C.Structure):
     _fields_ = [("mode", i32), ("top_k", i32), ("top_p", f32), ("temperature", f32), ("penalty", f32)]
 
 
+class RowsAdmitArgs(C.Structure):
+    """itts_rows_admit_args: the state arrays of B rows, the device sources and the host lists of the n admitted slots."""
+    _fields_ = [(n, vp) for n in ("seen", "unfinished", "cur_tok", "len", "kv_start", "ids", "forced", "uniforms", "forced_src",
+                                  "uniforms_src", "slots_host", "kv_start_host")] + \
+               [(n, i32) for n in ("n", "B", "V", "max_gen", "fake_id", "start_tok", "stop")]
+
+
 _lib = None
 _lib_f16 = None
 
@@ -176,6 +183,14 @@ _PROTOS = {
     "itts_gpt_rows": (i32, [vp]),
     "itts_rows_move": (i32, [vp, C.c_size_t, i32, C.c_size_t, C.c_size_t, i32, C.c_size_t, vp, vp, i32, vp]),
     "itts_retire_plan": (i32, [vp, i32, C.POINTER(i32), vp, vp, C.POINTER(i32)]),
+    "itts_gpt_admit_rows": (i32, [vp, vp, i32, vp, i32, i32, C.POINTER(RowSampling), vp, vp, i32, vp, vp]),
+    "itts_gpt_row_status": (i32, [vp, vp, vp, vp, vp]),
+    "itts_gpt_rows_total": (i32, [vp]),
+    "itts_gpt_graph_captures": (i32, [vp]),
+    "itts_gpt_keep_row_table": (i32, [vp, i32]),
+    "itts_kv_admit": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "itts_rows_admit": (i32, [C.POINTER(RowsAdmitArgs), vp]),
+    "itts_admit_plan": (i32, [vp, vp, i32, i32, i32, vp, C.POINTER(i32)]),
     "itts_gpt_latent": (i32, [vp, vp, vp, i32, vp, i32, vp, vp]),
     "itts_gpt_latent_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     "itts_bigvgan": (i32, [vp, vp, vp, i32, i32, vp, vp]),
