@@ -561,7 +561,7 @@ int itts_gpt_fetch(itts_engine* e, int32_t* codes_host, float* logits_host, itts
  * batch: itts_gpt_status counts the live rows, itts_gpt_fetch returns all B rows in their ORIGINAL order - retired rows with their
  * codes followed by the stop token, exactly what an unretired run holds, and with the logits of their LAST STEP BEFORE THE
  * RETIREMENT (an unretired run would keep computing logits for them; nothing reads those).  It is a no-op that reports the
- * unchanged row count without an active generation, under beams, under host sampling, while the step runs on the persistent
+ * unchanged row count without an active generation, under beams (unless itts_gpt_set_retire_beams opted in), under host sampling, while the step runs on the persistent
  * decode engine or the fused qkv + attention launch, and when no row or every row has finished.  After a retirement the
  * generation stays on the launch path even at <= 6 rows (itts_gpt_decode_mode answers 0).  The next itts_gpt_prefill resets it. */
 int itts_gpt_retire_rows(itts_engine* e, int* rows_now_host, itts_stream stream);
@@ -578,6 +578,31 @@ int itts_rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stri
 /* The compaction plan alone (host only): with n live rows of B, the live rows at slots >= n move into the dead slots < n, both
  * in ascending order; live rows below n keep their slot.  src_host / dst_host hold up to B entries. */
 int itts_retire_plan(const int* unfinished_host, int B, int* n_live, int* src_host, int* dst_host, int* n_moves);
+
+/* Retirement of finished beam groups (opt-in, sticky per engine object, default 0 = itts_gpt_retire_rows stays the no-op under beams
+ * that it is above).  With on = 1 itts_gpt_retire_rows compacts a beam generation (num_beams > 1) to the rows of its unfinished
+ * batch items: a group of num_beams rows moves as a unit and a beam keeps its index inside its group, so the cache ancestry, which
+ * is relative to the group, stays valid.  A retiring item is finalised at once from its hypothesis store - it is done, so nothing
+ * can change its result - and kept on the host by original item; K/V, the per-row and per-item beam state move with rows_move, the
+ * live half of the two ping-pong arrays (beam ids, ancestry) with itts_rows_gather below, the draws are re-packed by original
+ * item.  itts_gpt_fetch then returns [items * num_return_sequences][max_gen] codes in the ORIGINAL item order and logits [rows][V]
+ * in the original row order (retired rows: the logits of their last step before the retirement); itts_gpt_rows, itts_gpt_status
+ * and itts_gpt_row_status answer for the live rows.  Same bits as the unretired run while the row count stays inside one
+ * projection-kernel family.  Still a no-op that reports the unchanged row count: while the step runs on the persistent engine or
+ * the fused qkv + attention launch, under host sampling (host-side beam warpers), with `input_tokens`, and when no item or every
+ * item is done.  The environment variable ITTS_RETIRE_BEAMS (read per call) overrides the setter in both directions.
+ * Additions to ABI 4 (the version stays): itts_gpt_set_retire_beams, itts_rows_gather. */
+int itts_gpt_set_retire_beams(itts_engine* e, int on);
+
+/* Operator entry of rows_gather_kernel on caller memory, the out-of-place companion of itts_rows_move: for plane p < n_planes and
+ * j < n_rows copy row_bytes from src + p * src_plane_stride + src_rows[j] * row_bytes to dst + p * dst_plane_stride + j * row_bytes.
+ * 16-byte units where both bases, both strides and row_bytes are multiples of 16, else 4-byte units or single bytes.  n_rows = 0,
+ * n_planes = 0 or row_bytes = 0 launches nothing.  ITTS_E_INVALID before any HIP call for: a null dst or src, a null row list with
+ * n_rows > 0, negative counts, n_rows > 128, n_planes > 65536, a row index outside [0, 65536), row_bytes >= 4 GiB, a plane stride
+ * >= 1 TiB, n_planes > 1 with n_rows * row_bytes > dst_plane_stride (destination planes would overlap), and any byte that the
+ * launch would both read and write (the source rows and the destination blocks must not intersect). */
+int itts_rows_gather(void* dst, size_t dst_plane_stride, const void* src, size_t src_plane_stride, int n_planes, size_t row_bytes,
+                     const int* src_rows_host, int n_rows, itts_stream stream);
 
 /* Row admission into a running batched generation (opt-in; nothing changes for a caller that never calls it).  A token step costs
  * almost the same at every row count, so a slot whose row has finished is better given to the next waiting request than carried

@@ -318,6 +318,14 @@ int itts_rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stri
                    (hipStream_t)stream);
 }
 
+int itts_rows_gather(void* dst, size_t dst_plane_stride, const void* src, size_t src_plane_stride, int n_planes, size_t row_bytes,
+                     const int* src_rows_host, int n_rows, itts_stream stream) {
+  // refused before any HIP call
+  ITTS_TRY(rows_gather_check(dst, dst_plane_stride, src, src_plane_stride, n_planes, row_bytes, src_rows_host, n_rows));
+  (void)hipGetLastError();
+  return rows_gather(dst, dst_plane_stride, src, src_plane_stride, n_planes, row_bytes, src_rows_host, n_rows, (hipStream_t)stream);
+}
+
 int itts_retire_plan(const int* unfinished_host, int B, int* n_live, int* src_host, int* dst_host, int* n_moves) {
   return retire_plan(unfinished_host, B, n_live, src_host, dst_host, n_moves);
 }
@@ -943,6 +951,10 @@ int itts_gpt_fetch(itts_engine* e, int32_t* codes, float* logits, itts_stream s)
 int itts_gpt_retire_rows(itts_engine* e, int* rows_now_host, itts_stream s) {
   ENG(e);
   return e->e.gpt_retire_rows(rows_now_host, (hipStream_t)s);
+}
+int itts_gpt_set_retire_beams(itts_engine* e, int on) {
+  ENG(e);
+  return e->e.gpt_set_retire_beams(on);
 }
 int itts_gpt_rows(itts_engine* e) { return e ? (e->e.ds.active ? e->e.ds.B : 0) : -1; }
 int itts_gpt_admit_rows(itts_engine* e, const float* cond, int cond_rows, const int32_t* text_ids_host, int n, int L,

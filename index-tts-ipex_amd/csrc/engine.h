@@ -148,6 +148,10 @@ struct DecodeState {
   std::vector<uint8_t> retired;       // [B0]
   std::vector<int32_t> ret_codes;     // [B0][max_gen]
   std::vector<float> ret_logits;      // [B0][V]
+  // Retirement of finished beam groups (gpt_set_retire_beams, opt-in): a group of nb rows moves as a unit.  retired / ret_logits /
+  // orig stay per row; ret_codes is then [B0 / nb][ret_keep][max_gen] by original item, the finalised hypotheses of a retired item
+  int retire_beams = 0;               // the sticky switch (ITTS_RETIRE_BEAMS overrides it per call)
+  int ret_keep = 1;                   // beam_returns when the first group retired: the fetch returns as many per item
   // Row admission (Engine::gpt_admit_rows, opt-in): finished slots take new requests, which get the original rows B0, B0 + 1, ..
   // - so B0 grows while B and Bcache stay.  What the generation then owns by ORIGINAL row: the per-row settings (a table
   // generation; row_table is the caller's setting for the next prefill and keeps its size) and the draws [B0][max_gen]
@@ -341,12 +345,24 @@ struct Engine {
   int ensure_beam_wide_state(int rows, int nb, int V, hipStream_t s);
   int gpt_beam_picks(float* score_host, int32_t* tok_host, int32_t* beam_host, int32_t* kept_host, hipStream_t s);
   int beam_finalize(int32_t* codes_host, hipStream_t s);
+  // the scorer's state on the host (beam_read_state) and BeamSearchScorer.finalize for one batch item of it: what beam_finalize
+  // runs over every item at the fetch and gpt_retire_rows over the retiring items
+  struct BeamHost {
+    int k = 0;  // the common step
+    std::vector<int> done, hlen, hord;
+    std::vector<float> bscore, hscore;
+    std::vector<int32_t> ids, htok;  // the live half of beam_ids [rows][max_gen], hyp_tok [items][nb + 1][max_gen]
+  };
+  int beam_read_state(BeamHost& st, hipStream_t s);
+  int beam_finalize_item(const BeamHost& st, int b, int32_t* out) const;  // out [beam_returns][max_gen]
   std::vector<int32_t> forced_host;  // [forced_B][forced_n], uploaded by the next prefill
   int forced_B = 0, forced_n = 0;
   int gpt_status(int* steps, int* n_unf, hipStream_t s);
   int gpt_fetch(int32_t* codes, float* logits, hipStream_t s);
   int fetch_retired(int32_t* codes, float* logits, hipStream_t s);  // gpt_fetch after a retirement: original row order
   int gpt_retire_rows(int* rows_now, hipStream_t s);  // compact a running single-beam generation to its unfinished rows (opt-in)
+  int gpt_set_retire_beams(int on);                   // opt-in: gpt_retire_rows also retires the finished groups of a beam generation
+  int retire_beam_groups(int* rows_now, hipStream_t s);  // its beam branch
   // refill n finished slots of the running generation with new requests (opt-in); slots_out [n]: the slots they took
   int gpt_admit_rows(const float* cond, int cond_rows, const int32_t* text_ids, int n, int L, const RowSampling* rows_host,
                      const float* uniforms_host, const int32_t* forced_host, int n_forced, int32_t* slots_out, hipStream_t s);

@@ -194,6 +194,19 @@ int rows_move_check(const void* base, size_t outer_stride, int n_outer, size_t r
 int rows_move(void* base, size_t outer_stride, int n_outer, size_t row_stride, size_t chunk_stride, int n_chunks, size_t chunk_bytes,
               const int* src, const int* dst, int n_moves, hipStream_t s);
 int retire_plan(const int* unfinished, int B, int* n_live, int* src, int* dst, int* n_moves);  // host only
+// rows_gather_kernel, the out-of-place row gather behind the retirement of finished beam groups: row j of every destination plane
+// takes row src_rows[j] of the same source plane.  The source and destination byte ranges of one launch do not intersect
+struct RowsGatherArgs {
+  char* dst = nullptr;
+  const char* src = nullptr;
+  size_t dst_plane_stride = 0, src_plane_stride = 0, row_bytes = 0;
+  int n_planes = 0, n_rows = 0;
+  unsigned short src_rows[ROWS_MOVE_MAX];
+};
+int rows_gather_check(const void* dst, size_t dst_plane_stride, const void* src, size_t src_plane_stride, int n_planes, size_t row_bytes,
+                      const int* src_rows, int n_rows);  // host only: no HIP call
+int rows_gather(void* dst, size_t dst_plane_stride, const void* src, size_t src_plane_stride, int n_planes, size_t row_bytes,
+                const int* src_rows, int n_rows, hipStream_t s);
 
 // decode_admit.hip: the two kernels behind the row admission into a running batch (Engine::gpt_admit_rows).  The slots travel by
 // value in the argument blocks, at most ROWS_MOVE_MAX of them, as the moves of rows_move_kernel do

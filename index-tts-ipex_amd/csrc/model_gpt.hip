@@ -431,68 +431,87 @@ int Engine::gpt_set_beams(int num_beams, int do_sample, int top_k, float top_p, 
 // num_return_sequences, model.py:655,698-703; highest score first, the later one on ties) are returned per batch item as
 // codes [B * beam_returns][max_gen] padded with the stop token (eos = pad = stop_mel_token, model.py:698-700).
 int Engine::beam_finalize(int32_t* codes, hipStream_t s) {
+  BeamHost st;
+  ITTS_TRY(beam_read_state(st, s));
+  for (int b = 0; b < ds.B / ds.nb; ++b) ITTS_TRY(beam_finalize_item(st, b, codes + (size_t)b * beam_returns * ds.max_gen));
+  return OK;
+}
+
+// the scorer's state of the running rows: done flags, running scores, the hypothesis store and the live half of the beam ids
+int Engine::beam_read_state(BeamHost& st, hipStream_t s) {
   DecodeState& d = ds;
   const int nb = d.nb, rows = d.B, B = rows / nb, mg = d.max_gen;
-  std::vector<int> len(rows), done(B), hn(B), hlen((size_t)B * (nb + 1)), hord((size_t)B * (nb + 1));
-  std::vector<float> bscore(rows), hscore((size_t)B * (nb + 1));
+  std::vector<int> len(rows);
+  st.done.resize(B);
+  st.hlen.resize((size_t)B * (nb + 1));
+  st.hord.resize((size_t)B * (nb + 1));
+  st.bscore.resize(rows);
+  st.hscore.resize((size_t)B * (nb + 1));
   ITTS_HIP_CHECK(hipMemcpyAsync(len.data(), d.len, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-  ITTS_HIP_CHECK(hipMemcpyAsync(done.data(), d.beam_done, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-  ITTS_HIP_CHECK(hipMemcpyAsync(bscore.data(), d.beam_scores, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-  ITTS_HIP_CHECK(hipMemcpyAsync(hscore.data(), d.hyp_score, hscore.size() * 4, hipMemcpyDeviceToHost, s));
-  ITTS_HIP_CHECK(hipMemcpyAsync(hlen.data(), d.hyp_len, hlen.size() * 4, hipMemcpyDeviceToHost, s));
-  ITTS_HIP_CHECK(hipMemcpyAsync(hord.data(), d.hyp_order, hord.size() * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.done.data(), d.beam_done, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.bscore.data(), d.beam_scores, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.hscore.data(), d.hyp_score, st.hscore.size() * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.hlen.data(), d.hyp_len, st.hlen.size() * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.hord.data(), d.hyp_order, st.hord.size() * 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
-  const int k = len[0];
-  std::vector<int32_t> ids((size_t)rows * mg), htok((size_t)B * (nb + 1) * mg);
-  ITTS_HIP_CHECK(hipMemcpyAsync(ids.data(), d.beam_ids + (size_t)(k & 1) * rows * mg, ids.size() * 4, hipMemcpyDeviceToHost, s));
-  ITTS_HIP_CHECK(hipMemcpyAsync(htok.data(), d.hyp_tok, htok.size() * 4, hipMemcpyDeviceToHost, s));
+  const int k = st.k = len[0];
+  st.ids.resize((size_t)rows * mg);
+  st.htok.resize((size_t)B * (nb + 1) * mg);
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.ids.data(), d.beam_ids + (size_t)(k & 1) * rows * mg, st.ids.size() * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.htok.data(), d.hyp_tok, st.htok.size() * 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
-  for (int b = 0; b < B; ++b) {
-    struct Hyp {
-      float score;
-      int order, len;
-      const int32_t* tok;
-    };
-    std::vector<Hyp> hy;
-    for (int q = 0; q <= nb; ++q) {
-      const size_t i = (size_t)b * (nb + 1) + q;
-      if (hord[i] >= 0) hy.push_back({hscore[i], hord[i], hlen[i], htok.data() + i * mg});
-    }
-    if (!done[b]) {
-      // beam_hyp.add(final_tokens, final_score, generated_len) for every open beam, with BeamHypotheses.add's eviction
-      std::sort(hy.begin(), hy.end(), [](const Hyp& x, const Hyp& y) { return x.order < y.order; });
-      float worst = 1e9f;
-      for (const Hyp& h : hy) worst = std::min(worst, h.score);
-      int counter = 1 << 20;
-      const float lpdiv = d.length_penalty == 0.f ? 1.f : std::pow((float)(k - d.input_n), d.length_penalty);  // generated_len = k - given tokens
-      for (int q = 0; q < nb; ++q) {
-        const int row = b * nb + q;
-        const float score = bscore[row] / lpdiv;
-        if ((int)hy.size() < nb || score > worst) {
-          hy.push_back({score, counter++, k, ids.data() + (size_t)row * mg});
-          if ((int)hy.size() > nb) {
-            size_t lo = 0;
-            for (size_t i = 1; i < hy.size(); ++i)
-              if (hy[i].score < hy[lo].score || (hy[i].score == hy[lo].score && hy[i].order < hy[lo].order)) lo = i;
-            hy.erase(hy.begin() + lo);
-            worst = 1e9f;
-            for (const Hyp& h : hy) worst = std::min(worst, h.score);
-          } else {
-            worst = std::min(worst, score);
-          }
+  return OK;
+}
+
+// BeamSearchScorer.finalize for batch item b of the state st -> codes [beam_returns][max_gen].  A done item is read from its
+// hypothesis store alone: its result is final from the step at which it became done
+int Engine::beam_finalize_item(const BeamHost& st, int b, int32_t* codes) const {
+  const DecodeState& d = ds;
+  const int nb = d.nb, mg = d.max_gen, k = st.k;
+  struct Hyp {
+    float score;
+    int order, len;
+    const int32_t* tok;
+  };
+  std::vector<Hyp> hy;
+  for (int q = 0; q <= nb; ++q) {
+    const size_t i = (size_t)b * (nb + 1) + q;
+    if (st.hord[i] >= 0) hy.push_back({st.hscore[i], st.hord[i], st.hlen[i], st.htok.data() + i * mg});
+  }
+  if (!st.done[b]) {
+    // beam_hyp.add(final_tokens, final_score, generated_len) for every open beam, with BeamHypotheses.add's eviction
+    std::sort(hy.begin(), hy.end(), [](const Hyp& x, const Hyp& y) { return x.order < y.order; });
+    float worst = 1e9f;
+    for (const Hyp& h : hy) worst = std::min(worst, h.score);
+    int counter = 1 << 20;
+    const float lpdiv = d.length_penalty == 0.f ? 1.f : std::pow((float)(k - d.input_n), d.length_penalty);  // generated_len = k - given tokens
+    for (int q = 0; q < nb; ++q) {
+      const int row = b * nb + q;
+      const float score = st.bscore[row] / lpdiv;
+      if ((int)hy.size() < nb || score > worst) {
+        hy.push_back({score, counter++, k, st.ids.data() + (size_t)row * mg});
+        if ((int)hy.size() > nb) {
+          size_t lo = 0;
+          for (size_t i = 1; i < hy.size(); ++i)
+            if (hy[i].score < hy[lo].score || (hy[i].score == hy[lo].score && hy[i].order < hy[lo].order)) lo = i;
+          hy.erase(hy.begin() + lo);
+          worst = 1e9f;
+          for (const Hyp& h : hy) worst = std::min(worst, h.score);
+        } else {
+          worst = std::min(worst, score);
         }
       }
     }
-    const int keep = beam_returns;
-    ITTS_REQUIRE((int)hy.size() >= keep, "beam_finalize: fewer hypotheses than num_return_sequences for a batch item");
-    for (int r = 0; r < keep; ++r) {
-      size_t best = 0;  // sorted(key=score).pop(): highest score, the later insertion on ties
-      for (size_t i = 1; i < hy.size(); ++i)
-        if (hy[i].score > hy[best].score || (hy[i].score == hy[best].score && hy[i].order > hy[best].order)) best = i;
-      int32_t* out = codes + ((size_t)b * keep + r) * mg;
-      for (int i = 0; i < mg; ++i) out[i] = i < hy[best].len ? hy[best].tok[i] : cfg.stop_mel_token;
-      hy.erase(hy.begin() + best);
-    }
+  }
+  const int keep = beam_returns;
+  ITTS_REQUIRE((int)hy.size() >= keep, "beam_finalize: fewer hypotheses than num_return_sequences for a batch item");
+  for (int r = 0; r < keep; ++r) {
+    size_t best = 0;  // sorted(key=score).pop(): highest score, the later insertion on ties
+    for (size_t i = 1; i < hy.size(); ++i)
+      if (hy[i].score > hy[best].score || (hy[i].score == hy[best].score && hy[i].order > hy[best].order)) best = i;
+    int32_t* out = codes + (size_t)r * mg;
+    for (int i = 0; i < mg; ++i) out[i] = i < hy[best].len ? hy[best].tok[i] : cfg.stop_mel_token;
+    hy.erase(hy.begin() + best);
   }
   return OK;
 }
@@ -1527,23 +1546,28 @@ int Engine::gpt_fetch(int32_t* codes, float* logits, hipStream_t s) {
 }
 
 // gpt_fetch after a row retirement: [B0] rows in the ORIGINAL order - live rows from their slot, retired rows from the host store
-// (their codes followed by stop, as an unretired run holds them, and the logits of their last step before the retirement)
+// (their codes followed by stop, as an unretired run holds them, and the logits of their last step before the retirement).
+// Under beams the codes come per batch item, ret_keep hypotheses each: live items from beam_finalize over the live state
 int Engine::fetch_retired(int32_t* codes, float* logits, hipStream_t s) {
   const DecodeState& d = ds;
   const size_t mg = (size_t)d.max_gen, V = (size_t)cfg.number_mel_codes;
-  std::vector<int32_t> ids(codes ? (size_t)d.B * mg : 0);
+  const int nb = d.nb, keep = nb > 1 ? d.ret_keep : 1;  // an item: nb rows, keep code rows
+  ITTS_REQUIRE(nb == 1 || beam_returns == d.ret_keep, "gpt_fetch: num_return_sequences changed after a beam group was retired");
+  const size_t item = (size_t)keep * mg;
+  std::vector<int32_t> ids(codes ? (size_t)(d.B / nb) * item : 0);
   std::vector<float> lg(logits ? (size_t)d.B * V : 0);
-  if (codes) ITTS_HIP_CHECK(hipMemcpyAsync(ids.data(), d.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
+  if (codes && nb > 1) ITTS_TRY(beam_finalize(ids.data(), s));
+  if (codes && nb == 1) ITTS_HIP_CHECK(hipMemcpyAsync(ids.data(), d.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
   if (logits) ITTS_HIP_CHECK(hipMemcpyAsync(lg.data(), d.logits, lg.size() * 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   for (int r = 0; r < d.B0; ++r) {
     if (!d.retired[r]) continue;
-    if (codes) std::memcpy(codes + (size_t)r * mg, d.ret_codes.data() + (size_t)r * mg, mg * 4);
+    if (codes && r % nb == 0) std::memcpy(codes + (size_t)(r / nb) * item, d.ret_codes.data() + (size_t)(r / nb) * item, item * 4);
     if (logits) std::memcpy(logits + (size_t)r * V, d.ret_logits.data() + (size_t)r * V, V * 4);
   }
   for (int slot = 0; slot < d.B; ++slot) {
     const size_t r = (size_t)d.orig[slot];
-    if (codes) std::memcpy(codes + r * mg, ids.data() + (size_t)slot * mg, mg * 4);
+    if (codes && slot % nb == 0) std::memcpy(codes + r / nb * item, ids.data() + (size_t)(slot / nb) * item, item * 4);
     if (logits) std::memcpy(logits + r * V, lg.data() + (size_t)slot * V, V * 4);
   }
   return OK;
@@ -1554,7 +1578,8 @@ int Engine::fetch_retired(int32_t* codes, float* logits, hipStream_t s) {
 // for it), a row's results do not depend on its slot, so the caller sees the same generation.  The plan (retire_plan) moves live
 // rows from slots >= n into dead slots < n; rows_move_kernel copies their K/V history (the positions that hold history only:
 // what lies behind stays the dead row's finite bytes, which the attention multiplies by p = 0) and their state arrays.
-// No-op (the row count stays) without an active generation, under beams or host sampling, while the step runs on the persistent
+// No-op (the row count stays) without an active generation, under beams (unless gpt_set_retire_beams opted in: retire_beam_groups)
+// or host sampling, while the step runs on the persistent
 // engine or the fused qkv + attention launch, and when no row or every row has finished.
 int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
   DecodeState& d = ds;
@@ -1562,7 +1587,12 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
   if (!d.active) return OK;
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   static const bool env_fuse = getenv("ITTS_FUSE_QKV_ATTN") != nullptr && atoi(getenv("ITTS_FUSE_QKV_ATTN")) != 0;
-  if (d.nb > 1 || d.host_sample || engine_usable() || ((d.fuse || env_fuse) && !d.fuse_failed)) return OK;
+  if (d.nb > 1) {  // opt-in on its own (gpt_set_retire_beams; ITTS_RETIRE_BEAMS, read per call, overrides the setter both ways)
+    const char* rb = getenv("ITTS_RETIRE_BEAMS");
+    if (!(rb ? atoi(rb) != 0 : d.retire_beams != 0) || d.input_n > 0) return OK;
+  }
+  if (d.host_sample || engine_usable() || ((d.fuse || env_fuse) && !d.fuse_failed)) return OK;
+  if (d.nb > 1) return retire_beam_groups(rows_now, s);
   const itts_config& c = cfg;
   const int B = d.B, D = c.model_dim, H = c.heads, dh = D / H, V = c.number_mel_codes, mg = d.max_gen;
   std::vector<int> unf(B), lens(B), src(B), dst(B);
@@ -1625,6 +1655,131 @@ int Engine::gpt_retire_rows(int* rows_now, hipStream_t s) {
   d.B = n;
   // 4. the per-row settings travel with their rows, and the classes are those of the rows that are left (GraphKey::rows_classes)
   if (d.rows_active) ITTS_TRY(upload_row_table(s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  d.drop_graphs();  // every later step re-captures at the smaller row count (GraphKey::B / Bcache)
+  if (rows_now) *rows_now = n;
+  return OK;
+}
+
+int Engine::gpt_set_retire_beams(int on) {
+  ds.retire_beams = on != 0;
+  return OK;
+}
+
+// The beam branch of gpt_retire_rows (opt-in, gpt_set_retire_beams): compact a running beam generation to the rows of its
+// unfinished batch items.  Why a group may move as a unit: its nb rows are contiguous and aligned to nb, the cache ancestry names
+// a key's row relative to the group (decode_attn2_kernel<ANC>: (b / nb) * nb + anc[b][j]), and a done group is a no-op in every
+// beam kernel while beam_finalize reads nothing of it but its hypothesis store - so its result is final, taken here, and kept on
+// the host by original item.  With group-uniform flags retire_plan moves whole groups into whole holes and a beam keeps its index
+// inside its group (asserted below before anything changes).  The live groups share one step k, so len[0] stays the common step.
+//   1. the retiring items' hypotheses (beam_finalize_item) and their rows' last logits -> the host store
+//   2. rows_move with the row plan: K and V over all layers, h, logits, forced, len, kv_start, cur_tok, unfinished, beam_scores;
+//      with the item plan: the hypothesis store and the scorer's per-item words
+//   3. beam_ids [2][rows][max_gen] and anc [2][rows][Smax]: only the half of parity k & 1 is live (the next beam_select_kernel
+//      rewrites the other one completely for every live group), and every kernel computes the base of half 1 from the CURRENT row
+//      count.  Parity 0: rows_move in place.  Parity 1: the live rows go from base rows_old * row to base rows_new * row, ranges
+//      that may overlap - two rows_gather launches through the dead half 0: old half 1 -> [0, rows_new), then -> [rows_new, 2 rows_new)
+//   4. uniforms [max_gen][items][2 nb] re-packed from the host copy by original item
+// cand_*, scores2 and the whole-vocabulary sampler's block are scratch between the launches of one step, indexed by row or item
+// from pointers fixed at the prefill: nothing in them depends on the row count.
+int Engine::retire_beam_groups(int* rows_now, hipStream_t s) {
+  DecodeState& d = ds;
+  const itts_config& c = cfg;
+  const int nb = d.nb, B = d.B, items = B / nb, D = c.model_dim, H = c.heads, dh = D / H, V = c.number_mel_codes, mg = d.max_gen;
+  const int keep = beam_returns, nd = 2 * nb, items0 = d.B0 / nb;
+  std::vector<int> done(items), unf(B), lens(B), live(B), src(B), dst(B);
+  ITTS_HIP_CHECK(hipMemcpyAsync(done.data(), d.beam_done, (size_t)items * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(unf.data(), d.unfinished, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(lens.data(), d.len, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  for (int b = 0; b < B; ++b) live[b] = !done[b / nb];
+  int n = 0, nm = 0;
+  ITTS_TRY(retire_plan(live.data(), B, &n, src.data(), dst.data(), &nm));
+  if (n == B || n == 0) return OK;
+  // everything that could refuse, before anything is changed
+  const int k = lens[0];
+  ITTS_REQUIRE(k >= 0 && k <= mg, "gpt_retire_rows: decode state out of range");
+  for (int b = 0; b < B; ++b)
+    ITTS_REQUIRE(lens[b] == k && (live[b] || !unf[b]), "gpt_retire_rows: the beam groups do not share one step, or a done group has an unfinished row");
+  ITTS_REQUIRE(n % nb == 0 && nm % nb == 0 && nm <= ROWS_MOVE_MAX && n <= ROWS_MOVE_MAX, "gpt_retire_rows: beam groups need at most 128 live rows");
+  for (int i = 0; i < nm; ++i)  // whole groups into whole holes, a beam keeps its index inside its group
+    ITTS_REQUIRE(src[i] % nb == i % nb && dst[i] % nb == i % nb && src[i] - src[i - i % nb] == i % nb && dst[i] - dst[i - i % nb] == i % nb,
+                 "gpt_retire_rows: the plan splits a beam group");
+  ITTS_REQUIRE(keep >= 1 && keep <= nb && (d.orig.empty() || keep == d.ret_keep), "gpt_retire_rows: num_return_sequences changed inside a generation");
+  const bool draws = d.beam_sample && !d.host_sample;
+  ITTS_REQUIRE(!draws || sample_uniforms.size() >= (size_t)mg * items0 * nd, "gpt_retire_rows: the uniforms of this generation are gone");
+  std::vector<int> isrc(nm / nb), idst(nm / nb);  // the item plan
+  for (int g = 0; g < nm / nb; ++g) {
+    isrc[g] = src[g * nb] / nb;
+    idst[g] = dst[g * nb] / nb;
+  }
+  // 1. the retiring items' hypotheses and last logits go to the host store, by original item / row
+  {
+    BeamHost st;
+    ITTS_TRY(beam_read_state(st, s));
+    std::vector<int32_t> fin((size_t)items * keep * mg);
+    for (int b = 0; b < items; ++b)
+      if (done[b]) ITTS_TRY(beam_finalize_item(st, b, fin.data() + (size_t)b * keep * mg));
+    std::vector<float> lg((size_t)B * V);
+    ITTS_HIP_CHECK(hipMemcpyAsync(lg.data(), d.logits, lg.size() * 4, hipMemcpyDeviceToHost, s));
+    ITTS_HIP_CHECK(hipStreamSynchronize(s));
+    if (d.orig.empty()) {
+      d.orig.resize(B);
+      for (int b = 0; b < B; ++b) d.orig[b] = b;
+      d.retired.assign((size_t)d.B0, 0);
+      d.ret_keep = keep;
+      d.ret_codes.assign((size_t)items0 * keep * mg, c.stop_mel_token);
+      d.ret_logits.assign((size_t)d.B0 * V, 0.f);
+    }
+    for (int b = 0; b < B; ++b) {
+      if (live[b]) continue;
+      const size_t r = (size_t)d.orig[b];
+      d.retired[r] = 1;
+      if (b % nb == 0) std::memcpy(d.ret_codes.data() + r / nb * keep * mg, fin.data() + (size_t)(b / nb) * keep * mg, (size_t)keep * mg * 4);
+      std::memcpy(d.ret_logits.data() + r * V, lg.data() + (size_t)b * V, (size_t)V * 4);
+    }
+  }
+  // 2. K and V over all layers (heads as chunks, the positions that hold history), the per-row and the per-item arrays
+  const size_t head = (size_t)d.Smax * dh * d.ces, row = (size_t)H * head;
+  const size_t hist = (size_t)std::min(d.Smax, d.prefix + k + 1) * dh * d.ces;
+  for (void* cache : {d.kc, d.vc})
+    ITTS_TRY(rows_move(cache, (size_t)d.Bcache * row, c.layers, row, head, H, hist, src.data(), dst.data(), nm, s));
+  const std::pair<void*, size_t> by_row[] = {{d.h, (size_t)D * 4}, {d.logits, (size_t)V * 4}, {d.forced, (size_t)mg * 4}, {d.len, 4},
+                                             {d.kv_start, 4},      {d.cur_tok, 4},            {d.unfinished, 4},          {d.beam_scores, 4}};
+  for (const auto& a : by_row)
+    ITTS_TRY(rows_move(a.first, 0, 1, a.second, a.second, 1, a.second, src.data(), dst.data(), nm, s));
+  const size_t slots = (size_t)(nb + 1) * 4;  // the nb + 1 hypothesis slots of an item
+  const std::pair<void*, size_t> by_item[] = {{d.hyp_tok, slots * mg}, {d.hyp_score, slots}, {d.hyp_len, slots},  {d.hyp_order, slots},
+                                              {d.hyp_n, 4},            {d.hyp_worst, 4},     {d.hyp_counter, 4}, {d.beam_done, 4}};
+  for (const auto& a : by_item)
+    ITTS_TRY(rows_move(a.first, 0, 1, a.second, a.second, 1, a.second, isrc.data(), idst.data(), nm / nb, s));
+  // 3. the live half of the two ping-pong arrays
+  const std::pair<void*, size_t> halves[] = {{d.beam_ids, (size_t)mg * 4}, {d.anc, (size_t)d.Smax}};
+  if ((k & 1) == 0) {
+    for (const auto& a : halves)
+      ITTS_TRY(rows_move(a.first, 0, 1, a.second, a.second, 1, a.second, src.data(), dst.data(), nm, s));
+  } else {
+    std::vector<int> from(n), iota(n);  // from[j]: the row of the old half 1 that slot j holds after the retirement
+    for (int j = 0; j < n; ++j) from[j] = B + j, iota[j] = j;
+    for (int i = 0; i < nm; ++i) from[dst[i]] = B + src[i];
+    for (const auto& a : halves) {
+      ITTS_TRY(rows_gather(a.first, 0, a.first, 0, 1, a.second, from.data(), n, s));
+      ITTS_TRY(rows_gather((char*)a.first + (size_t)n * a.second, 0, a.first, 0, 1, a.second, iota.data(), n, s));
+    }
+  }
+  for (int i = 0; i < nm; ++i) d.orig[dst[i]] = d.orig[src[i]];
+  d.orig.resize(n);
+  // 4. beam_select_kernel reads uniforms[(k * items + item) * 2 nb + j]: re-packed by original item
+  std::vector<float> u;
+  if (draws) {
+    const int ni = n / nb;
+    u.resize((size_t)mg * ni * nd);
+    for (int q = 0; q < mg; ++q)
+      for (int i = 0; i < ni; ++i)
+        std::memcpy(u.data() + ((size_t)q * ni + i) * nd, sample_uniforms.data() + ((size_t)q * items0 + d.orig[i * nb] / nb) * nd, (size_t)nd * 4);
+    ITTS_HIP_CHECK(hipMemcpyAsync(d.uniforms, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
+  }
+  d.B = n;
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   d.drop_graphs();  // every later step re-captures at the smaller row count (GraphKey::B / Bcache)
   if (rows_now) *rows_now = n;

@@ -30,6 +30,9 @@ def build_parser():
     p.add_argument("--retire-rows", type=float, default=None, metavar="R",
                    help="batched generations retire their finished rows whenever unfinished <= R * running rows (0 < R <= 1; more "
                         "than 6 rows); unset: ITTS_RETIRE_ROWS, else off")
+    p.add_argument("--retire-beams", action="store_true", default=None,
+                   help="with --retire-rows: beam generations (the default, num_beams=3) retire the rows of their finished sentences "
+                        "too; unset: ITTS_RETIRE_BEAMS, else off")
     p.add_argument("--ragged-vocoder", action="store_true", default=False,
                    help="batched synthesis (IndexTTS.infer_batch): sentences of unequal length share vocoder passes; "
                         "ITTS_RAGGED_VOCODER=0 / 1 overrides")
@@ -59,7 +62,7 @@ def main():
 
     tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8, kv_fp8=a.kv_fp8,
                    wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler, retire_rows=a.retire_rows,
-                   engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder, admit_rows=a.admit_rows)
+                   engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder, admit_rows=a.admit_rows, retire_beams=a.retire_beams)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

@@ -35,6 +35,9 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `retire_rows=r` (not in the reference; a ratio in (0, 1], None: ITTS_RETIRE_ROWS, else off) lets the batched generations
     of `infer_fast` / `infer_batch` retire their finished rows: whenever the unfinished rows are <= r * the running rows (and more
     than 6 rows run), the decode state is compacted and the following steps run at the smaller row count (Engine.generate).
+  * `retire_beams=True` (not in the reference; None: ITTS_RETIRE_BEAMS, else off; acts only together with `retire_rows`) extends
+    the row retirement to the beam generations - the mode of the default kwargs, `num_beams=3`: a finished sentence's group of
+    `num_beams` rows is retired as a unit and its hypotheses are kept by sentence (Engine.generate(retire_beams=..)).
   * `ragged_vocoder=True` (not in the reference; default off; ITTS_RAGGED_VOCODER=1 / 0 overrides it in both directions) lets the
     sentences of `infer_batch` share vocoder passes although their lengths differ (Engine.bigvgan_grouped(ragged=True)); without
     it only sentences of equal length do.  `infer` / `infer_fast` are not affected.
@@ -73,7 +76,7 @@ class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
-                 mixed_batch=False, admit_rows=False):
+                 mixed_batch=False, admit_rows=False, retire_beams=None):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -101,6 +104,7 @@ class IndexTTS:
         # the same choice for several beams (beam_sample with top_k = 0 / None or > 128): None: ITTS_WIDE_BEAM_SAMPLER, else "host"
         self.wide_beam_sampler = wide_beam_sampler
         self.retire_rows = retire_rows  # row retirement of the batched generations (Engine.generate); None: ITTS_RETIRE_ROWS, else off
+        self.retire_beams = retire_beams  # with retire_rows: beam generations retire their finished groups; None: ITTS_RETIRE_BEAMS, else off
         self.ragged_vocoder = bool(ragged_vocoder)  # infer_batch: sentences of unequal length share vocoder passes (ITTS_RAGGED_VOCODER overrides)
         self.mixed_batch = bool(mixed_batch)  # infer_batch: one decode batch across voices and sampling settings (ITTS_MIXED_BATCH overrides)
         self.admit_rows = bool(admit_rows)  # infer_batch with mixed_batch: finished decode rows are refilled from the waiting sentences (ITTS_ADMIT_ROWS overrides)
@@ -209,7 +213,7 @@ class IndexTTS:
             ids = infer_core.pad_tokens_cat(grp, self.cfg.gpt.stop_text_token)
             codes = self.engine.generate(cond, ids, g["max_mel_tokens"], repetition_penalty=g["repetition_penalty"],
                                          wide_sampler=self.wide_sampler, wide_beam_sampler=self.wide_beam_sampler,
-                                         retire_rows=self.retire_rows, **sample_kw)
+                                         retire_rows=self.retire_rows, retire_beams=self.retire_beams, **sample_kw)
             rows.extend(codes[r] for r in range(len(grp)))
         return rows
 
@@ -423,7 +427,7 @@ class IndexTTS:
                 if one:
                     kw["slots"] = cap
                 codes = self.engine.generate(cond, ids, g0["max_mel_tokens"], wide_sampler=self.wide_sampler,
-                                             wide_beam_sampler=self.wide_beam_sampler, retire_rows=self.retire_rows, **kw)
+                                             wide_beam_sampler=self.wide_beam_sampler, retire_rows=self.retire_rows, retire_beams=self.retire_beams, **kw)
                 for j, i in enumerate(sel):
                     code_rows[i] = codes[j]
             if any(r[-1] != self.stop_mel_token for r in code_rows):

@@ -343,11 +343,21 @@ class Engine:
         """Opt-in: compact the running generation to its unfinished rows (itts_gpt_retire_rows; synchronises).  The following
         decode steps run at the smaller row count, which is returned; status() counts the live rows, fetch() still returns every
         original row in its original order (retired rows: their codes followed by stop, the logits of their last step before the
-        retirement).  A no-op that returns the unchanged count under beams, host sampling, on the persistent engine (<= 6 rows)
-        and when no row or every row has finished."""
+        retirement).  A no-op that returns the unchanged count under beams (unless set_retire_beams opted in), host sampling, on
+        the persistent engine (<= 6 rows) and when no row or every row has finished."""
         n = C.c_int()
         self._ck(self.lib.itts_gpt_retire_rows(self.h, C.byref(n), self._s()), "gpt_retire_rows")
         return n.value
+
+    def set_retire_beams(self, on: bool = True):
+        """Opt-in: retire_rows() also works under beams - it retires the finished batch items of a beam generation, num_beams rows
+        as a unit (itts_gpt_set_retire_beams).  A retired item's hypotheses are final and kept by original item: fetch() returns
+        [items * num_return_sequences] code rows in the original order, and the bits of the unretired run while the row count
+        stays inside one projection-kernel family.  Still a no-op on the persistent engine (<= 6 rows), under host-side beam
+        warpers, with `input_tokens`, and when no item or every item is done.  Sticky, default off.  ITTS_RETIRE_BEAMS=0 / 1 in
+        the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_retire_beams(self.h, int(bool(on))), "gpt_set_retire_beams")
+        self._retire_beams = bool(on)
 
     def rows(self) -> int:
         """Rows the decode steps of the active generation run at (0: no generation)."""
@@ -417,7 +427,7 @@ class Engine:
                  uniforms: Optional[np.ndarray] = None, num_beams: int = 1, typical_mass: float = 0.0,
                  length_penalty: float = 0.0, num_return_sequences: int = 1, wide_sampler: Optional[str] = None,
                  wide_beam_sampler: Optional[str] = None, retire_rows: Optional[float] = None, slots: Optional[int] = None,
-                 admit_min: float = 0.125, return_log: bool = False) -> np.ndarray:
+                 admit_min: float = 0.125, return_log: bool = False, retire_beams: Optional[bool] = None) -> np.ndarray:
         """Greedy decode (do_sample=False, num_beams=1 of tests/padding_test.py:35-46) or, with do_sample, HF
         GenerationMixin.sample (top-k / top-p / temperature, num_beams=1; draws from `uniforms` or a numpy Generator
         seeded with `seed`).  Returns int64 codes [B, n] with n <= max_gen: HF stops when every row has emitted stop
@@ -440,6 +450,10 @@ class Engine:
         (e.g. 12 -> 3 rows) within the project's cross-family bound.  None: the environment's ITTS_RETIRE_ROWS, else off.
         Suggested value: 0.5 - measured with tools/bench_row_retire.py (profiles/row_retire.txt): 64 ragged
         rows decode 1.18 x faster at 0.5 and 1.19 x at 0.75; 20 rows with fp8 weights gain nothing at 0.5 and lose 3 % at 0.75.
+        retire_beams: opt-in on top of retire_rows for num_beams > 1 (set_retire_beams for the duration of the call): the loop
+        applies the same rule to a beam generation and retires its finished batch items, num_beams rows as a unit.  Off, a beam
+        generation ignores retire_rows as before.  None: the environment's ITTS_RETIRE_BEAMS, else off.  Measured with
+        tools/bench_beam_retire.py (profiles/beam_retire.txt).
         Mixed batches: do_sample, top_k, top_p, temperature, repetition_penalty and seed also take a sequence of length B, one
         entry per row (single beam, no typical filter: ValueError otherwise).  Entries that are all equal - with one seed - are the
         scalar request, on today's path.  Otherwise every row chooses its tokens with its own entry (infer_core.row_sampling_table,
@@ -488,6 +502,8 @@ class Engine:
         retire_rows = float(retire_rows)
         if not 0.0 <= retire_rows <= 1.0:
             raise ValueError(f"retire_rows must be a ratio in (0, 1] (or 0 / None: off), not {retire_rows!r}")
+        if retire_beams is None:
+            retire_beams = bool(int(os.environ.get("ITTS_RETIRE_BEAMS") or 0))
         if wide_sampler is None:
             wide_sampler = os.environ.get("ITTS_WIDE_SAMPLER") or "host"
         if wide_sampler not in ("host", "device"):
@@ -513,7 +529,7 @@ class Engine:
             return out if return_log else out[0]
         if return_log:
             raise ValueError("return_log needs slots= and more rows than slots")
-        kw = dict(retire_rows=retire_rows, wide_sampler=wide_sampler, wide_beam_sampler=wide_beam_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
+        kw = dict(retire_rows=retire_rows, retire_beams=bool(retire_beams), wide_sampler=wide_sampler, wide_beam_sampler=wide_beam_sampler, repetition_penalty=repetition_penalty, suppress_stop=suppress_stop, check_every=check_every, do_sample=do_sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, uniforms=uniforms, num_beams=num_beams,
                   typical_mass=typical_mass, length_penalty=length_penalty, num_return_sequences=num_return_sequences, rows=rows)
         try:
@@ -527,7 +543,7 @@ class Engine:
 
     def _generate_once(self, cond, text_ids, max_gen, repetition_penalty, suppress_stop, check_every, do_sample, top_k, top_p,
                        temperature, seed, uniforms, num_beams, typical_mass, length_penalty, num_return_sequences,
-                       wide_sampler="host", wide_beam_sampler="host", retire_rows=0.0, rows=None) -> np.ndarray:
+                       wide_sampler="host", wide_beam_sampler="host", retire_rows=0.0, rows=None, retire_beams=False) -> np.ndarray:
         """rows: the per-row table of a mixed batch (generate; do_sample is False then and the scalar settings are not read)."""
         beams = num_beams > 1
         if num_return_sequences != 1 and not beams:
@@ -557,9 +573,13 @@ class Engine:
             if uniforms is None:
                 uniforms = np.random.default_rng(seed).random((max_gen, nrow), dtype=np.float32)
             self.set_sampling(True, top_k, top_p, temperature, uniforms)
+        retire_beams = bool(retire_beams and retire_rows and beams)
+        held_rb = getattr(self, "_retire_beams", False)  # what set_retire_beams holds: the caller's setting
         try:
             if rows is not None:
                 self.set_sampling_rows(rows, uniforms)
+            if retire_beams:
+                self.set_retire_beams(True)
             self.prefill(cond, text_ids, max_gen, repetition_penalty, suppress_stop)
             done = 1
             while done < max_gen:
@@ -568,9 +588,9 @@ class Engine:
                     done = step
                     if unf == 0:
                         break
-                    if retire_rows and not beams:
-                        rows = self.rows()
-                        if rows > 6 and unf <= retire_rows * rows:
+                    if retire_rows and (not beams or retire_beams):
+                        rows_now = self.rows()
+                        if rows_now > 6 and unf <= retire_rows * rows_now:
                             self.retire_rows()
                 n = min(check_every, max_gen - done)
                 self.decode(n)
@@ -587,6 +607,8 @@ class Engine:
                 self.set_sampling(False)
             if rows is not None:
                 self.set_sampling_rows(None)
+            if retire_beams:
+                self.set_retire_beams(held_rb)  # the caller's setting, as it was
         # HF stops right after the step in which the last running row emitted stop: trim the look-ahead steps
         stop = self.ccfg.stop_mel_token
         n = 0
@@ -938,13 +960,14 @@ def _dvae_code_len(T: int, layers: int) -> int:
 
 def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1234, parts=("gpt", "bigvgan", "dvae"),
                  state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False,
-                 kv_fp8: bool = False, engine_kv_fp8: bool = False) -> Engine:
+                 kv_fp8: bool = False, engine_kv_fp8: bool = False, retire_beams: bool = False) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
     "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
     engine_fp8: Engine.set_engine_fp8(True) - the fp8 model's small-batch decode steps on the persistent decode engine.
     kv_fp8: Engine.set_kv_fp8(True) - the decode steps' K/V cache as fp8-e4m3 bytes (16-bit engines).
-    engine_kv_fp8: Engine.set_engine_kv_fp8(True) - with an fp8 cache the small-batch decode steps stay on the persistent engine."""
+    engine_kv_fp8: Engine.set_engine_kv_fp8(True) - with an fp8 cache the small-batch decode steps stay on the persistent engine.
+    retire_beams: Engine.set_retire_beams(True) - retire_rows() also retires the finished groups of a beam generation."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -965,4 +988,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
         eng.set_kv_fp8(True)
     if engine_kv_fp8:
         eng.set_engine_kv_fp8(True)
+    if retire_beams:
+        eng.set_retire_beams(True)
     return eng

@@ -183,6 +183,8 @@ _PROTOS = {
     "itts_gpt_rows": (i32, [vp]),
     "itts_rows_move": (i32, [vp, C.c_size_t, i32, C.c_size_t, C.c_size_t, i32, C.c_size_t, vp, vp, i32, vp]),
     "itts_retire_plan": (i32, [vp, i32, C.POINTER(i32), vp, vp, C.POINTER(i32)]),
+    "itts_gpt_set_retire_beams": (i32, [vp, i32]),
+    "itts_rows_gather": (i32, [vp, C.c_size_t, vp, C.c_size_t, i32, C.c_size_t, vp, i32, vp]),
     "itts_gpt_admit_rows": (i32, [vp, vp, i32, vp, i32, i32, C.POINTER(RowSampling), vp, vp, i32, vp, vp]),
     "itts_gpt_row_status": (i32, [vp, vp, vp, vp, vp]),
     "itts_gpt_rows_total": (i32, [vp]),
