@@ -149,6 +149,28 @@ int itts_attention_kernel(void* o, const void* q, const void* k, const void* v, 
 int itts_attention_which(const void* q, const void* k, const void* v, int B, int H, int Sq, int Sk, int dqk, int dv, int ldq,
                          int ldk, int ldv, int ldo, float scale, int causal, const int* kv_start, int dtype);
 
+/* Causal self-attention over PACKED sequences (csrc/attention_varlen.hip): sequence b owns token rows [seq_off_host[b],
+ * seq_off_host[b + 1]) of q, k, v and o (row r, head h, dim d at q[r * ldq + h * dqk + d], likewise k, v with dv, o with ldo); query i
+ * of a sequence sees keys 0 .. i of the same sequence and nothing else.  No pad rows, and every sequence is tiled from its own key 0:
+ * a sequence's output has the same bits alone, with any companions and in any order, and they are the bits of
+ * itts_attention_kernel(B = 1, Sq = Sk = len, causal = 1, kv_start = NULL) of the same kernel family on that sequence's rows.
+ * seq_off_host: nseq + 1 host ints, passed to the kernel by value (no upload; the array may be reused once the call returns).
+ * kernel: 0 = the dispatcher, 1 = attn_varlen_simple (vector ALU, fp32 or the 16-bit type, dqk <= 128, dv <= 64), 2 =
+ * attn_varlen_mfma (matrix cores: the 16-bit type, dqk = dv = 64, ldq / ldk / ldv % 8 == 0, q / k / v 16-byte aligned - and EVERY
+ * length >= 1).  The named kernel runs or nothing does.  The dispatcher's pick depends on type, head dims, leading dims and
+ * alignment only, never on a length (ITTS_ATTN_SIMPLE, read once per process, makes it 1).
+ * itts_attention_varlen_which: 1 or 2, that pick, without a launch; -1 for a call the entry refuses.
+ * Both share one host-side check, made before any HIP call, that answers ITTS_E_INVALID with a message that begins with the entry's
+ * name: a null q / k / v / o / seq_off_host; nseq outside 1 .. ITTS_VARLEN_MAX_SEQ; seq_off_host[0] != 0; offsets that are not strictly
+ * increasing (a length < 1); H outside 1 .. 65535; a dtype other than ITTS_F32 / ITTS_BF16 (the library's 16-bit type); dqk outside
+ * 1..128 or dv outside 1..64; ldq or ldk < H * dqk, ldv or ldo < H * dv; a kernel other than 0, 1, 2; and for kernel 2 whatever the
+ * matrix-core kernel's rule above rejects. */
+#define ITTS_VARLEN_MAX_SEQ 128
+int itts_attention_varlen(void* o, const void* q, const void* k, const void* v, const int32_t* seq_off_host, int nseq, int H, int dqk,
+                          int dv, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, int kernel, itts_stream stream);
+int itts_attention_varlen_which(const void* q, const void* k, const void* v, const int32_t* seq_off_host, int nseq, int H, int dqk,
+                                int dv, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, int kernel);
+
 /* Decode-step batched GEMV (GPT2 Conv1D on one token per row, HF GPT2Attention/GPT2MLP):
  * Y[b, n] (+)= act(prologue(X)[b, :] . W[n, :] + bias[n]); X, Y fp32; prologue 0 none, 1 LayerNorm, 2 LN o LN.
  * version 0 = auto, 1 = generic kernel, 2 = register-resident kernel (B <= 4). */
@@ -678,6 +700,14 @@ int itts_gpt_latent_batch(itts_engine* e, const float* cond, const int32_t* text
 int itts_gpt_latent_batch_cond(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond,
                                const int32_t* text_ids_host, const int32_t* text_lens_host, const int32_t* codes_host,
                                const int32_t* code_lens_host, int nseq, void* latent_out, itts_stream stream);
+/* The PACKED latent pass: the interface of itts_gpt_latent_batch_cond (cond_index_host may be NULL = block 0 for every sentence;
+ * n_cond >= 1), 1 <= nseq <= ITTS_VARLEN_MAX_SEQ.  The tokens of all sentences lie back to back [sum S_i, D] with no pad rows, the
+ * attention tiles every sentence from its own key 0 (itts_attention_varlen's dispatcher), no GEMM splits K and the GEMM kernel
+ * family is picked from the projection's own dims, never from the row count: a sentence's latent has the same bits alone, with any
+ * companions, in any order and in any chunking.  Writes no K/V cache.  latent_out = [sum T_i, D] in the engine dtype. */
+int itts_gpt_latent_packed(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond,
+                           const int32_t* text_ids_host, const int32_t* text_lens_host, const int32_t* codes_host,
+                           const int32_t* code_lens_host, int nseq, void* latent_out, itts_stream stream);
 
 /* V1-V5  BigVGAN.forward given the speaker embedding (BigVGAN/models.py:201-250):
  * latent [B, T, gpt_dim] (engine dtype), spk fp32 [B, spk_dim] -> wav fp32 [B, T * prod(up_rates)] */

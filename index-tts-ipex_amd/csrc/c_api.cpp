@@ -258,6 +258,43 @@ int itts_attention_which(const void* q, const void* k, const void* v, int B, int
   return attention_refusal(a, dtype, 0) ? E_INVALID : attention_which(a, dtype);
 }
 
+// itts_attention_varlen / itts_attention_varlen_which: one host-side check (attention_varlen_refusal) before any HIP call
+static const char* to_varlen_args(VarlenArgs& a, void* o, const void* q, const void* k, const void* v, const int32_t* seq_off_host, int nseq,
+                                  int H, int dqk, int dv, int ldq, int ldk, int ldv, int ldo, float scale) {
+  a.q = q; a.k = k; a.v = v; a.o = o; a.H = H; a.dqk = dqk; a.dv = dv;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale; a.nseq = nseq;
+  if (!seq_off_host) return "null pointer (q, k, v, o, seq_off_host)";
+  if (nseq < 1 || nseq > VARLEN_MAX_SEQ) return "nseq outside 1 .. 128";  // (before the copy: the array holds nseq + 1 ints)
+  for (int i = 0; i <= nseq; ++i) a.off[i] = seq_off_host[i];
+  return nullptr;
+}
+
+int itts_attention_varlen(void* o, const void* q, const void* k, const void* v, const int32_t* seq_off_host, int nseq, int H, int dqk,
+                          int dv, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, int kernel, itts_stream stream) {
+  VarlenArgs a;
+  const char* why = to_varlen_args(a, o, q, k, v, seq_off_host, nseq, H, dqk, dv, ldq, ldk, ldv, ldo, scale);
+  if (!why) why = attention_varlen_refusal(a, dtype, kernel);
+  if (why) {
+    set_error(std::string("itts_attention_varlen: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  return attention_varlen(a, dtype, kernel, (hipStream_t)stream);
+}
+
+int itts_attention_varlen_which(const void* q, const void* k, const void* v, const int32_t* seq_off_host, int nseq, int H, int dqk,
+                                int dv, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, int kernel) {
+  static const float dummy_o = 0.f;  // a real call has its output; the rule only asks whether it is there
+  VarlenArgs a;
+  const char* why = to_varlen_args(a, const_cast<float*>(&dummy_o), q, k, v, seq_off_host, nseq, H, dqk, dv, ldq, ldk, ldv, ldo, scale);
+  if (!why) why = attention_varlen_refusal(a, dtype, kernel);
+  if (why) {
+    set_error(std::string("itts_attention_varlen_which: ") + why);
+    return E_INVALID;
+  }
+  return kernel ? kernel : attention_varlen_which(a, dtype);
+}
+
 int itts_gemv(float* Y, const float* X, const void* W, const float* bias, int B, int N, int K, int act, int accumulate,
               int prologue, const float* ln_gamma, const float* ln_beta, const float* ln2_gamma, const float* ln2_beta,
               int dtype_w, int version, itts_stream stream) {
@@ -996,6 +1033,13 @@ int itts_gpt_latent_batch_cond(itts_engine* e, const float* cond, const int32_t*
   }
   return e->e.gpt_latent_batch(cond, text_ids_host, text_lens_host, codes_host, code_lens_host, nseq, latent_out, (hipStream_t)s,
                                cond_index_host, n_cond);
+}
+int itts_gpt_latent_packed(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond, const int32_t* text_ids_host,
+                           const int32_t* text_lens_host, const int32_t* codes_host, const int32_t* code_lens_host, int nseq,
+                           void* latent_out, itts_stream s) {
+  ENG(e);
+  return e->e.gpt_latent_packed(cond, text_ids_host, text_lens_host, codes_host, code_lens_host, nseq, latent_out, (hipStream_t)s,
+                                cond_index_host, n_cond);
 }
 int itts_bigvgan(itts_engine* e, const void* latent, const float* spk, int B, int T, float* wav_out, itts_stream s) {
   ENG(e);

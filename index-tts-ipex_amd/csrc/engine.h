@@ -282,6 +282,14 @@ struct Engine {
       std::swap(e.ws_cap, e.ws_b_cap);
     }
   };
+  // The packed latent pass (gpt_latent_packed) runs its GEMMs under both: no K split (ksplit_off, the flag above) and the kernel
+  // family picked without looking at M (gemm_pin -> gemm_pinned) - what makes a sequence's latent independent of its companions.
+  bool gemm_pin = false;
+  struct PackedPass {
+    Engine& e;
+    explicit PackedPass(Engine& en) : e(en) { e.ksplit_off = e.gemm_pin = true; }
+    ~PackedPass() { e.ksplit_off = e.gemm_pin = false; }
+  };
   // raw partial sums of K-split GEMMs (Engine::conv): [split][M][N] fp32, allocated at the first split launch
   static constexpr size_t KSPLIT_WS_BYTES = size_t(64) << 20;
   float* ksplit_ws = nullptr;
@@ -371,6 +379,10 @@ struct Engine {
                  hipStream_t s);
   int gpt_latent_batch(const float* cond, const int32_t* text_ids, const int* Ls, const int32_t* codes, const int* Ts,
                        int nseq, void* latent_out, hipStream_t s, const int32_t* cond_index = nullptr, int n_cond = 1);
+  // the same interface on PACKED rows [sum S_i, D]: no pad rows, varlen attention, pinned GEMM family, no K split, no K/V cache;
+  // nseq <= VARLEN_MAX_SEQ.  A sequence's latent has the same bits alone, with any companions, in any order.
+  int gpt_latent_packed(const float* cond, const int32_t* text_ids, const int* Ls, const int32_t* codes, const int* Ts,
+                        int nseq, void* latent_out, hipStream_t s, const int32_t* cond_index = nullptr, int n_cond = 1);
   // lens_host (optional, [B], each in [1, T]): a padded ragged batch - item b is a latent of lens_host[b] frames, whatever its rows
   // behind them hold; its waveform is that of the item alone, zeros from sample lens_host[b] * up on
   int bigvgan(const void* latent, const float* spk, int B, int T, float* wav, hipStream_t s, const int* lens_host = nullptr);
@@ -380,6 +392,9 @@ struct Engine {
   // internals
   // admit_slots (host, [B]): the cache rows the B rows of this pass go to (kv_admit); nullptr: rows 0 .. B - 1 (kv_scatter)
   int gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, bool write_cache, hipStream_t s, const int* admit_slots = nullptr);
+  // gpt_layers_full's sibling for the packed latent pass: the 24 blocks over h fp32 [M = seqs.off[nseq], D] (in place), attention
+  // per sequence (attention_varlen's dispatcher; seqs carries nseq and off, the rest is filled here); writes no cache
+  int gpt_layers_packed(float* h, const VarlenArgs& seqs, hipStream_t s);
   int decode_step_launch(hipStream_t s);
   GraphKey graph_key() const;
   EngArgs engine_args(int& eng_first, bool& fold_head, bool& fold_samp) const;

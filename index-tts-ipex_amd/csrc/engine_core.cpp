@@ -98,6 +98,10 @@ int Engine::conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* 
     ITTS_REQUIRE(!lens, "conv: per-item lengths on the vector-ALU kernel");
     return gemm_simple(g, ta, tw, tc, s);
   }
+  if (gemm_pin) {  // the packed latent pass: a family that does not move with M, no K split (gemm_select.cpp gemm_which_pinned)
+    ITTS_REQUIRE(!lens, "conv: per-item lengths in a packed pass");
+    return gemm_pinned(g, ta, tw, tc, s);
+  }
   // few-tile deep-K shapes split K over workgroups (this engine's own fp32 workspace: engines on other streams have theirs)
   const int S = ksplit_off ? 1 : gemm_ksplit_plan(g, ta, tw, tc, KSPLIT_WS_BYTES);
   if (S > 1) {

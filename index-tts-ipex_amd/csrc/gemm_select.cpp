@@ -93,6 +93,27 @@ int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* le
   }
 }
 
+// The PINNED selector of the packed latent pass (Engine::gpt_latent_packed): one family per projection, picked from the operand types,
+// N, K and alignment - never from M.  A sequence alone and the same sequence among 127 others must run the same kernel family (the
+// families sum K in one order inside a family; across families the bits differ), and gemm_which moves with the tile count.  gemm_p8
+// wherever it can run the shape (every GPT projection at full dims; it is the family gemm_which takes at the row counts a packed pass
+// is for), else gemm_mfma (M >= 16: the caller's duty), else the vector ALU.  Never a K split.
+int gemm_which_pinned(const GemmArgs& g, int ta, int tw, int tc) {
+  const Switches sw;
+  if (sw.p8 && g.nphase == 1 && gemm_p8_tiles(g, ta, tw, tc) > 0) return 3;
+  if (gemm_mfma_supported(g, ta, tw, tc)) return 1;
+  return 0;
+}
+
+int gemm_pinned(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
+  ITTS_REQUIRE(!(g.pre_alpha || g.pre_beta || g.pre_filt) && g.ksplit == 1, "gemm_pinned: no fused activation, no K split");
+  switch (gemm_which_pinned(g, ta, tw, tc)) {
+    case 3: return gemm_p8(g, ta, tw, tc, s);
+    case 1: return gemm_mfma(g, ta, tw, tc, s);
+    default: return gemm_simple(g, ta, tw, tc, s);
+  }
+}
+
 // ---- one family by name (itts_gemm_family: the operator tests run each kernel at the smallest shapes that reach its paths, far below
 //      the performance gates of gemm_which).  The refusal repeats, in words, every condition of that family's launcher, so that the
 //      entry answers on the host before any HIP call; the launchers keep their own ITTS_REQUIREs behind it. ----

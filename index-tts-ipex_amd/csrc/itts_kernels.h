@@ -35,6 +35,9 @@ int gemm_which(const GemmArgs& g, int ta, int tw, int tc);           // the kern
 const char* gemm_family_refusal(const GemmArgs& g, int ta, int tw, int tc, int family, int variant);
 int gemm_family(const GemmArgs& g, int ta, int tw, int tc, int family, int variant, hipStream_t s);
 bool gemm_act_fused(const GemmArgs& g, int ta, int tw, int tc);      // a call with g.pre_* runs Activation1d inside the conv: family 4 and conv_lds_act_supported
+// The packed latent pass's selector: the family by operand types, N, K and alignment, never by M (1, 3 or 0); no K split
+int gemm_which_pinned(const GemmArgs& g, int ta, int tw, int tc);
+int gemm_pinned(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
 
 // ---- anti-aliased SnakeBeta (snake.hip); x,y [B,T,C] ----
 int snake_aa(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12,
@@ -100,5 +103,26 @@ int attention(const AttnArgs& a, int dt, hipStream_t s);  // dispatcher
 // (null = it can), no HIP call.  kernel 0 = the dispatcher, 1 = attention_simple, 2 = attention_mfma (then also its own rule).
 const char* attention_refusal(const AttnArgs& a, int dt, int kernel);
 int attention_which(const AttnArgs& a, int dt);  // 1 / 2: the kernel attention() takes (ITTS_ATTN_SIMPLE honoured), no launch
+
+// ---- causal self-attention over packed sequences (attention_varlen.hip) ----
+constexpr int VARLEN_MAX_SEQ = 128;
+// Sequence b owns rows [off[b], off[b + 1]) of q, k, v and o (row r, head h, dim d at q[r*ldq + h*dqk + d] and alike); query i of a
+// sequence sees keys 0 .. i of that sequence.  The offsets travel by value in the argument block (host-checked, no upload).
+struct VarlenArgs {
+  const void* q = nullptr;
+  const void* k = nullptr;
+  const void* v = nullptr;
+  void* o = nullptr;
+  int ldq = 0, ldk = 0, ldv = 0, ldo = 0;
+  float scale = 1.f;
+  int H = 1, dqk = 64, dv = 64, nseq = 0;
+  int off[VARLEN_MAX_SEQ + 1] = {0};
+};
+// why the call cannot run (null = it can), no HIP call.  kernel 0 = the dispatcher, 1 = attn_varlen_simple_kernel (fp32 or the 16-bit
+// type, dqk <= 128, dv <= 64), 2 = attn_varlen_mfma_kernel (then also attention_varlen_mfma_supported)
+const char* attention_varlen_refusal(const VarlenArgs& a, int dt, int kernel);
+bool attention_varlen_mfma_supported(const VarlenArgs& a, int dt);  // type, head dims, leading dims, alignment: never a length
+int attention_varlen_which(const VarlenArgs& a, int dt);            // 1 / 2: the dispatcher's pick (ITTS_ATTN_SIMPLE honoured), no launch
+int attention_varlen(const VarlenArgs& a, int dt, int kernel, hipStream_t s);  // the named kernel runs or nothing does
 
 }  // namespace itts

@@ -123,6 +123,37 @@ int Engine::gpt_layers_full(float* h, int B, int S, const int* kv_start_dev, boo
   return OK;
 }
 
+// the same 24 blocks over PACKED rows: sequence b is rows [seqs.off[b], seqs.off[b + 1]) of h; no pad rows, no cache
+int Engine::gpt_layers_packed(float* h, const VarlenArgs& seqs, hipStream_t s) {
+  const itts_config& c = cfg;
+  const int D = c.model_dim, H = c.heads, dh = D / H, M = seqs.off[seqs.nseq];
+  void* xn = alloc((size_t)M * D * es);
+  void* qkv = alloc((size_t)M * 3 * D * es);
+  void* ctx = alloc((size_t)M * D * es);
+  void* act = alloc((size_t)M * 4 * D * es);
+  VarlenArgs a = seqs;
+  a.q = qkv;
+  a.k = (const char*)qkv + (size_t)D * es;
+  a.v = (const char*)qkv + (size_t)2 * D * es;
+  a.o = ctx;
+  a.H = H;
+  a.dqk = a.dv = dh;
+  a.ldq = a.ldk = a.ldv = 3 * D;
+  a.ldo = D;
+  a.scale = 1.f / std::sqrt((float)dh);
+  for (int l = 0; l < c.layers; ++l) {
+    const GptLayerW& L = gpt.layers[l];
+    ITTS_TRY(ln(xn, adt, h, F32, L.ln1, M, D, s));
+    ITTS_TRY(lin(qkv, adt, xn, adt, D, L.attn, M, 3 * D, s));
+    K(attention_varlen(a, adt, force_simple ? 1 : 0, s));
+    ITTS_TRY(lin(h, F32, ctx, adt, D, L.proj, M, D, s, ACT_NONE, h, D));
+    ITTS_TRY(ln(xn, adt, h, F32, L.ln2, M, D, s));
+    ITTS_TRY(lin(act, adt, xn, adt, D, L.fc, M, 4 * D, s, ACT_GELU_NEW));
+    ITTS_TRY(lin(h, F32, act, adt, 4 * D, L.proj2, M, D, s, ACT_NONE, h, D));
+  }
+  return OK;
+}
+
 static int dev_alloc(void** p, size_t bytes) {
   if (*p) (void)hipFree(*p);
   *p = nullptr;
@@ -2114,6 +2145,96 @@ int Engine::gpt_latent_batch(const float* cond_dev, const int32_t* text_ids, con
   };
   ITTS_TRY(two_pass(body, s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));  // rd / kvs are host buffers
+  return OK;
+}
+
+// The latent pass on PACKED rows: [cond, text, mel] of every sentence back to back, no pad rows (RowDesc kinds 1 - 3 only).  Each
+// sentence is tiled by the attention from its own key 0 (attention_varlen.hip), the GEMMs run without a K split on a kernel family
+// that does not depend on the row count (PackedPass), LayerNorm and the embedding are row-wise: a sentence's latent has the same
+// bits alone, with any companions, in any order.  Same interface and output as gpt_latent_batch; nseq <= VARLEN_MAX_SEQ.
+int Engine::gpt_latent_packed(const float* cond_dev, const int32_t* text_ids, const int* Ls, const int32_t* codes,
+                              const int* Ts, int nseq, void* latent_out, hipStream_t s, const int32_t* cond_index, int n_cond) {
+  if (!finalized || !gpt.ok) {
+    set_error("gpt_latent_packed: GPT weights not bound");
+    return E_STATE;
+  }
+  const itts_config& c = cfg;
+  ITTS_REQUIRE(cond_dev && text_ids && codes && latent_out && Ls && Ts, "gpt_latent_packed: null pointer");
+  ITTS_REQUIRE(nseq >= 1 && nseq <= VARLEN_MAX_SEQ, "gpt_latent_packed: 1 <= nseq <= 128");
+  ITTS_REQUIRE(n_cond >= 1, "gpt_latent_packed: n_cond >= 1");
+  const int D = c.model_dim, nl = c.cond_latents;
+  // the matrix-core GEMM of the pinned selector needs 16 rows: every sentence has nl + 6 or more, alone as in company
+  ITTS_REQUIRE(adt == F32 || force_simple || nl + 6 >= 16, "gpt_latent_packed: a 16-bit engine needs cond_latents >= 10");
+  VarlenArgs seqs;
+  seqs.nseq = nseq;
+  long Ttot = 0, Mtot = 0;
+  for (int i = 0; i < nseq; ++i) {
+    ITTS_REQUIRE(Ls[i] > 0 && Ts[i] > 0, "gpt_latent_packed: empty sentence");
+    ITTS_REQUIRE(Ls[i] + 2 <= c.max_text_tokens + 2 && Ts[i] + 2 <= c.max_mel_tokens + 3, "gpt_latent_packed: sequence too long");
+    const int cb = cond_index ? cond_index[i] : 0;
+    ITTS_REQUIRE(cb >= 0 && cb < n_cond, "gpt_latent_packed: conditioning index outside [0, n_cond)");
+    seqs.off[i] = (int)Mtot;
+    Mtot += nl + Ls[i] + 2 + Ts[i] + 2;
+    Ttot += Ts[i];
+    ITTS_REQUIRE(Mtot < (1L << 24), "gpt_latent_packed: more than 2^24 rows in one pass");
+  }
+  seqs.off[nseq] = (int)Mtot;
+  std::vector<RowDesc> rd((size_t)Mtot);
+  std::vector<int> mel_row(nseq);
+  long to = 0, co = 0;
+  for (int b = 0; b < nseq; ++b) {
+    const int L = Ls[b], T = Ts[b];
+    RowDesc* r = rd.data() + seqs.off[b];
+    int k = 0;
+    const int cb = cond_index ? cond_index[b] : 0;
+    for (int i = 0; i < nl; ++i) r[k++] = {1, cb * nl + i, 0, 0};
+    r[k++] = {2, c.start_text_token, 0, 0};
+    for (int i = 0; i < L; ++i) {
+      const int t = text_ids[to + i];
+      ITTS_REQUIRE(t >= 0 && t <= c.number_text_tokens, "gpt_latent_packed: text id out of range");
+      r[k++] = {2, t, i + 1, 0};
+    }
+    r[k++] = {2, c.stop_text_token, L + 1, 0};
+    mel_row[b] = seqs.off[b] + k;  // first mel row (the start token); model.py:578 keeps rows [0, T) of the mel part
+    r[k++] = {3, c.start_mel_token, 0, 0};
+    for (int i = 0; i < T; ++i) {
+      const int m = codes[co + i];
+      ITTS_REQUIRE(m >= 0 && m < c.number_mel_codes, "gpt_latent_packed: mel code out of range");
+      r[k++] = {3, m, i + 1, 0};
+    }
+    r[k++] = {3, c.stop_mel_token, T + 1, 0};
+    to += L;
+    co += T;
+  }
+  PackedPass packed(*this);
+  auto body = [&]() -> int {
+    RowDesc* rd_dev = (RowDesc*)alloc(rd.size() * sizeof(RowDesc));
+    float* h = (float*)alloc((size_t)Mtot * D * 4);
+    float* hn = (float*)alloc((size_t)Ttot * D * 4);
+    if (!dry) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(rd_dev, rd.data(), rd.size() * sizeof(RowDesc), hipMemcpyHostToDevice, s));
+      if (adt == F32)
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<float>, dim3((unsigned)Mtot), dim3(256), 0, s, h, rd_dev, cond_dev,
+                           (const float*)gpt.text_emb, (const float*)gpt.text_pos, (const float*)gpt.mel_emb,
+                           (const float*)gpt.mel_pos, D);
+      else
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<bf16_t>, dim3((unsigned)Mtot), dim3(256), 0, s, h, rd_dev, cond_dev,
+                           (const bf16_t*)gpt.text_emb, (const bf16_t*)gpt.text_pos, (const bf16_t*)gpt.mel_emb,
+                           (const bf16_t*)gpt.mel_pos, D);
+      ITTS_HIP_CHECK(hipGetLastError());
+    }
+    ITTS_TRY(gpt_layers_packed(h, seqs, s));
+    long off = 0;
+    for (int b = 0; b < nseq; ++b) {
+      K(double_ln(hn + off * D, h + (size_t)mel_row[b] * D, gpt.ln_f.g, gpt.ln_f.b, gpt.final_norm.g, gpt.final_norm.b,
+                  Ts[b], D, 1e-5f, s));
+      off += Ts[b];
+    }
+    K(cast_copy(latent_out, adt, hn, F32, Ttot * D, s));
+    return OK;
+  };
+  ITTS_TRY(two_pass(body, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));  // rd is a host buffer
   return OK;
 }
 

@@ -51,6 +51,10 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     `max_batch` decode as ONE generation of `max_batch` rows: a finished row's slot takes the next waiting sentence
     (Engine.generate(slots=..)) instead of every `max_batch`-sized generation draining to its slowest row.  Single beam, no
     typical filter, more than 6 rows.  `infer` / `infer_fast` are not affected.
+  * `packed_latent=True` (not in the reference; default off; ITTS_PACKED_LATENT=1 / 0 overrides it in both directions) runs the
+    latent pass of `infer_batch` on packed rows (Engine.latent_packed: no pad rows, a sentence's latent has the same bits
+    whoever shares its pass); with `mixed_batch` the utterances of a decode group then share ONE latent pass instead of one
+    per utterance.  The vocoder stays per utterance.  `infer` / `infer_fast` are not affected.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -76,7 +80,7 @@ class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
-                 mixed_batch=False, admit_rows=False, retire_beams=None):
+                 mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -109,6 +113,7 @@ class IndexTTS:
         self.mixed_batch = bool(mixed_batch)  # infer_batch: one decode batch across voices and sampling settings (ITTS_MIXED_BATCH overrides)
         self.admit_rows = bool(admit_rows)  # infer_batch with mixed_batch: finished decode rows are refilled from the waiting sentences (ITTS_ADMIT_ROWS overrides)
         self._admit_told = False
+        self.packed_latent = bool(packed_latent)  # infer_batch: the latent pass on packed rows, one per decode group (ITTS_PACKED_LATENT overrides)
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
         if self.kv_fp8 and not self.is_fp16:
             raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
@@ -217,9 +222,9 @@ class IndexTTS:
             rows.extend(codes[r] for r in range(len(grp)))
         return rows
 
-    def _clean_and_latents(self, cond, sents, code_rows, max_mel_tokens):
+    def _clean_and_latents(self, cond, sents, code_rows, max_mel_tokens, packed=False):
         """remove_long_silence per sentence (infer.py:190 / :463), then the latent pass (batch-1 semantics per sentence,
-        stacked as masked left-padded rows in one launch sequence)."""
+        stacked as masked left-padded rows in one launch sequence; packed: as packed rows, Engine.latent_packed)."""
         if any(r[-1] != self.stop_mel_token for r in code_rows):
             warnings.warn(f"WARN: generation stopped due to exceeding `max_mel_tokens` ({max_mel_tokens}). "
                           "Consider reducing `max_text_tokens_per_sentence` or increasing `max_mel_tokens`.", RuntimeWarning)
@@ -227,6 +232,8 @@ class IndexTTS:
         for r in code_rows:
             c, n = infer_core.remove_long_silence(np.asarray(r)[None], self.stop_mel_token)
             clean.append(c[0, : int(n[0])])
+        if packed:
+            return self.engine.latent_packed(cond, sents, clean)
         lats = []
         cap = self.engine.ccfg.max_batch
         for lo in range(0, len(sents), cap):
@@ -348,7 +355,8 @@ class IndexTTS:
                 code_rows = [None] * len(flat)
                 for i, r in zip(order, rows):
                     code_rows[i] = r
-                lats = self._clean_and_latents(cond, [f[2] for f in flat], code_rows, g["max_mel_tokens"])
+                lats = self._clean_and_latents(cond, [f[2] for f in flat], code_rows, g["max_mel_tokens"],
+                                               packed=infer_core.env_switch("ITTS_PACKED_LATENT", self.packed_latent))
                 wav_parts = {u: [] for u in us}
                 ragged = {"1": True, "0": False}.get(os.environ.get("ITTS_RAGGED_VOCODER", ""), self.ragged_vocoder)
                 # equal lengths share a launch sequence; with ragged, unequal ones too
@@ -443,16 +451,26 @@ class IndexTTS:
             # tiles by the row count - so batches across utterances would make a request's waveform depend, in
             # its last bits, on the requests it happened to be served with (measured on the micro checkpoint: latents 1e-6,
             # 2.5 % of the int16 samples one unit apart).  The decode steps are where the rows pay; these passes run once.
+            # With packed_latent the latent pass has no such dependence (Engine.latent_packed: no pad rows, every sentence tiled from
+            # its own key 0, no K split, the GEMM family not chosen by the row count), so the whole decode group shares ONE pass;
+            # the vocoder stays per utterance.
             cap = self.engine.ccfg.max_batch
+            group_lats = None
+            if infer_core.env_switch("ITTS_PACKED_LATENT", self.packed_latent):
+                group_lats = self.engine.latent_packed(cond_all, [f[2] for f in flat], clean,
+                                                       cond_index=[voice[id(prompts[f[0]])] for f in flat])
             for u in us:
                 idx = [i for i, f in enumerate(flat) if f[0] == u]
                 if not idx:
                     continue
                 v = [voice[id(prompts[u])]] * len(idx)
-                lats = []
-                for lo in range(0, len(idx), cap):
-                    sel = idx[lo:lo + cap]
-                    lats.extend(self.engine.latent_batch(cond_all, [flat[i][2] for i in sel], [clean[i] for i in sel], cond_index=v[:len(sel)]))
+                if group_lats is not None:
+                    lats = [group_lats[i] for i in idx]
+                else:
+                    lats = []
+                    for lo in range(0, len(idx), cap):
+                        sel = idx[lo:lo + cap]
+                        lats.extend(self.engine.latent_batch(cond_all, [flat[i][2] for i in sel], [clean[i] for i in sel], cond_index=v[:len(sel)]))
                 results[u] = [self._to_int16_range(w) for w in self.engine.bigvgan_grouped(lats, spk_all[v], ragged=ragged)]
 
     def _prompt(self, prompt_mel, audio_prompt):

@@ -833,6 +833,45 @@ class Engine:
             o += int(n)
         return res
 
+    def latent_packed(self, cond: torch.Tensor, texts, codes, cond_index=None, max_tokens=None) -> List[torch.Tensor]:
+        """latent_batch on PACKED rows (itts_gpt_latent_packed): the tokens of all sentences back to back, no pad rows, attention
+        per sentence from its own key 0, no K split, the GEMM family not chosen by the row count - a sentence's latent has the
+        same bits alone, with any companions, in any order and in any chunking.  Runs in chunks of at most 128 sentences and
+        max_tokens token rows (infer_core.packed_chunks; None: infer_core.PACKED_MAX_TOKENS).  cond / cond_index as latent_batch.
+        -> list of latents [1, T_i, D] (views of one buffer)."""
+        from . import infer_core
+
+        ts = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in texts]
+        cs = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in codes]
+        if not ts or len(ts) != len(cs):
+            raise ValueError(f"latent_packed: {len(ts)} texts / {len(cs)} code rows")
+        cond = cond.to(device=self.device, dtype=torch.float32).contiguous().view(-1, self.ccfg.model_dim)
+        n_cond, rem = divmod(cond.shape[0], self.ccfg.cond_latents)
+        ci = None
+        if cond_index is not None:
+            ci = np.ascontiguousarray(cond_index, dtype=np.int32).reshape(-1)
+            if ci.shape[0] != len(ts):
+                raise ValueError(f"latent_packed: {ci.shape[0]} indices for {len(ts)} sentences")
+        if rem or n_cond < 1:
+            raise ValueError(f"latent_packed: cond {tuple(cond.shape)} is not a whole number of [{self.ccfg.cond_latents}, D] blocks")
+        cl = [int(c.shape[0]) for c in cs]
+        rows = [self.ccfg.cond_latents + int(t.shape[0]) + 2 + n + 2 for t, n in zip(ts, cl)]
+        out = torch.empty(sum(cl), self.ccfg.model_dim, dtype=self.tdt, device=self.device)
+        starts = np.concatenate([[0], np.cumsum(cl)]).astype(np.int64)
+        es = out.element_size() * self.ccfg.model_dim
+        self._enter()
+        for chunk in infer_core.packed_chunks(rows, max_tokens or infer_core.PACKED_MAX_TOKENS):
+            tl = np.asarray([ts[i].shape[0] for i in chunk], dtype=np.int32)
+            kl = np.asarray([cl[i] for i in chunk], dtype=np.int32)
+            tcat, ccat = np.concatenate([ts[i] for i in chunk]), np.concatenate([cs[i] for i in chunk])
+            cc = None if ci is None else np.ascontiguousarray(ci[chunk])
+            self._ck(self.lib.itts_gpt_latent_packed(self.h, cond.data_ptr(), None if cc is None else cc.ctypes.data_as(C.c_void_p), n_cond,
+                                                    tcat.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p),
+                                                    ccat.ctypes.data_as(C.c_void_p), kl.ctypes.data_as(C.c_void_p), len(chunk),
+                                                    out.data_ptr() + int(starts[chunk[0]]) * es, self._s()), "gpt_latent_packed")
+        self._exit()
+        return [out[int(starts[i]):int(starts[i + 1])].unsqueeze(0) for i in range(len(cl))]
+
     def bigvgan(self, latent: torch.Tensor, spk: torch.Tensor) -> torch.Tensor:
         """latent [B, T, D], spk [B, E] -> wav fp32 [B, 1, T*up]."""
         lat = self.to_act(latent)

@@ -5,6 +5,8 @@ Mirrors /root/reference/indextts/infer.py: `remove_long_silence` (:244-298), `bu
 tests/golden/silence_cases.npz (tests/test_host_logic.py)."""
 from __future__ import annotations
 
+import os
+
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -234,6 +236,38 @@ class AdmitScheduler:
     def order(self) -> List[int]:
         """The request of every original row of the generation: the first rows, then the admitted ones in admission order."""
         return self.first + [r for _, req in self.log for r in req]
+
+
+# ---- packed latent pass (Engine.latent_packed): chunks and the A/B switch ----
+PACKED_MAX_SEQ = 128       # ITTS_VARLEN_MAX_SEQ: the sequence offsets travel in the kernel's argument block
+PACKED_MAX_TOKENS = 65536  # default token budget of one pass: about 33 KiB (16-bit) / 55 KiB (fp32) of scratch per token row at D = 1280
+
+
+def packed_chunks(lengths: Sequence[int], max_tokens: int = PACKED_MAX_TOKENS, max_seqs: int = PACKED_MAX_SEQ) -> List[List[int]]:
+    """Consecutive runs of sequence indices for one packed pass each: order-preserving, at most max_seqs sequences and at most
+    max_tokens token rows a chunk; a sequence longer than the budget is a chunk of its own.  (Any chunking gives the same bits -
+    a sequence's latent does not depend on its companions - so this only bounds the scratch.)"""
+    if max_tokens < 1 or max_seqs < 1:
+        raise ValueError(f"packed_chunks: max_tokens {max_tokens} / max_seqs {max_seqs} must be >= 1")
+    chunks, cur, tok = [], [], 0
+    for i, n in enumerate(lengths):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"packed_chunks: sequence {i} has length {n}")
+        if cur and (len(cur) >= max_seqs or tok + n > max_tokens):
+            chunks.append(cur)
+            cur, tok = [], 0
+        cur.append(i)
+        tok += n
+    if cur:
+        chunks.append(cur)
+    return chunks
+
+
+def env_switch(name: str, setting: bool) -> bool:
+    """An A/B switch of IndexTTS: the environment variable overrides the constructor's setting in both directions ("1" on, "0" off);
+    unset or anything else leaves the setting."""
+    return {"1": True, "0": False}.get(os.environ.get(name, ""), bool(setting))
 
 
 # ---- host-side token choice (HF GenerationMixin.sample over the whole vocabulary) ----

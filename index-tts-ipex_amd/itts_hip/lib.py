@@ -131,6 +131,8 @@ _PROTOS = {
     "itts_attention": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, i32, vp]),
     "itts_attention_kernel": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, i32, i32, vp]),
     "itts_attention_which": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, i32]),
+    "itts_attention_varlen": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "itts_attention_varlen_which": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32]),
     "itts_gemv": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp]),
     "itts_gemv_bf16": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "itts_decode_attn": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
@@ -152,6 +154,7 @@ _PROTOS = {
     "itts_sampler_step_rows": (i32, [C.POINTER(SamplerStepArgs), C.POINTER(RowSampling), vp, vp]),
     "itts_gpt_set_sampling_rows": (i32, [vp, C.POINTER(RowSampling), i32, vp, i64]),
     "itts_gpt_latent_batch_cond": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
+    "itts_gpt_latent_packed": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
     "itts_engine_create": (i32, [C.POINTER(Config), C.POINTER(vp)]),
     "itts_engine_destroy": (None, [vp]),
     "itts_engine_bind_tensor": (i32, [vp, C.c_char_p, vp, i32, i32, C.POINTER(i64)]),
