@@ -643,8 +643,8 @@ int itts_rows_gather(void* dst, size_t dst_plane_stride, const void* src, size_t
  *   slots_host [n] (optional) receives the slots.
  * The new rows become original rows B0, B0 + 1, ..: itts_gpt_fetch then returns all B0 rows (itts_gpt_rows_total) in that order,
  * a replaced row with its codes followed by the stop token and its last logits.  itts_gpt_status still counts slots;
- * itts_gpt_row_status answers per slot.  Refused with a message before anything is changed: no active generation, beams,
- * typical filtering, host sampling, `input_tokens`, the fused qkv + attention launch, a step on the persistent engine (<= 6
+ * itts_gpt_row_status answers per slot.  Refused with a message before anything is changed: no active generation, beams (unless
+ * itts_gpt_set_admit_beams opted in, see below), typical filtering, host sampling, `input_tokens`, the fused qkv + attention launch, a step on the persistent engine (<= 6
  * rows), after a retirement, fewer finished slots than n, n > 128, a text id out of range, L not the generation's, an entry the
  * prefill would refuse, uniforms missing for a sampled row, a sampled row in a generation without room for draws.
  * Additions to ABI 4 (the version stays): itts_gpt_admit_rows, itts_gpt_row_status, itts_gpt_rows_total, itts_gpt_graph_captures,
@@ -684,6 +684,45 @@ typedef struct {
 int itts_rows_admit(const itts_rows_admit_args* args, itts_stream stream);
 /* The slot choice alone (host only): the min(n, *n_free) lowest finished slots in ascending order, *n_free = all finished slots. */
 int itts_admit_plan(const int* unfinished_host, const int* len_host, int B, int max_gen, int n, int* slots_host, int* n_free);
+
+/* Row admission under beams (opt-in, sticky per engine object, default 0 = itts_gpt_admit_rows refuses a beam generation as above).
+ * With on = 1 itts_gpt_admit_rows admits whole BATCH ITEMS into a running beam generation (num_beams > 1, beam_sample or
+ * beam_search on the device): n counts items, text_ids_host is [n][L], cond_rows is 1 or n (items), uniforms_host is
+ * [n][max_gen][2 * num_beams] (required for beam_sample, ignored for beam_search), rows_host and forced_host must be null, and
+ * slots_host [n] receives ITEM slots.  An item is finished when it is done or its rows hold max_gen tokens; the n lowest finished
+ * items leave: they are finalised on the host at their own step (itts_gpt_set_beam_returns hypotheses each) and kept, with their
+ * rows' last logits, by original item.  The new items are prefilled as n * num_beams rows - the rows and kernels of a fresh
+ * generation of those items -, their K/V goes to rows item * num_beams + beam (itts_kv_admit), the rows' state is reset
+ * (itts_rows_admit), the groups' beam state is reset (itts_beam_admit) and their first token is chosen by the beam kernels on a
+ * grid of one item each; the running groups are neither stepped nor touched, and the captured step is kept.  Every beam kernel
+ * takes its step, its ping-pong half and its draws from the item's own len, so the groups then run at different steps.  The new
+ * items become original items items0, items0 + 1, ..: itts_gpt_fetch returns [itts_gpt_rows_total / num_beams *
+ * num_return_sequences][max_gen] codes in original item order and logits [itts_gpt_rows_total][V] in original row order;
+ * itts_gpt_rows_total counts rows, itts_gpt_row_status answers per row.  Within one projection-kernel family an admitted item's
+ * codes and logits are those of a fresh generation of the admitted items.  itts_gpt_retire_rows (with itts_gpt_set_retire_beams)
+ * still retires done groups afterwards: both ping-pong halves move, the draws are re-packed from the generation's own copy by
+ * original item; an admission after a retirement stays refused.  itts_gpt_status keeps reporting the step of row 0.
+ * Refused with a message before anything is changed: typical filtering, host sampling (host-side beam warpers), `input_tokens`,
+ * the fused qkv + attention launch, a step on the persistent engine (<= 6 rows), after a retirement, fewer finished items than n,
+ * n * num_beams > 128, a non-null rows_host or forced_host, draws missing for beam_sample, and what the single-beam form refuses
+ * for its texts.  The environment variable ITTS_ADMIT_BEAMS (read per call) overrides the setter in both directions.
+ * Additions to ABI 4 (the version stays): itts_gpt_set_admit_beams, itts_beam_admit. */
+int itts_gpt_set_admit_beams(itts_engine* e, int on);
+/* Operator entry of beam_admit_kernel on caller memory: the beam state of a fresh generation for n of `items` batch items of nb
+ * beams - beam_scores [items * nb] (0; with do_sample = 0: 0 for an item's first beam and -1e9 behind it), both halves of anc
+ * [2][items * nb][Smax] bytes (row item * nb + q filled with q), hyp_order [items][nb + 1] = -1, hyp_n = 0, hyp_worst = 1e9,
+ * hyp_counter = 0, beam_done = 0 (each [items]) and, uniforms_src [n][max_gen][2 * nb] (device) given, the item's column of
+ * uniforms [max_gen][items][2 * nb].  Nothing else is written.  ITTS_E_INVALID before any HIP call for: a null pointer (uniforms
+ * and uniforms_src may be null, uniforms_src without uniforms may not), n outside [1, 128], nb outside [2, 10], n * nb > 128,
+ * items * nb outside [1, 65536], max_gen outside [1, 65536], Smax outside [16, 65536] or no multiple of 16, anc not 16-byte
+ * aligned, an item outside [0, items), an item twice. */
+typedef struct {
+  void *beam_scores, *anc, *hyp_order, *hyp_n, *hyp_worst, *hyp_counter, *beam_done, *uniforms;
+  const void* uniforms_src;
+  const int* items_host; /* [n] */
+  int n, nb, items, Smax, max_gen, do_sample;
+} itts_beam_admit_args;
+int itts_beam_admit(const itts_beam_admit_args* args, itts_stream stream);
 
 /* G8  UnifiedVoice.forward(return_latent=True) for one sentence (model.py:521-589):
  * text ids host [L], codes host [T] -> latent [T, D] in the engine dtype. */

@@ -867,6 +867,69 @@ int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w) {
   return OK;
 }
 
+// beam_sample_step for ONE batch item (the first token of an admitted beam group, Engine::admit_beam_groups): the same kernels on a
+// grid of one item, with every per-row pointer advanced by item * nb rows and every per-item pointer by item - so the kernels'
+// blockIdx-relative item 0 is that item - while a.B stays the full item count: the kernels use a.B only for the bases of the
+// ping-pong halves (Beff = a.B * nb rows behind ids / anc) and for the stride of the draws ((k * a.B + bi) * 2 nb), and both are
+// relative to pointers that moved by the item's own offset inside a half / a step.  prefix_dev and the embedding tables stay
+int beam_item_step(const BeamArgs& a, int item, hipStream_t s, const BeamWide* w) {
+  ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB && item >= 0 && item < a.B, "beam_item_step: 2 <= num_beams <= 10, item inside [0, B)");
+  ITTS_REQUIRE(!a.preprocessed && !a.host_sc, "beam_item_step: no typical pre-pass and no host picks");
+  const size_t r0 = (size_t)item * a.nb, mg = (size_t)a.max_gen, nd = 2 * (size_t)a.nb;
+  BeamArgs b = a;
+  b.logits = a.logits + r0 * a.V;
+  if (a.uniforms) b.uniforms = a.uniforms + item * nd;
+  b.len = a.len + r0;
+  b.cur_tok = a.cur_tok + r0;
+  b.unfinished = a.unfinished + r0;
+  b.ids = a.ids + r0 * mg;
+  b.anc = a.anc + r0 * a.Smax;
+  b.beam_scores = a.beam_scores + r0;
+  b.hyp_tok = a.hyp_tok + (size_t)item * (a.nb + 1) * mg;
+  b.hyp_score = a.hyp_score + (size_t)item * (a.nb + 1);
+  b.hyp_len = a.hyp_len + (size_t)item * (a.nb + 1);
+  b.hyp_order = a.hyp_order + (size_t)item * (a.nb + 1);
+  b.hyp_n = a.hyp_n + item;
+  b.hyp_worst = a.hyp_worst + item;
+  b.hyp_counter = a.hyp_counter + item;
+  b.done = a.done + item;
+  if (a.h_next) b.h_next = a.h_next + r0 * a.D;
+  if (a.cand_sc) b.cand_sc = a.cand_sc + r0 * BEAM_MAX_CAND;
+  if (a.cand_tok) b.cand_tok = a.cand_tok + r0 * BEAM_MAX_CAND;
+  if (a.cand_n) b.cand_n = a.cand_n + r0;
+  if (a.forced) b.forced = a.forced + r0 * mg;
+  if (a.do_sample && (a.top_k < 1 || a.top_k > BEAM_MAX_CAND)) {
+    ITTS_REQUIRE(w && w->sc && w->kept && w->pick_sc && w->pick_tok && w->pick_beam && !w->one_step, "beam_item_step: whole-vocabulary scratch missing");
+    ITTS_REQUIRE(a.V >= 2 && a.V <= BEAM_WIDE_MAX_V && a.top_p > 0.f && a.temperature > 0.f, "beam_item_step: vocabulary of at most 16384, top_p > 0, temperature > 0");
+    ITTS_REQUIRE(a.logits && a.uniforms && a.ids && a.anc && a.len && a.done && a.beam_scores && a.hyp_tok, "beam_item_step: null state");
+    BeamWide v = *w;
+    v.sc = w->sc + r0 * a.V;
+    v.kept = w->kept + r0;
+    v.pick_sc = w->pick_sc + item * nd;
+    v.pick_tok = w->pick_tok + item * nd;
+    v.pick_beam = w->pick_beam + item * nd;
+    ITTS_TRY(beam_wide_prepare());
+    int np = 1024;
+    while (np < a.V) np <<= 1;
+    hipLaunchKernelGGL(beam_wide_cand_kernel, dim3(a.nb, 1), dim3(1024), (size_t)np * 6, s, b, v, np);
+    hipLaunchKernelGGL(beam_wide_pick_kernel, dim3(1), dim3(1024), 0, s, b, v);
+    b.host_sc = v.pick_sc;
+    b.host_tok = v.pick_tok;
+    b.host_beam = v.pick_beam;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(1024), 0, s, b);
+    ITTS_HIP_CHECK(hipGetLastError());
+    return OK;
+  }
+  ITTS_REQUIRE(!a.do_sample || (a.top_p > 0.f && a.temperature > 0.f), "beam_item_step: top_p > 0, temperature > 0");
+  ITTS_REQUIRE(a.V <= 15000, "beam_item_step: vocabulary too large for the LDS-resident sampler");
+  ITTS_REQUIRE(a.logits && (a.uniforms || !a.do_sample) && a.ids && a.anc && a.len && a.hyp_tok && a.done, "beam_item_step: null state");
+  ITTS_REQUIRE(a.cand_sc && a.cand_tok && a.cand_n, "beam_item_step: candidate scratch missing");
+  hipLaunchKernelGGL(beam_cand_kernel, dim3(a.nb, 1), dim3(1024), (size_t)a.V * 4, s, b);
+  hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(1024), 0, s, b);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
 int beam_commit_step(const BeamArgs& a, hipStream_t s) {
   ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB, "beam_commit: 2 <= num_beams <= 10");
   ITTS_REQUIRE(a.host_sc && a.host_tok && a.host_beam, "beam_commit: picks missing");

@@ -404,6 +404,29 @@ int itts_admit_plan(const int* unfinished_host, const int* len_host, int B, int 
   return admit_plan(unfinished_host, len_host, B, max_gen, n, slots_host, n_free);
 }
 
+int itts_beam_admit(const itts_beam_admit_args* p, itts_stream stream) {
+  ITTS_REQUIRE(p, "itts_beam_admit: null argument block");
+  BeamAdmitArgs a;
+  a.beam_scores = (float*)p->beam_scores;
+  a.anc = (uint8_t*)p->anc;
+  a.hyp_order = (int*)p->hyp_order;
+  a.hyp_n = (int*)p->hyp_n;
+  a.hyp_worst = (float*)p->hyp_worst;
+  a.hyp_counter = (int*)p->hyp_counter;
+  a.done = (int*)p->beam_done;
+  a.uniforms = (float*)p->uniforms;
+  a.uniforms_src = (const float*)p->uniforms_src;
+  a.n = p->n;
+  a.nb = p->nb;
+  a.items = p->items;
+  a.Smax = p->Smax;
+  a.max_gen = p->max_gen;
+  a.do_sample = p->do_sample;
+  ITTS_TRY(beam_admit_check(a, p->items_host));  // refused before any HIP call
+  (void)hipGetLastError();
+  return beam_admit(a, p->items_host, (hipStream_t)stream);
+}
+
 int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
                      int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
                      void* scratch, size_t scratch_bytes, itts_stream stream) {
@@ -992,6 +1015,10 @@ int itts_gpt_retire_rows(itts_engine* e, int* rows_now_host, itts_stream s) {
 int itts_gpt_set_retire_beams(itts_engine* e, int on) {
   ENG(e);
   return e->e.gpt_set_retire_beams(on);
+}
+int itts_gpt_set_admit_beams(itts_engine* e, int on) {
+  ENG(e);
+  return e->e.gpt_set_admit_beams(on);
 }
 int itts_gpt_rows(itts_engine* e) { return e ? (e->e.ds.active ? e->e.ds.B : 0) : -1; }
 int itts_gpt_admit_rows(itts_engine* e, const float* cond, int cond_rows, const int32_t* text_ids_host, int n, int L,

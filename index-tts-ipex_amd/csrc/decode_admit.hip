@@ -1,6 +1,8 @@
 // Row admission into a running batched decode (Engine::gpt_admit_rows, itts_kv_admit, itts_rows_admit): kv_admit_kernel writes the
 // K/V of an admission prefill into chosen slots of the cache, rows_admit_kernel gives those slots the state of a fresh generation,
-// and admit_plan is the host function that says which slots are free.
+// and admit_plan is the host function that says which slots are free.  Under beams (itts_beam_admit) beam_admit_kernel adds the
+// beam state of a fresh generation for the admitted batch items.
+#include <algorithm>
 #include <cstdint>
 
 #include "itts_decode.h"
@@ -72,6 +74,44 @@ __global__ __launch_bounds__(256) void rows_admit_kernel(RowsAdmitArgs a) {
     a.cur_tok[slot] = a.start_tok;
     a.len[slot] = 0;
     a.kv_start[slot] = a.kvs[i];
+  }
+}
+
+// The beam state of a fresh generation for the admitted batch items: what beam_init_kernel writes per group - running scores 0
+// (beam_search: -1e9 for the beams behind the first, so that step 0 expands beam 0 only), the identity cache ancestry in BOTH
+// ping-pong halves (the half base is rows * Smax with rows = items * nb, as every reader computes it), an empty hypothesis store
+// (hyp_order = -1 marks a slot free), not done - and, uniforms_src [n][max_gen][2 * nb] given, the item's column of the draws
+// [max_gen][items][2 * nb].  hyp_tok, hyp_score, hyp_len and beam_ids are not reset: nothing reads a history beyond the group's own
+// len, and a hypothesis slot is read only where hyp_order >= 0.  blockIdx.y is the admitted item; no other item is touched.  An
+// ancestry row is Smax bytes with Smax a multiple of 16: one 16-byte store per lane.  Every element is written once by one lane:
+// no LDS, no atomics, no hand-off.
+__global__ __launch_bounds__(256) void beam_admit_kernel(BeamAdmitArgs a) {
+  const int i = blockIdx.y, g = a.item[i];
+  const int nb = a.nb, nd = 2 * nb, cpr = a.Smax / 16;  // 16-byte chunks per ancestry row
+  const int n_anc = 2 * nb * cpr, n_u = (a.uniforms && a.uniforms_src) ? a.max_gen * nd : 0;
+  const size_t half = (size_t)a.items * nb * a.Smax;
+  const int lim = n_anc > n_u ? n_anc : n_u;
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < lim; j += gridDim.x * 256) {
+    if (j < n_anc) {
+      const int h = j / (nb * cpr), r = j - h * nb * cpr, q = r / cpr, c = r - q * cpr;
+      const unsigned w = (unsigned)q * 0x01010101u;
+      *reinterpret_cast<u32x4*>(a.anc + h * half + ((size_t)g * nb + q) * a.Smax + (size_t)c * 16) = u32x4{w, w, w, w};
+    }
+    if (j < n_u) {
+      const int k = j / nd, e = j - k * nd;
+      a.uniforms[((size_t)k * a.items + g) * nd + e] = a.uniforms_src[((size_t)i * a.max_gen + k) * nd + e];
+    }
+  }
+  if (blockIdx.x == 0) {
+    const int t = threadIdx.x;
+    if (t < nb) a.beam_scores[g * nb + t] = (a.do_sample || t == 0) ? 0.f : -1e9f;
+    if (t <= nb) a.hyp_order[g * (nb + 1) + t] = -1;
+    if (t == 0) {
+      a.hyp_n[g] = 0;
+      a.hyp_worst[g] = 1e9f;
+      a.hyp_counter[g] = 0;
+      a.done[g] = 0;
+    }
   }
 }
 
@@ -164,6 +204,33 @@ int admit_plan(const int* unfinished, const int* len, int B, int max_gen, int n,
     ++f;
   }
   *n_free = f;
+  return OK;
+}
+
+// everything beam_admit refuses, without a HIP call.  items: host list of a.n batch items
+int beam_admit_check(const BeamAdmitArgs& a, const int* items) {
+  ITTS_REQUIRE(a.beam_scores && a.anc && a.hyp_order && a.hyp_n && a.hyp_worst && a.hyp_counter && a.done && items, "beam_admit: null pointer");
+  ITTS_REQUIRE(a.n >= 1 && a.n <= ROWS_MOVE_MAX, "beam_admit: 1 <= n <= 128 items");
+  ITTS_REQUIRE(a.nb >= 2 && a.nb <= 10, "beam_admit: 2 <= num_beams <= 10");
+  ITTS_REQUIRE(a.n * a.nb <= ROWS_MOVE_MAX, "beam_admit: more than 128 rows (n * num_beams) in one admission");
+  ITTS_REQUIRE(a.items >= 1 && a.items <= 65536 / a.nb && a.max_gen >= 1 && a.max_gen <= 65536 && a.Smax >= 16 && a.Smax <= 65536,
+               "beam_admit: need 1 <= items * num_beams <= 65536, 1 <= max_gen <= 65536, 16 <= Smax <= 65536");
+  ITTS_REQUIRE(a.Smax % 16 == 0 && (uintptr_t)a.anc % 16 == 0, "beam_admit: Smax must be a multiple of 16 and anc 16-byte aligned");
+  ITTS_REQUIRE(!a.uniforms_src || a.uniforms, "beam_admit: uniforms without a uniforms table");
+  for (int i = 0; i < a.n; ++i) {
+    ITTS_REQUIRE(items[i] >= 0 && items[i] < a.items, "beam_admit: item outside [0, items)");
+    for (int j = 0; j < i; ++j) ITTS_REQUIRE(items[i] != items[j], "beam_admit: an item is written twice");
+  }
+  return OK;
+}
+
+int beam_admit(BeamAdmitArgs a, const int* items, hipStream_t s) {
+  ITTS_TRY(beam_admit_check(a, items));
+  for (int i = 0; i < a.n; ++i) a.item[i] = (unsigned short)items[i];
+  const int n_anc = 2 * a.nb * (a.Smax / 16), n_u = (a.uniforms && a.uniforms_src) ? a.max_gen * 2 * a.nb : 0;
+  const int bx = (std::max(n_anc, n_u) + 255) / 256;
+  hipLaunchKernelGGL(beam_admit_kernel, dim3((unsigned)(bx < 64 ? bx : 64), (unsigned)a.n), dim3(256), 0, s, a);
+  ITTS_HIP_CHECK(hipGetLastError());
   return OK;
 }
 

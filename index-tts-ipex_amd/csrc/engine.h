@@ -158,6 +158,10 @@ struct DecodeState {
   int admitted = 0;                   // rows admitted so far (0: everything as before)
   std::vector<RowSampling> adm_rows;  // [B0], empty in a scalar generation
   std::vector<float> adm_uniforms;    // [B0][max_gen], empty when no row of the generation draws
+  // Admission under beams (gpt_set_admit_beams, opt-in): whole batch items are admitted, nb rows each, so B0 grows by nb per item
+  // and the groups run at different steps from then on (the host reads every item's own len).  adm_uniforms is then
+  // [B0 / nb][max_gen][2 * nb] by original item, ret_codes [B0 / nb][ret_keep][max_gen]
+  int admit_beams = 0;                // the sticky switch (ITTS_ADMIT_BEAMS overrides it per call)
   size_t cache_bytes = 0;
   void *kc = nullptr, *vc = nullptr;  // [layers][B][H][Smax][dh], elements of type ct
   // element type of the cache: the engine's own (F32 / BF16) or, opt-in on a 16-bit engine, FP8 = e4m3 bytes (itts_gpt_set_kv_fp8 /
@@ -356,7 +360,9 @@ struct Engine {
   // the scorer's state on the host (beam_read_state) and BeamSearchScorer.finalize for one batch item of it: what beam_finalize
   // runs over every item at the fetch and gpt_retire_rows over the retiring items
   struct BeamHost {
-    int k = 0;  // the common step
+    int k = 0;  // the common step (of row 0 once beam groups were admitted: item b then reads len[b * nb])
+    bool both = false;     // groups were admitted: ids holds BOTH halves [2][rows][max_gen], an item's live half is len & 1
+    std::vector<int> len;  // [rows]
     std::vector<int> done, hlen, hord;
     std::vector<float> bscore, hscore;
     std::vector<int32_t> ids, htok;  // the live half of beam_ids [rows][max_gen], hyp_tok [items][nb + 1][max_gen]
@@ -374,6 +380,10 @@ struct Engine {
   // refill n finished slots of the running generation with new requests (opt-in); slots_out [n]: the slots they took
   int gpt_admit_rows(const float* cond, int cond_rows, const int32_t* text_ids, int n, int L, const RowSampling* rows_host,
                      const float* uniforms_host, const int32_t* forced_host, int n_forced, int32_t* slots_out, hipStream_t s);
+  int gpt_set_admit_beams(int on);  // opt-in: gpt_admit_rows admits whole batch items into a beam generation
+  // its beam branch: n items, text_ids [n][L], uniforms_host [n][max_gen][2 * nb]; items_out [n]: the item slots they took
+  int admit_beam_groups(const float* cond, int cond_rows, const int32_t* text_ids, int n, int L, const float* uniforms_host,
+                        int32_t* items_out, hipStream_t s);
   int gpt_row_status(int32_t* orig_host, int32_t* len_host, int32_t* unf_host, hipStream_t s);  // per slot, [B] each
   int gpt_latent(const float* cond, const int32_t* text_ids, int L, const int32_t* codes, int T, void* latent_out,
                  hipStream_t s);

@@ -161,6 +161,9 @@ int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s);
 // w: needed when a.do_sample and a.top_k < 1 or > BEAM_MAX_CAND (the wide pair + beam_select_kernel on its picks)
 int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w = nullptr);
 int beam_commit_step(const BeamArgs& a, hipStream_t s);  // host picks -> scorer bookkeeping (beam_select_kernel only)
+// the same step for batch item `item` alone (grid of one item, pointers advanced to it, a.B the full item count): the first token
+// of an admitted beam group.  No typical pre-pass, no host picks
+int beam_item_step(const BeamArgs& a, int item, hipStream_t s, const BeamWide* w = nullptr);
 
 // TypicalLogitsWarper pre-pass (beam.hip): processed scores of every row -> out [rows, V] with the filtered ones at -inf
 struct TypicalArgs {
@@ -234,6 +237,21 @@ struct RowsAdmitArgs {
 int rows_admit_check(const RowsAdmitArgs& a, const int* slots, const int* kvs);  // host only
 int rows_admit(RowsAdmitArgs a, const int* slots, const int* kvs, hipStream_t s);
 int admit_plan(const int* unfinished, const int* len, int B, int max_gen, int n, int* slots, int* n_free);  // host only
+// beam_admit_kernel: the beam state of a fresh generation for n batch items of a running beam generation (the beam branch of
+// Engine::gpt_admit_rows).  The items travel by value, n * nb <= ROWS_MOVE_MAX rows; rows_admit does the per-row part
+struct BeamAdmitArgs {
+  float* beam_scores = nullptr;                                        // [items * nb]
+  uint8_t* anc = nullptr;                                              // [2][items * nb][Smax]
+  int *hyp_order = nullptr, *hyp_n = nullptr, *hyp_counter = nullptr;  // [items][nb + 1], [items], [items]
+  float* hyp_worst = nullptr;                                          // [items]
+  int* done = nullptr;                                                 // [items]
+  float* uniforms = nullptr;                                           // [max_gen][items][2 * nb] or null
+  const float* uniforms_src = nullptr;                                 // [n][max_gen][2 * nb] device, or null: the columns stay
+  int n = 0, nb = 0, items = 0, Smax = 0, max_gen = 0, do_sample = 0;
+  unsigned short item[ROWS_MOVE_MAX];                                  // filled by beam_admit from its host list
+};
+int beam_admit_check(const BeamAdmitArgs& a, const int* items);  // host only
+int beam_admit(BeamAdmitArgs a, const int* items, hipStream_t s);
 
 // second generation, one file per kernel family.  decode_gemv.hip:
 bool gemv2_supported(const GemvArgs& g);

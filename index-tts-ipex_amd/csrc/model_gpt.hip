@@ -472,7 +472,8 @@ int Engine::beam_finalize(int32_t* codes, hipStream_t s) {
 int Engine::beam_read_state(BeamHost& st, hipStream_t s) {
   DecodeState& d = ds;
   const int nb = d.nb, rows = d.B, B = rows / nb, mg = d.max_gen;
-  std::vector<int> len(rows);
+  std::vector<int>& len = st.len;
+  len.resize(rows);
   st.done.resize(B);
   st.hlen.resize((size_t)B * (nb + 1));
   st.hord.resize((size_t)B * (nb + 1));
@@ -486,9 +487,11 @@ int Engine::beam_read_state(BeamHost& st, hipStream_t s) {
   ITTS_HIP_CHECK(hipMemcpyAsync(st.hord.data(), d.hyp_order, st.hord.size() * 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   const int k = st.k = len[0];
-  st.ids.resize((size_t)rows * mg);
+  // admitted groups (admit_beam_groups) started later: every item then has its own step and its own live half - both are read
+  st.both = d.admitted > 0;
+  st.ids.resize((size_t)(st.both ? 2 : 1) * rows * mg);
   st.htok.resize((size_t)B * (nb + 1) * mg);
-  ITTS_HIP_CHECK(hipMemcpyAsync(st.ids.data(), d.beam_ids + (size_t)(k & 1) * rows * mg, st.ids.size() * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(st.ids.data(), d.beam_ids + (st.both ? 0 : (size_t)(k & 1) * rows * mg), st.ids.size() * 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(hipMemcpyAsync(st.htok.data(), d.hyp_tok, st.htok.size() * 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(hipStreamSynchronize(s));
   return OK;
@@ -498,7 +501,9 @@ int Engine::beam_read_state(BeamHost& st, hipStream_t s) {
 // hypothesis store alone: its result is final from the step at which it became done
 int Engine::beam_finalize_item(const BeamHost& st, int b, int32_t* codes) const {
   const DecodeState& d = ds;
-  const int nb = d.nb, mg = d.max_gen, k = st.k;
+  const int nb = d.nb, mg = d.max_gen;
+  const int k = st.both ? std::min(std::max(st.len[(size_t)b * nb], 0), mg) : st.k;  // the item's own step: parity and lpdiv
+  const int32_t* ids = st.ids.data() + (st.both ? (size_t)(k & 1) * st.len.size() * mg : 0);
   struct Hyp {
     float score;
     int order, len;
@@ -520,7 +525,7 @@ int Engine::beam_finalize_item(const BeamHost& st, int b, int32_t* codes) const 
       const int row = b * nb + q;
       const float score = st.bscore[row] / lpdiv;
       if ((int)hy.size() < nb || score > worst) {
-        hy.push_back({score, counter++, k, st.ids.data() + (size_t)row * mg});
+        hy.push_back({score, counter++, k, ids + (size_t)row * mg});
         if ((int)hy.size() > nb) {
           size_t lo = 0;
           for (size_t i = 1; i < hy.size(); ++i)
@@ -1702,7 +1707,8 @@ int Engine::gpt_set_retire_beams(int on) {
 // a key's row relative to the group (decode_attn2_kernel<ANC>: (b / nb) * nb + anc[b][j]), and a done group is a no-op in every
 // beam kernel while beam_finalize reads nothing of it but its hypothesis store - so its result is final, taken here, and kept on
 // the host by original item.  With group-uniform flags retire_plan moves whole groups into whole holes and a beam keeps its index
-// inside its group (asserted below before anything changes).  The live groups share one step k, so len[0] stays the common step.
+// inside its group (asserted below before anything changes).  The live groups share one step k, so len[0] stays the common step - unless groups
+// were admitted (admit_beam_groups): then every group has its own step, the host reads len per item, and both halves of step 3 move.
 //   1. the retiring items' hypotheses (beam_finalize_item) and their rows' last logits -> the host store
 //   2. rows_move with the row plan: K and V over all layers, h, logits, forced, len, kv_start, cur_tok, unfinished, beam_scores;
 //      with the item plan: the hypothesis store and the scorer's per-item words
@@ -1728,17 +1734,24 @@ int Engine::retire_beam_groups(int* rows_now, hipStream_t s) {
   ITTS_TRY(retire_plan(live.data(), B, &n, src.data(), dst.data(), &nm));
   if (n == B || n == 0) return OK;
   // everything that could refuse, before anything is changed
-  const int k = lens[0];
+  // groups that were admitted (admit_beam_groups) started later: then every group has its own step and BOTH ping-pong halves are
+  // live - k is the longest history (what the K/V moves copy), and step 3 moves both halves
+  const bool mixed = d.admitted > 0;
+  int k = lens[0];
   ITTS_REQUIRE(k >= 0 && k <= mg, "gpt_retire_rows: decode state out of range");
-  for (int b = 0; b < B; ++b)
-    ITTS_REQUIRE(lens[b] == k && (live[b] || !unf[b]), "gpt_retire_rows: the beam groups do not share one step, or a done group has an unfinished row");
+  for (int b = 0; b < B; ++b) {
+    ITTS_REQUIRE(lens[b] == (mixed ? lens[b - b % nb] : k) && (live[b] || !unf[b]), "gpt_retire_rows: the beam groups do not share one step, or a done group has an unfinished row");
+    ITTS_REQUIRE(lens[b] >= 0 && lens[b] <= mg, "gpt_retire_rows: decode state out of range");
+  }
+  for (int b = 0; b < B; ++b) k = std::max(k, lens[b]);
   ITTS_REQUIRE(n % nb == 0 && nm % nb == 0 && nm <= ROWS_MOVE_MAX && n <= ROWS_MOVE_MAX, "gpt_retire_rows: beam groups need at most 128 live rows");
   for (int i = 0; i < nm; ++i)  // whole groups into whole holes, a beam keeps its index inside its group
     ITTS_REQUIRE(src[i] % nb == i % nb && dst[i] % nb == i % nb && src[i] - src[i - i % nb] == i % nb && dst[i] - dst[i - i % nb] == i % nb,
                  "gpt_retire_rows: the plan splits a beam group");
   ITTS_REQUIRE(keep >= 1 && keep <= nb && (d.orig.empty() || keep == d.ret_keep), "gpt_retire_rows: num_return_sequences changed inside a generation");
   const bool draws = d.beam_sample && !d.host_sample;
-  ITTS_REQUIRE(!draws || sample_uniforms.size() >= (size_t)mg * items0 * nd, "gpt_retire_rows: the uniforms of this generation are gone");
+  ITTS_REQUIRE(!draws || (mixed ? d.adm_uniforms.size() == (size_t)mg * items0 * nd : sample_uniforms.size() >= (size_t)mg * items0 * nd),
+               "gpt_retire_rows: the uniforms of this generation are gone");
   std::vector<int> isrc(nm / nb), idst(nm / nb);  // the item plan
   for (int g = 0; g < nm / nb; ++g) {
     isrc[g] = src[g * nb] / nb;
@@ -1786,7 +1799,22 @@ int Engine::retire_beam_groups(int* rows_now, hipStream_t s) {
     ITTS_TRY(rows_move(a.first, 0, 1, a.second, a.second, 1, a.second, isrc.data(), idst.data(), nm / nb, s));
   // 3. the live half of the two ping-pong arrays
   const std::pair<void*, size_t> halves[] = {{d.beam_ids, (size_t)mg * 4}, {d.anc, (size_t)d.Smax}};
-  if ((k & 1) == 0) {
+  if (mixed) {
+    // both halves are live, so there is no dead half to stage through: half 0 moves in place, half 1 goes from base rows_old * row
+    // to base rows_new * row through a staging block of the scratch arena (two rows_gather launches, stream-ordered)
+    std::vector<int> from(n), iota(n);
+    for (int j = 0; j < n; ++j) from[j] = B + j, iota[j] = j;
+    for (int i = 0; i < nm; ++i) from[dst[i]] = B + src[i];
+    const size_t stage_bytes = (size_t)n * std::max((size_t)mg * 4, (size_t)d.Smax);
+    ITTS_TRY(ws_reserve(stage_bytes + 4096, s));
+    ws_reset();
+    void* stage = alloc(stage_bytes);
+    for (const auto& a : halves) {
+      ITTS_TRY(rows_move(a.first, 0, 1, a.second, a.second, 1, a.second, src.data(), dst.data(), nm, s));
+      ITTS_TRY(rows_gather(stage, 0, a.first, 0, 1, a.second, from.data(), n, s));
+      ITTS_TRY(rows_gather((char*)a.first + (size_t)n * a.second, 0, stage, 0, 1, a.second, iota.data(), n, s));
+    }
+  } else if ((k & 1) == 0) {
     for (const auto& a : halves)
       ITTS_TRY(rows_move(a.first, 0, 1, a.second, a.second, 1, a.second, src.data(), dst.data(), nm, s));
   } else {
@@ -1807,7 +1835,10 @@ int Engine::retire_beam_groups(int* rows_now, hipStream_t s) {
     u.resize((size_t)mg * ni * nd);
     for (int q = 0; q < mg; ++q)
       for (int i = 0; i < ni; ++i)
-        std::memcpy(u.data() + ((size_t)q * ni + i) * nd, sample_uniforms.data() + ((size_t)q * items0 + d.orig[i * nb] / nb) * nd, (size_t)nd * 4);
+        std::memcpy(u.data() + ((size_t)q * ni + i) * nd,
+                    mixed ? d.adm_uniforms.data() + ((size_t)(d.orig[i * nb] / nb) * mg + q) * nd
+                          : sample_uniforms.data() + ((size_t)q * items0 + d.orig[i * nb] / nb) * nd,
+                    (size_t)nd * 4);
     ITTS_HIP_CHECK(hipMemcpyAsync(d.uniforms, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
   }
   d.B = n;
@@ -1865,6 +1896,13 @@ int Engine::gpt_admit_rows(const float* cond_dev, int cond_rows, const int32_t* 
   const int D = c.model_dim, nl = c.cond_latents, V = c.number_mel_codes, B = d.B, mg = d.max_gen;
   ITTS_REQUIRE(cond_dev && text_ids && n >= 1 && L >= 1 && (cond_rows == 1 || cond_rows == n), "gpt_admit_rows: bad arguments");
   ITTS_REQUIRE(n <= ROWS_MOVE_MAX, "gpt_admit_rows: more than 128 rows in one admission");
+  if (d.nb > 1) {  // opt-in on its own (gpt_set_admit_beams; ITTS_ADMIT_BEAMS, read per call, overrides the setter both ways)
+    const char* ab = getenv("ITTS_ADMIT_BEAMS");
+    if (ab ? atoi(ab) != 0 : d.admit_beams != 0) {
+      ITTS_REQUIRE(!rows_host && !forced_host, "gpt_admit_rows: under beams there are no per-row settings and no forced tokens (rows_host and forced_host must be null)");
+      return admit_beam_groups(cond_dev, cond_rows, text_ids, n, L, uniforms_host, slots_out, s);
+    }
+  }
   ITTS_REQUIRE(d.nb == 1, "gpt_admit_rows: rows cannot be admitted under beams");
   ITTS_REQUIRE(!(d.typical_mass > 0.f), "gpt_admit_rows: rows cannot be admitted with typical filtering");
   ITTS_REQUIRE(!d.host_sample, "gpt_admit_rows: rows cannot be admitted with host sampling");
@@ -2059,6 +2097,216 @@ int Engine::gpt_admit_rows(const float* cond_dev, int cond_rows, const int32_t* 
   ITTS_HIP_CHECK(hipStreamSynchronize(s));  // rd / kvs / the tables are host buffers of this call
   if (slots_out)
     for (int i = 0; i < n; ++i) slots_out[i] = slots[i];
+  return OK;
+}
+
+int Engine::gpt_set_admit_beams(int on) {
+  ds.admit_beams = on != 0;
+  return OK;
+}
+
+// The beam branch of gpt_admit_rows (opt-in, gpt_set_admit_beams): n finished batch items of a running beam generation take n new
+// requests, nb rows each.  Why the device allows it: beam_cand_kernel, beam_select_kernel and the whole-vocabulary pair take their
+// step from the item's own state (k = len[item * nb]), with it the ping-pong half (k & 1) and the draws (uniforms[(k * items +
+// item) * 2 nb + j]); decode_attn2_kernel<ANC> takes its ancestry half from len[row] & 1.  So a group with len = 0, the beam state
+// of a fresh generation and its prefix in its rows' cache is a fresh generation that happens to sit beside older ones.  What the
+// host assumed - one common step, one live half (beam_read_state, beam_finalize_item, retire_beam_groups) - reads per item from
+// the first admission on (DecodeState::admitted).
+//   1. every refusal; synchronise; the n lowest finished items (admit_plan over per-item flags: done, or len >= max_gen)
+//   2. the leaving items are finalised at their own step (beam_finalize_item) and kept, with their rows' last logits, by original
+//      item / row; the new items become original items items0, items0 + 1, .. and their draws join the host copy by original item
+//   3. embedding + the blocks over the n * nb rows in scratch, expanded as gpt_prefill expands them (the rows and kernels of a
+//      fresh generation of those items), K/V into rows item * nb + q (kv_admit)
+//   4. rows_admit_kernel on those rows, beam_admit_kernel on the items
+//   5. the head on the rows' last position in scratch, logits to their rows, beam_item_step per admitted item: the running groups
+//      are neither stepped nor touched, no pointer of the captured step changes
+int Engine::admit_beam_groups(const float* cond_dev, int cond_rows, const int32_t* text_ids, int n, int L, const float* uniforms_host,
+                              int32_t* items_out, hipStream_t s) {
+  DecodeState& d = ds;
+  const itts_config& c = cfg;
+  const int D = c.model_dim, nl = c.cond_latents, V = c.number_mel_codes, B = d.B, mg = d.max_gen;
+  const int nb = d.nb, items = B / nb, nd = 2 * nb, nr = n * nb, keep = beam_returns;
+  ITTS_REQUIRE(nr <= ROWS_MOVE_MAX, "gpt_admit_rows: more than 128 rows (items * num_beams) in one admission");
+  ITTS_REQUIRE(!(d.typical_mass > 0.f), "gpt_admit_rows: beam groups cannot be admitted with typical filtering");
+  ITTS_REQUIRE(!d.host_sample, "gpt_admit_rows: beam groups cannot be admitted with host sampling (host-side beam warpers)");
+  static const bool env_fuse = getenv("ITTS_FUSE_QKV_ATTN") != nullptr && atoi(getenv("ITTS_FUSE_QKV_ATTN")) != 0;
+  ITTS_REQUIRE(!((d.fuse || env_fuse) && !d.fuse_failed), "gpt_admit_rows: beam groups cannot be admitted with the fused qkv + attention launch");
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  ITTS_REQUIRE(!engine_usable(), "gpt_admit_rows: beam groups cannot be admitted while the step runs on the persistent engine (<= 6 rows)");
+  ITTS_REQUIRE(d.B == d.Bcache, "gpt_admit_rows: beam groups cannot be admitted after a retirement");
+  ITTS_REQUIRE(d.input_n == 0 && !d.use_forced, "gpt_admit_rows: beam groups cannot be admitted into a generation with `input_tokens`");
+  ITTS_REQUIRE(L == d.prefix - nl - 2, "gpt_admit_rows: L must be the text length of the running generation");
+  ITTS_REQUIRE((D / c.heads) % (d.ct == F32 ? 4 : 8) == 0 && d.Bcache <= 65536 && ((uintptr_t)d.kc | (uintptr_t)d.vc) % 16 == 0,
+               "gpt_admit_rows: the cache write needs a head dim that is a multiple of 8 (4: fp32 cache) and at most 65536 cache rows");
+  ITTS_REQUIRE(B % nb == 0 && d.B0 % nb == 0 && d.Smax % 16 == 0 && d.beam_ids && d.anc, "gpt_admit_rows: beam state out of range");
+  ITTS_REQUIRE(keep >= 1 && keep <= nb && (d.orig.empty() || keep == d.ret_keep), "gpt_admit_rows: num_return_sequences changed inside a generation");
+  const bool draws = d.beam_sample != 0;
+  const bool wide = draws && (d.top_k < 1 || d.top_k > BEAM_MAX_CAND);
+  const size_t items0 = (size_t)d.B0 / nb;
+  ITTS_REQUIRE(!draws || uniforms_host, "gpt_admit_rows: uniforms missing for beam_sample");
+  ITTS_REQUIRE(!draws || (d.uniforms && d.uniforms_cap >= (size_t)mg * items * nd &&
+                          (d.admitted ? d.adm_uniforms.size() == items0 * mg * nd : sample_uniforms.size() >= items0 * mg * nd)),
+               "gpt_admit_rows: the uniforms of this generation are gone");
+  ITTS_REQUIRE(!wide || (d.wide_valid && d.wide.sc), "gpt_admit_rows: the whole-vocabulary beam sampler's scratch is missing");
+  // the text rows, stripped, left-padded and repeated per beam as gpt_prefill does
+  const int sp = d.prefix, S0 = sp + 1;
+  std::vector<RowDesc> rd((size_t)nr * S0);
+  std::vector<int> kvs(nr);
+  for (int b = 0; b < nr; ++b) {
+    const int it = b / nb;
+    std::vector<int> ids;
+    for (int i = 0; i < L; ++i) {
+      const int t = text_ids[(size_t)it * L + i];
+      if (t != c.start_text_token && t != c.stop_text_token) {
+        ITTS_REQUIRE(t >= 0 && t <= c.number_text_tokens, "gpt_admit_rows: text id out of range");
+        ids.push_back(t);
+      }
+    }
+    const int nt = (int)ids.size(), pad = L - nt;
+    kvs[b] = pad;
+    RowDesc* r = rd.data() + (size_t)b * S0;
+    int k = 0;
+    for (int i = 0; i < pad; ++i) r[k++] = {0, 0, 0, 0};
+    for (int i = 0; i < nl; ++i) r[k++] = {1, (cond_rows == n && n > 1 ? it * nl : 0) + i, 0, 0};
+    r[k++] = {2, c.start_text_token, 0, 0};
+    for (int i = 0; i < nt; ++i) r[k++] = {2, ids[i], i + 1, 0};
+    r[k++] = {2, c.stop_text_token, nt + 1, 0};
+    r[k++] = {3, c.start_mel_token, 0, 0};
+  }
+  // 1. the items
+  std::vector<int> unf(B), lens(B), done(items), iunf(items), ilen(items), took(n), rows(nr);
+  ITTS_HIP_CHECK(hipMemcpyAsync(unf.data(), d.unfinished, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(lens.data(), d.len, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipMemcpyAsync(done.data(), d.beam_done, (size_t)items * 4, hipMemcpyDeviceToHost, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  for (int b = 0; b < B; ++b)
+    ITTS_REQUIRE(lens[b] >= 0 && lens[b] <= mg && lens[b] == lens[b - b % nb], "gpt_admit_rows: decode state out of range");
+  for (int g = 0; g < items; ++g) {
+    iunf[g] = !done[g];
+    ilen[g] = lens[g * nb];
+  }
+  int n_free = 0;
+  ITTS_TRY(admit_plan(iunf.data(), ilen.data(), items, mg, n, took.data(), &n_free));
+  ITTS_REQUIRE(n_free >= n, "gpt_admit_rows: fewer finished items than items to admit");
+  for (int i = 0; i < nr; ++i) rows[i] = took[i / nb] * nb + i % nb;
+  // 2. the leaving items: finalised at their own step, before anything is changed
+  std::vector<int32_t> fin((size_t)n * keep * mg);
+  std::vector<float> lg_old((size_t)nr * V);
+  {
+    BeamHost st;
+    ITTS_TRY(beam_read_state(st, s));
+    for (int i = 0; i < n; ++i) {
+      ITTS_TRY(beam_finalize_item(st, took[i], fin.data() + (size_t)i * keep * mg));
+      ITTS_HIP_CHECK(hipMemcpyAsync(lg_old.data() + (size_t)i * nb * V, d.logits + (size_t)took[i] * nb * V, (size_t)nb * V * 4, hipMemcpyDeviceToHost, s));
+    }
+    ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  // ---- nothing was changed up to here ----
+  if (d.orig.empty()) {
+    d.orig.resize(B);
+    for (int b = 0; b < B; ++b) d.orig[b] = b;
+    d.retired.assign((size_t)d.B0, 0);
+    d.ret_keep = keep;
+    d.ret_codes.assign(items0 * keep * mg, c.stop_mel_token);
+    d.ret_logits.assign((size_t)d.B0 * V, 0.f);
+  }
+  if (!d.admitted && draws) {  // the generation takes its own copy of the draws, by original item
+    d.adm_uniforms.resize(items0 * mg * nd);
+    for (int q = 0; q < mg; ++q)
+      for (size_t it = 0; it < items0; ++it)
+        std::memcpy(d.adm_uniforms.data() + (it * mg + q) * nd, sample_uniforms.data() + ((size_t)q * items0 + it) * nd, (size_t)nd * 4);
+  }
+  for (int i = 0; i < n; ++i) {
+    const size_t r = (size_t)d.orig[took[i] * nb];  // the group's first original row
+    for (int q = 0; q < nb; ++q) d.retired[r + q] = 1;
+    std::memcpy(d.ret_codes.data() + r / nb * keep * mg, fin.data() + (size_t)i * keep * mg, (size_t)keep * mg * 4);
+    std::memcpy(d.ret_logits.data() + r * V, lg_old.data() + (size_t)i * nb * V, (size_t)nb * V * 4);
+  }
+  const int first = d.B0;  // the new original rows; original items first / nb ..
+  d.B0 += nr;
+  d.admitted += nr;
+  d.retired.resize((size_t)d.B0, 0);
+  d.ret_codes.resize((size_t)d.B0 / nb * keep * mg, c.stop_mel_token);
+  d.ret_logits.resize((size_t)d.B0 * V, 0.f);
+  for (int i = 0; i < nr; ++i) d.orig[rows[i]] = first + i;
+  if (draws) {
+    d.adm_uniforms.resize((size_t)d.B0 / nb * mg * nd, 0.f);
+    std::memcpy(d.adm_uniforms.data() + (size_t)first / nb * mg * nd, uniforms_host, (size_t)n * mg * nd * 4);
+  }
+  d.pend_split = 0;
+  const int nr16 = (nr + 15) / 16 * 16;  // the batched head keeps its bf16 rows in 16-row tiles
+  auto body = [&]() -> int {
+    RowDesc* rd_dev = (RowDesc*)alloc(rd.size() * sizeof(RowDesc));
+    int* kvs_dev = (int*)alloc((size_t)nr * 4);
+    float* h = (float*)alloc((size_t)nr * S0 * D * 4);
+    float* h_last = (float*)alloc((size_t)nr16 * D * 4);
+    float* hn = (float*)alloc((size_t)nr16 * D * 4);
+    float* lg = (float*)alloc((size_t)nr16 * V * 4);
+    float* u_dev = draws ? (float*)alloc((size_t)n * mg * nd * 4) : nullptr;
+    if (!dry) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(rd_dev, rd.data(), rd.size() * sizeof(RowDesc), hipMemcpyHostToDevice, s));
+      ITTS_HIP_CHECK(hipMemcpyAsync(kvs_dev, kvs.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+      if (u_dev) ITTS_HIP_CHECK(hipMemcpyAsync(u_dev, d.adm_uniforms.data() + (size_t)first / nb * mg * nd, (size_t)n * mg * nd * 4, hipMemcpyHostToDevice, s));
+      if (adt == F32)
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<float>, dim3(nr * S0), dim3(256), 0, s, h, rd_dev, cond_dev,
+                           (const float*)gpt.text_emb, (const float*)gpt.text_pos, (const float*)gpt.mel_emb,
+                           (const float*)gpt.mel_pos, D);
+      else
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<bf16_t>, dim3(nr * S0), dim3(256), 0, s, h, rd_dev, cond_dev,
+                           (const bf16_t*)gpt.text_emb, (const bf16_t*)gpt.text_pos, (const bf16_t*)gpt.mel_emb,
+                           (const bf16_t*)gpt.mel_pos, D);
+      ITTS_HIP_CHECK(hipGetLastError());
+    }
+    // 3.
+    ITTS_TRY(gpt_layers_full(h, nr, S0, kvs_dev, true, s, rows.data()));
+    if (dry) return OK;
+    // 4.
+    RowsAdmitArgs ra;
+    ra.seen = d.seen;
+    ra.unfinished = d.unfinished;
+    ra.cur_tok = d.cur_tok;
+    ra.len = d.len;
+    ra.kv_start = d.kv_start;
+    ra.ids = d.ids;
+    ra.n = nr;
+    ra.B = B;
+    ra.V = V;
+    ra.max_gen = mg;
+    ra.fake_id = 1;
+    ra.start_tok = c.start_mel_token;
+    ra.stop = c.stop_mel_token;
+    ITTS_TRY(rows_admit(ra, rows.data(), kvs.data(), s));
+    BeamAdmitArgs bg;
+    bg.beam_scores = d.beam_scores;
+    bg.anc = d.anc;
+    bg.hyp_order = d.hyp_order;
+    bg.hyp_n = d.hyp_n;
+    bg.hyp_worst = d.hyp_worst;
+    bg.hyp_counter = d.hyp_counter;
+    bg.done = d.beam_done;
+    bg.uniforms = u_dev ? d.uniforms : nullptr;
+    bg.uniforms_src = u_dev;
+    bg.n = n;
+    bg.nb = nb;
+    bg.items = items;
+    bg.Smax = d.Smax;
+    bg.max_gen = mg;
+    bg.do_sample = d.beam_sample;
+    ITTS_TRY(beam_admit(bg, took.data(), s));
+    // 5. (beam_select_kernel writes the next step's input rows h[item * nb ..] itself)
+    ITTS_TRY(copy_rows(h_last, D, h + (size_t)(S0 - 1) * D, S0 * D, nr, D, F32, s));
+    ITTS_TRY(head_rows(h_last, hn, lg, nr, s));
+    const BeamArgs ba = beam_args(d.logits, false);
+    for (int i = 0; i < n; ++i) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(d.logits + (size_t)took[i] * nb * V, lg + (size_t)i * nb * V, (size_t)nb * V * 4, hipMemcpyDeviceToDevice, s));
+      ITTS_TRY(beam_item_step(ba, took[i], s, wide ? &d.wide : nullptr));
+    }
+    return OK;
+  };
+  ITTS_TRY(two_pass(body, s));
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));  // rd / kvs are host buffers of this call
+  if (items_out)
+    for (int i = 0; i < n; ++i) items_out[i] = took[i];
   return OK;
 }
 

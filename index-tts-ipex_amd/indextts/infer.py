@@ -51,6 +51,11 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     `max_batch` decode as ONE generation of `max_batch` rows: a finished row's slot takes the next waiting sentence
     (Engine.generate(slots=..)) instead of every `max_batch`-sized generation draining to its slowest row.  Single beam, no
     typical filter, more than 6 rows.  `infer` / `infer_fast` are not affected.
+  * `admit_beams=True` (not in the reference; default off; ITTS_ADMIT_BEAMS=1 / 0 overrides it in both directions; acts only on top
+    of `admit_rows` + `mixed_batch`) extends the row admission to the beam groups of `infer_batch` - the mode of the default
+    kwargs, `num_beams=3` - without typical filtering: a group with more sentences than `max_batch // num_beams` decodes as ONE
+    generation of that many item slots, a finished sentence's group of `num_beams` rows takes the next waiting sentence
+    (Engine.generate(slots=.., admit_beams=True)).  `infer` / `infer_fast` and plain `infer_batch` are not affected.
   * `packed_latent=True` (not in the reference; default off; ITTS_PACKED_LATENT=1 / 0 overrides it in both directions) runs the
     latent pass of `infer_batch` on packed rows (Engine.latent_packed: no pad rows, a sentence's latent has the same bits
     whoever shares its pass); with `mixed_batch` the utterances of a decode group then share ONE latent pass instead of one
@@ -80,7 +85,7 @@ class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
-                 mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False):
+                 mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -112,6 +117,7 @@ class IndexTTS:
         self.ragged_vocoder = bool(ragged_vocoder)  # infer_batch: sentences of unequal length share vocoder passes (ITTS_RAGGED_VOCODER overrides)
         self.mixed_batch = bool(mixed_batch)  # infer_batch: one decode batch across voices and sampling settings (ITTS_MIXED_BATCH overrides)
         self.admit_rows = bool(admit_rows)  # infer_batch with mixed_batch: finished decode rows are refilled from the waiting sentences (ITTS_ADMIT_ROWS overrides)
+        self.admit_beams = bool(admit_beams)  # on top of admit_rows: beam groups (the default kwargs' mode) are refilled too (ITTS_ADMIT_BEAMS overrides)
         self._admit_told = False
         self.packed_latent = bool(packed_latent)  # infer_batch: the latent pass on packed rows, one per decode group (ITTS_PACKED_LATENT overrides)
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
@@ -418,6 +424,15 @@ class IndexTTS:
                                                       kws[u].get("temperature", 1.0), settings[u]["repetition_penalty"])[0] for u in us}
                 e0 = next(iter(ents))
                 one = not (len(ents) == 1 and e0[0] == 1 and not 1 <= e0[1] <= 128)
+            # admission under beams (admit_beams, on top of admit_rows): a beam group - several beams, no typical filter; mixed_groups
+            # made its settings equal - with more sentences than its cap is ONE generation of cap item slots
+            nbeam = shared.get("num_beams", 1)
+            beam_one = (admit and infer_core.env_switch("ITTS_ADMIT_BEAMS", self.admit_beams) and nbeam > 1
+                        and not shared.get("typical_mass") and cap * nbeam > 6 and len(order) > cap)
+            if beam_one and kws[us[0]].get("do_sample") and not 1 <= int(kws[us[0]].get("top_k") or 0) <= 128:
+                # the whole-vocabulary warpers run on the host unless the device beam sampler was chosen: that path cannot admit
+                beam_one = (self.wide_beam_sampler or os.environ.get("ITTS_WIDE_BEAM_SAMPLER") or "host") == "device"
+            one = one or beam_one
             for lo in range(0, len(order), len(order) if one else cap):
                 sel = order if one else order[lo:lo + cap]
                 ids = infer_core.pad_tokens_cat([flat[i][2] for i in sel], self.cfg.gpt.stop_text_token)
@@ -434,6 +449,9 @@ class IndexTTS:
                     kw = dict(kws[us[0]], repetition_penalty=g0["repetition_penalty"])
                 if one:
                     kw["slots"] = cap
+                if beam_one:
+                    kw["admit_beams"] = True
+                    kw["admit_min"] = 0.25  # an admission prefills num_beams rows per sentence: 1/4 measured best (profiles/admit_beams.txt)
                 codes = self.engine.generate(cond, ids, g0["max_mel_tokens"], wide_sampler=self.wide_sampler,
                                              wide_beam_sampler=self.wide_beam_sampler, retire_rows=self.retire_rows, retire_beams=self.retire_beams, **kw)
                 for j, i in enumerate(sel):

@@ -384,7 +384,7 @@ class Engine:
         (a table generation; None: the generation's own settings); uniforms [n, max_gen]: the draws of sampled rows; forced
         [n, k] (-1 free): only in a generation that was started with forced tokens.  The new rows become original rows
         B0, B0 + 1, ..: fetch() then returns them behind the earlier ones.  The running rows are not stepped.  -> the slots taken.
-        Raises (nothing changed) under beams, typical filtering, host sampling, at <= 6 rows on the persistent engine, after a
+        Raises (nothing changed) under beams (unless set_admit_beams opted in: see there), typical filtering, host sampling, at <= 6 rows on the persistent engine, after a
         retirement, and when fewer than n slots are finished (a row at max_gen counts as finished)."""
         ids = np.ascontiguousarray(text_ids, dtype=np.int32)
         assert ids.ndim == 2
@@ -399,8 +399,9 @@ class Engine:
                 raise ValueError(f"admit_rows: {len(rows)} settings for {n} rows")
             tab = (L.RowSampling * n)(*[L.RowSampling(int(m), int(k), float(p), float(t), float(pen)) for m, k, p, t, pen in rows])
         u = None if uniforms is None else np.ascontiguousarray(uniforms, dtype=np.float32)
-        if u is not None and u.shape != (n, self._gen[1]):
-            raise ValueError(f"admit_rows: uniforms {u.shape}, expected {(n, self._gen[1])}")
+        nb = getattr(self, "_nb", 1)  # under beams (set_admit_beams): n batch items, the draws of every item's 2 * nb picks per step
+        if u is not None and u.shape != ((n, self._gen[1]) if nb <= 1 else (n, self._gen[1], 2 * nb)):
+            raise ValueError(f"admit_rows: uniforms {u.shape}, expected {(n, self._gen[1]) if nb <= 1 else (n, self._gen[1], 2 * nb)}")
         f = None if forced is None else np.ascontiguousarray(np.atleast_2d(forced), dtype=np.int32)
         if f is not None and f.shape[0] != n:
             raise ValueError(f"admit_rows: forced tokens {f.shape} for {n} rows")
@@ -410,8 +411,22 @@ class Engine:
                                              None if u is None else u.ctypes.data_as(C.c_void_p),
                                              None if f is None else f.ctypes.data_as(C.c_void_p), 0 if f is None else f.shape[1],
                                              slots.ctypes.data_as(C.c_void_p), self._s()), "gpt_admit_rows")
-        self._gen = (int(self.lib.itts_gpt_rows_total(self.h)), self._gen[1])
+        self._gen = (int(self.lib.itts_gpt_rows_total(self.h)) // max(nb, 1), self._gen[1])  # (fetch counts batch items)
         return slots
+
+    def set_admit_beams(self, on: bool = True):
+        """Opt-in: admit_rows() also works under beams (itts_gpt_set_admit_beams) - it then admits whole batch items into a
+        running beam generation (beam_sample or beam_search on the device): text_ids [n, L] and cond count items, uniforms is
+        [n, max_gen, 2 * num_beams] (beam_sample only), rows and forced must stay None, and the returned slots are ITEM slots.
+        An item is finished when it is done or holds max_gen tokens; a leaving item's num_return_sequences hypotheses are final and
+        kept by original item, the new items become original items behind the earlier ones: fetch() returns
+        [items * num_return_sequences] code rows in that order, row_status() stays per row (item i: rows i * num_beams ..).
+        Within one projection-kernel family an admitted item's bits are those of a fresh generation of the admitted items.
+        retire_rows() (with set_retire_beams) still works afterwards; admission after a retirement does not.  Still refused:
+        typical filtering, host-side beam warpers, `input_tokens`, the persistent engine (<= 6 rows).  Sticky, default off.
+        ITTS_ADMIT_BEAMS=0 / 1 in the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_admit_beams(self.h, int(bool(on))), "gpt_set_admit_beams")
+        self._admit_beams = bool(on)
 
     def fetch(self, logits: bool = False):
         B, mg = self._gen
@@ -427,7 +442,8 @@ class Engine:
                  uniforms: Optional[np.ndarray] = None, num_beams: int = 1, typical_mass: float = 0.0,
                  length_penalty: float = 0.0, num_return_sequences: int = 1, wide_sampler: Optional[str] = None,
                  wide_beam_sampler: Optional[str] = None, retire_rows: Optional[float] = None, slots: Optional[int] = None,
-                 admit_min: float = 0.125, return_log: bool = False, retire_beams: Optional[bool] = None) -> np.ndarray:
+                 admit_min: float = 0.125, return_log: bool = False, retire_beams: Optional[bool] = None,
+                 admit_beams: Optional[bool] = None) -> np.ndarray:
         """Greedy decode (do_sample=False, num_beams=1 of tests/padding_test.py:35-46) or, with do_sample, HF
         GenerationMixin.sample (top-k / top-p / temperature, num_beams=1; draws from `uniforms` or a numpy Generator
         seeded with `seed`).  Returns int64 codes [B, n] with n <= max_gen: HF stops when every row has emitted stop
@@ -473,7 +489,14 @@ class Engine:
         Suggested admit_min: 0.125, the default - measured with tools/bench_admit_rows.py (profiles/admit_rows.txt, DESIGN.md
         section 5i): 192 ragged requests through 64 slots take 1708 ms at 1/8, 1746 ms at 1/4 and 1932 ms at 1/2 against 2149 ms
         as three 64-row generations (1900 ms with retire_rows=0.5): an admission of 8 rows costs 5 ms, about three token steps, so
-        small groups do not lose."""
+        small groups do not lose.
+        admit_beams: opt-in on top of slots= for num_beams > 1 (set_admit_beams for the duration of the call): S counts batch
+        ITEMS (S * num_beams rows, <= max_batch and > 6), whole items are admitted and leave, uniforms is (max_gen, N, 2 *
+        num_beams) by request (drawn from `seed` when absent), num_return_sequences is allowed and the result is [N * returns, n]
+        in the caller's order; the log holds item slots.  One setting for all requests, no typical filter; do_sample with top_k
+        outside 1 .. 128 needs wide_beam_sampler="device" (ValueError otherwise).  Once the list is empty retire_rows applies only
+        together with retire_beams.  Off, slots= with beams raises as before.  None: the environment's ITTS_ADMIT_BEAMS, else off.
+        Measured with tools/bench_admit_beams.py (profiles/admit_beams.txt)."""
         rows = None
         per_row = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty)
         if any(isinstance(v, (list, tuple, np.ndarray)) for v in list(per_row.values()) + [seed]):
@@ -512,6 +535,28 @@ class Engine:
             wide_beam_sampler = os.environ.get("ITTS_WIDE_BEAM_SAMPLER") or "host"
         if wide_beam_sampler not in ("host", "device"):
             raise ValueError(f"wide_beam_sampler must be 'host' or 'device', not {wide_beam_sampler!r}")
+        if admit_beams is None:
+            admit_beams = bool(int(os.environ.get("ITTS_ADMIT_BEAMS") or 0))
+        if slots is not None and np.asarray(text_ids).shape[0] > int(slots) and num_beams > 1 and admit_beams:
+            nb, S = int(num_beams), int(slots)
+            if typical_mass:
+                raise ValueError("row admission under beams (slots=, admit_beams=True) runs without typical filtering only")
+            if rows is not None:
+                raise ValueError("row admission under beams (slots=, admit_beams=True) takes one setting for every request")
+            if do_sample and not 1 <= int(top_k or 0) <= 128 and wide_beam_sampler != "device":
+                raise ValueError("row admission under beams (slots=, admit_beams=True) with top_k outside 1 .. 128 runs on the device's "
+                                 "whole-vocabulary beam sampler only: pass wide_beam_sampler='device' (the host-side warpers cannot admit)")
+            if not 6 < S * nb <= self.ccfg.max_batch:
+                raise ValueError(f"row admission under beams: slots * num_beams = {S * nb} must be above 6 (the persistent engine's "
+                                 f"rows) and at most max_batch = {self.ccfg.max_batch}")
+            nrow = np.asarray(text_ids).shape[0]
+            if do_sample and uniforms is None:
+                uniforms = np.random.default_rng(seed).random((max_gen, nrow, 2 * nb), dtype=np.float32)
+            out = self._generate_admit_beams(cond, text_ids, max_gen, S, float(admit_min), suppress_stop, check_every, retire_rows,
+                                             bool(retire_beams), bool(do_sample), int(top_k or 0), top_p, temperature,
+                                             uniforms if do_sample else None, nb, length_penalty, int(num_return_sequences),
+                                             float(repetition_penalty))
+            return out if return_log else out[0]
         if slots is not None and np.asarray(text_ids).shape[0] > int(slots):
             if num_beams > 1 or typical_mass:
                 raise ValueError("row admission (slots=) runs with one beam and without typical filtering only")
@@ -693,6 +738,78 @@ class Engine:
         assert sorted(order) == list(range(N)) and codes.shape[0] == N, (order, codes.shape)
         out = np.empty_like(codes)
         out[order] = codes
+        n = 0
+        for row in out:
+            hit = np.nonzero(row == stop)[0]
+            n = max(n, int(hit[0]) + 1 if len(hit) else max_gen)
+        return out[:, :n], log
+
+    def _generate_admit_beams(self, cond, text_ids, max_gen, slots, admit_min, suppress_stop, check_every, retire_rows, retire_beams,
+                              do_sample, top_k, top_p, temperature, uniforms, num_beams, length_penalty, num_return_sequences,
+                              repetition_penalty):
+        """generate(slots=.., num_beams > 1, admit_beams=True): one beam generation of `slots` batch items over all N requests;
+        infer_core.AdmitScheduler runs with items as slots.  uniforms [max_gen, N, 2 * num_beams] by request (None: beam_search).
+        -> (codes int64 [N * num_return_sequences, n] in the caller's order, the admission log with item slots)"""
+        from . import infer_core
+
+        ids = np.ascontiguousarray(text_ids, dtype=np.int32)
+        N, nb, nret = ids.shape[0], num_beams, num_return_sequences
+        cc = self.ccfg
+        lengths = [int(np.count_nonzero((r != cc.start_text_token) & (r != cc.stop_text_token))) for r in ids]
+        sched = infer_core.AdmitScheduler(lengths, slots, admit_min)
+        cond = cond.to(device=self.device, dtype=torch.float32).contiguous().view(-1, cc.cond_latents, cc.model_dim)
+        if cond.shape[0] not in (1, N):
+            raise ValueError(f"generate(slots=): cond holds {cond.shape[0]} blocks for {N} rows")
+        cond_of = (lambda req: cond[0]) if cond.shape[0] == 1 else (lambda req: cond[list(req)])
+        u = None if uniforms is None else np.ascontiguousarray(uniforms, dtype=np.float32).reshape(max_gen, N, 2 * nb)
+        log, stop = [], cc.stop_mel_token
+        first = sched.first
+        retire = bool(retire_rows and retire_beams)
+        held_ab, held_rb = getattr(self, "_admit_beams", False), getattr(self, "_retire_beams", False)  # the caller's settings
+        try:
+            self.set_admit_beams(True)
+            if retire:
+                self.set_retire_beams(True)
+            self.set_beam_sample(nb, top_k, top_p, temperature, None if u is None else u[:, first], do_sample=do_sample,
+                                 length_penalty=length_penalty, num_return_sequences=nret)
+            self.prefill(cond_of(first), ids[first], max_gen, repetition_penalty, suppress_stop)
+            steps, retired = 1, False
+            while True:
+                orig, ln, unf = self.row_status()
+                il, iu = ln[::nb].copy(), unf[::nb]  # per item: an item's rows step together
+                live = (iu != 0) & (il < max_gen)
+                if sched.waiting and not retired:
+                    sl, req = sched.take(np.nonzero(~live)[0].tolist())
+                    if req:
+                        took = self.admit_rows(cond_of(req), ids[req],
+                                               uniforms=None if u is None else np.ascontiguousarray(u[:, req].transpose(1, 0, 2)))
+                        assert took.tolist() == sl, (took, sl)
+                        log.append((steps, sl, req))
+                        il[sl], live[sl] = 1, True
+                if not sched.waiting:
+                    if not live.any():
+                        break
+                    rows_now = self.rows()
+                    n_live = int(live.sum()) * nb
+                    if retire and rows_now > 6 and n_live <= retire_rows * rows_now and n_live < rows_now:
+                        if self.retire_rows() != rows_now:  # the item slots are another set now: read them again
+                            retired = True
+                            continue
+                n = min(check_every, max_gen - int(il[live].min())) if live.any() else check_every
+                self.decode(n)
+                steps += n
+            codes = self.fetch().astype(np.int64)  # [N * nret, max_gen] by original item, stop behind every hypothesis
+            self._exit()
+        finally:
+            self.set_beam_sample(1)
+            if retire:
+                self.set_retire_beams(held_rb)
+            self.set_admit_beams(held_ab)
+        order = sched.order()
+        assert sorted(order) == list(range(N)) and codes.shape[0] == N * nret, (order, codes.shape)
+        out = np.empty_like(codes).reshape(N, nret, max_gen)
+        out[order] = codes.reshape(N, nret, max_gen)
+        out = out.reshape(N * nret, max_gen)
         n = 0
         for row in out:
             hit = np.nonzero(row == stop)[0]

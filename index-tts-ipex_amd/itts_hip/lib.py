@@ -106,6 +106,14 @@ class RowsAdmitArgs(C.Structure):
                [(n, i32) for n in ("n", "B", "V", "max_gen", "fake_id", "start_tok", "stop")]
 
 
+class BeamAdmitArgs(C.Structure):
+    """itts_beam_admit_args: the beam state arrays of `items` batch items, the device source of the draws, the host list of the n
+    admitted items."""
+    _fields_ = [(n, vp) for n in ("beam_scores", "anc", "hyp_order", "hyp_n", "hyp_worst", "hyp_counter", "beam_done", "uniforms",
+                                  "uniforms_src", "items_host")] + \
+               [(n, i32) for n in ("n", "nb", "items", "Smax", "max_gen", "do_sample")]
+
+
 _lib = None
 _lib_f16 = None
 
@@ -196,6 +204,8 @@ _PROTOS = {
     "itts_kv_admit": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "itts_rows_admit": (i32, [C.POINTER(RowsAdmitArgs), vp]),
     "itts_admit_plan": (i32, [vp, vp, i32, i32, i32, vp, C.POINTER(i32)]),
+    "itts_gpt_set_admit_beams": (i32, [vp, i32]),
+    "itts_beam_admit": (i32, [C.POINTER(BeamAdmitArgs), vp]),
     "itts_gpt_latent": (i32, [vp, vp, vp, i32, vp, i32, vp, vp]),
     "itts_gpt_latent_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     "itts_bigvgan": (i32, [vp, vp, vp, i32, i32, vp, vp]),
