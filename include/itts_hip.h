@@ -116,6 +116,37 @@ int itts_snake_aa_fwd_len(void* dst, const void* src, const float* up12, const f
 int itts_act_conv_len(const itts_gemm_args* args, const float* log_alpha, const float* log_beta, const float* filt12,
                       const int* lens_dev, int mul, itts_stream stream);
 int itts_zero_tail_rows(void* x, int B, int T, int C, const int* lens_dev, int mul, int dtype, itts_stream stream);
+/* ---- packed sentences (the vocoder over sentences back to back in ONE item) ----
+ * A [off[n] * mul, C] tensor holds n sentences back to back in time: sentence b owns rows [off_host[b] * mul, off_host[b + 1] * mul) -
+ * its capacity - of which the first lens_host[b] * mul are signal (off_host: host int32 [n + 1], lens_host: host int32 [n]; mul >= 1,
+ * the up-sampling between the unit of the table and this tensor's rows).  The table is read on the host and travels by value in the
+ * kernels' argument block: nothing of the caller's outlives the call.  All three refuse with ITTS_E_INVALID before any HIP call:
+ * null pointers, n outside [1, 128], mul < 1, off[0] < 0, a length < 1, offsets not increasing, a capacity below its length,
+ * off[n] * mul >= 2^31, C < 1, an unsupported dtype.  Rows outside [off[0] * mul, off[n] * mul) are never written.
+ *
+ * itts_snake_aa_fwd_seg: itts_snake_aa_fwd (layout 1) per sentence - the replicate padding is taken at the sentence's own last signal
+ * row; its signal rows have the bits of itts_snake_aa_fwd on the sentence cut out, the rest of its capacity is written as zeros.
+ * dtype 0 / 1 / 5.
+ * itts_act_conv_seg: itts_act_conv per sentence (one grid row each): rows before a sentence's first and behind its last signal row
+ * enter the convolution as zeros, output rows are stored up to the capacity and never beyond.  args->M == args->T >= off[n] * mul (one
+ * item that holds the pack).  Signal rows have the bits of itts_snake_aa_fwd_seg followed by itts_gemm on the whole pack wherever
+ * the gaps are at least the convolution's reach.  The shape rule is itts_gemm_which_pinned_conv == 4, i.e. that of itts_act_conv
+ * apart from the row count (a sentence of one row runs); also refused: force_simple, a dtype that is not the 16-bit one,
+ * lda != Cin, a bias with bias_bstride != 0 (the pack is one item and its bias one row of N; per-sentence rows are
+ * itts_seg_bias_mask's), ITTS_NO_CONV_LDS / ITTS_NO_CONV_ACT set.
+ * itts_seg_bias_mask: the signal rows of sentence b get bias[b][0 .. C) added (fp32 [n, C], one fp32 sum rounded to the tensor's type;
+ * bias NULL = they are left alone), the rest of its capacity becomes zeros.  dtype 0 / 1.  16-byte units where a row is a whole number
+ * of them and x is 16-byte aligned, else one element (4 or 2 bytes) per lane.
+ * itts_gemm_which_pinned_conv: the family the packed vocoder takes for a convolution (no launch): 4 where the shape apart from its
+ * row count is the narrow conv's, else 3 (gemm_p8 wherever it can run the shape), 1, 0 - never 2, never by M or T. */
+int itts_snake_aa_fwd_seg(void* dst, const void* src, const float* up12, const float* down12, const float* log_alpha,
+                          const float* log_beta, int C, const int32_t* off_host, const int32_t* lens_host, int n, int mul, int dtype,
+                          itts_stream stream);
+int itts_act_conv_seg(const itts_gemm_args* args, const float* log_alpha, const float* log_beta, const float* filt12,
+                      const int32_t* off_host, const int32_t* lens_host, int n, int mul, itts_stream stream);
+int itts_seg_bias_mask(void* x, const float* bias, int C, const int32_t* off_host, const int32_t* lens_host, int n, int mul, int dtype,
+                       itts_stream stream);
+int itts_gemm_which_pinned_conv(const itts_gemm_args* args);
 /* Which instantiation the bf16 decode GEMV of the launch path (1-4 rows) takes for a call (no launch): -1 = it does not take the
  * call, else nb | rpw << 4 | nch << 8 | waves << 16 (batch rows compiled in, weight rows per wave, 512-column chunks per lane, waves
  * per workgroup).  w5 = the ITTS_GEMV_W5 rows.  tests/test_gemv_selector.py uses it. */
@@ -760,6 +791,25 @@ int itts_bigvgan(itts_engine* e, const void* latent, const float* spk, int B, in
  * a length outside [1, T].  lens_host is consumed before the call returns. */
 int itts_bigvgan_ragged(itts_engine* e, const void* latent, const float* spk, int B, int T, const int32_t* lens_host, float* wav_out,
                         itts_stream stream);
+
+/* The same over PACKED sentences (opt-in): latent [off_host[n], gpt_dim] (engine dtype) holds n sentences back to back,
+ * sentence b the frames [off_host[b], off_host[b + 1]) of which the first lens_host[b] are signal; whatever the rest holds is not read
+ * as signal (latent is not modified).  spk fp32 [n, spk_dim], one row per sentence.  wav_out fp32 [off_host[n] * prod(up_rates)]:
+ * samples [off_host[b] * up, (off_host[b] + lens_host[b]) * up) are the waveform of sentence b, the rest of its capacity is zero.  The
+ * matrix kernels see one item; a tap that leaves a sentence reads the zeros of a gap, which is the zero "same" padding the sentence
+ * sees alone, so every capacity must be at least lens_host[b] + itts_bigvgan_packed_gap(cfg) frames.  No GEMM splits K and every
+ * kernel family is picked without looking at the row count (short packs are extended by zero frames to the families' minimum rows):
+ * a sentence's samples are the same bits alone, with any companions, in any order and in any chunking.
+ * Refused with ITTS_E_INVALID before any HIP call (itts_bigvgan_packed_check is that judgement alone, engine-free, on host memory):
+ * null engine / pointers, n outside [1, 128], off_host[0] != 0, a length < 1, offsets not increasing, a capacity below
+ * len + gap ("gap too small"), more than 2^31 - 1 output samples.  off_host / lens_host are consumed before the call returns. */
+int itts_bigvgan_packed(itts_engine* e, const void* latent, const float* spk, const int32_t* off_host, const int32_t* lens_host, int n,
+                        float* wav_out, itts_stream stream);
+int itts_bigvgan_packed_check(const itts_config* cfg, const void* latent, const float* spk, const int32_t* off_host,
+                              const int32_t* lens_host, int n, const float* wav_out);
+/* The zero frames a packed sentence needs behind its signal: the largest reach of any convolution of the generator (conv_pre, every
+ * ups[i] at its input rate, every AMP conv (k * d - d) / 2 at its stage's rate, conv_post) in latent frames, rounded up. */
+int itts_bigvgan_packed_gap(const itts_config* cfg);
 
 /* Q1  DiscreteVAE.decode (vqvae/xtts_dvae.py:332-351): codes host int32 [B, T] -> mel [B, 4T, channels] engine dtype */
 int itts_dvae_decode(itts_engine* e, const int32_t* codes_host, int B, int T, void* mel_out, itts_stream stream);

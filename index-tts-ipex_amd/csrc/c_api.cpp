@@ -194,6 +194,93 @@ int itts_zero_tail_rows(void* x, int B, int T, int C, const int* lens_dev, int m
   return zero_tail_rows(x, B, T, C, lens_dev, mul, dtype, (hipStream_t)stream);
 }
 
+// ---- packed sentences: offsets and lengths are HOST arrays, so every entry judges the whole call before any HIP call ----
+static const char* seg_entry_refusal(SegTable& seg, const int* off_host, const int* lens_host, int n, int mul) {
+  if (!off_host || !lens_host) return "null pointer";
+  if (n < 1 || n > SEG_MAX) return "n outside [1, 128]";
+  (void)seg_table_fill(seg, off_host, lens_host, n);
+  return seg_table_refusal(seg, mul, 0);
+}
+
+int itts_snake_aa_fwd_seg(void* dst, const void* src, const float* up12, const float* down12, const float* log_alpha,
+                          const float* log_beta, int C, const int* off_host, const int* lens_host, int n, int mul, int dtype,
+                          itts_stream stream) {
+  SegTable seg;
+  const char* why = (!dst || !src || !up12 || !down12 || !log_alpha || !log_beta) ? "null pointer" : seg_entry_refusal(seg, off_host, lens_host, n, mul);
+  if (!why && C < 1) why = "C must be >= 1";
+  if (!why && dtype != F32 && dtype != BF16 && dtype != F16) why = "unsupported dtype";
+  if (why) {
+    set_error(std::string("itts_snake_aa_fwd_seg: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  return snake_aa_seg(dst, src, log_alpha, log_beta, up12, down12, C, seg, mul, dtype, (hipStream_t)stream);
+}
+
+int itts_act_conv_seg(const itts_gemm_args* a, const float* log_alpha, const float* log_beta, const float* filt12, const int* off_host,
+                      const int* lens_host, int n, int mul, itts_stream stream) {
+  SegTable seg;
+  GemmArgs g;
+  const char* why = !a ? "null args" : (!a->A || !a->W || !a->C || !log_alpha || !log_beta || !filt12) ? "null pointer" : nullptr;
+  if (!why && a->force_simple) why = "force_simple: the vector-ALU kernel has no fused activation";
+  if (!why && (a->dtype_a != BF16 || a->dtype_w != BF16 || a->dtype_c != BF16)) why = "dtype: A, W and C must be the 16-bit type of the library";
+  if (!why && a->lda != a->Cin) why = "lda != Cin: the fused form stages whole dense rows";
+  // one item: the kernel would step the bias by SENTENCE with a stride (per-sentence rows are itts_seg_bias_mask's business)
+  if (!why && a->bias && a->bias_bstride != 0) why = "bias_bstride != 0: the pack is one item, its bias is one row";
+  if (!why) {
+    to_gemm_args(a, g);
+    g.pre_alpha = log_alpha, g.pre_beta = log_beta, g.pre_filt = filt12;
+    if (gemm_which_pinned_conv(g, BF16, BF16, BF16) != 4) why = "shape: not the LDS-tiled narrow conv (itts_gemm_which_pinned_conv != 4)";
+    else if (!gemm_pinned_conv_fused(g, BF16, BF16, BF16)) why = "the fused activation is switched off (ITTS_NO_CONV_ACT)";
+  }
+  if (!why) why = seg_entry_refusal(seg, off_host, lens_host, n, mul);
+  if (!why && (a->M != a->T || (long)a->T < (long)seg.off[n] * mul)) why = "M == T >= off[n] * mul expected: one item that holds the whole pack";
+  if (why) {
+    set_error(std::string("itts_act_conv_seg: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  return gemm_pinned_conv(g, BF16, BF16, BF16, (hipStream_t)stream, &seg, mul);
+}
+
+int itts_seg_bias_mask(void* x, const float* bias, int C, const int* off_host, const int* lens_host, int n, int mul, int dtype,
+                       itts_stream stream) {
+  SegTable seg;
+  const char* why = !x ? "null pointer" : seg_entry_refusal(seg, off_host, lens_host, n, mul);
+  if (!why && C < 1) why = "C must be >= 1";
+  if (!why && dtype != F32 && dtype != BF16) why = "unsupported dtype";
+  if (!why) {
+    long cap = 0;
+    for (int b = 0; b < n; ++b) cap = std::max<long>(cap, seg.off[b + 1] - seg.off[b]);
+    if (cap * mul * C > 0x7fffffffL) why = "a sentence of more than 2^31 - 1 elements";
+  }
+  if (why) {
+    set_error(std::string("itts_seg_bias_mask: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  return seg_bias_mask(x, bias, C, seg, mul, dtype, (hipStream_t)stream);
+}
+
+int itts_gemm_which_pinned_conv(const itts_gemm_args* a) {
+  if (!a) return E_INVALID;
+  GemmArgs g;
+  to_gemm_args(a, g);
+  return a->force_simple ? 0 : gemm_which_pinned_conv(g, a->dtype_a, a->dtype_w, a->dtype_c);
+}
+
+int itts_bigvgan_packed_gap(const itts_config* cfg) { return cfg ? bigvgan_packed_gap(*cfg) : E_INVALID; }
+
+int itts_bigvgan_packed_check(const itts_config* cfg, const void* latent, const float* spk, const int32_t* off_host,
+                              const int32_t* lens_host, int n, const float* wav_out) {
+  const char* why = !cfg ? "null config" : bigvgan_packed_refusal(*cfg, latent, spk, off_host, lens_host, n, wav_out);
+  if (why) {
+    set_error(std::string("itts_bigvgan_packed: ") + why);
+    return E_INVALID;
+  }
+  return OK;
+}
+
 int itts_act_conv_supported(const itts_gemm_args* a) {
   static const float dummy = 0.f;  // a real call has its three parameter vectors; the rule only asks whether they are there
   return act_conv_refusal(a, &dummy, &dummy, &dummy) ? 0 : 1;
@@ -1086,6 +1173,16 @@ int itts_bigvgan_ragged(itts_engine* e, const void* latent, const float* spk, in
   }
   (void)hipGetLastError();
   return e->e.bigvgan(latent, spk, B, T, wav_out, (hipStream_t)s, lens_host);
+}
+int itts_bigvgan_packed(itts_engine* e, const void* latent, const float* spk, const int32_t* off_host, const int32_t* lens_host, int n,
+                        float* wav_out, itts_stream s) {
+  if (!e) {
+    set_error("itts_bigvgan_packed: null engine");
+    return E_INVALID;
+  }
+  if (int st = itts_bigvgan_packed_check(&e->e.cfg, latent, spk, off_host, lens_host, n, wav_out)) return st;  // before any HIP call
+  (void)hipGetLastError();
+  return e->e.bigvgan_packed(latent, spk, off_host, lens_host, n, wav_out, (hipStream_t)s);
 }
 int itts_dvae_decode(itts_engine* e, const int32_t* codes_host, int B, int T, void* mel_out, itts_stream s) {
   ENG(e);

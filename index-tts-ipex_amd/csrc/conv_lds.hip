@@ -22,7 +22,9 @@
 // every lane slides down one channel (itts_snake_dev.h: the stand-alone kernel's loop, same operations) and writes the bf16
 // result straight into the MFMA planes.  The stand-alone pass read and wrote the whole tensor once more per convolution: on these
 // stages (HBM-bound convolutions, VALU-bound activation) that was 4 of the 10 tensor passes of an AMP iteration.
+#include <algorithm>
 #include <cstdlib>
+#include <string>
 
 #include "itts_kernels.h"
 #include "itts_snake_dev.h"
@@ -41,18 +43,27 @@ __device__ __forceinline__ int swz4(int row) { return (row >> 1) & 2; }
 #define ITTS_CONV_RAG 1  // conv_lds_rag_kernel: the fused-activation form over a padded ragged batch
 #include "conv_lds_kernel_text.h"
 #undef ITTS_CONV_RAG
+#define ITTS_CONV_RAG 2  // conv_lds_seg_kernel: the fused-activation form over packed sentences
+#include "conv_lds_kernel_text.h"
+#undef ITTS_CONV_RAG
 
 // LDS bytes per activation row over all planes (bf16 elements): channels rounded up to whole 32-channel k-steps
 inline int row_pitch(int C) { return (C + 31) / 32 * 32; }
+
+// dynamic LDS of one workgroup: planes + (staged weights | raw tile), or the fp32 epilogue tile
+template <int BM, int NP, bool ACT>
+size_t lds_bytes(const GemmArgs& g, int HR, int CP) {
+  const size_t lds_w = (size_t)2 * NP * WROW * 2, lds_raw = ACT ? (size_t)(HR + 12) * g.Cin * 2 : 0;
+  const size_t lds_main = (size_t)HR * CP * 2 + (lds_w > lds_raw ? lds_w : lds_raw);
+  const size_t lds_epi = (size_t)BM * (NP + 4) * 4;
+  return lds_main > lds_epi ? lds_main : lds_epi;
+}
 
 template <int MT, int NT, int WAVES_M, int WAVES_N, bool ACT>
 int launch(const GemmArgs& g, hipStream_t s, const int* lens = nullptr, int mul = 1) {
   constexpr int BM = WAVES_M * MT * 16, NP = WAVES_N * NT * 16;
   const int HR = BM + (g.taps - 1) * g.dil, CP = row_pitch(g.Cin);
-  const size_t lds_w = (size_t)2 * NP * WROW * 2, lds_raw = ACT ? (size_t)(HR + 12) * g.Cin * 2 : 0;
-  const size_t lds_main = (size_t)HR * CP * 2 + (lds_w > lds_raw ? lds_w : lds_raw);
-  const size_t lds_epi = (size_t)BM * (NP + 4) * 4;
-  const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
+  const size_t lds = lds_bytes<BM, NP, ACT>(g, HR, CP);
   const int B = g.M / g.T, tiles = (g.T + BM - 1) / BM;
   if constexpr (ACT) {
     if (lens) {
@@ -70,7 +81,31 @@ int launch(const GemmArgs& g, hipStream_t s, const int* lens = nullptr, int mul 
   return OK;
 }
 
+// the segment form: grid (tiles of the longest capacity, sentences)
+template <int MT, int NT, int WAVES_M, int WAVES_N>
+int launch_seg(const GemmArgs& g, hipStream_t s, const SegTable& seg, int mul) {
+  constexpr int BM = WAVES_M * MT * 16, NP = WAVES_N * NT * 16;
+  const int HR = BM + (g.taps - 1) * g.dil, CP = row_pitch(g.Cin);
+  const size_t lds = lds_bytes<BM, NP, true>(g, HR, CP);
+  int cap = 0;
+  for (int b = 0; b < seg.n; ++b) cap = std::max(cap, seg.off[b + 1] - seg.off[b]);
+  const int tiles = (int)(((long)cap * mul + BM - 1) / BM);
+  static DynLdsLatch latch;
+  ITTS_TRY(allow_dynamic_lds(latch, (const void*)conv_lds_seg_kernel<MT, NT, WAVES_M, WAVES_N, true>, 160 * 1024));
+  hipLaunchKernelGGL((conv_lds_seg_kernel<MT, NT, WAVES_M, WAVES_N, true>), dim3(tiles, seg.n), dim3(256), lds, s, g, tiles, HR, CP, seg, mul);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
 }  // namespace
+
+// conv_lds_supported apart from the row count: what the pinned selector of the packed vocoder asks (a sentence alone and the same
+// sentence in a pack of 64 take one family; the pass pads the pack to the kernel's 256 rows where it has to)
+bool conv_lds_shape_supported(const GemmArgs& g, int ta, int tw, int tc) {
+  GemmArgs q = g;
+  q.M = q.T = 256;
+  return conv_lds_supported(q, ta, tw, tc);
+}
 
 bool conv_lds_supported(const GemmArgs& g, int ta, int tw, int tc) {
   if (ta != BF16 || tw != BF16 || tc != BF16) return false;
@@ -106,6 +141,22 @@ int conv_lds(const GemmArgs& g, hipStream_t s, const int* lens, int mul) {
   if (g.N <= 32) return launch<4, 2, 4, 1, false>(g, s);
   if (g.N <= 48) return launch<4, 3, 4, 1, false>(g, s);
   return launch<4, 3, 2, 2, false>(g, s);
+}
+
+// The fused activation + convolution over packed sentences (conv_lds_seg_kernel): g.M = g.T = the rows of the pack (off[n] * mul),
+// sentence b the rows [off[b] * mul, off[b + 1] * mul) of A, C, R and ADD.  Any row count: the 256-row rule of conv_lds_supported is
+// about where the family pays, the kernel tiles a sentence of one row as well.
+int conv_lds_seg(const GemmArgs& g, hipStream_t s, const SegTable& seg, int mul) {
+  ITTS_REQUIRE(g.A && g.W && g.C, "conv_lds_seg: null pointer");
+  const char* why = seg_table_refusal(seg, mul, 0);
+  ITTS_REQUIRE(!why, (std::string("conv_lds_seg: ") + why).c_str());
+  ITTS_REQUIRE(g.pre_alpha && g.pre_beta && g.pre_filt && g.lda == g.Cin && conv_lds_shape_supported(g, BF16, BF16, BF16),
+               "conv_lds_seg: not a fused-activation shape of the LDS-tiled narrow conv");
+  ITTS_REQUIRE(g.M == g.T && (long)g.T >= (long)seg.off[seg.n] * mul, "conv_lds_seg: the pack is longer than the operands");
+  ITTS_REQUIRE(!g.bias || g.bias_bstride == 0, "conv_lds_seg: one item, one bias row (bias_bstride == 0)");
+  if (g.N <= 32) return launch_seg<4, 2, 4, 1>(g, s, seg, mul);
+  if (g.N <= 48) return launch_seg<2, 3, 4, 1>(g, s, seg, mul);
+  return launch_seg<4, 3, 2, 2>(g, s, seg, mul);
 }
 
 }  // namespace itts

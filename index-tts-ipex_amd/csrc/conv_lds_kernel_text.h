@@ -1,18 +1,29 @@
-// The text of conv_lds_kernel (conv_lds.hip), compiled twice (no include guard):
+// The text of conv_lds_kernel (conv_lds.hip), compiled three times (no include guard):
 //   ITTS_CONV_RAG 0   conv_lds_kernel       every item is a signal of g.T rows
 //   ITTS_CONV_RAG 1   conv_lds_rag_kernel   (ACT only) padded ragged batch: item b is the signal of its first Tv = lens[b] * mul rows inside
 //                     the g.T-row buffer.  Tv stands for T in exactly the four places that mean "signal length" - the replicate clamp
 //                     of the raw-row load, the two zero-fill loops and snake_run; the item stride and the epilogue keep g.T (rows behind
 //                     Tv are computed from zero-padded input and stored like any other).  lens / mul are kernel parameters of this form
 //                     only: GemmArgs, a by-value argument of every GEMM kernel, does not grow.
+//   ITTS_CONV_RAG 2   conv_lds_seg_kernel   (ACT only) packed sentences, one grid row (blockIdx.y) per sentence: sentence b owns rows
+//                     [off[b] * mul, off[b + 1] * mul) of every operand - that capacity stands for T in the item base, the tile bound and
+//                     the epilogue - and its signal is the first Tv = len[b] * mul of them.  Halo rows with t < 0 or t >= Tv are zero
+//                     as in form 1 (the zero "same" padding the sentence would see alone); no output row outside the capacity is stored
+//                     and a tile behind the capacity leaves before the first barrier.  The table is a by-value parameter of this form.
 // One text, so the two forms cannot drift apart; a second inclusion instead of a template flag, so that the symbols, arguments and
 // instructions of the plain kernels stay exactly what they were.
-#if ITTS_CONV_RAG
+#if ITTS_CONV_RAG == 2
+#define CONV_LDS_KERNEL conv_lds_seg_kernel
+#define CONV_LDS_RAG_PARAMS , SegTable seg, int mul
+#define CONV_LDS_ITEM_ROW0(b, T) ((size_t)seg.off[b] * mul)  // first row of sentence b
+#elif ITTS_CONV_RAG
 #define CONV_LDS_KERNEL conv_lds_rag_kernel
 #define CONV_LDS_RAG_PARAMS , const int* __restrict__ lens, int mul
+#define CONV_LDS_ITEM_ROW0(b, T) (size_t)b * T
 #else
 #define CONV_LDS_KERNEL conv_lds_kernel
 #define CONV_LDS_RAG_PARAMS
+#define CONV_LDS_ITEM_ROW0(b, T) (size_t)b * T
 #endif
 
 // MT x NT 16x16 tiles per wave, WAVES_M x WAVES_N waves (= 4)
@@ -31,9 +42,15 @@ __global__ __launch_bounds__(256) void CONV_LDS_KERNEL(GemmArgs g, int tiles_per
   float* sC = reinterpret_cast<float*>(smem);                                // epilogue: [BM][NP + 4]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+#if ITTS_CONV_RAG == 2
+  const int b = blockIdx.y, t0 = blockIdx.x * BM;  // grid (tiles of the longest capacity, sentences)
+  const int T = (seg.off[b + 1] - seg.off[b]) * mul, C = g.Cin, K = g.taps * C;  // T: rows of the sentence's capacity
+  if (t0 >= T) return;  // (workgroup-uniform, before the first barrier)
+#else
   const int b = blockIdx.x / tiles_per_item, t0 = (blockIdx.x - b * tiles_per_item) * BM;
   const int T = g.T, C = g.Cin, K = g.taps * C;
-  const bf16_t* __restrict__ A = (const bf16_t*)g.A + (size_t)b * T * g.lda;
+#endif
+  const bf16_t* __restrict__ A = (const bf16_t*)g.A + CONV_LDS_ITEM_ROW0(b, T) * g.lda;
   const bf16_t* __restrict__ W = (const bf16_t*)g.W;
 
   // ---- resident input tile: rows t0 - pad_left + i, zero outside [0, T); pad columns zero ----
@@ -54,7 +71,10 @@ __global__ __launch_bounds__(256) void CONV_LDS_KERNEL(GemmArgs g, int tiles_per
     }
   } else {
     const int tlo = t0 - g.pad_left;  // time of plane row 0
-#if ITTS_CONV_RAG
+#if ITTS_CONV_RAG == 2
+    const long lv = (long)seg.len[b] * mul;
+    const int Tv = lv < 1 ? 1 : (lv > T ? T : (int)lv);  // signal length of this sentence
+#elif ITTS_CONV_RAG
     const long lv = (long)lens[b] * mul;
     const int Tv = lv < 1 ? 1 : (lv > T ? T : (int)lv);  // signal length of this item (device lengths are clamped to [1, T])
 #else
@@ -198,9 +218,9 @@ __global__ __launch_bounds__(256) void CONV_LDS_KERNEL(GemmArgs g, int tiles_per
       for (int r = 0; r < 4; ++r) sC[(size_t)(wm * MT * 16 + i * 16 + cr + r) * CS + wn * NT * 16 + j * 16 + cc] = acc[i][j][r];
   __syncthreads();
   const int nv = g.N >> 3;  // 8-column vectors per row
-  bf16_t* __restrict__ Cc = (bf16_t*)g.C + (size_t)b * T * g.ldc;
-  const bf16_t* __restrict__ R = g.R ? (const bf16_t*)g.R + (size_t)b * T * g.ldr : nullptr;
-  const bf16_t* __restrict__ ADD = g.ADD ? (const bf16_t*)g.ADD + (size_t)b * T * g.ldadd : nullptr;
+  bf16_t* __restrict__ Cc = (bf16_t*)g.C + CONV_LDS_ITEM_ROW0(b, T) * g.ldc;
+  const bf16_t* __restrict__ R = g.R ? (const bf16_t*)g.R + CONV_LDS_ITEM_ROW0(b, T) * g.ldr : nullptr;
+  const bf16_t* __restrict__ ADD = g.ADD ? (const bf16_t*)g.ADD + CONV_LDS_ITEM_ROW0(b, T) * g.ldadd : nullptr;
   const float* bias = g.bias ? g.bias + (size_t)b * g.bias_bstride : nullptr;
   const bool plain = g.act == ACT_NONE && g.act2 == ACT_NONE && !g.scale && !g.shift && (!bias || ((uintptr_t)bias & 15) == 0);
   const int dm = 256 / nv, dq2 = 256 - dm * nv;
@@ -261,3 +281,4 @@ __global__ __launch_bounds__(256) void CONV_LDS_KERNEL(GemmArgs g, int tiles_per
 
 #undef CONV_LDS_KERNEL
 #undef CONV_LDS_RAG_PARAMS
+#undef CONV_LDS_ITEM_ROW0

@@ -526,4 +526,62 @@ int zero_tail_rows(void* x, int B, int T_, int C, const int* lens, int mul, int 
   CHECK_LAUNCH();
 }
 
+// ---- packed sentences: the speaker bias of each sentence and the zeros of its gap in one pass ---------------------------------------
+// x [off[n] * mul, C]: sentence b (blockIdx.y) owns rows [off[b] * mul, off[b + 1] * mul); its first len[b] * mul rows get bias[b][:]
+// added (fp32 sum, rounded once to T; bias null = they are neither read nor written), the rest of its capacity becomes zeros - what
+// bias_bstride and zero_tail_rows do for a batch, for ONE item whose sentences lie back to back.  VEC elements per lane: a 16-byte
+// unit where a row is a whole number of them, else one element (4 or 2 bytes).  Plain vector loads and stores, no LDS.
+namespace {
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void seg_bias_mask_kernel(T* __restrict__ x, const float* __restrict__ bias, int C, SegTable seg, int mul) {
+  const int b = blockIdx.y;
+  const unsigned upr = (unsigned)(C / VEC);  // units per row
+  const unsigned cap = (unsigned)(seg.off[b + 1] - seg.off[b]) * mul;
+  const long lv = (long)seg.len[b] * mul;
+  const unsigned sig = lv < 0 ? 0u : (lv > (long)cap ? cap : (unsigned)lv);
+  T* __restrict__ xb = x + (size_t)seg.off[b] * mul * C;
+  const float* __restrict__ bb = bias ? bias + (size_t)b * C : nullptr;
+  const unsigned n = cap * upr;  // (the launcher has checked that a sentence's units fit 31 bits)
+  for (unsigned i = (bias ? 0u : sig * upr) + blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+    const unsigned r = i / upr, q = i - r * upr;
+    T* p = xb + (size_t)i * VEC;
+    if constexpr (VEC == 1) {
+      if (r >= sig) stf(p, 0.f);
+      else stf(p, ldf(p) + bb[q]);
+    } else {
+      u32x4 v = u32x4{0u, 0u, 0u, 0u};
+      if (r < sig) {
+        v = *reinterpret_cast<const u32x4*>(p);
+        T* e = reinterpret_cast<T*>(&v);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) stf(e + k, ldf(e + k) + bb[q * VEC + k]);
+      }
+      *reinterpret_cast<u32x4*>(p) = v;
+    }
+  }
+}
+}  // namespace
+
+int seg_bias_mask(void* x, const float* bias, int C, const SegTable& seg, int mul, int dt, hipStream_t s) {
+  ITTS_REQUIRE(x, "seg_bias_mask: null pointer");
+  const char* why = seg_table_refusal(seg, mul, 0);
+  ITTS_REQUIRE(!why, (std::string("seg_bias_mask: ") + why).c_str());
+  ITTS_REQUIRE(C > 0, "seg_bias_mask: bad dims");
+  ITTS_REQUIRE(dt == F32 || dt == BF16, "seg_bias_mask: dtype");
+  long cap = 0;
+  for (int b = 0; b < seg.n; ++b) cap = std::max<long>(cap, seg.off[b + 1] - seg.off[b]);
+  ITTS_REQUIRE(cap * mul * C <= 0x7fffffffL, "seg_bias_mask: a sentence of more than 2^31 - 1 elements");
+  const int vec = dt == F32 ? 4 : 8;
+  if (C % vec == 0 && !((uintptr_t)x & 15)) {
+    const dim3 grid((unsigned)std::min<long>(nblk(cap * mul * (C / vec)), 65535), seg.n);
+    if (dt == F32) hipLaunchKernelGGL((seg_bias_mask_kernel<float, 4>), grid, dim3(256), 0, s, (float*)x, bias, C, seg, mul);
+    else hipLaunchKernelGGL((seg_bias_mask_kernel<bf16_t, 8>), grid, dim3(256), 0, s, (bf16_t*)x, bias, C, seg, mul);
+  } else {
+    const dim3 grid((unsigned)std::min<long>(nblk(cap * mul * C), 65535), seg.n);
+    if (dt == F32) hipLaunchKernelGGL((seg_bias_mask_kernel<float, 1>), grid, dim3(256), 0, s, (float*)x, bias, C, seg, mul);
+    else hipLaunchKernelGGL((seg_bias_mask_kernel<bf16_t, 1>), grid, dim3(256), 0, s, (bf16_t*)x, bias, C, seg, mul);
+  }
+  CHECK_LAUNCH();
+}
+
 }  // namespace itts

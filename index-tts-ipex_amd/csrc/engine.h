@@ -245,6 +245,10 @@ struct DecodeState {
   bool active = false;
 };
 
+int bigvgan_packed_gap(const itts_config& c);  // zero frames a packed sentence needs behind its signal: the convolutions' largest reach
+const char* bigvgan_packed_refusal(const itts_config& c, const void* latent, const float* spk, const int* off_host, const int* lens_host,
+                                   int n, const float* wav);  // null = the call can run; host memory only
+
 struct Engine {
   itts_config cfg;
   int adt = 0;  // activation / weight dtype
@@ -294,6 +298,14 @@ struct Engine {
     explicit PackedPass(Engine& en) : e(en) { e.ksplit_off = e.gemm_pin = true; }
     ~PackedPass() { e.ksplit_off = e.gemm_pin = false; }
   };
+  // The packed vocoder (bigvgan_packed) likewise: no K split, and every convolution through gemm_pinned_conv (conv_pin) - the narrow
+  // conv where the shape apart from its row count is one of its own, else gemm_which_pinned's order; never gemm_glds.
+  bool conv_pin = false;
+  struct PackedVocoderPass {
+    Engine& e;
+    explicit PackedVocoderPass(Engine& en) : e(en) { e.ksplit_off = e.conv_pin = true; }
+    ~PackedVocoderPass() { e.ksplit_off = e.conv_pin = false; }
+  };
   // raw partial sums of K-split GEMMs (Engine::conv): [split][M][N] fp32, allocated at the first split launch
   static constexpr size_t KSPLIT_WS_BYTES = size_t(64) << 20;
   float* ksplit_ws = nullptr;
@@ -313,6 +325,8 @@ struct Engine {
   int lin(void* C, int tc, const void* A, int ta, int lda, const Lin& w, int M, int ldc, hipStream_t s, int act = ACT_NONE,
           const void* R = nullptr, int ldr = 0, float alpha = 1.f);
   int conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* lens = nullptr, int mul = 1);  // lens / mul: gemm()
+  // a fused-activation call (g.pre_*) of the packed vocoder: the segment form of the narrow conv or nothing (gemm_pinned_conv)
+  int conv_seg(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const SegTable& seg, int mul);
   int ln(void* y, int ty, const void* x, int tx, const Norm& n, int rows, int D, hipStream_t s, int act = ACT_NONE,
          float eps = 1e-5f);
 
@@ -396,6 +410,11 @@ struct Engine {
   // lens_host (optional, [B], each in [1, T]): a padded ragged batch - item b is a latent of lens_host[b] frames, whatever its rows
   // behind them hold; its waveform is that of the item alone, zeros from sample lens_host[b] * up on
   int bigvgan(const void* latent, const float* spk, int B, int T, float* wav, hipStream_t s, const int* lens_host = nullptr);
+  // The sentences of a call back to back as ONE item (opt-in): latent [off_host[n], D], sentence b the frames
+  // [off_host[b], off_host[b + 1]) of which the first lens_host[b] are signal and at least bigvgan_packed_gap(cfg) are left over;
+  // spk fp32 [n, E]; wav fp32 [off_host[n] * up], zeros in every gap.  A sentence's samples do not depend on its companions, their
+  // order or the chunking.  n <= SEG_MAX; every refusal (bigvgan_packed_refusal) is made on the host before any HIP call.
+  int bigvgan_packed(const void* latent, const float* spk, const int* off_host, const int* lens_host, int n, float* wav, hipStream_t s);
   int dvae_decode(const int32_t* codes, int B, int T, void* mel_out, hipStream_t s);
   int dvae_encode(const void* mel, int B, int T, int32_t* codes_host, hipStream_t s);
 

@@ -102,6 +102,10 @@ int Engine::conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* 
     ITTS_REQUIRE(!lens, "conv: per-item lengths in a packed pass");
     return gemm_pinned(g, ta, tw, tc, s);
   }
+  if (conv_pin) {  // the packed vocoder: the same promise for convolutions (gemm_select.cpp gemm_which_pinned_conv)
+    ITTS_REQUIRE(!lens, "conv: per-item lengths in a packed pass");
+    return gemm_pinned_conv(g, ta, tw, tc, s);
+  }
   // few-tile deep-K shapes split K over workgroups (this engine's own fp32 workspace: engines on other streams have theirs)
   const int S = ksplit_off ? 1 : gemm_ksplit_plan(g, ta, tw, tc, KSPLIT_WS_BYTES);
   if (S > 1) {
@@ -117,6 +121,12 @@ int Engine::conv(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* 
     g.ksplit = S;
   }
   return gemm(g, ta, tw, tc, s, lens, mul);
+}
+
+int Engine::conv_seg(GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const SegTable& seg, int mul) {
+  if (dry) return OK;
+  ITTS_REQUIRE(conv_pin && !force_simple, "conv_seg: outside a packed vocoder pass");
+  return gemm_pinned_conv(g, ta, tw, tc, s, &seg, mul);
 }
 
 int Engine::ln(void* y, int ty, const void* x, int tx, const Norm& n, int rows, int D, hipStream_t s, int act, float eps) {

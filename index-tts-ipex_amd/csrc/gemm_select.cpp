@@ -114,6 +114,36 @@ int gemm_pinned(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s) {
   }
 }
 
+// The pinned selector of the packed vocoder's convolutions (Engine::bigvgan_packed): as above, with the LDS-tiled narrow conv in front
+// where the shape - apart from its row count - is one of its own.  The pass pads a short pack to that kernel's 256 rows, so a one-frame
+// sentence alone takes the family it takes inside a pack of 64.  gemm_glds is never an answer: its gate is a tile count.
+int gemm_which_pinned_conv(const GemmArgs& g, int ta, int tw, int tc) {
+  const Switches sw;
+  if (sw.conv_lds && conv_lds_shape_supported(g, ta, tw, tc)) return 4;
+  return gemm_which_pinned(g, ta, tw, tc);
+}
+
+bool gemm_pinned_conv_fused(const GemmArgs& g, int ta, int tw, int tc) {
+  const bool off = getenv("ITTS_NO_CONV_ACT") != nullptr;
+  return !off && g.pre_alpha && g.pre_beta && g.pre_filt && g.lda == g.Cin && gemm_which_pinned_conv(g, ta, tw, tc) == 4;
+}
+
+// seg / mul: the sentences of a fused-activation call (g.pre_*), which only family 4 runs - in its segment form
+int gemm_pinned_conv(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const SegTable* seg, int mul) {
+  ITTS_REQUIRE(g.ksplit == 1, "gemm_pinned_conv: no K split");
+  const bool pre = g.pre_alpha || g.pre_beta || g.pre_filt;
+  ITTS_REQUIRE(!pre || (seg && gemm_pinned_conv_fused(g, ta, tw, tc)),
+               "gemm_pinned_conv: pre_alpha / pre_beta / pre_filt set on a call that does not run the fused segment kernel");
+  ITTS_REQUIRE(pre || !seg, "gemm_pinned_conv: a segment table on a call without the fused activation");
+  if (pre) return conv_lds_seg(g, s, *seg, mul);
+  switch (gemm_which_pinned_conv(g, ta, tw, tc)) {
+    case 4: return conv_lds(g, s);  // (plain form on the whole pack: its own 256-row rule applies, the pass has padded for it)
+    case 3: return gemm_p8(g, ta, tw, tc, s);
+    case 1: return gemm_mfma(g, ta, tw, tc, s);
+    default: return gemm_simple(g, ta, tw, tc, s);
+  }
+}
+
 // ---- one family by name (itts_gemm_family: the operator tests run each kernel at the smallest shapes that reach its paths, far below
 //      the performance gates of gemm_which).  The refusal repeats, in words, every condition of that family's launcher, so that the
 //      entry answers on the host before any HIP call; the launchers keep their own ITTS_REQUIREs behind it. ----

@@ -6,6 +6,21 @@
 
 namespace itts {
 
+// ---- packed sentences (the packed vocoder): one item whose sentences lie back to back in time ----
+// Sentence b owns frames [off[b], off[b + 1]) - its capacity - of which the first len[b] are signal and the rest zeros; a tensor at
+// up-sampling mul holds mul rows per frame.  The table travels BY VALUE in the argument block of every segment kernel (host-checked,
+// no upload: nothing of the caller's outlives the call).
+constexpr int SEG_MAX = 128;
+struct SegTable {
+  int n = 0;
+  int off[SEG_MAX + 1] = {0};
+  int len[SEG_MAX] = {0};
+};
+// why a table cannot run (null = it can), no HIP call: n in [1, SEG_MAX], mul >= 1, off[0] >= 0, every len >= 1, offsets increasing,
+// every capacity >= len + gap, off[n] * mul below 2^31
+const char* seg_table_refusal(const SegTable& seg, int mul, int gap);
+int seg_table_fill(SegTable& seg, const int* off_host, const int* lens_host, int n);
+
 // ---- GEMM / conv family (gemm_simple.hip, gemm_mfma.hip, gemm_glds.hip, gemm_p8.hip, conv_lds.hip; selector: gemm_select.cpp) ----
 int gemm_simple(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
 bool gemm_operands_ok(const GemmArgs& g, int ta, int tw, int tc);  // the operand gate of the three matrix-core GEMMs: half A / W, half or fp32 C, lda % 8, 16-byte aligned
@@ -28,6 +43,9 @@ bool conv_lds_act_supported(const GemmArgs& g, int ta, int tw, int tc);  // ... 
 // lens / mul (ragged batches, next to the args so that GemmArgs - a by-value argument of every GEMM kernel - does not grow): item b of
 // a fused-activation call is the signal of its first lens[b] * mul rows (device ints, one per batch item); null = all T rows
 int conv_lds(const GemmArgs& g, hipStream_t s, const int* lens = nullptr, int mul = 1);
+bool conv_lds_shape_supported(const GemmArgs& g, int ta, int tw, int tc);  // conv_lds_supported apart from the row count
+// the fused activation + conv over packed sentences (conv_lds_seg_kernel): g.M = g.T >= off[n] * mul rows, any row count
+int conv_lds_seg(const GemmArgs& g, hipStream_t s, const SegTable& seg, int mul);
 int gemm(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const int* lens = nullptr, int mul = 1);  // dispatcher
 int gemm_which(const GemmArgs& g, int ta, int tw, int tc);           // the kernel family the dispatcher takes: 0 VALU, 1 mfma, 2 glds, 3 p8, 4 conv_lds
 // One family (0 - 3) by name, whatever the selector would take: why it cannot run the call (null = it can; no HIP call), and the
@@ -38,6 +56,12 @@ bool gemm_act_fused(const GemmArgs& g, int ta, int tw, int tc);      // a call w
 // The packed latent pass's selector: the family by operand types, N, K and alignment, never by M (1, 3 or 0); no K split
 int gemm_which_pinned(const GemmArgs& g, int ta, int tw, int tc);
 int gemm_pinned(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s);
+// The packed vocoder's selector for convolutions: 4 where conv_lds_shape_supported holds (the shape apart from its row count), then
+// gemm_which_pinned's order (3, 1, 0); never gemm_glds, never by M or T.  A family-4 answer for a call with g.pre_* means the
+// fused segment form (gemm_pinned_conv_fused: also conv_lds_act's own rule), else the caller activates first.
+int gemm_which_pinned_conv(const GemmArgs& g, int ta, int tw, int tc);
+bool gemm_pinned_conv_fused(const GemmArgs& g, int ta, int tw, int tc);
+int gemm_pinned_conv(const GemmArgs& g, int ta, int tw, int tc, hipStream_t s, const SegTable* seg = nullptr, int mul = 1);
 
 // ---- anti-aliased SnakeBeta (snake.hip); x,y [B,T,C] ----
 int snake_aa(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12,
@@ -46,6 +70,10 @@ int snake_aa(void* y, const void* x, const float* log_alpha, const float* log_be
 // end), the rows behind it are written as zeros; lens: device ints [B]
 int snake_aa_len(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12, const float* down12,
                  int B, int T, int C, const int* lens, int mul, int dt, hipStream_t s);
+// ... over packed sentences: sentence b is rows [off[b] * mul, off[b + 1] * mul) of x / y, its signal the first len[b] * mul of them;
+// the rest of its capacity is written as zeros, rows outside the pack are not touched
+int snake_aa_seg(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12, const float* down12,
+                 int C, const SegTable& seg, int mul, int dt, hipStream_t s);
 // same op on the reference's [B,C,T] layout (drop-in for anti_alias_activation_cuda.forward)
 int snake_aa_bct(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12,
                  const float* down12, int B, int C, int T, int dt, hipStream_t s);
@@ -76,6 +104,9 @@ int relpos_pack(void* qc, void* kc, const void* qkv, const void* p, const float*
 int tanh_rows(void* y, const void* x, long n, int dt, hipStream_t s);
 // x [B, T, C]: rows [lens[b] * mul, T) of item b become zeros (the padding of a ragged batch and nothing else is written)
 int zero_tail_rows(void* x, int B, int T, int C, const int* lens, int mul, int dt, hipStream_t s);
+// x [off[n] * mul, C] over packed sentences: the signal rows of sentence b get bias[b][:] (fp32 [n, C]; null = left alone) added, the
+// rest of its capacity becomes zeros; rows outside the pack are not touched
+int seg_bias_mask(void* x, const float* bias, int C, const SegTable& seg, int mul, int dt, hipStream_t s);
 
 // ---- the DVAE encoder's small kernels (model_vocoder.hip) ----
 // y[B][(Tin + 1) / 2][2 C] = x[B][2t][:] | x[B][2t + 1][:], zero past Tin (the row pairs of a stride-2 convolution)

@@ -363,6 +363,194 @@ int Engine::bigvgan(const void* latent_in, const float* spk, int B, int T, float
 }
 
 // ------------------------------------------------------------------------------------------------
+// BigVGAN generator over PACKED sentences (opt-in)
+// ------------------------------------------------------------------------------------------------
+// The zero frames a sentence needs behind its signal: the largest reach of any convolution of the generator, in latent frames,
+// rounded up.  A tap that leaves a sentence then reads zeros of its own gap (or of its predecessor's) - the zero "same" padding the
+// sentence sees alone.  Activation1d reads no gap: its replicate clamp ends at the sentence's own last row.
+int bigvgan_packed_gap(const itts_config& c) {
+  auto frames = [](long rows, long U) { return (int)((rows + U - 1) / U); };
+  int gap = 3;  // conv_pre: k = 7, pad 3 at the latent rate
+  long U = 1;
+  for (int i = 0; i < c.bv_num_up; ++i) {
+    const int u = c.bv_up_rates[i], k = c.bv_up_kernels[i], p = (k - u) / 2, taps = k / u;
+    // ups[i] at its INPUT rate: out[q * u + ph] reads x[q + (ph + p) / u - m], m = 0 .. taps - 1
+    gap = std::max(gap, frames(std::max((u - 1 + p) / u, taps - 1 - p / u), U));
+    U *= u;
+    for (int j = 0; j < c.bv_num_res; ++j)
+      for (int l = 0; l < c.bv_num_dil; ++l) {
+        const int ks = c.bv_res_kernels[j], d = c.bv_res_dils[j][l];
+        gap = std::max(gap, frames(std::max((ks * d - d) / 2, (ks - 1) / 2), U));  // AMP convs c1 (dilated) and c2
+      }
+  }
+  return std::max(gap, frames(3, U));  // conv_post: k = 7, pad 3 at the output rate
+}
+
+// why a packed call cannot run (null = it can): every question is answered on host memory, before any HIP call
+const char* bigvgan_packed_refusal(const itts_config& c, const void* latent, const float* spk, const int* off_host, const int* lens_host,
+                                   int n, const float* wav) {
+  if (!latent || !spk || !off_host || !lens_host || !wav) return "null pointer";
+  if (n < 1 || n > SEG_MAX) return "n outside [1, 128]";
+  if (off_host[0] != 0) return "off[0] != 0";
+  long up = 1;
+  for (int i = 0; i < c.bv_num_up; ++i) up *= c.bv_up_rates[i];
+  const int gap = bigvgan_packed_gap(c);
+  for (int b = 0; b < n; ++b) {
+    if (lens_host[b] < 1) return "a length < 1";
+    if (off_host[b + 1] <= off_host[b]) return "offsets not increasing";
+    if ((long)off_host[b + 1] - off_host[b] < (long)lens_host[b] + gap) return "gap too small: a capacity below len + the convolutions' reach";
+  }
+  if (((long)off_host[n] + 256) * up > 0x7fffffffL) return "the pack has more than 2^31 - 1 output samples";
+  return nullptr;
+}
+
+int Engine::bigvgan_packed(const void* latent_in, const float* spk, const int* off_host, const int* lens_host, int n, float* wav,
+                           hipStream_t s) {
+  if (!finalized || !bv.ok) {
+    set_error("bigvgan_packed: generator weights not bound");
+    return E_STATE;
+  }
+  const itts_config& c = cfg;
+  if (const char* why = bigvgan_packed_refusal(c, latent_in, spk, off_host, lens_host, n, wav)) {
+    set_error(std::string("bigvgan_packed: ") + why);
+    return E_INVALID;
+  }
+  const int C0 = c.bv_init_ch, E = c.bv_spk_dim, nk = c.bv_num_res, nd = c.bv_num_dil;
+  const int Ttot = off_host[n];
+  // Rows the pinned families need whatever the pack holds: gemm_mfma 16, the LDS-tiled narrow conv 256 at its stage's rate.  The pack
+  // is extended by zero frames up to that (they join the last sentence's capacity), so that a one-frame sentence alone runs the
+  // kernel families it runs inside a pack of 64.
+  int T = std::max(Ttot, 16);
+  {
+    long U = 1;
+    int ch = C0;
+    for (int i = 0; i < c.bv_num_up; ++i) {
+      U *= c.bv_up_rates[i];
+      ch /= 2;
+      for (int j = 0; j < nk; ++j)
+        for (int l = 0; l < nd; ++l) {
+          GemmArgs q;
+          q.N = q.Cin = q.lda = q.ldc = q.ldr = ch;
+          q.taps = c.bv_res_kernels[j];
+          q.dil = c.bv_res_dils[j][l];
+          if (gemm_which_pinned_conv(q, adt, bv.res[i * nk + j].c1[l].dt, adt) == 4) T = std::max<long>(T, (256 + U - 1) / U);
+        }
+    }
+  }
+  SegTable seg;
+  ITTS_TRY(seg_table_fill(seg, off_host, lens_host, n));
+  seg.off[n] = T;
+  auto body = [&]() -> int {
+    // Every tensor a convolution reads is zero in every sentence's gap (seg_bias_mask behind conv_pre, every ups[i] and every stage;
+    // the segment Activation1d writes its own zeros); residual and accumulate tensors keep whatever their gaps hold, nothing reads them
+    // but a segment activation (signal rows only) or the next mask.  The matrix kernels see ONE item of T * U rows.
+    void* lat = alloc((size_t)T * c.bv_gpt_dim * es);
+    if (!dry) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(lat, latent_in, (size_t)Ttot * c.bv_gpt_dim * es, hipMemcpyDeviceToDevice, s));
+      if (T > Ttot) ITTS_HIP_CHECK(hipMemsetAsync((char*)lat + (size_t)Ttot * c.bv_gpt_dim * es, 0, (size_t)(T - Ttot) * c.bv_gpt_dim * es, s));
+    }
+    K(seg_bias_mask(lat, nullptr, c.bv_gpt_dim, seg, 1, adt, s));  // the caller's gap rows are not read as signal
+    // speaker conditioning -> one bias row per SENTENCE (cond_layer / conds[i] are 1x1 convs of a length-1 signal).  With one item the
+    // GEMM epilogue's bias_bstride cannot index sentences: the layer's own bias stays in the epilogue, the sentence's row is added by
+    // the mask pass that zeroes its gap anyway.
+    float* cb = (float*)alloc((size_t)n * C0 * 4);
+    ITTS_TRY(lin(cb, F32, spk, F32, E, bv.cond_layer, n, C0, s));
+    void* x = alloc((size_t)T * C0 * es);
+    {
+      GemmArgs g = conv_args(lat, c.bv_gpt_dim, bv.conv_pre, x, C0, T, T);
+      g.pad_left = 3;
+      ITTS_TRY(conv(g, adt, bv.conv_pre.dt, adt, s));
+    }
+    K(seg_bias_mask(x, cb, C0, seg, 1, adt, s));
+    int Tc = T, ch = C0, mul = 1;
+    for (int i = 0; i < c.bv_num_up; ++i) {
+      const int u = c.bv_up_rates[i], k = c.bv_up_kernels[i], p = (k - u) / 2;
+      const int cout = ch / 2, To = Tc * u;
+      const Lin& up = bv.ups[i];
+      float* ub = (float*)alloc((size_t)n * cout * 4);
+      ITTS_TRY(lin(ub, F32, spk, F32, E, bv.conds[i], n, cout, s));
+      void* xu = alloc((size_t)To * cout * es);
+      {
+        GemmArgs g = conv_args(x, ch, up, xu, u * cout, Tc, Tc);
+        g.dil = -1;
+        g.pad_left = 0;
+        g.nphase = u;
+        for (int ph = 0; ph < u; ++ph) g.phase_shift[ph] = (ph + p) / u;
+        ITTS_TRY(conv(g, adt, up.dt, adt, s));
+      }
+      Tc = To;
+      ch = cout;
+      mul *= u;
+      K(seg_bias_mask(xu, ub, ch, seg, mul, adt, s));
+      const size_t nel = (size_t)Tc * ch;
+      void* xs = alloc(nel * es);
+      void* xa = alloc(nel * es);
+      void* xb = alloc(nel * es);
+      void* t1 = alloc(nel * es);
+      void* t2 = alloc(nel * es);
+      // a -> conv: fused in the segment form of the narrow conv where the pinned selector answers 4, else the segment activation into
+      // `tact` and the pinned family over the whole pack
+      auto act_conv = [&](GemmArgs& q, const void* xraw, const float* la, const float* lb, void* tact, int wdt) -> int {
+        q.A = xraw;
+        q.pre_alpha = la;
+        q.pre_beta = lb;
+        q.pre_filt = bv.filter;
+        if (!force_simple && gemm_pinned_conv_fused(q, adt, wdt, adt)) return conv_seg(q, adt, wdt, adt, s, seg, mul);
+        q.pre_alpha = q.pre_beta = q.pre_filt = nullptr;
+        K(snake_aa_seg(tact, xraw, la, lb, bv.filter, bv.filter, ch, seg, mul, adt, s));
+        q.A = tact;
+        return conv(q, adt, wdt, adt, s);
+      };
+      for (int j = 0; j < nk; ++j) {
+        const AmpW& A = bv.res[i * nk + j];
+        const int ks = c.bv_res_kernels[j];
+        const void* cur = xu;
+        for (int l = 0; l < nd; ++l) {
+          const int d = c.bv_res_dils[j][l];
+          GemmArgs g = conv_args(nullptr, ch, A.c1[l], t2, ch, Tc, Tc);
+          g.dil = d;
+          g.pad_left = (ks * d - d) / 2;
+          ITTS_TRY(act_conv(g, cur, A.a1[l], A.b1[l], t1, A.c1[l].dt));
+          GemmArgs h = conv_args(nullptr, ch, A.c2[l], nullptr, ch, Tc, Tc);
+          h.pad_left = (ks - 1) / 2;
+          h.R = cur;
+          h.ldr = ch;
+          if (l == nd - 1) {  // x = (sum_j AMP_j(x)) / nk, accumulated in the epilogue
+            h.C = xs;
+            h.alpha = 1.f / nk;
+            if (j > 0) {
+              h.ADD = xs;
+              h.ldadd = ch;
+              h.beta = 1.f;
+            }
+          } else {
+            h.C = (cur == xa) ? xb : xa;
+          }
+          ITTS_TRY(act_conv(h, t2, A.a2[l], A.b2[l], t1, A.c2[l].dt));
+          cur = h.C;
+        }
+      }
+      if (i + 1 < c.bv_num_up) K(seg_bias_mask(xs, nullptr, ch, seg, mul, adt, s));  // what the next ups[] reads
+      x = xs;
+    }
+    void* t1 = alloc((size_t)Tc * ch * es);
+    K(snake_aa_seg(t1, x, bv.post_alpha, bv.post_beta, bv.filter, bv.filter, ch, seg, mul, adt, s));
+    float* wv = (float*)alloc((size_t)Tc * 4);  // T * up samples: the caller's buffer ends at off[n] * up
+    {
+      GemmArgs g = conv_args(t1, ch, bv.conv_post, wv, 1, Tc, Tc);
+      g.pad_left = 3;
+      g.act = ACT_TANH;
+      ITTS_TRY(conv(g, adt, bv.conv_post.dt, F32, s));
+    }
+    K(seg_bias_mask(wv, nullptr, 1, seg, mul, F32, s));
+    if (!dry) ITTS_HIP_CHECK(hipMemcpyAsync(wav, wv, (size_t)Ttot * mul * 4, hipMemcpyDeviceToDevice, s));
+    return OK;
+  };
+  PackedVocoderPass guard(*this);  // no K split; every family picked without looking at the row count
+  return two_pass(body, s);
+}
+
+// ------------------------------------------------------------------------------------------------
 // DVAE decoder
 // ------------------------------------------------------------------------------------------------
 int Engine::dvae_decode(const int32_t* codes_host, int B, int T, void* mel_out, hipStream_t s) {

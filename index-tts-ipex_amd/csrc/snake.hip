@@ -12,7 +12,9 @@
 // and the 6-sample input window in registers: per output it does 2 new up-FIR phases (12 FMA), 2
 // SnakeBeta evaluations and the 12-tap down-FIR (no 2x intermediate ever reaches HBM).  fp32 math,
 // I/O in fp32 or bf16.
+#include <algorithm>
 #include <cstdlib>
+#include <string>
 
 #include "itts_kernels.h"
 #include "itts_snake_dev.h"
@@ -63,12 +65,23 @@ __device__ __forceinline__ int valid_rows(const int* __restrict__ lens, int mul,
   return v < 0 ? 0 : (v > Tb ? Tb : (int)v);
 }
 
+// sentence b of a pack: the rows of its capacity and of its signal (len[b] * mul clamped to the capacity)
+__device__ __forceinline__ int seg_rows(const SegTable& seg, int mul, int b) { return (seg.off[b + 1] - seg.off[b]) * mul; }
+__device__ __forceinline__ int seg_valid_rows(const SegTable& seg, int mul, int b, int Tb) {
+  const long v = (long)seg.len[b] * mul;
+  return v < 0 ? 0 : (v > Tb ? Tb : (int)v);
+}
+
 // snake_aa_kernel (register window, any C) and snake_aa_lds_kernel (LDS-tiled, C % 8 == 0), then their length-aware forms
-// snake_aa_len_kernel / snake_aa_lds_len_kernel: the same text compiled a second time
+// snake_aa_len_kernel / snake_aa_lds_len_kernel and their segment forms snake_aa_seg_kernel / snake_aa_lds_seg_kernel: the same
+// text compiled a second and a third time
 #define ITTS_SNAKE_LEN 0
 #include "snake_kernels_text.h"
 #undef ITTS_SNAKE_LEN
 #define ITTS_SNAKE_LEN 1
+#include "snake_kernels_text.h"
+#undef ITTS_SNAKE_LEN
+#define ITTS_SNAKE_LEN 2
 #include "snake_kernels_text.h"
 #undef ITTS_SNAKE_LEN
 
@@ -93,6 +106,23 @@ static int launch_snake_lds(void* y, const void* x, const float* la, const float
   return OK;
 }
 
+// the segment form: grid (tiles of the longest capacity x slabs, sentences)
+template <typename T, bool FAST>
+static int launch_snake_lds_seg(void* y, const void* x, const float* la, const float* lb, const float* up12, const float* dn12,
+                                int Tmax, int C, hipStream_t s, const SegTable& seg, int mul) {
+  int CT = C;
+  if (C > 64) {
+    CT = 64;
+    while (C % CT) CT -= 8;
+  }
+  const int runs = 256 / CT, TT = runs * RUNL;
+  const int tiles_t = (Tmax + TT - 1) / TT, slabs = C / CT;
+  const size_t lds = ((size_t)(TT + 12) * CT + (size_t)TT * CT) * sizeof(T);
+  hipLaunchKernelGGL((snake_aa_lds_seg_kernel<T, FAST>), dim3((unsigned)((long)tiles_t * slabs), seg.n), dim3(256), lds, s, (T*)y,
+                     (const T*)x, la, lb, up12, dn12, Tmax, C, CT, tiles_t, slabs, seg, mul);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
 
 // ---- [B,C,T] layout (the reference's native-op contract): one (b,c) row per blockIdx.y/z, LDS-staged tile ----
 constexpr int BCT_TILE = 1024;
@@ -228,6 +258,65 @@ int snake_aa_len(void* y, const void* x, const float* log_alpha, const float* lo
                        log_beta, up12, down12, B, T, C, nchunk, lens, mul);
   else {
     set_error("snake_aa_len: unsupported dtype");
+    return E_INVALID;
+  }
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+// why a segment table cannot be run (null = it can): pure host code, asked by every entry that takes one before any HIP call
+const char* seg_table_refusal(const SegTable& seg, int mul, int gap) {
+  if (seg.n < 1 || seg.n > SEG_MAX) return "n outside [1, 128]";
+  if (mul < 1) return "mul < 1";
+  if (gap < 0) return "gap < 0";
+  if (seg.off[0] < 0) return "off[0] < 0";
+  for (int b = 0; b < seg.n; ++b) {
+    if (seg.len[b] < 1) return "a length < 1";
+    if (seg.off[b + 1] <= seg.off[b]) return "offsets not increasing";
+    if ((long)seg.off[b + 1] - seg.off[b] < (long)seg.len[b] + gap) return "gap too small: a capacity below len + gap";
+  }
+  if ((long)seg.off[seg.n] * mul > 0x7fffffffL) return "the pack has more than 2^31 - 1 rows";
+  return nullptr;
+}
+
+int seg_table_fill(SegTable& seg, const int* off_host, const int* lens_host, int n) {
+  ITTS_REQUIRE(off_host && lens_host && n >= 1 && n <= SEG_MAX, "segment table: null pointer or n outside [1, 128]");
+  seg.n = n;
+  for (int b = 0; b <= n; ++b) seg.off[b] = off_host[b];
+  for (int b = 0; b < n; ++b) seg.len[b] = lens_host[b];
+  return OK;
+}
+
+// snake_aa over packed sentences: sentence b is rows [off[b] * mul, off[b + 1] * mul) of x / y [off[n] * mul, C], its signal the first
+// len[b] * mul of them (replicate clamp at ITS last row), the rest of its capacity is written as zeros.  The signal rows have the bits
+// of snake_aa on the sentence cut out; rows outside [off[0] * mul, off[n] * mul) are not touched.
+int snake_aa_seg(void* y, const void* x, const float* log_alpha, const float* log_beta, const float* up12, const float* down12,
+                 int C, const SegTable& seg, int mul, int dt, hipStream_t s) {
+  ITTS_REQUIRE(y && x && log_alpha && log_beta && up12 && down12, "snake_aa_seg: null pointer");
+  const char* why = seg_table_refusal(seg, mul, 0);
+  ITTS_REQUIRE(!why, (std::string("snake_aa_seg: ") + why).c_str());
+  ITTS_REQUIRE(C > 0, "snake_aa_seg: bad dims");
+  int cap = 0;
+  for (int b = 0; b < seg.n; ++b) cap = std::max(cap, seg.off[b + 1] - seg.off[b]);
+  const long Tmax = (long)cap * mul;
+  static const bool no_lds = getenv("ITTS_SNAKE_REG") != nullptr;
+  if (!no_lds && C % 8 == 0 && C >= 8 && (dt == F32 || dt == BF16) && !(((uintptr_t)x | (uintptr_t)y) & 15)) {
+    if (dt == F32) return launch_snake_lds_seg<float, false>(y, x, log_alpha, log_beta, up12, down12, (int)Tmax, C, s, seg, mul);
+    return launch_snake_lds_seg<bf16_t, true>(y, x, log_alpha, log_beta, up12, down12, (int)Tmax, C, s, seg, mul);
+  }
+  const int nchunk = (int)((Tmax + RUN - 1) / RUN);
+  const dim3 grid((unsigned)(((long)nchunk * C + 255) / 256), seg.n);
+  if (dt == F32)
+    hipLaunchKernelGGL(snake_aa_seg_kernel<float>, grid, dim3(256), 0, s, (float*)y, (const float*)x, log_alpha, log_beta, up12,
+                       down12, 1, (int)Tmax, C, nchunk, seg, mul);
+  else if (dt == BF16)
+    hipLaunchKernelGGL(snake_aa_seg_kernel<bf16_t>, grid, dim3(256), 0, s, (bf16_t*)y, (const bf16_t*)x, log_alpha, log_beta, up12,
+                       down12, 1, (int)Tmax, C, nchunk, seg, mul);
+  else if (dt == F16)
+    hipLaunchKernelGGL(snake_aa_seg_kernel<f16_t>, grid, dim3(256), 0, s, (f16_t*)y, (const f16_t*)x, log_alpha, log_beta, up12,
+                       down12, 1, (int)Tmax, C, nchunk, seg, mul);
+  else {
+    set_error("snake_aa_seg: unsupported dtype");
     return E_INVALID;
   }
   ITTS_HIP_CHECK(hipGetLastError());

@@ -1,17 +1,28 @@
-// The text of the two channels-last Activation1d kernels of snake.hip, compiled twice (no include guard):
+// The text of the two channels-last Activation1d kernels of snake.hip, compiled three times (no include guard):
 //   ITTS_SNAKE_LEN 0   snake_aa_kernel, snake_aa_lds_kernel                  every item is a signal of Tn rows
 //   ITTS_SNAKE_LEN 1   snake_aa_len_kernel, snake_aa_lds_len_kernel          padded ragged batch: Tn stays the row count (stride) of the
 //                      buffer, the signal of item b is its first lens[b] * mul rows - the replicate clamp is taken at ITS last row -
 //                      and the rows behind it are written as zeros (the zero "same" padding the next convolution reads).  A chunk /
 //                      tile that lies wholly behind the signal stores zeros and reads nothing.
+//   ITTS_SNAKE_LEN 2   snake_aa_seg_kernel, snake_aa_lds_seg_kernel          packed sentences (one item, back to back in time): sentence b =
+//                      blockIdx.y owns rows [off[b] * mul, off[b + 1] * mul) - its CAPACITY stands where the length-aware form has the
+//                      rows of the buffer - and its signal is the first len[b] * mul of them.  Base and capacity are the only differences
+//                      from form 1; a chunk / tile behind the capacity leaves at once (before any barrier), so nothing is ever written
+//                      into the next sentence.  The table travels by value in the argument block.
 // One text, so the two forms cannot drift apart; a second inclusion instead of a template flag, so that the symbols, arguments and
 // instructions of the plain kernels stay exactly what they were.
-#if ITTS_SNAKE_LEN
+#if ITTS_SNAKE_LEN == 2
+#define SNAKE_KERNEL(name) name##_seg_kernel
+#define SNAKE_LEN_PARAMS , SegTable seg, int mul
+#define SNAKE_ITEM_ROW0(b, Tb) ((size_t)seg.off[b] * mul)  // first row of sentence b
+#elif ITTS_SNAKE_LEN
 #define SNAKE_KERNEL(name) name##_len_kernel
 #define SNAKE_LEN_PARAMS , const int* __restrict__ lens, int mul
+#define SNAKE_ITEM_ROW0(b, Tb) (size_t)b * Tb
 #else
 #define SNAKE_KERNEL(name) name##_kernel
 #define SNAKE_LEN_PARAMS
+#define SNAKE_ITEM_ROW0(b, Tb) (size_t)b * Tb
 #endif
 
 template <typename T>
@@ -20,22 +31,35 @@ __global__ __launch_bounds__(256) void SNAKE_KERNEL(snake_aa)(T* __restrict__ y,
                                                               const float* __restrict__ up12, const float* __restrict__ dn12,
                                                               int B, int Tn, int C, int nchunk SNAKE_LEN_PARAMS) {
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+#if ITTS_SNAKE_LEN == 2
+  if (gid >= (long)nchunk * C) return;  // grid (chunks of the longest capacity x channels, sentences)
+  const int c = (int)(gid % C);
+  const int ch = (int)(gid / C);
+  const int b = blockIdx.y;
+  const int Tb = seg_rows(seg, mul, b);  // rows of the sentence's capacity
+  if (ch * RUN >= Tb) return;
+#else
   const long total = (long)B * nchunk * C;
   if (gid >= total) return;
   const int c = (int)(gid % C);
   const int ch = (int)((gid / C) % nchunk);
   const int b = (int)(gid / ((long)C * nchunk));
   const int Tb = Tn;  // rows of the buffer
+#endif
 #if ITTS_SNAKE_LEN
+#if ITTS_SNAKE_LEN == 2
+  Tn = seg_valid_rows(seg, mul, b, Tb);
+#else
   Tn = valid_rows(lens, mul, b, Tb);
+#endif
   {
-    T* __restrict__ yz = y + (size_t)b * Tb * C + c;
+    T* __restrict__ yz = y + SNAKE_ITEM_ROW0(b, Tb) * C + c;
     for (int t = max(ch * RUN, Tn); t < min(ch * RUN + RUN, Tb); ++t) stf(yz + (size_t)t * C, 0.f);
     if (ch * RUN >= Tn) return;
   }
 #endif
   SnakeCtx<T> k;
-  k.x = x + (size_t)b * Tb * C + c;
+  k.x = x + SNAKE_ITEM_ROW0(b, Tb) * C + c;
   k.Tn = Tn;
   k.C = C;
   k.ea = expf(la[c]);
@@ -45,7 +69,7 @@ __global__ __launch_bounds__(256) void SNAKE_KERNEL(snake_aa)(T* __restrict__ y,
     k.fu[i] = up12[i];
     k.fd[i] = dn12[i];
   }
-  T* __restrict__ yo = y + (size_t)b * Tb * C + c;
+  T* __restrict__ yo = y + SNAKE_ITEM_ROW0(b, Tb) * C + c;
   const int t0 = ch * RUN;
   const int t1 = min(t0 + RUN, Tn);
   // window v[j] = V(2t - 5 + j), j = 0..11
@@ -101,14 +125,25 @@ __global__ __launch_bounds__(256) void SNAKE_KERNEL(snake_aa_lds)(T* __restrict_
   int bid = blockIdx.x;
   const int slab = bid % slabs;
   bid /= slabs;
+#if ITTS_SNAKE_LEN == 2
+  const int tile = bid, b = blockIdx.y;  // grid (tiles of the longest capacity x slabs, sentences)
+  const int t0 = tile * TT, c0 = slab * CT;
+  const int Tb = seg_rows(seg, mul, b);  // rows of the sentence's capacity
+  if (t0 >= Tb) return;                  // (workgroup-uniform, before the first barrier) a tile behind the capacity
+#else
   const int tile = bid % tiles_t, b = bid / tiles_t;
   const int t0 = tile * TT, c0 = slab * CT;
   const int Tb = Tn;  // rows of the buffer
-  const T* __restrict__ xb = x + (size_t)b * Tb * C + c0;
-  T* __restrict__ yb = y + (size_t)b * Tb * C + c0;
+#endif
+  const T* __restrict__ xb = x + SNAKE_ITEM_ROW0(b, Tb) * C + c0;
+  T* __restrict__ yb = y + SNAKE_ITEM_ROW0(b, Tb) * C + c0;
   const int tid = threadIdx.x;
 #if ITTS_SNAKE_LEN
+#if ITTS_SNAKE_LEN == 2
+  Tn = seg_valid_rows(seg, mul, b, Tb);
+#else
   Tn = valid_rows(lens, mul, b, Tb);
+#endif
   if (t0 >= Tn) {  // (workgroup-uniform) nothing of the signal in this tile
     const int vpr = CT / VEC, nvec = min(TT, Tb - t0) * vpr;
     for (int v = tid; v < nvec; v += 256) {
@@ -171,3 +206,4 @@ __global__ __launch_bounds__(256) void SNAKE_KERNEL(snake_aa_lds)(T* __restrict_
 
 #undef SNAKE_KERNEL
 #undef SNAKE_LEN_PARAMS
+#undef SNAKE_ITEM_ROW0

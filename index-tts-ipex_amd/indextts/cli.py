@@ -45,6 +45,9 @@ def build_parser():
     p.add_argument("--packed-latent", action="store_true", default=False,
                    help="batched synthesis (IndexTTS.infer_batch): the latent pass runs on packed rows without padding, one pass per "
                         "decode group under mixed batches; ITTS_PACKED_LATENT=0 / 1 overrides")
+    p.add_argument("--packed-vocoder", action="store_true", default=False,
+                   help="batched synthesis (IndexTTS.infer_batch): the vocoder runs over the sentences back to back as one item without "
+                        "padding, one pass per decode group under mixed batches; ITTS_PACKED_VOCODER=0 / 1 overrides")
     return p
 
 
@@ -69,7 +72,7 @@ def main():
     tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8, kv_fp8=a.kv_fp8,
                    wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler, retire_rows=a.retire_rows,
                    engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder, admit_rows=a.admit_rows, retire_beams=a.retire_beams,
-                   packed_latent=a.packed_latent, admit_beams=a.admit_beams)
+                   packed_latent=a.packed_latent, admit_beams=a.admit_beams, packed_vocoder=a.packed_vocoder)
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

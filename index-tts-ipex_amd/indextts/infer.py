@@ -59,7 +59,12 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `packed_latent=True` (not in the reference; default off; ITTS_PACKED_LATENT=1 / 0 overrides it in both directions) runs the
     latent pass of `infer_batch` on packed rows (Engine.latent_packed: no pad rows, a sentence's latent has the same bits
     whoever shares its pass); with `mixed_batch` the utterances of a decode group then share ONE latent pass instead of one
-    per utterance.  The vocoder stays per utterance.  `infer` / `infer_fast` are not affected.
+    per utterance.  The vocoder stays per utterance unless `packed_vocoder` is on.  `infer` / `infer_fast` are not affected.
+  * `packed_vocoder=True` (not in the reference; default off; ITTS_PACKED_VOCODER=1 / 0 overrides it in both directions) runs the
+    vocoder of `infer_batch` over its sentences back to back as one item (Engine.bigvgan_packed: no padding to a common length, a
+    sentence's waveform has the same bits whoever shares its pass) where it otherwise calls Engine.bigvgan_grouped; with
+    `mixed_batch` the utterances and voices of a decode group then share ONE vocoder pass instead of one set of passes per
+    utterance.  It takes precedence over `ragged_vocoder`.  `infer` / `infer_fast` are not affected.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -85,7 +90,8 @@ class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
-                 mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False):
+                 mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False,
+                 packed_vocoder=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -120,6 +126,7 @@ class IndexTTS:
         self.admit_beams = bool(admit_beams)  # on top of admit_rows: beam groups (the default kwargs' mode) are refilled too (ITTS_ADMIT_BEAMS overrides)
         self._admit_told = False
         self.packed_latent = bool(packed_latent)  # infer_batch: the latent pass on packed rows, one per decode group (ITTS_PACKED_LATENT overrides)
+        self.packed_vocoder = bool(packed_vocoder)  # infer_batch: the vocoder over sentences back to back, one pass per decode group (ITTS_PACKED_VOCODER overrides)
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
         if self.kv_fp8 and not self.is_fp16:
             raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
@@ -365,8 +372,12 @@ class IndexTTS:
                                                packed=infer_core.env_switch("ITTS_PACKED_LATENT", self.packed_latent))
                 wav_parts = {u: [] for u in us}
                 ragged = {"1": True, "0": False}.get(os.environ.get("ITTS_RAGGED_VOCODER", ""), self.ragged_vocoder)
-                # equal lengths share a launch sequence; with ragged, unequal ones too
-                for (u, k, _), wav in zip(flat, self.engine.bigvgan_grouped(lats, spk, ragged=ragged)):
+                # equal lengths share a launch sequence; with ragged, unequal ones too; packed: all of them back to back in one item
+                if infer_core.env_switch("ITTS_PACKED_VOCODER", self.packed_vocoder):
+                    wavs = self.engine.bigvgan_packed(lats, spk)
+                else:
+                    wavs = self.engine.bigvgan_grouped(lats, spk, ragged=ragged)
+                for (u, k, _), wav in zip(flat, wavs):
                     wav_parts[u].append(self._to_int16_range(wav))
                 for u in us:
                     if wav_parts[u]:
@@ -471,8 +482,12 @@ class IndexTTS:
             # 2.5 % of the int16 samples one unit apart).  The decode steps are where the rows pay; these passes run once.
             # With packed_latent the latent pass has no such dependence (Engine.latent_packed: no pad rows, every sentence tiled from
             # its own key 0, no K split, the GEMM family not chosen by the row count), so the whole decode group shares ONE pass;
-            # the vocoder stays per utterance.
+            # the vocoder stays per utterance - unless packed_vocoder is on: Engine.bigvgan_packed makes the same promise for the
+            # waveform (sentences back to back in one item, no K split, families not chosen by the row count, one speaker row per
+            # sentence), so the whole decode group, across utterances and voices, shares ONE vocoder pass.
             cap = self.engine.ccfg.max_batch
+            packed_voc = infer_core.env_switch("ITTS_PACKED_VOCODER", self.packed_vocoder)
+            held = []  # packed vocoder: (utterance, its latents) of the whole group
             group_lats = None
             if infer_core.env_switch("ITTS_PACKED_LATENT", self.packed_latent):
                 group_lats = self.engine.latent_packed(cond_all, [f[2] for f in flat], clean,
@@ -489,7 +504,16 @@ class IndexTTS:
                     for lo in range(0, len(idx), cap):
                         sel = idx[lo:lo + cap]
                         lats.extend(self.engine.latent_batch(cond_all, [flat[i][2] for i in sel], [clean[i] for i in sel], cond_index=v[:len(sel)]))
+                if packed_voc:
+                    held.append((u, lats))
+                    continue
                 results[u] = [self._to_int16_range(w) for w in self.engine.bigvgan_grouped(lats, spk_all[v], ragged=ragged)]
+            if held:
+                rows = [voice[id(prompts[u])] for u, lats in held for _ in lats]
+                wavs = self.engine.bigvgan_packed([l for _, lats in held for l in lats], spk_all[rows])
+                for u, lats in held:
+                    results[u] = [self._to_int16_range(w) for w in wavs[:len(lats)]]
+                    wavs = wavs[len(lats):]
 
     def _prompt(self, prompt_mel, audio_prompt):
         if prompt_mel is None and audio_prompt is None:

@@ -1039,6 +1039,58 @@ class Engine:
         spk.record_stream(self.stream)
         return [out[b:b + 1, :, :int(lens[b]) * self.up_total] for b in range(B)]
 
+    def bigvgan_packed_gap(self) -> int:
+        """Zero frames a packed sentence needs behind its signal (infer_core.packed_vocoder_gap over this engine's config)."""
+        from . import infer_core
+
+        c = self.ccfg
+        nu, nr, nd = int(c.bv_num_up), int(c.bv_num_res), int(c.bv_num_dil)
+        return infer_core.packed_vocoder_gap(list(c.bv_up_rates)[:nu], list(c.bv_up_kernels)[:nu], list(c.bv_res_kernels)[:nr],
+                                             [list(c.bv_res_dils[j])[:nd] for j in range(nr)])
+
+    def bigvgan_packed(self, lats: List[torch.Tensor], spk: torch.Tensor, max_frames: Optional[int] = None) -> List[torch.Tensor]:
+        """Vocoder over latents [1, T_i, D] back to back as ONE item (itts_bigvgan_packed; opt-in): no padding to a common length -
+        each sentence is followed by bigvgan_packed_gap() zero frames, the reach of the widest convolution - no K split and every
+        kernel family picked without looking at the row count, so a sentence's samples are the same bits alone, with any companions
+        (of any voice), in any order and in any chunking.  spk [E], [1, E] (shared) or [n, E], one voice per sentence.
+        max_frames: the frame budget of one pass (infer_core.packed_vocoder_plan; default PACKED_VOCODER_MAX_FRAMES).
+        -> wavs fp32 [1, 1, T_i * up], in the order of lats."""
+        from . import infer_core
+
+        n = len(lats)
+        if n == 0:
+            return []  # as bigvgan_grouped, which it stands in for
+        lens = [int(l.shape[1]) for l in lats]
+        D = int(lats[0].shape[2])
+        spk = spk.to(device=self.device, dtype=torch.float32).reshape(-1, spk.shape[-1])
+        if spk.shape[0] not in (1, n):
+            raise ValueError(f"bigvgan_packed: {spk.shape[0]} speaker embeddings for {n} latents (one, or one per latent)")
+        spk = (spk.expand(n, -1) if spk.shape[0] == 1 else spk).contiguous()
+        gap = self.bigvgan_packed_gap()
+        chunks, offsets, frames = infer_core.packed_vocoder_plan(lens, gap, max_frames or infer_core.PACKED_VOCODER_MAX_FRAMES)
+        res: List[Optional[torch.Tensor]] = [None] * n
+        passes = []  # the operands of every pass, made on the caller's stream before the engine's stream starts to wait for it
+        for sel, off, tot in zip(chunks, offsets, frames):
+            lat = torch.zeros(tot, D, dtype=self.tdt, device=self.device)
+            for j, i in enumerate(sel):
+                lat[off[j]:off[j] + lens[i]] = lats[i][0].to(device=self.device, dtype=self.tdt)
+            sp = spk[sel[0]:sel[-1] + 1].contiguous()  # (chunks are consecutive runs)
+            out = torch.empty(tot * self.up_total, dtype=torch.float32, device=self.device)
+            passes.append((sel, off, lat, sp, out))
+        self._enter()
+        self._join_side()
+        for sel, off, lat, sp, out in passes:
+            offs = np.asarray(off, dtype=np.int32)
+            ln = np.asarray([lens[i] for i in sel], dtype=np.int32)
+            self._ck(self.lib.itts_bigvgan_packed(self.h, lat.data_ptr(), sp.data_ptr(), offs.ctypes.data_as(C.c_void_p),
+                                                  ln.ctypes.data_as(C.c_void_p), len(sel), out.data_ptr(), self._s()), "bigvgan_packed")
+            lat.record_stream(self.stream)
+            sp.record_stream(self.stream)
+            for j, i in enumerate(sel):
+                res[i] = out[off[j] * self.up_total:(off[j] + lens[i]) * self.up_total].view(1, 1, -1)
+        self._exit()
+        return res
+
     def bigvgan_grouped(self, lats: List[torch.Tensor], spk: torch.Tensor, ragged: bool = False,
                         max_pad: float = 0.1) -> List[torch.Tensor]:
         """Vocoder over several sentences: latents [1, T_i, D] of EQUAL length share one batched launch sequence (rows of

@@ -264,6 +264,60 @@ def packed_chunks(lengths: Sequence[int], max_tokens: int = PACKED_MAX_TOKENS, m
     return chunks
 
 
+# ---- packed vocoder (Engine.bigvgan_packed): the gap rule and the chunks ----
+PACKED_VOCODER_MAX_SEQ = 128        # SEG_MAX: offsets and lengths travel in the kernels' argument block
+PACKED_VOCODER_MAX_FRAMES = 16384   # default frame budget of one pass, see packed_vocoder_plan
+
+
+def packed_vocoder_gap(up_rates: Sequence[int], up_kernels: Sequence[int], res_kernels: Sequence[int],
+                       res_dils: Sequence[Sequence[int]]) -> int:
+    """Zero frames a packed sentence needs behind its signal: the largest reach of any convolution of the generator, in latent
+    frames, rounded up - conv_pre (k = 7: 3 frames), every ups[i] at its INPUT rate (polyphase: output q * u + ph reads
+    x[q + (ph + p) // u - m], m < k // u, p = (k - u) // 2), every AMP conv at its stage's rate ((k * d - d) // 2 rows, and
+    (k - 1) // 2 for the undilated second conv), conv_post (3 rows at the output rate).  The rule of csrc/model_vocoder.hip
+    bigvgan_packed_gap, which checks every call against it again."""
+    ceil_div = lambda a, b: -(-int(a) // int(b))  # noqa: E731
+    gap, U = 3, 1
+    for u, k in zip(up_rates, up_kernels):
+        u, k = int(u), int(k)
+        p, taps = (k - u) // 2, k // u
+        gap = max(gap, ceil_div(max((u - 1 + p) // u, taps - 1 - p // u), U))
+        U *= u
+        for ks, dils in zip(res_kernels, res_dils):
+            for d in dils:
+                gap = max(gap, ceil_div(max((int(ks) * int(d) - int(d)) // 2, (int(ks) - 1) // 2), U))
+    return max(gap, ceil_div(3, U))
+
+
+def packed_vocoder_plan(lengths: Sequence[int], gap: int, max_frames: int = PACKED_VOCODER_MAX_FRAMES,
+                        max_seqs: int = PACKED_VOCODER_MAX_SEQ) -> Tuple[List[List[int]], List[List[int]], List[int]]:
+    """Chunks of one packed vocoder pass each: -> (chunks, offsets, frames).  chunks[k]: a consecutive run of sentence indices
+    (order-preserving); offsets[k]: len(chunks[k]) + 1 frame offsets, sentence j of the chunk owns [offsets[k][j], offsets[k][j + 1]),
+    a capacity of exactly len + gap; frames[k] = offsets[k][-1], the frames the pass computes - at most max_frames, except that a
+    sentence whose len + gap is over the budget is a chunk of its own; at most max_seqs sentences a chunk.  Pure.  (Any chunking
+    gives the same samples - a sentence does not depend on its companions - so this only bounds the scratch.)
+    The default budget, 16384 frames, is sized from the pass's scratch: the bump allocator keeps six tensors of every stage, at
+    full dims 6 * (4 * 768 + 16 * 384 + 64 * 192 + 3 * 24576) elements per latent frame - about 1.2 MiB (16-bit) / 2.4 MiB (fp32)
+    a frame, so about 19 / 38 GiB a pass; the batched form already runs 64 x 480 = 30720 frames in one pass."""
+    gap, max_frames, max_seqs = int(gap), int(max_frames), int(max_seqs)
+    if gap < 0 or max_frames < 1 or max_seqs < 1:
+        raise ValueError(f"packed_vocoder_plan: gap {gap} >= 0, max_frames {max_frames} >= 1 and max_seqs {max_seqs} >= 1 expected")
+    chunks, offsets, frames = [], [], []
+    cur, off = [], [0]
+    for i, n in enumerate(lengths):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"packed_vocoder_plan: sentence {i} has length {n}")
+        if cur and (len(cur) >= max_seqs or off[-1] + n + gap > max_frames):
+            chunks.append(cur), offsets.append(off), frames.append(off[-1])
+            cur, off = [], [0]
+        cur.append(i)
+        off.append(off[-1] + n + gap)
+    if cur:
+        chunks.append(cur), offsets.append(off), frames.append(off[-1])
+    return chunks, offsets, frames
+
+
 def env_switch(name: str, setting: bool) -> bool:
     """An A/B switch of IndexTTS: the environment variable overrides the constructor's setting in both directions ("1" on, "0" off);
     unset or anything else leaves the setting."""

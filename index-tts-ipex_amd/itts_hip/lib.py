@@ -132,6 +132,10 @@ _PROTOS = {
     "itts_snake_aa_fwd_len": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]),
     "itts_act_conv_len": (i32, [C.POINTER(GemmArgs), vp, vp, vp, vp, i32, vp]),
     "itts_zero_tail_rows": (i32, [vp, i32, i32, i32, vp, i32, i32, vp]),
+    "itts_snake_aa_fwd_seg": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+    "itts_act_conv_seg": (i32, [C.POINTER(GemmArgs), vp, vp, vp, vp, vp, i32, i32, vp]),
+    "itts_seg_bias_mask": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+    "itts_gemm_which_pinned_conv": (i32, [C.POINTER(GemmArgs)]),
     "itts_gemv_which": (i32, [i32] * 7),
     "itts_gemm_ws": (i32, [C.POINTER(GemmArgs), vp, C.c_size_t, vp]),
     "itts_gemm_ksplit": (i32, [C.POINTER(GemmArgs), C.c_size_t]),
@@ -210,6 +214,9 @@ _PROTOS = {
     "itts_gpt_latent_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     "itts_bigvgan": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "itts_bigvgan_ragged": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "itts_bigvgan_packed": (i32, [vp, vp, vp, vp, vp, i32, vp, vp]),
+    "itts_bigvgan_packed_check": (i32, [C.POINTER(Config), vp, vp, vp, vp, i32, vp]),
+    "itts_bigvgan_packed_gap": (i32, [C.POINTER(Config)]),
     "itts_dvae_decode": (i32, [vp, vp, i32, i32, vp, vp]),
     "itts_dvae_encode": (i32, [vp, vp, i32, i32, vp, vp]),
     "itts_debug_fetch": (i64, [vp, C.c_char_p, vp, i64]),
