@@ -202,6 +202,42 @@ int itts_attention_varlen(void* o, const void* q, const void* k, const void* v, 
 int itts_attention_varlen_which(const void* q, const void* k, const void* v, const int32_t* seq_off_host, int nseq, int H, int dqk,
                                 int dv, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, int kernel);
 
+/* Causal self-attention for APPENDED rows (csrc/attention_append.hip; the incremental packed latent pass).  Sequence b
+ * brings n_new_host[b] new queries, positions pos0_host[b] .. pos0_host[b] + n_new_host[b] - 1, in rows q_off_host[b] .. of q and o (the
+ * chunk's buffers: row r, head h, dim d at q[r * ldq + h * dqk + d], o likewise with dv and ldo); its keys and values are rows
+ * 0 .. pos0 + n_new - 1 of its block of a K/V history, which starts at row kv_off_host[b] of k_hist / v_hist (ldk, ldv) and holds
+ * kv_off_host[b + 1] - kv_off_host[b] rows - the new rows' k / v are already there (itts_kv_rows_append).  Query at position i sees keys
+ * 0 .. i.  n_new_host[b] = 0 leaves sequence b alone.
+ * The bit relation: a delivered row has the bits itts_attention_varlen of the same kernel number gives that row in a pass over the
+ * COMPLETE sequence (query tiles aligned to the sequence's key 0, 64-key tiles from key 0, the same mask, online-softmax update, P
+ * rounding and store).  Rows of a tile in front of pos0 are never stored; o rows outside the appended ranges are not touched; no key
+ * row at or behind pos0 + n_new is read, whatever the history holds there.
+ * q_off_host, kv_off_host: nseq + 1 host ints each (non-decreasing, [0] >= 0); pos0_host, n_new_host: nseq host ints; all four are
+ * passed to the kernel by value (no upload; the arrays may be reused once the call returns).
+ * kernel: 0 = the dispatcher, 1 = attn_append_simple (vector ALU, fp32 or the 16-bit type, dqk <= 128, dv <= 64), 2 = attn_append_mfma
+ * (matrix cores: the 16-bit type, dqk = dv = 64, ldq / ldk / ldv % 8 == 0, q / k_hist / v_hist 16-byte aligned).  The named kernel runs or
+ * nothing does.  The dispatcher's pick is itts_attention_varlen's rule: type, head dims, leading dims and alignment only, never a length
+ * or a count (ITTS_ATTN_SIMPLE, read once per process, makes it 1).
+ * itts_attention_append_which: 1 or 2, that pick, without a launch; -1 for a call the entry refuses.
+ * Both share one host-side check, made before any HIP call, that answers ITTS_E_INVALID with a message that begins with the entry's
+ * name: a null q / k_hist / v_hist / o or array; nseq outside 1 .. ITTS_VARLEN_MAX_SEQ; a negative offset, pos0 or n_new; offsets that
+ * decrease; n_new past the sequence's rows of q / o; pos0 + n_new past the sequence's history block; H outside 1 .. 65535; a dtype other
+ * than ITTS_F32 / ITTS_BF16 (the library's 16-bit type); dqk outside 1..128 or dv outside 1..64; ldq or ldk < H * dqk, ldv or ldo < H * dv;
+ * a kernel other than 0, 1, 2; and for kernel 2 whatever the matrix-core kernel's rule above rejects. */
+int itts_attention_append(void* o, const void* q, const void* k_hist, const void* v_hist, const int32_t* q_off_host,
+                          const int32_t* kv_off_host, const int32_t* pos0_host, const int32_t* n_new_host, int nseq, int H, int dqk, int dv,
+                          int ldq, int ldk, int ldv, int ldo, float scale, int dtype, int kernel, itts_stream stream);
+int itts_attention_append_which(const void* q, const void* k_hist, const void* v_hist, const int32_t* q_off_host,
+                                const int32_t* kv_off_host, const int32_t* pos0_host, const int32_t* n_new_host, int nseq, int H, int dqk,
+                                int dv, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, int kernel);
+/* The history write that goes in front of it (kv_rows_append_kernel, one launch): for r < n_new_host[b], columns [0, wk) of k_src row
+ * q_off_host[b] + r go to k_hist row kv_off_host[b] + pos0_host[b] + r, columns [0, wv) of v_src to the same row of v_hist (ld_src is
+ * the row stride of both sources - the k and v thirds of a qkv tensor).  fp32 or the 16-bit type, no conversion.  The same arrays and
+ * the same host-side refusals as above (message "itts_kv_rows_append: ..."), plus widths < 1 and a leading dim below its width. */
+int itts_kv_rows_append(void* k_hist, void* v_hist, const void* k_src, const void* v_src, const int32_t* q_off_host,
+                        const int32_t* kv_off_host, const int32_t* pos0_host, const int32_t* n_new_host, int nseq, int ld_src, int ldk,
+                        int ldv, int wk, int wv, int dtype, itts_stream stream);
+
 /* Decode-step batched GEMV (GPT2 Conv1D on one token per row, HF GPT2Attention/GPT2MLP):
  * Y[b, n] (+)= act(prologue(X)[b, :] . W[n, :] + bias[n]); X, Y fp32; prologue 0 none, 1 LayerNorm, 2 LN o LN.
  * version 0 = auto, 1 = generic kernel, 2 = register-resident kernel (B <= 4). */
@@ -778,6 +814,28 @@ int itts_gpt_latent_batch_cond(itts_engine* e, const float* cond, const int32_t*
 int itts_gpt_latent_packed(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond,
                            const int32_t* text_ids_host, const int32_t* text_lens_host, const int32_t* codes_host,
                            const int32_t* code_lens_host, int nseq, void* latent_out, itts_stream stream);
+
+/* The INCREMENTAL packed latent pass (opt-in): the sequences of itts_gpt_latent_packed, opened together and fed their
+ * codes in pieces while they are still being decoded.  The engine keeps each sequence's K/V history ([layers][nseq][prefix + max_codes]
+ * [2 D] in the engine dtype), allocated by open and freed by close - never inside an append, and no buffer of a captured decode step
+ * moves.  One stream per engine.
+ * itts_gpt_latent_stream_open: cond / cond_index_host / n_cond / text_ids_host / text_lens_host / nseq as itts_gpt_latent_packed (cond
+ * must stay valid until close); max_codes = the most codes any sequence will be given (1 .. max_mel_tokens + 1).
+ * itts_gpt_latent_stream_append: counts_host[b] more codes for sequence b (0 leaves it alone), codes_host = those codes, sequence after
+ * sequence; latent_out [sum counts, D] in the engine dtype receives one latent row per code, sequence after sequence.  The identity:
+ * after any sequence of appends the rows delivered so far are, bit for bit, the first rows itts_gpt_latent_packed gives for the final
+ * codes (latent row j reads the start token and the codes < j, so a code's own row is computed by the append that follows it).  A
+ * call with fewer than 16 rows on a 16-bit engine re-runs the last rows it already computed, so that every GEMM keeps the kernel
+ * family of the packed pass.  Synchronises the stream before it returns.
+ * itts_gpt_latent_stream_close: frees the history; without an open stream it does nothing.
+ * Refused with ITTS_E_INVALID before any HIP call, with a message that begins with the entry's name: an append without an open stream;
+ * an append past max_codes; a mel code outside [0, number_mel_codes); a negative count; a second open; null pointers; nseq outside
+ * 1 .. ITTS_VARLEN_MAX_SEQ; a text length or id, a conditioning index or max_codes out of range. */
+int itts_gpt_latent_stream_open(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond,
+                                const int32_t* text_ids_host, const int32_t* text_lens_host, int nseq, int max_codes, itts_stream stream);
+int itts_gpt_latent_stream_append(itts_engine* e, const int32_t* codes_host, const int32_t* counts_host, void* latent_out,
+                                  itts_stream stream);
+int itts_gpt_latent_stream_close(itts_engine* e);
 
 /* V1-V5  BigVGAN.forward given the speaker embedding (BigVGAN/models.py:201-250):
  * latent [B, T, gpt_dim] (engine dtype), spk fp32 [B, spk_dim] -> wav fp32 [B, T * prod(up_rates)] */

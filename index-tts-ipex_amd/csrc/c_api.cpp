@@ -382,6 +382,62 @@ int itts_attention_varlen_which(const void* q, const void* k, const void* v, con
   return kernel ? kernel : attention_varlen_which(a, dtype);
 }
 
+// itts_attention_append / itts_attention_append_which / itts_kv_rows_append: one host-side check (append_check.cpp) before any HIP call
+static const char* to_append_args(AppendArgs& a, void* o, const void* q, const void* k, const void* v, const int32_t* q_off_host,
+                                  const int32_t* kv_off_host, const int32_t* pos0_host, const int32_t* n_new_host, int nseq, int H, int dqk,
+                                  int dv, int ldq, int ldk, int ldv, int ldo, float scale) {
+  a.q = q; a.k = k; a.v = v; a.o = o; a.H = H; a.dqk = dqk; a.dv = dv;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale; a.nseq = nseq;
+  if (!q_off_host || !kv_off_host || !pos0_host || !n_new_host) return "null pointer (q, k, v, o, q_off_host, kv_off_host, pos0_host, n_new_host)";
+  if (nseq < 1 || nseq > VARLEN_MAX_SEQ) return "nseq outside 1 .. 128";  // (before the copy: the arrays hold nseq (+ 1) ints)
+  for (int i = 0; i <= nseq; ++i) a.q_off[i] = q_off_host[i], a.kv_off[i] = kv_off_host[i];
+  for (int i = 0; i < nseq; ++i) a.pos0[i] = pos0_host[i], a.n_new[i] = n_new_host[i];
+  return nullptr;
+}
+
+int itts_attention_append(void* o, const void* q, const void* k_hist, const void* v_hist, const int32_t* q_off_host, const int32_t* kv_off_host,
+                          const int32_t* pos0_host, const int32_t* n_new_host, int nseq, int H, int dqk, int dv, int ldq, int ldk, int ldv,
+                          int ldo, float scale, int dtype, int kernel, itts_stream stream) {
+  AppendArgs a;
+  const char* why = to_append_args(a, o, q, k_hist, v_hist, q_off_host, kv_off_host, pos0_host, n_new_host, nseq, H, dqk, dv, ldq, ldk, ldv, ldo, scale);
+  if (!why) why = attention_append_refusal(a, dtype, kernel);
+  if (why) {
+    set_error(std::string("itts_attention_append: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  return attention_append(a, dtype, kernel, (hipStream_t)stream);
+}
+
+int itts_attention_append_which(const void* q, const void* k_hist, const void* v_hist, const int32_t* q_off_host, const int32_t* kv_off_host,
+                                const int32_t* pos0_host, const int32_t* n_new_host, int nseq, int H, int dqk, int dv, int ldq, int ldk,
+                                int ldv, int ldo, float scale, int dtype, int kernel) {
+  static const float dummy_o = 0.f;  // a real call has its output; the rule only asks whether it is there
+  AppendArgs a;
+  const char* why = to_append_args(a, const_cast<float*>(&dummy_o), q, k_hist, v_hist, q_off_host, kv_off_host, pos0_host, n_new_host, nseq, H, dqk,
+                                   dv, ldq, ldk, ldv, ldo, scale);
+  if (!why) why = attention_append_refusal(a, dtype, kernel);
+  if (why) {
+    set_error(std::string("itts_attention_append_which: ") + why);
+    return E_INVALID;
+  }
+  return kernel ? kernel : attention_append_which(a, dtype);
+}
+
+int itts_kv_rows_append(void* k_hist, void* v_hist, const void* k_src, const void* v_src, const int32_t* q_off_host, const int32_t* kv_off_host,
+                        const int32_t* pos0_host, const int32_t* n_new_host, int nseq, int ld_src, int ldk, int ldv, int wk, int wv, int dtype,
+                        itts_stream stream) {
+  AppendArgs a;
+  const char* why = to_append_args(a, nullptr, nullptr, k_hist, v_hist, q_off_host, kv_off_host, pos0_host, n_new_host, nseq, 1, 1, 1, 0, ldk, ldv, 0, 1.f);
+  if (!why) why = kv_rows_append_refusal(a, k_src, v_src, ld_src, wk, wv, dtype);
+  if (why) {
+    set_error(std::string("itts_kv_rows_append: ") + why);
+    return E_INVALID;
+  }
+  (void)hipGetLastError();  // drop stale errors left by other HIP users (torch)
+  return kv_rows_append(a, k_src, v_src, ld_src, wk, wv, dtype, (hipStream_t)stream);
+}
+
 int itts_gemv(float* Y, const float* X, const void* W, const float* bias, int B, int N, int K, int act, int accumulate,
               int prologue, const float* ln_gamma, const float* ln_beta, const float* ln2_gamma, const float* ln2_beta,
               int dtype_w, int version, itts_stream stream) {
@@ -1154,6 +1210,31 @@ int itts_gpt_latent_packed(itts_engine* e, const float* cond, const int32_t* con
   ENG(e);
   return e->e.gpt_latent_packed(cond, text_ids_host, text_lens_host, codes_host, code_lens_host, nseq, latent_out, (hipStream_t)s,
                                 cond_index_host, n_cond);
+}
+int itts_gpt_latent_stream_open(itts_engine* e, const float* cond, const int32_t* cond_index_host, int n_cond, const int32_t* text_ids_host,
+                                const int32_t* text_lens_host, int nseq, int max_codes, itts_stream s) {
+  if (!e) {
+    set_error("itts_gpt_latent_stream_open: null engine");
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  return e->e.gpt_latent_stream_open(cond, cond_index_host, n_cond, text_ids_host, text_lens_host, nseq, max_codes, (hipStream_t)s);
+}
+int itts_gpt_latent_stream_append(itts_engine* e, const int32_t* codes_host, const int32_t* counts_host, void* latent_out, itts_stream s) {
+  if (!e) {
+    set_error("itts_gpt_latent_stream_append: null engine");
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  return e->e.gpt_latent_stream_append(codes_host, counts_host, latent_out, (hipStream_t)s);
+}
+int itts_gpt_latent_stream_close(itts_engine* e) {
+  if (!e) {
+    set_error("itts_gpt_latent_stream_close: null engine");
+    return E_INVALID;
+  }
+  (void)hipGetLastError();
+  return e->e.gpt_latent_stream_close(nullptr);
 }
 int itts_bigvgan(itts_engine* e, const void* latent, const float* spk, int B, int T, float* wav_out, itts_stream s) {
   ENG(e);

@@ -407,6 +407,33 @@ struct Engine {
   // nseq <= VARLEN_MAX_SEQ.  A sequence's latent has the same bits alone, with any companions, in any order.
   int gpt_latent_packed(const float* cond, const int32_t* text_ids, const int* Ls, const int32_t* codes, const int* Ts,
                         int nseq, void* latent_out, hipStream_t s, const int32_t* cond_index = nullptr, int n_cond = 1);
+  // The INCREMENTAL packed latent pass (opt-in): up to VARLEN_MAX_SEQ sequences opened together, each fed its codes in
+  // pieces.  The state below lives from open to close; the K/V history is allocated at open and freed at close (never inside a pass,
+  // and nothing of it is known to a captured decode step, whose buffers are DecodeState's).  After any sequence of appends the rows
+  // delivered so far are, bit for bit, the first rows of gpt_latent_packed over the final codes.
+  struct LatentStream {
+    bool open = false;
+    int nseq = 0, max_codes = 0;
+    int cap = 0;           // history rows per sequence: the longest prefix + max_codes
+    int kernel = 1;        // the attention family gpt_latent_packed takes on this engine (1 simple, 2 mfma), fixed at open
+    void* hist = nullptr;  // [layers][nseq * cap][2 D] in the engine's activation type: k | v of every computed row
+    const float* cond = nullptr;  // the caller's conditioning (device), read by every first append
+    std::vector<int> prefix;      // [nseq] rows in front of the start-mel row: cond_latents + L + 2
+    std::vector<int> done;        // [nseq] codes taken so far = latent rows delivered
+    std::vector<int> computed;    // [nseq] rows whose k / v the history holds (0, or prefix + done)
+    std::vector<std::vector<int>> rd;  // [nseq] the row descriptors of [cond, text, start-mel, codes so far], 4 ints per row
+  };
+  LatentStream lstream;
+  int gpt_latent_stream_open(const float* cond, const int32_t* cond_index, int n_cond, const int32_t* text_ids, const int* Ls, int nseq,
+                             int max_codes, hipStream_t s);
+  // codes [sum counts], counts [nseq] (0 leaves a sequence alone); latent_out [sum counts, D] in the engine dtype, sequence after sequence
+  int gpt_latent_stream_append(const int32_t* codes, const int* counts, void* latent_out, hipStream_t s);
+  int gpt_latent_stream_close(hipStream_t s);
+  // gpt_layers_packed with kv_rows_append + attention_append in place of attention_varlen: h fp32 [M, D] holds the chunk's rows
+  // (sequence b's at rows app.q_off[b] ..; rows that belong to no sequence are carried along and ignored)
+  int gpt_layers_append(float* h, int M, const AppendArgs& app, hipStream_t s);
+  int latent_stream_pass(const int* rd_host, int M, const AppendArgs& app, const int* out_row, const int* out_n, long Ttot, void* latent_out,
+                         hipStream_t s);
   // lens_host (optional, [B], each in [1, T]): a padded ragged batch - item b is a latent of lens_host[b] frames, whatever its rows
   // behind them hold; its waveform is that of the item alone, zeros from sample lens_host[b] * up on
   int bigvgan(const void* latent, const float* spk, int B, int T, float* wav, hipStream_t s, const int* lens_host = nullptr);

@@ -17,6 +17,7 @@ Engine::~Engine() {
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (ksplit_ws) (void)hipFree(ksplit_ws);
+  if (lstream.hist) (void)hipFree(lstream.hist);
   if (d.graph) (void)hipGraphExecDestroy(d.graph);
   if (d.graphK) (void)hipGraphExecDestroy(d.graphK);
 }

@@ -156,4 +156,48 @@ bool attention_varlen_mfma_supported(const VarlenArgs& a, int dt);  // type, hea
 int attention_varlen_which(const VarlenArgs& a, int dt);            // 1 / 2: the dispatcher's pick (ITTS_ATTN_SIMPLE honoured), no launch
 int attention_varlen(const VarlenArgs& a, int dt, int kernel, hipStream_t s);  // the named kernel runs or nothing does
 
+// ---- causal self-attention for APPENDED rows (attention_append.hip; the incremental packed latent pass) ----
+// Sequence b: its n_new[b] new queries are positions pos0[b] .. pos0[b] + n_new[b] - 1, rows q_off[b] .. of q and o (the chunk's
+// buffers; q_off[b + 1] - q_off[b] >= n_new[b]); its keys / values are rows 0 .. pos0[b] + n_new[b] - 1 of its block of a K/V history,
+// which starts at row kv_off[b] of k / v and holds kv_off[b + 1] - kv_off[b] rows - the new rows' k / v already written.  Query at
+// position i sees keys 0 .. i.  A delivered row has the bits attn_varlen_* of the same family gives it in a pass over the complete
+// sequence: the query tiles stay aligned to the sequence's key 0, rows of a tile in front of pos0 are never stored, no key row at or
+// behind pos0 + n_new is read.  n_new[b] = 0 leaves sequence b alone.  The four arrays travel by value (host-checked, no upload).
+struct AppendArgs {
+  const void* q = nullptr;
+  const void* k = nullptr;
+  const void* v = nullptr;
+  void* o = nullptr;
+  int ldq = 0, ldk = 0, ldv = 0, ldo = 0;
+  float scale = 1.f;
+  int H = 1, dqk = 64, dv = 64, nseq = 0;
+  int q_off[VARLEN_MAX_SEQ + 1] = {0};
+  int kv_off[VARLEN_MAX_SEQ + 1] = {0};
+  int pos0[VARLEN_MAX_SEQ + 1] = {0};
+  int n_new[VARLEN_MAX_SEQ + 1] = {0};
+};
+// why the call cannot run (null = it can): host memory only, no HIP call (append_check.cpp).  kernel 0 = the dispatcher, 1 =
+// attn_append_simple_kernel, 2 = attn_append_mfma_kernel (then also attention_append_mfma_supported)
+const char* attention_append_refusal(const AppendArgs& a, int dt, int kernel);
+bool attention_append_mfma_supported(const AppendArgs& a, int dt);  // attention_varlen_mfma_supported's rule: never a length or a count
+int attention_append_which(const AppendArgs& a, int dt);            // 1 / 2: the dispatcher's pick (ITTS_ATTN_SIMPLE honoured), no launch
+int attention_append(const AppendArgs& a, int dt, int kernel, hipStream_t s);  // the named kernel runs or nothing does
+// The history write that goes in front of it: columns [0, wk) of ksrc row q_off[b] + r go to k row kv_off[b] + pos0[b] + r, columns
+// [0, wv) of vsrc likewise to v, r < n_new[b] (a.k / a.v are written; a.q / a.o / H / dqk / dv are not used).  fp32 or the 16-bit
+// type, no conversion.  why it cannot run: kv_rows_append_refusal (host only).
+const char* kv_rows_append_refusal(const AppendArgs& a, const void* ksrc, const void* vsrc, int lds, int wk, int wv, int dt);
+int kv_rows_append(const AppendArgs& a, const void* ksrc, const void* vsrc, int lds, int wk, int wv, int dt, hipStream_t s);
+
+// ---- the latent stream's argument checks (append_check.cpp): host memory only, no HIP call ----
+// The state a stream entry judges a call against; Engine keeps one (engine.h LatentStream).
+struct LatentStreamState {
+  bool open = false;
+  int nseq = 0, max_codes = 0, number_mel_codes = 0;
+  const int* done = nullptr;  // [nseq] codes taken so far
+};
+const char* latent_stream_open_refusal(const LatentStreamState& st, const void* cond, const int32_t* cond_index, int n_cond,
+                                       const int32_t* text_ids, const int32_t* text_lens, int nseq, int max_codes, int max_text_tokens,
+                                       int max_mel_tokens, int number_text_tokens);
+const char* latent_stream_append_refusal(const LatentStreamState& st, const int32_t* codes, const int32_t* counts, const void* latent_out);
+
 }  // namespace itts

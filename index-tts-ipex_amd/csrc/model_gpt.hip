@@ -2486,6 +2486,251 @@ int Engine::gpt_latent_packed(const float* cond_dev, const int32_t* text_ids, co
   return OK;
 }
 
+// ---- the incremental packed latent pass (engine.h LatentStream) ----
+
+// gpt_layers_packed over the chunk's rows alone: every row-wise step is the packed pass's on those rows; each layer's k / v of the new
+// rows go to the history (kv_rows_append) and the attention reads the history (attention_append, the family fixed at open)
+int Engine::gpt_layers_append(float* h, int M, const AppendArgs& app, hipStream_t s) {
+  const itts_config& c = cfg;
+  const int D = c.model_dim, H = c.heads, dh = D / H;
+  void* xn = alloc((size_t)M * D * es);
+  void* qkv = alloc((size_t)M * 3 * D * es);
+  void* ctx = alloc((size_t)M * D * es);
+  void* act = alloc((size_t)M * 4 * D * es);
+  if (!dry) ITTS_HIP_CHECK(hipMemsetAsync(ctx, 0, (size_t)M * D * es, s));  // rows of no sequence: the attention never stores them
+  AppendArgs a = app;
+  a.q = qkv;
+  a.o = ctx;
+  a.H = H;
+  a.dqk = a.dv = dh;
+  a.ldq = 3 * D;
+  a.ldk = a.ldv = 2 * D;
+  a.ldo = D;
+  a.scale = 1.f / std::sqrt((float)dh);
+  const size_t layer_bytes = (size_t)lstream.nseq * lstream.cap * 2 * D * es;
+  for (int l = 0; l < c.layers; ++l) {
+    const GptLayerW& L = gpt.layers[l];
+    a.k = (const char*)lstream.hist + l * layer_bytes;
+    a.v = (const char*)a.k + (size_t)D * es;
+    ITTS_TRY(ln(xn, adt, h, F32, L.ln1, M, D, s));
+    ITTS_TRY(lin(qkv, adt, xn, adt, D, L.attn, M, 3 * D, s));
+    K(kv_rows_append(a, (const char*)qkv + (size_t)D * es, (const char*)qkv + (size_t)2 * D * es, 3 * D, D, D, adt, s));
+    K(attention_append(a, adt, lstream.kernel, s));
+    ITTS_TRY(lin(h, F32, ctx, adt, D, L.proj, M, D, s, ACT_NONE, h, D));
+    ITTS_TRY(ln(xn, adt, h, F32, L.ln2, M, D, s));
+    ITTS_TRY(lin(act, adt, xn, adt, D, L.fc, M, 4 * D, s, ACT_GELU_NEW));
+    ITTS_TRY(lin(h, F32, act, adt, 4 * D, L.proj2, M, D, s, ACT_NONE, h, D));
+  }
+  return OK;
+}
+
+// embedding of the chunk's M rows, the blocks, then ln_f -> final_norm -> cast of out_n[b] rows from chunk row out_row[b] of every
+// sequence, contiguously (what gpt_latent_packed does with a sentence's mel rows).  rd_host = nullptr: the sizing run of open.
+int Engine::latent_stream_pass(const int* rd_host, int M, const AppendArgs& app, const int* out_row, const int* out_n, long Ttot,
+                               void* latent_out, hipStream_t s) {
+  const int D = cfg.model_dim;
+  PackedPass packed(*this);
+  auto body = [&]() -> int {
+    RowDesc* rd_dev = (RowDesc*)alloc((size_t)M * sizeof(RowDesc));
+    float* h = (float*)alloc((size_t)M * D * 4);
+    float* hn = (float*)alloc((size_t)Ttot * D * 4);
+    if (!dry) {
+      ITTS_HIP_CHECK(hipMemcpyAsync(rd_dev, rd_host, (size_t)M * sizeof(RowDesc), hipMemcpyHostToDevice, s));
+      if (adt == F32)
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, h, rd_dev, lstream.cond,
+                           (const float*)gpt.text_emb, (const float*)gpt.text_pos, (const float*)gpt.mel_emb,
+                           (const float*)gpt.mel_pos, D);
+      else
+        hipLaunchKernelGGL(gpt_embed_rows_kernel<bf16_t>, dim3((unsigned)M), dim3(256), 0, s, h, rd_dev, lstream.cond,
+                           (const bf16_t*)gpt.text_emb, (const bf16_t*)gpt.text_pos, (const bf16_t*)gpt.mel_emb,
+                           (const bf16_t*)gpt.mel_pos, D);
+      ITTS_HIP_CHECK(hipGetLastError());
+    }
+    ITTS_TRY(gpt_layers_append(h, M, app, s));
+    long off = 0;
+    for (int b = 0; b < app.nseq; ++b) {
+      if (out_n[b] < 1) continue;
+      K(double_ln(hn + off * D, h + (size_t)out_row[b] * D, gpt.ln_f.g, gpt.ln_f.b, gpt.final_norm.g, gpt.final_norm.b, out_n[b], D,
+                  1e-5f, s));
+      off += out_n[b];
+    }
+    K(cast_copy(latent_out, adt, hn, F32, Ttot * D, s));
+    return OK;
+  };
+  if (!rd_host) {  // open: size the scratch for the largest pass this stream can ask for, so that no append allocates
+    dry = true;
+    ws_reset();
+    const int st = body();
+    dry = false;
+    ITTS_TRY(st);
+    return ws_reserve(ws_off + 4096, s);
+  }
+  return two_pass(body, s);
+}
+
+int Engine::gpt_latent_stream_open(const float* cond_dev, const int32_t* cond_index, int n_cond, const int32_t* text_ids, const int* Ls,
+                                   int nseq, int max_codes, hipStream_t s) {
+  if (!finalized || !gpt.ok) {
+    set_error("itts_gpt_latent_stream_open: GPT weights not bound");
+    return E_STATE;
+  }
+  const itts_config& c = cfg;
+  LatentStream& st = lstream;
+  LatentStreamState view;
+  view.open = st.open;
+  if (const char* why = latent_stream_open_refusal(view, cond_dev, cond_index, n_cond, text_ids, Ls, nseq, max_codes, c.max_text_tokens,
+                                                   c.max_mel_tokens, c.number_text_tokens)) {
+    set_error(std::string("itts_gpt_latent_stream_open: ") + why);
+    return E_INVALID;
+  }
+  const int D = c.model_dim, nl = c.cond_latents, H = c.heads, dh = D / H;
+  // gpt_latent_packed's rule: the matrix-core GEMM of the pinned selector needs 16 rows, and so does every append (the re-run rule)
+  if (!(adt == F32 || force_simple || nl + 6 >= 16)) {
+    set_error("itts_gpt_latent_stream_open: a 16-bit engine needs cond_latents >= 10");
+    return E_INVALID;
+  }
+  // the attention family of the packed pass on this engine (its qkv: 256-byte aligned, ld 3 D) - the stream takes the same one
+  VarlenArgs va;
+  va.q = (const void*)(uintptr_t)0x1000;
+  va.k = (const char*)va.q + (size_t)D * es;
+  va.v = (const char*)va.q + (size_t)2 * D * es;
+  va.dqk = va.dv = dh;
+  va.ldq = va.ldk = va.ldv = 3 * D;
+  const int kernel = force_simple ? 1 : attention_varlen_which(va, adt);
+  AppendArgs pa;  // ... and it has to be able to read the history's layout (k | v rows of 2 D, 256-byte aligned)
+  pa.q = va.q, pa.k = va.q, pa.v = va.k;
+  pa.dqk = pa.dv = dh;
+  pa.ldq = 3 * D, pa.ldk = pa.ldv = 2 * D;
+  if (kernel == 2 && !attention_append_mfma_supported(pa, adt)) {
+    set_error("itts_gpt_latent_stream_open: the packed pass runs attn_varlen_mfma on this engine, attn_append_mfma cannot read the history layout");
+    return E_INVALID;
+  }
+  int pmax = 0;
+  long rows_max = 0;
+  std::vector<int> prefix(nseq);
+  std::vector<std::vector<int>> rd(nseq);
+  long to = 0;
+  for (int b = 0; b < nseq; ++b) {
+    const int L = Ls[b], cb = cond_index ? cond_index[b] : 0;
+    prefix[b] = nl + L + 2;
+    pmax = std::max(pmax, prefix[b]);
+    rows_max += prefix[b] + max_codes;
+    std::vector<int>& r = rd[b];
+    r.reserve((size_t)(prefix[b] + 1 + max_codes) * 4);
+    auto push = [&r](int kind, int a0, int b0) { r.insert(r.end(), {kind, a0, b0, 0}); };
+    for (int i = 0; i < nl; ++i) push(1, cb * nl + i, 0);
+    push(2, c.start_text_token, 0);
+    for (int i = 0; i < L; ++i) push(2, text_ids[to + i], i + 1);
+    push(2, c.stop_text_token, L + 1);
+    push(3, c.start_mel_token, 0);
+    to += L;
+  }
+  if (rows_max + 16 >= (1L << 24)) {
+    set_error("itts_gpt_latent_stream_open: more than 2^24 rows in one pass");
+    return E_INVALID;
+  }
+  const int cap = pmax + max_codes;
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));
+  void* hist = nullptr;
+  ITTS_TRY(dev_alloc(&hist, (size_t)c.layers * nseq * cap * 2 * D * es));
+  st.nseq = nseq, st.max_codes = max_codes, st.cap = cap, st.kernel = kernel, st.hist = hist, st.cond = cond_dev;
+  st.prefix = prefix;
+  st.done.assign(nseq, 0);
+  st.computed.assign(nseq, 0);
+  st.rd = std::move(rd);
+  // the scratch of the largest pass: every sequence's first append carrying all its codes at once
+  AppendArgs none;
+  none.nseq = nseq;
+  std::vector<int> zero(nseq, 0);
+  const int status = latent_stream_pass(nullptr, (int)rows_max + 16, none, zero.data(), zero.data(), (long)nseq * max_codes, nullptr, s);
+  if (status != OK) {
+    (void)hipFree(hist);
+    st.hist = nullptr;
+    return status;
+  }
+  st.open = true;
+  return OK;
+}
+
+int Engine::gpt_latent_stream_append(const int32_t* codes, const int* counts, void* latent_out, hipStream_t s) {
+  LatentStream& st = lstream;
+  LatentStreamState view;
+  view.open = st.open, view.nseq = st.nseq, view.max_codes = st.max_codes, view.number_mel_codes = cfg.number_mel_codes;
+  view.done = st.done.data();
+  if (const char* why = latent_stream_append_refusal(view, codes, counts, latent_out)) {
+    set_error(std::string("itts_gpt_latent_stream_append: ") + why);
+    return E_INVALID;
+  }
+  const int nseq = st.nseq;
+  // the rows of this call: sequence b's new positions [computed, prefix + done + count) - the row of a code is computed by the append
+  // that brings the NEXT code's latent (latent row j reads the start token and codes < j), so a first append carries the prefix, the
+  // start-mel row and all but its last code, a later one the held code and all but its last
+  AppendArgs app;
+  app.nseq = nseq;
+  std::vector<int> out_n(nseq, 0), out_row(nseq, 0);
+  long co = 0, Ttot = 0, M = 0;
+  for (int b = 0; b < nseq; ++b) {
+    const int n = counts[b];
+    for (int i = 0; i < n; ++i) st.rd[b].insert(st.rd[b].end(), {3, codes[co + i], st.done[b] + i + 1, 0});
+    co += n;
+    app.kv_off[b] = b * st.cap;
+    app.pos0[b] = st.computed[b];
+    app.n_new[b] = n > 0 ? st.prefix[b] + st.done[b] + n - st.computed[b] : 0;
+    out_n[b] = n;
+    M += app.n_new[b];
+    Ttot += n;
+  }
+  app.kv_off[nseq] = nseq * st.cap;
+  if (Ttot == 0) return OK;
+  // The 16-row rule: below 16 GEMM rows the pinned selector of a 16-bit engine changes family, and with it the bits.  A short call
+  // re-runs the last rows it already computed (their history rows are rewritten with the same bits, their outputs dropped); where a
+  // sequence has too few of those, zero rows that belong to no sequence fill the rest (every step outside the attention is row-wise).
+  long pad = 0;
+  if (adt != F32 && !force_simple && M < 16) {
+    long need = 16 - M;
+    for (int b = 0; b < nseq && need > 0; ++b) {
+      if (app.n_new[b] < 1) continue;
+      const int back = (int)std::min<long>(need, app.pos0[b]);
+      app.pos0[b] -= back, app.n_new[b] += back;
+      need -= back;
+    }
+    M = 16 - need;
+    pad = need;
+  }
+  std::vector<int> rd((size_t)(M + pad) * 4, 0);  // (kind 0 = a zero row)
+  long row = 0;
+  for (int b = 0; b < nseq; ++b) {
+    app.q_off[b] = (int)row;
+    if (app.n_new[b] > 0) {
+      std::copy(st.rd[b].begin() + (size_t)app.pos0[b] * 4, st.rd[b].begin() + (size_t)(app.pos0[b] + app.n_new[b]) * 4, rd.begin() + row * 4);
+      out_row[b] = (int)row + st.prefix[b] + st.done[b] - app.pos0[b];  // latent row j is position prefix + j
+    }
+    row += app.n_new[b];
+  }
+  app.q_off[nseq] = (int)row;
+  const int status = latent_stream_pass(rd.data(), (int)(M + pad), app, out_row.data(), out_n.data(), Ttot, latent_out, s);
+  if (status != OK) {  // the codes of a failed call are not taken
+    for (int b = 0; b < nseq; ++b) st.rd[b].resize((size_t)(st.prefix[b] + 1 + st.done[b]) * 4);
+    return status;
+  }
+  ITTS_HIP_CHECK(hipStreamSynchronize(s));  // rd is a host buffer
+  for (int b = 0; b < nseq; ++b)
+    if (counts[b] > 0) {
+      st.done[b] += counts[b];
+      st.computed[b] = st.prefix[b] + st.done[b];
+    }
+  return OK;
+}
+
+int Engine::gpt_latent_stream_close(hipStream_t s) {
+  LatentStream& st = lstream;
+  if (!st.open) return OK;
+  (void)s;  // every append ends with a synchronise of its stream: nothing in flight reads the history (hipFree waits for the device anyway)
+  if (st.hist) ITTS_HIP_CHECK(hipFree(st.hist));
+  st = LatentStream();
+  return OK;
+}
+
 int Engine::gpt_latent(const float* cond_dev, const int32_t* text_ids, int L, const int32_t* codes, int T,
                        void* latent_out, hipStream_t s) {
   return gpt_latent_batch(cond_dev, text_ids, &L, codes, &T, 1, latent_out, s);

@@ -48,7 +48,36 @@ def build_parser():
     p.add_argument("--packed-vocoder", action="store_true", default=False,
                    help="batched synthesis (IndexTTS.infer_batch): the vocoder runs over the sentences back to back as one item without "
                         "padding, one pass per decode group under mixed batches; ITTS_PACKED_VOCODER=0 / 1 overrides")
+    p.add_argument("--stream", action="store_true", default=False,
+                   help="synthesize with IndexTTS.infer_stream (one beam): audio chunks arrive while a sentence still decodes; writes the "
+                        "same file and prints the time to the first chunk")
+    p.add_argument("--chunk-frames", type=int, default=None, metavar="N",
+                   help="with --stream: latent frames per audio chunk (1 frame = 1024 samples); unset: ITTS_STREAM_CHUNK, else the default")
     return p
+
+
+def stream_to_file(tts, a):
+    """--stream: the chunks of infer_stream, written as one wav file; -> seconds to the first chunk"""
+    import time
+
+    import numpy as np
+    from scipy.io import wavfile
+
+    t0 = time.perf_counter()
+    first, parts = None, []
+    for _, pcm in tts.infer_stream(audio_prompt=a.voice, text=a.text.strip(), chunk_frames=a.chunk_frames):
+        if first is None:
+            first = time.perf_counter() - t0
+        parts.append(pcm)
+    total = time.perf_counter() - t0
+    wav = np.concatenate(parts, 0)
+    if os.path.isfile(a.output_path):
+        os.remove(a.output_path)
+    if os.path.dirname(a.output_path):
+        os.makedirs(os.path.dirname(a.output_path), exist_ok=True)
+    wavfile.write(a.output_path, 24000, wav)
+    print(f">> streamed {len(parts)} chunks: first chunk after {first:.3f} s, all after {total:.3f} s; generated audio: {wav.shape[0] / 24000:.2f} s")
+    return first
 
 
 def main():
@@ -73,6 +102,9 @@ def main():
                    wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler, retire_rows=a.retire_rows,
                    engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder, admit_rows=a.admit_rows, retire_beams=a.retire_beams,
                    packed_latent=a.packed_latent, admit_beams=a.admit_beams, packed_vocoder=a.packed_vocoder)
+    if a.stream:
+        stream_to_file(tts, a)
+        return
     tts.infer(audio_prompt=a.voice, text=a.text.strip(), output_path=a.output_path)
 
 

@@ -65,6 +65,9 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     sentence's waveform has the same bits whoever shares its pass) where it otherwise calls Engine.bigvgan_grouped; with
     `mixed_batch` the utterances and voices of a decode group then share ONE vocoder pass instead of one set of passes per
     utterance.  It takes precedence over `ragged_vocoder`.  `infer` / `infer_fast` are not affected.
+  * `infer_stream(...)` (not in the reference) is `infer` as a GENERATOR of (24000, int16 [n, 1]) chunks: a sentence's
+    audio starts to arrive while its codes are still being decoded.  One beam only.  `stream_chunk_frames=N` holds the default
+    chunk size in latent frames (ITTS_STREAM_CHUNK overrides it).  `infer` / `infer_fast` / `infer_batch` are not affected.
 There is no CPU fallback: without a GPU / libitts_hip.so construction raises."""
 from __future__ import annotations
 
@@ -91,7 +94,7 @@ class IndexTTS:
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
                  mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False,
-                 packed_vocoder=False):
+                 packed_vocoder=False, stream_chunk_frames=None):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -127,6 +130,8 @@ class IndexTTS:
         self._admit_told = False
         self.packed_latent = bool(packed_latent)  # infer_batch: the latent pass on packed rows, one per decode group (ITTS_PACKED_LATENT overrides)
         self.packed_vocoder = bool(packed_vocoder)  # infer_batch: the vocoder over sentences back to back, one pass per decode group (ITTS_PACKED_VOCODER overrides)
+        # infer_stream: latent frames per audio chunk (1 frame = 1024 samples); None: infer_core.STREAM_CHUNK_FRAMES; ITTS_STREAM_CHUNK overrides
+        self.stream_chunk_frames = None if stream_chunk_frames is None else max(1, int(stream_chunk_frames))
         self.kv_fp8 = bool(kv_fp8)  # fp8-e4m3 K/V cache of the decode steps: either 16-bit engine
         if self.kv_fp8 and not self.is_fp16:
             raise ValueError("kv_fp8=True needs is_fp16=True: the fp8 K/V cache is a mode of the 16-bit engines, not the fp32 one")
@@ -528,6 +533,77 @@ class IndexTTS:
               audio_prompt=None, **generation_kwargs):
         return self._synthesize(self._prompt(prompt_mel, audio_prompt), text, output_path, max_text_tokens_per_sentence,
                                 10 ** 9, verbose, generation_kwargs, fast=False)
+
+    def infer_stream(self, prompt_mel=None, text=None, audio_prompt=None, chunk_frames=None, first_chunk_frames=None,
+                     max_text_tokens_per_sentence=120, check_every=16, **generation_kwargs):
+        """`infer` as a generator of (24000, int16 [n, 1]) chunks (not in the reference; opt-in).  The sentences run
+        one after another, each on one decode row (at batch 1 the decode step stays on the persistent engine).  Within a sentence
+        the codes are fetched every `check_every` decode steps (Engine.generate_stream), cleaned by the causal silence rule
+        (infer_core.stream_clean), turned into latent rows by the incremental packed latent pass (Engine.latent_stream) and
+        vocoded window by window (Engine.bigvgan_stream): frames [a, b) are emitted as soon as b + R latent rows exist, R =
+        Engine.vocoder_reach() - once `first_chunk_frames` frames are final for the sentence's first chunk, `chunk_frames` for the
+        later ones; a sentence's end flushes the rest.  Decode steps, latent appends and vocoder windows alternate on the engine's one
+        stream; the speaker encoder is joined before the first decode step.  Every chunk is final: the concatenation is, sample for
+        sample, the per-sentence composition generate -> stream_clean -> latent_packed -> bigvgan_packed (`infer_batch` on an
+        object with packed_latent + packed_vocoder, where stream_clean and remove_long_silence agree - see stream_clean).
+        chunk_frames: None = the object's default - ITTS_STREAM_CHUNK, else IndexTTS(stream_chunk_frames=..), else infer_core.STREAM_CHUNK_FRAMES;
+        first_chunk_frames: None = min(infer_core.STREAM_FIRST_CHUNK_FRAMES, chunk_frames).  generation kwargs as `infer`, with
+        num_beams defaulting to 1 - beams are refused (ValueError, at the call): a beam's prefix is not final - plus `seed`
+        (sentence k draws from seed + k; None: drawn from torch's global RNG as `infer` does)."""
+        kw = dict(generation_kwargs)
+        kw.setdefault("num_beams", 1)
+        seed = kw.pop("seed", None)
+        g = self._gen_kwargs(kw)
+        if g["num_beams"] is not None and int(g["num_beams"]) > 1:
+            raise ValueError("infer_stream: num_beams > 1 cannot stream (a beam's prefix is not final); use infer / infer_batch")
+        wide = self.wide_sampler or os.environ.get("ITTS_WIDE_SAMPLER") or "host"
+        if g["do_sample"] and not 1 <= int(g["top_k"] or 0) <= 128 and wide != "device":
+            raise ValueError("infer_stream: top_k outside 1 .. 128 takes the host-side token choice, which cannot stream "
+                             "(IndexTTS(wide_sampler='device') runs it on the device)")
+        if chunk_frames is None:  # the object's default, which the environment overrides
+            chunk_frames = os.environ.get("ITTS_STREAM_CHUNK") or self.stream_chunk_frames or infer_core.STREAM_CHUNK_FRAMES
+        chunk = max(1, int(chunk_frames))
+        first = max(1, int(first_chunk_frames)) if first_chunk_frames is not None else min(infer_core.STREAM_FIRST_CHUNK_FRAMES, chunk)
+        mel = self._prompt(prompt_mel, audio_prompt)
+        sents = self._sentences_to_ids(text, max_text_tokens_per_sentence)
+        if not sents:
+            raise RuntimeError("IndexTTS: the text produced no sentences (empty input)")
+        return self._infer_stream(mel, sents, g, seed, chunk, first, int(check_every), wide)
+
+    @torch.no_grad()
+    def _infer_stream(self, mel, sents, g, seed, chunk, first, check_every, wide):
+        def pcm(wav):
+            return self._to_int16_range(wav).type(torch.int16).numpy().T  # what _finish does with a whole utterance
+
+        with self.engine.lock:
+            spk = self.engine.ecapa(mel.transpose(1, 2), overlap=True)
+            cond = self.gpt.get_conditioning(mel)
+            for k, sent in enumerate(sents):
+                sample_kw = infer_core.sampling_kwargs(g["do_sample"], 1, g["top_k"], g["top_p"], g["temperature"], g["typical_sampling"],
+                                                       g["typical_mass"], g["length_penalty"])
+                if seed is not None and "seed" in sample_kw:
+                    sample_kw["seed"] = int(seed) + k
+                for name in ("num_beams", "length_penalty"):
+                    sample_kw.pop(name, None)
+                ids = infer_core.pad_tokens_cat([sent], self.cfg.gpt.stop_text_token)
+                voc = self.engine.bigvgan_stream(spk, chunk, first)
+                state, last_code = None, None
+                with self.engine.latent_stream(cond, [sent], g["max_mel_tokens"]) as ls:
+                    for new in self.engine.generate_stream(cond, ids, g["max_mel_tokens"], repetition_penalty=g["repetition_penalty"],
+                                                           check_every=check_every, wide_sampler=wide, **sample_kw):
+                        last_code = int(new[-1])
+                        kept, state = infer_core.stream_clean(new, self.stop_mel_token, state=state)
+                        if not len(kept):
+                            continue
+                        wav = voc.push(ls.append([kept])[0])
+                        if wav.shape[-1]:
+                            yield (24000, pcm(wav))
+                if last_code != self.stop_mel_token:
+                    warnings.warn(f"WARN: generation stopped due to exceeding `max_mel_tokens` ({g['max_mel_tokens']}). "
+                                  "Consider reducing `max_text_tokens_per_sentence` or increasing `max_mel_tokens`.", RuntimeWarning)
+                wav = voc.push(None, last=True)
+                if wav.shape[-1]:
+                    yield (24000, pcm(wav))
 
     def infer_fast(self, prompt_mel=None, text=None, output_path=None, max_text_tokens_per_sentence=120, verbose=False,
                    sentences_bucket_max_size=4, audio_prompt=None, **generation_kwargs):

@@ -662,6 +662,75 @@ class Engine:
             n = max(n, int(hit[0]) + 1 if len(hit) else step)
         return codes[:, :n]
 
+    def generate_stream(self, cond: torch.Tensor, text_ids: np.ndarray, max_gen: int, repetition_penalty: float = 10.0,
+                        check_every: int = 16, do_sample: bool = False, top_k: int = 30, top_p: float = 0.8, temperature: float = 1.0,
+                        seed: Optional[int] = None, uniforms: Optional[np.ndarray] = None, num_beams: int = 1,
+                        typical_mass: float = 0.0, wide_sampler: Optional[str] = None, input_tokens=None, suppress_stop: bool = False):
+        """The _generate_once loop as a GENERATOR, for one row and one beam: after the prefill and after every `check_every`
+        decode steps it fetches and yields the codes decoded since the last yield (int64 [n], the stop token included; the
+        generation ends behind it or at max_gen).  Greedy, device sampling (top_k 1 .. 128, or any top_k with
+        wide_sampler="device"), typical filtering and the repetition penalty; the same prefill, steps and uniforms as
+        generate(), so the codes yielded are generate()'s.  Between two yields the engine's stream is free for the caller's
+        latent appends and vocoder windows (no decode buffer moves; nothing runs beside a decode step).
+        ValueError: num_beams > 1 (a beam's prefix is not final), host-side sampling (top_k outside 1 .. 128 without
+        wide_sampler="device"), input_tokens, more than one row.  Checked here, before the generator is returned.
+        suppress_stop: the stop token cannot be chosen (bench.py's forced length): the generation runs to max_gen."""
+        ids = np.ascontiguousarray(text_ids, dtype=np.int32)
+        ids = ids[None] if ids.ndim == 1 else ids
+        if ids.shape[0] != 1:
+            raise ValueError(f"generate_stream: one row, not {ids.shape[0]}")
+        if num_beams is not None and int(num_beams) > 1:
+            raise ValueError("generate_stream: num_beams > 1 cannot stream - a beam's prefix is not final until the search ends")
+        if input_tokens is not None:
+            raise ValueError("generate_stream: input_tokens are not supported")
+        if wide_sampler is None:
+            wide_sampler = os.environ.get("ITTS_WIDE_SAMPLER") or "host"
+        if do_sample and (not top_k or int(top_k) < 1 or int(top_k) > 128) and wide_sampler != "device":
+            raise ValueError("generate_stream: top_k outside 1 .. 128 takes the host-side token choice, which cannot stream; pass "
+                             "wide_sampler='device' for the whole-vocabulary device sampler")
+        max_gen = int(max_gen)
+        if do_sample and uniforms is None:
+            uniforms = np.random.default_rng(seed).random((max_gen, 1), dtype=np.float32)
+        return self._generate_stream(cond, ids, max_gen, float(repetition_penalty), max(1, int(check_every)), bool(do_sample),
+                                     int(top_k or 0), top_p, temperature, uniforms, float(typical_mass or 0.0), bool(suppress_stop))
+
+    def _generate_stream(self, cond, ids, max_gen, repetition_penalty, check_every, do_sample, top_k, top_p, temperature, uniforms,
+                         typical_mass, suppress_stop=False):
+        stop = self.ccfg.stop_mel_token
+        sent = 0  # codes yielded so far
+        for attempt in (0, 1):
+            try:
+                if typical_mass:
+                    self._ck(self.lib.itts_gpt_set_typical(self.h, typical_mass), "gpt_set_typical")
+                if do_sample:
+                    self.set_sampling(True, top_k, top_p, temperature, uniforms)
+                try:
+                    self.prefill(cond, ids, max_gen, repetition_penalty, suppress_stop)
+                    while True:
+                        step, unf = self.status()
+                        row = self.fetch()[0, :step].astype(np.int64)
+                        hit = np.nonzero(row == stop)[0]
+                        end = int(hit[0]) + 1 if len(hit) else step
+                        if end > sent:
+                            new, sent = row[sent:end], end
+                            yield new
+                        if unf == 0 or len(hit) or step >= max_gen:
+                            break
+                        self.decode(min(check_every, max_gen - step))
+                    self._exit()
+                finally:
+                    if typical_mass:
+                        self._ck(self.lib.itts_gpt_set_typical(self.h, 0.0), "gpt_set_typical")
+                    if do_sample:
+                        self.set_sampling(False)
+                return
+            except L.HandoffTimeout as e:
+                # as generate(): the library has switched this engine object to the launch path; the utterance is decoded again from
+                # its prefill with the same draws, and the codes already yielded are skipped
+                if attempt:
+                    raise
+                _warn_downgrade(e)
+
     def _generate_admit(self, cond, text_ids, max_gen, table, scalar, uniforms, slots, admit_min, suppress_stop, check_every,
                         retire_rows):
         """generate(slots=..): one generation of `slots` rows over all N requests (infer_core.AdmitScheduler says who starts and
@@ -989,6 +1058,33 @@ class Engine:
         self._exit()
         return [out[int(starts[i]):int(starts[i + 1])].unsqueeze(0) for i in range(len(cl))]
 
+    def latent_stream(self, cond: torch.Tensor, texts, max_codes: int, cond_index=None) -> "LatentStream":
+        """The INCREMENTAL packed latent pass (itts_gpt_latent_stream_*; opt-in): the sentences of latent_packed opened together and
+        fed their codes in pieces.  -> an object with .append(list of code arrays, one per sentence, empty = leave it alone) ->
+        list of latents [1, n_i, D] for the codes just given, and .close(); also a context manager.  After any sequence of appends
+        the rows delivered so far are, bit for bit, the first rows of latent_packed over the final codes.  The engine keeps the
+        K/V history of every computed row from here to close(); one stream per engine.  cond / cond_index as latent_batch;
+        max_codes: the most codes any sentence will be given."""
+        return LatentStream(self, cond, texts, max_codes, cond_index)
+
+    def bigvgan_stream(self, spk: torch.Tensor, chunk_frames: int = 1, first_chunk_frames: Optional[int] = None) -> "VocoderStream":
+        """Streaming vocoder for one sentence of one voice (spk [E] or [1, E]): an object with .push(latent_frames [1, n, D] or
+        [n, D], last=False) -> wav fp32 [1, 1, m * up].  chunk_frames / first_chunk_frames: a push returns nothing (and runs nothing)
+        until that many frames are final (infer_core.StreamWindow; 1 = everything that is final, at every push).  Every push runs bigvgan_packed over one window - the frames not yet sent
+        plus R = infer_core.vocoder_reach(..) frames of context on either side - and returns only samples whose frames lie R away
+        from an artificial window edge, so everything returned is final; the concatenation over the pushes (the last one with
+        last=True) equals bigvgan_packed([whole latent], spk)[0] bit for bit.  No kernel of its own."""
+        return VocoderStream(self, spk, chunk_frames, first_chunk_frames)
+
+    def vocoder_reach(self) -> int:
+        """infer_core.vocoder_reach over this engine's generator: the one-sided reach R of the whole vocoder in latent frames."""
+        from . import infer_core
+
+        c = self.ccfg
+        nu, nr, nd = int(c.bv_num_up), int(c.bv_num_res), int(c.bv_num_dil)
+        return infer_core.vocoder_reach(list(c.bv_up_rates)[:nu], list(c.bv_up_kernels)[:nu], list(c.bv_res_kernels)[:nr],
+                                        [list(c.bv_res_dils[j])[:nd] for j in range(nr)])
+
     def bigvgan(self, latent: torch.Tensor, spk: torch.Tensor) -> torch.Tensor:
         """latent [B, T, D], spk [B, E] -> wav fp32 [B, 1, T*up]."""
         lat = self.to_act(latent)
@@ -1148,6 +1244,105 @@ class Engine:
         self._ck(self.lib.itts_dvae_decode(self.h, c.ctypes.data_as(C.c_void_p), B, T, out.data_ptr(), self._s()), "dvae_decode")
         self._exit()
         return out.transpose(1, 2)
+
+
+class LatentStream:
+    """Engine.latent_stream's object: the engine-side stream state from construction to close()."""
+
+    def __init__(self, eng: Engine, cond: torch.Tensor, texts, max_codes: int, cond_index=None):
+        self.eng = eng
+        ts = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in texts]
+        if not ts:
+            raise ValueError("latent_stream: no texts")
+        D = eng.ccfg.model_dim
+        self.cond = cond.to(device=eng.device, dtype=torch.float32).contiguous().view(-1, D)  # kept: the engine reads it at every first append
+        n_cond, rem = divmod(self.cond.shape[0], eng.ccfg.cond_latents)
+        if rem or n_cond < 1:
+            raise ValueError(f"latent_stream: cond {tuple(cond.shape)} is not a whole number of [{eng.ccfg.cond_latents}, D] blocks")
+        ci = None
+        if cond_index is not None:
+            ci = np.ascontiguousarray(cond_index, dtype=np.int32).reshape(-1)
+            if ci.shape[0] != len(ts):
+                raise ValueError(f"latent_stream: {ci.shape[0]} indices for {len(ts)} sentences")
+        self.n = len(ts)
+        tl = np.asarray([t.shape[0] for t in ts], dtype=np.int32)
+        tcat = np.concatenate(ts)
+        self.open = False
+        eng._enter()
+        eng._ck(eng.lib.itts_gpt_latent_stream_open(eng.h, self.cond.data_ptr(), None if ci is None else ci.ctypes.data_as(C.c_void_p), n_cond,
+                                                    tcat.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p), self.n, int(max_codes),
+                                                    eng._s()), "gpt_latent_stream_open")
+        eng._exit()
+        self.open = True
+
+    def append(self, codes) -> List[torch.Tensor]:
+        eng = self.eng
+        cs = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in codes]
+        if len(cs) != self.n:
+            raise ValueError(f"latent_stream.append: {len(cs)} code arrays for {self.n} sentences")
+        counts = np.asarray([c.shape[0] for c in cs], dtype=np.int32)
+        ccat = np.concatenate(cs) if int(counts.sum()) else np.zeros(1, dtype=np.int32)
+        out = torch.empty(int(counts.sum()), eng.ccfg.model_dim, dtype=eng.tdt, device=eng.device)
+        eng._enter()
+        eng._ck(eng.lib.itts_gpt_latent_stream_append(eng.h, ccat.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                      out.data_ptr() if out.numel() else self.cond.data_ptr(), eng._s()),
+                "gpt_latent_stream_append")
+        eng._exit()
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        return [out[int(starts[i]):int(starts[i + 1])].unsqueeze(0) for i in range(self.n)]
+
+    def close(self):
+        if self.open:
+            self.open = False
+            self.eng._ck(self.eng.lib.itts_gpt_latent_stream_close(self.eng.h), "gpt_latent_stream_close")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VocoderStream:
+    """Engine.bigvgan_stream's object.  State: the latent frames from R in front of the first frame not yet sent (`lo` = that
+    buffer's first frame index) and how many frames were sent."""
+
+    def __init__(self, eng: Engine, spk: torch.Tensor, chunk_frames: int = 1, first_chunk_frames: Optional[int] = None):
+        from . import infer_core
+
+        self.eng = eng
+        self.spk = spk.to(device=eng.device, dtype=torch.float32).reshape(1, -1)
+        self.R = eng.vocoder_reach()
+        self.plan = infer_core.StreamWindow(self.R, chunk_frames, first_chunk_frames)
+        self.buf = None  # [n, D]: frames [plan.lo, plan.have)
+        self.done = False
+
+    def push(self, latent: Optional[torch.Tensor], last: bool = False) -> torch.Tensor:
+        """latent [1, n, D] / [n, D] (n >= 0; None = nothing new) -> the samples that became final, fp32 [1, 1, m * up]"""
+        eng = self.eng
+        if self.done:
+            raise ValueError("bigvgan_stream.push: the stream has ended (last=True was given)")
+        D = eng.ccfg.model_dim
+        new = torch.empty(0, D, dtype=eng.tdt, device=eng.device) if latent is None else eng.to_act(latent).reshape(-1, D)
+        self.buf = new if self.buf is None else torch.cat([self.buf, new], 0)
+        lo, a, b = self.plan.push(int(new.shape[0]), last)  # the window starts at frame lo; frames [a, b) become final
+        self.done = bool(last)
+        up = eng.up_total
+        if b <= a:
+            return torch.empty(1, 1, 0, dtype=torch.float32, device=eng.device)
+        wav = eng.bigvgan_packed([self.buf.unsqueeze(0)], self.spk)[0]
+        out = wav[:, :, (a - lo) * up:(b - lo) * up].clone()
+        keep = self.plan.lo - lo  # frames the window no longer needs
+        if keep > 0:
+            self.buf = self.buf[keep:]
+        return out
 
 
 def _warn_downgrade(err):

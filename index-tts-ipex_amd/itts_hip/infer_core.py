@@ -318,6 +318,109 @@ def packed_vocoder_plan(lengths: Sequence[int], gap: int, max_frames: int = PACK
     return chunks, offsets, frames
 
 
+# ---- streaming synthesis (Engine.bigvgan_stream, IndexTTS.infer_stream) ----
+STREAM_CHUNK_FRAMES = 48        # default frames per chunk (about 2 s of audio): unmeasured, see tools/bench_stream.py
+STREAM_FIRST_CHUNK_FRAMES = 24  # default frames of a sentence's first chunk (about 1 s)
+ACT1D_REACH = 5                 # Activation1d, one side, in samples of its own rate (derived below)
+
+
+def vocoder_reach(up_rates: Sequence[int], up_kernels: Sequence[int], res_kernels: Sequence[int],
+                  res_dils: Sequence[Sequence[int]]) -> int:
+    """The accumulated one-sided reach R of the whole generator in latent frames: frame t of the latent changes no output sample
+    outside frames [t - R, t + R], and whatever lies outside a window [a - R, b + R) changes nothing inside [a, b).  Pure.
+    Unlike packed_vocoder_gap - the LARGEST reach of one layer, enough to keep a neighbour's signal out of one convolution - this
+    is the SUM over the cascade: a layer that reaches e samples to a side at up-sampling rate m adds e / m frames, the sum is
+    rounded up once (a perturbed frame is m whole samples at rate m, so the fractions of the layers add before they are cut).
+      conv_pre (k = 7, pad 3)                                3 samples at rate 1
+      ups[i] (ConvTranspose1d k, stride u, pad p = (k - u) // 2: input i feeds outputs i * u - p .. i * u - p + k - 1)
+                                                             max(p, k - u - p) samples at its OUTPUT rate
+      Activation1d (replicate pad 5 / 5, 12-tap transposed conv stride 2, crop 15 / 15; SnakeBeta; replicate pad 5 / 6, 12-tap conv
+      stride 2): x[i] feeds the 2x samples 2i - 5 .. 2i + 6, and y[t] reads the 2x samples 2t - 5 .. 2t + 6, so x[i] reaches
+      y[i - 5 .. i + 5]                                      5 samples at the stage rate; the replicate clamp at a segment's own end
+                                                             copies the edge sample into those pads, which reaches no further
+      AMP block, kernel ks, per dilation d: Activation1d, conv (ks, dilation d), Activation1d, conv (ks), plus the skip - the
+      longest path                                           sum over d of 5 + d * (ks - 1) / 2 + 5 + (ks - 1) / 2; per stage the
+                                                             deepest branch, i.e. the largest such sum over the kernels
+      activation_post, conv_post (k = 7)                     5 + 3 samples at the output rate
+    IndexTTS-1.5 (rates 4 4 4 4 2 2, kernels 8 8 4 4 4 4, AMP kernels 3 7 11, dilations 1 3 5): 3 + 2/4 + 90/4 + 2/16 + 90/16 +
+    90/64 + 90/256 + 1/512 + 90/512 + 1/1024 + 90/1024 + 8/1024 = 33.8 -> R = 34 frames."""
+    from fractions import Fraction
+
+    reach, rate = Fraction(3), 1
+    for u, k in zip(up_rates, up_kernels):
+        u, k = int(u), int(k)
+        p = (k - u) // 2
+        rate *= u
+        reach += Fraction(max(p, k - u - p, 0), rate)
+        amp = 0
+        for ks, dils in zip(res_kernels, res_dils):
+            ks = int(ks)
+            amp = max(amp, sum(2 * ACT1D_REACH + int(d) * (ks - 1) // 2 + (ks - 1) // 2 for d in dils))
+        reach += Fraction(amp, rate)
+    reach += Fraction(ACT1D_REACH + 3, rate)
+    return int(-(-reach.numerator // reach.denominator))
+
+
+class StreamWindow:
+    """The emit and hold-back arithmetic of one streamed sentence (Engine.bigvgan_stream).  Frames arrive in pieces; a vocoder
+    window is the frames [lo, have) held so far, and frame f of it is FINAL when it lies R frames away from every artificial
+    window edge: f >= lo + R unless lo = 0 (the sentence's true left edge), f < have - R unless the sentence has ended (its true
+    right edge).  lo = max(0, sent - R) keeps exactly the left context the next window needs.
+    push(n, last) -> (lo, a, b): n more frames arrived; run the window [lo, have) and emit frames [a, b) - or nothing (b == a) while
+    fewer than `chunk` frames (`first_chunk` for the sentence's first emission) are final; last=True emits everything left.
+    Everything emitted is final; the emissions are consecutive and, after last, cover [0, have).  Pure host arithmetic."""
+
+    def __init__(self, R: int, chunk: int = 1, first_chunk: int = None):
+        self.R, self.chunk = int(R), max(1, int(chunk))
+        self.first = self.chunk if first_chunk is None else max(1, int(first_chunk))
+        self.have = self.sent = self.lo = 0
+        self.ended = False
+
+    def push(self, n: int, last: bool = False) -> Tuple[int, int, int]:
+        if self.ended or int(n) < 0:
+            raise ValueError("StreamWindow.push: the sentence has ended" if self.ended else "StreamWindow.push: n < 0")
+        self.have += int(n)
+        self.ended = bool(last)
+        lo, a = self.lo, self.sent
+        b = self.have if last else max(a, self.have - self.R)
+        if not last and b - a < (self.first if a == 0 else self.chunk):
+            b = a  # hold back: not a whole chunk yet
+        self.sent = b
+        self.lo = max(0, b - self.R)
+        return lo, a, b
+
+
+def stream_clean(codes, stop_mel_token: int, silent_token: int = 52, max_consecutive: int = 30, state: dict = None):
+    """The causal form of remove_long_silence for ONE row that arrives in pieces: -> (kept codes of this piece, state).  Pass the
+    returned state with the next piece (None = a fresh row).  The row ends at its first stop token (nothing from there on is kept).
+    Silent code i at 0-based position r of its run of silent codes is dropped iff r >= 10 and the silent codes seen so far, itself
+    included, number more than max_consecutive - a decision that needs nothing behind code i, so what was kept stays kept.
+    Where it differs from remove_long_silence: that rule first counts the silent codes of the WHOLE row and, if there are more than
+    max_consecutive, drops every silent code with r >= 10 - also one that came among the row's first max_consecutive silent codes,
+    which the causal rule has already passed on.  So the two differ only for a silent code with r >= 10 among a row's first
+    max_consecutive silent codes, in a row that ends with more than max_consecutive; they agree on every row with at most
+    max_consecutive silent codes and on every row whose runs longer than 10 begin after its max_consecutive-th silent code."""
+    st = dict(state) if state else dict(run=0, silent=0, stopped=False)
+    keep = []
+    for c in np.asarray(codes).reshape(-1):
+        c = int(c)
+        if st["stopped"]:
+            break
+        if c == stop_mel_token:
+            st["stopped"] = True
+            break
+        if c == silent_token:
+            r = st["run"]
+            st["run"] += 1
+            st["silent"] += 1
+            if r >= 10 and st["silent"] > max_consecutive:
+                continue
+        else:
+            st["run"] = 0
+        keep.append(c)
+    return np.asarray(keep, dtype=np.int64), st
+
+
 def env_switch(name: str, setting: bool) -> bool:
     """An A/B switch of IndexTTS: the environment variable overrides the constructor's setting in both directions ("1" on, "0" off);
     unset or anything else leaves the setting."""

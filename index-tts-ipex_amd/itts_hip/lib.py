@@ -145,6 +145,9 @@ _PROTOS = {
     "itts_attention_which": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, i32]),
     "itts_attention_varlen": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
     "itts_attention_varlen_which": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32]),
+    "itts_attention_append": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "itts_attention_append_which": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32]),
+    "itts_kv_rows_append": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "itts_gemv": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp]),
     "itts_gemv_bf16": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "itts_decode_attn": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
@@ -167,6 +170,9 @@ _PROTOS = {
     "itts_gpt_set_sampling_rows": (i32, [vp, C.POINTER(RowSampling), i32, vp, i64]),
     "itts_gpt_latent_batch_cond": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
     "itts_gpt_latent_packed": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
+    "itts_gpt_latent_stream_open": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, vp]),
+    "itts_gpt_latent_stream_append": (i32, [vp, vp, vp, vp, vp]),
+    "itts_gpt_latent_stream_close": (i32, [vp]),
     "itts_engine_create": (i32, [C.POINTER(Config), C.POINTER(vp)]),
     "itts_engine_destroy": (None, [vp]),
     "itts_engine_bind_tensor": (i32, [vp, C.c_char_p, vp, i32, i32, C.POINTER(i64)]),
