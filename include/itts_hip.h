@@ -281,6 +281,16 @@ int itts_decode_attn(void* ctx, int to, const float* qkv, void* kc, void* vc, co
                      int B, int H, int dh, int Smax, int tc, int ctx_tiled, float* part_o, float* part_ml, const uint8_t* anc, int nb,
                      itts_stream stream);
 
+/* The same step for beam rows with the beam GROUP as the unit of work (csrc/decode_attn_group.hip, what itts_gpt_set_group_attn
+ * switches the batched decode step to): one workgroup per (head, batch item) fetches every needed (position, physical row) once and
+ * scores it for all nb beams of the item on the matrix cores.  Arguments as itts_decode_attn without the split partials; the
+ * result is the same attention (another summation order: equal to the 16-bit bounds, not bit for bit), the appended rows are the
+ * same bits.  tc and `to` must be 1 (the 16-bit type of the library), dh 64, 2 <= nb <= 16, B % nb == 0, anc set; ctx row-major
+ * or, ctx_tiled = 1, in MFMA-fragment tiles.  Everything else is refused with an error status and nothing is launched. */
+int itts_decode_attn_group(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                           const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
+                           itts_stream stream);
+
 /* The prefill's K/V cache write (csrc/decode.hip kv_scatter) on caller memory: the k and v thirds of qkv [B][S][3 * H * dh]
  * (type tq) go to rows 0 .. S - 1 of each [Smax][dh] block of kc / vc [B][H][Smax][dh] (type tc), rounded to the cache type
  * (ITTS_FP8: clamped to [-448, 448], then nearest even); rows S .. Smax - 1 are not touched.  (tq, tc): fp32 -> fp32, 16-bit ->
@@ -901,6 +911,16 @@ int itts_gpt_set_kv_fp8(itts_engine* e, int on);
  * path's whole-form attention and the engine read the same cache bytes but sum in another order: results agree to a tolerance,
  * not bit for bit (profiles/engine_kv_fp8.txt). */
 int itts_gpt_set_engine_kv_fp8(itts_engine* e, int on);
+
+/* Opt-in: the decode steps of a beam generation (num_beams > 1) that run on the launch path at more than 6 rows take the grouped
+ * cache attention (itts_decode_attn_group) instead of one workgroup per beam row, on a 16-bit K/V cache.  Both libraries.  Sticky
+ * per engine object, default 0 = every step as before, bit for bit.  Steps on the persistent engine (<= 6 rows), an fp8 cache and
+ * fp32 engines keep their kernels whatever the switch says.  The environment variable ITTS_GROUP_ATTN, read per call, overrides
+ * it in both directions (1: on for every engine, 0: off).  A change re-captures the step.  Results agree with the default path to
+ * the 16-bit bounds, not bit for bit (profiles/group_attn.txt).
+ * itts_gpt_group_attn_used: 1 if the last decode step ran the grouped kernel, else 0 (-1 for a null engine). */
+int itts_gpt_set_group_attn(itts_engine* e, int on);
+int itts_gpt_group_attn_used(itts_engine* e);
 
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);

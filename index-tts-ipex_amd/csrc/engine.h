@@ -129,8 +129,9 @@ struct GraphKey {
   // mixed batch (DecodeState::rows_active): the step launches one sampler kernel per class present (bits ROWCLS_*).  The entries
   // themselves live in device memory behind a pointer that only changes together with dropped graphs
   int rows_active = 0, rows_classes = 0;
+  int group_attn = 0;  // derived: Engine::group_attn_on() - which cache attention kernel a beam step at > 6 rows launches
   bool operator==(const GraphKey& o) const {
-    return rows_active == o.rows_active && rows_classes == o.rows_classes && B == o.B &&Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
+    return group_attn == o.group_attn && rows_active == o.rows_active && rows_classes == o.rows_classes && B == o.B &&Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
            host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample && ct == o.ct &&
            length_penalty == o.length_penalty && typical_mass == o.typical_mass && penalty == o.penalty &&
            suppress_stop == o.suppress_stop && do_sample == o.do_sample && top_k == o.top_k && top_p == o.top_p &&
@@ -234,6 +235,8 @@ struct DecodeState {
   int eng_failed = 0;                    // a hand-off timed out: launch path from then on
   int eng_fp8 = 0;                       // itts_gpt_set_engine_fp8: a model with fp8 GPT weights may use the engine (sticky; default: launch path)
   int eng_kv8 = 0;                       // itts_gpt_set_engine_kv_fp8: a generation with an fp8 K/V cache may use the engine (sticky; default: launch path)
+  int group_attn = 0;                    // itts_gpt_set_group_attn: beam steps at > 6 rows run the grouped cache attention (sticky; default: decode_attn2)
+  int last_grp = 0, graph_grp = 0;       // 1: the last launched / the captured decode step ran decode_attn_group (itts_gpt_group_attn_used)
   int graph_mode = 0;                    // last_mode of the captured step
   float typical_mass = 0.f;                        // TypicalLogitsWarper pre-pass (0 = off)
   float* scores2 = nullptr;                        // [cap_B][V] its output
@@ -457,6 +460,8 @@ struct Engine {
   bool rows_on_mfma(int B) const;  // the batched decode step: weights streamed once, batch on MFMA
   bool engine_usable() const;
   int gpt_set_engine_kv_fp8(int on);  // opt-in: the persistent engine reads and appends an fp8 K/V cache (decode_engine_kernel<.., KV8>)
+  int gpt_set_group_attn(int on);     // opt-in: beam steps on the launch path at > 6 rows run decode_attn_group (decode_attn_group.hip)
+  bool group_attn_on() const;         // the switch as ITTS_GROUP_ATTN (read per call) or the setter says
   bool engine_fp8_model() const;  // every projection of every block and the head carry an fp8 copy + row scales
   int ensure_engine_state(hipStream_t s);
   int engine_check(hipStream_t s);

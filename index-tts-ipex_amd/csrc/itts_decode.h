@@ -267,6 +267,12 @@ constexpr int ATTN_NSPLIT = 4;  // workgroups per (row, head) in the split form 
 int decode_attn2(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
                  const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled = 0,
                  float* part_o = nullptr, float* part_ml = nullptr, const uint8_t* anc = nullptr, int nb = 1);
+// decode_attn_group.hip (opt-in, beams only): the same step with the beam group as the unit - one workgroup per (head, item)
+// fetches every needed (position, physical row) once and scores it for all nb queries on the matrix cores.  16-bit cache and ctx
+// (row-major or tile_off), head dim 64, 2 <= nb <= 16, the ancestry `anc` [2][B][Smax]; no split partials
+int decode_attn_group(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                      const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
+                      const uint8_t* anc, int nb);
 // decode_fused.hip: LN + c_attn projection and the cache attention of one layer in one launch (qkv_attn_fused_kernel)
 bool qkv_attn_fused_supported(const GemvArgs& g, int H, int dh);
 int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* kc, void* vc, const int* len,

@@ -260,6 +260,17 @@ int Engine::gpt_set_engine_kv_fp8(int on) {
   return OK;
 }
 
+// Opt-in (sticky; ITTS_GROUP_ATTN overrides it per call, =0 included): the beam steps of the launch path at > 6 rows run the
+// grouped cache attention (decode_attn_group.hip) on a 16-bit cache.  The switch is part of the graph key: flipping it re-captures.
+int Engine::gpt_set_group_attn(int on) {
+  ds.group_attn = on != 0;
+  return OK;
+}
+bool Engine::group_attn_on() const {
+  const char* ev = getenv("ITTS_GROUP_ATTN");  // read per call, like ITTS_ENGINE_KV_FP8
+  return ev ? atoi(ev) != 0 : ds.group_attn != 0;
+}
+
 int Engine::ensure_engine_state(hipStream_t s) {
   DecodeState& d = ds;
   if (d.eng_gran) return OK;
@@ -1039,6 +1050,7 @@ int Engine::decode_step_launch(hipStream_t s) {
   const bool skinny = rows_on_mfma(B);      // weights once, batch on MFMA
   ds.pend_split = 0;
   ds.last_mode = 0;
+  ds.last_grp = 0;
   int eng_first = 0;
   if (engine_usable()) {  // <= 6 rows: the 24 blocks (+ head, + greedy sampler) as ONE persistent launch
     ITTS_REQUIRE(ds.eng_gran && ds.eng_ctr, "decode engine: state not allocated (prefill first)");
@@ -1111,6 +1123,10 @@ int Engine::decode_step_launch(hipStream_t s) {
   const bool bf_act = skinny || (fast && gemv_bf16_supported(probe));
   probe.K = D;
   const bool bf_ctx = skinny || (fast && gemv_bf16_supported(probe));
+  // opt-in: the beam group as the unit of the cache attention (decode_attn_group.hip) - the > 6-row steps of a beam generation on a
+  // 16-bit cache; everything else (the engine's row counts, an fp8 cache, fp32 engines, the split and fused forms) keeps decode_attn2
+  const bool grouped = group_attn_on() && ds.nb > 1 && ds.nb <= 16 && ds.anc && ds.ct == BF16 && skinny && B > ENG_MAX_ROWS && B % ds.nb == 0;
+  ds.last_grp = grouped && eng_first < c.layers;
   for (int l = eng_first; l < c.layers; ++l) {
     const GptLayerW& L = gpt.layers[l];
     GemvArgs g = lin_gemv(L.attn, B);  // qkv = LN1(h) Wqkv + b
@@ -1141,7 +1157,10 @@ int Engine::decode_step_launch(hipStream_t s) {
 #endif
     if (l == l_tap) ITTS_TRY(tap("lp_qkv", ds.qkv, F32, (int64_t)B * 3 * D, s));
     if (fused) {
-    } else if (split)
+    } else if (grouped)
+      ITTS_TRY(decode_attn_group(ds.ctx, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B, H,
+                                 dh, ds.Smax, ds.ct, s, 1, ds.anc, ds.nb));
+    else if (split)
       ITTS_TRY(decode_attn2(nullptr, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B, H,
                             dh, ds.Smax, ds.ct, s, 0, ds.attn_o, ds.attn_ml, ds.nb > 1 ? ds.anc : nullptr, ds.nb));
     else
@@ -1462,6 +1481,7 @@ GraphKey Engine::graph_key() const {
   k.temperature = d.temperature;
   k.rows_active = d.rows_active;
   k.rows_classes = d.rows_classes;
+  k.group_attn = (int)group_attn_on();
   return k;
 }
 
@@ -1496,9 +1516,11 @@ int Engine::gpt_decode_steps(int nsteps, hipStream_t s) {
       }
       d.graph_key = key;
       d.graph_mode = d.last_mode;  // what the captured step runs on
+      d.graph_grp = d.last_grp;
       ++d.graph_captures;
     }
     d.last_mode = d.graph_mode;  // a replayed graph: the mode it was captured with
+    d.last_grp = d.graph_grp;
     int left = nsteps;
     if (d.graphK)
       for (; left >= GK; left -= GK) ITTS_HIP_CHECK(hipGraphLaunch(d.graphK, s));

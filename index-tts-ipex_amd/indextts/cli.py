@@ -42,6 +42,9 @@ def build_parser():
     p.add_argument("--admit-beams", action="store_true", default=False,
                    help="with --admit-rows: beam groups (the default, num_beams=3) are refilled too, a finished sentence's rows take "
                         "the next waiting sentence; ITTS_ADMIT_BEAMS=0 / 1 overrides")
+    p.add_argument("--group-attn", action="store_true", default=False,
+                   help="beam decode steps at more than 6 rows run the grouped cache attention, which reads the history the beams "
+                        "of a sentence share once; ITTS_GROUP_ATTN=0 / 1 overrides")
     p.add_argument("--packed-latent", action="store_true", default=False,
                    help="batched synthesis (IndexTTS.infer_batch): the latent pass runs on packed rows without padding, one pass per "
                         "decode group under mixed batches; ITTS_PACKED_LATENT=0 / 1 overrides")
@@ -101,7 +104,8 @@ def main():
     tts = IndexTTS(cfg_path=a.config, model_dir=a.model_dir, is_fp16=not a.fp32, device=a.device, gpt_fp8=a.gpt_fp8, kv_fp8=a.kv_fp8,
                    wide_sampler=a.wide_sampler, wide_beam_sampler=a.wide_beam_sampler, retire_rows=a.retire_rows,
                    engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder, admit_rows=a.admit_rows, retire_beams=a.retire_beams,
-                   packed_latent=a.packed_latent, admit_beams=a.admit_beams, packed_vocoder=a.packed_vocoder)
+                   packed_latent=a.packed_latent, admit_beams=a.admit_beams, packed_vocoder=a.packed_vocoder,
+                   group_attn=a.group_attn)
     if a.stream:
         stream_to_file(tts, a)
         return

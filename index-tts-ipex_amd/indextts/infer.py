@@ -65,6 +65,10 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
     sentence's waveform has the same bits whoever shares its pass) where it otherwise calls Engine.bigvgan_grouped; with
     `mixed_batch` the utterances and voices of a decode group then share ONE vocoder pass instead of one set of passes per
     utterance.  It takes precedence over `ragged_vocoder`.  `infer` / `infer_fast` are not affected.
+  * `group_attn=True` (not in the reference; default off; ITTS_GROUP_ATTN=1 / 0 overrides it in both directions; needs
+    `is_fp16=True`) lets the beam decode steps at more than 6 rows - the mode of the default kwargs, `num_beams=3`, from 3 sentences
+    on - run the grouped cache attention: one workgroup per (head, sentence) reads the history the beams share once
+    (Engine.set_group_attn).  Not with `kv_fp8`, which keeps its own kernel.
   * `infer_stream(...)` (not in the reference) is `infer` as a GENERATOR of (24000, int16 [n, 1]) chunks: a sentence's
     audio starts to arrive while its codes are still being decoded.  One beam only.  `stream_chunk_frames=N` holds the default
     chunk size in latent frames (ITTS_STREAM_CHUNK overrides it).  `infer` / `infer_fast` / `infer_batch` are not affected.
@@ -94,12 +98,16 @@ class IndexTTS:
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
                  mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False,
-                 packed_vocoder=False, stream_chunk_frames=None):
+                 packed_vocoder=False, stream_chunk_frames=None, group_attn=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
             raise ValueError("engine_kv_fp8=True needs kv_fp8=True: it keeps the fp8 K/V cache's small-batch decode steps on the "
                              "persistent decode engine and has no effect on the 16-bit cache")
+        self.group_attn = bool(group_attn)  # beam steps at > 6 rows: the grouped cache attention (ITTS_GROUP_ATTN overrides)
+        if self.group_attn and not is_fp16:
+            raise ValueError("group_attn=True needs is_fp16=True: the grouped cache attention reads a 16-bit K/V cache, the fp32 "
+                             "engine has none")
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -165,6 +173,8 @@ class IndexTTS:
             self.engine.set_kv_fp8(True)
         if self.engine_kv_fp8:
             self.engine.set_engine_kv_fp8(True)
+        if self.group_attn:
+            self.engine.set_group_attn(True)
         self.gpt =UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])

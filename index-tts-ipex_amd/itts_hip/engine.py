@@ -331,6 +331,18 @@ class Engine:
         also together with set_engine_fp8.  ITTS_ENGINE_KV_FP8=0 / 1 in the environment overrides this setting."""
         self._ck(self.lib.itts_gpt_set_engine_kv_fp8(self.h, int(bool(on))), "gpt_set_engine_kv_fp8")
 
+    def set_group_attn(self, on: bool = True):
+        """Opt-in: the decode steps of a beam generation that run on the launch path at more than 6 rows take the grouped cache
+        attention (decode_attn_group: one workgroup per (head, batch item) fetches every shared K/V row once and scores it for
+        all beams on the matrix cores); off (the default) every step is the one it was, bit for bit.  16-bit K/V cache only: an
+        fp8 cache, fp32 engines and the persistent engine's row counts keep their kernels.  Same attention in another summation
+        order.  ITTS_GROUP_ATTN=0 / 1 in the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_group_attn(self.h, int(bool(on))), "gpt_set_group_attn")
+
+    def group_attn_used(self) -> int:
+        """1 if the last decode step ran the grouped cache attention, else 0."""
+        return int(self.lib.itts_gpt_group_attn_used(self.h))
+
     def decode(self, nsteps: int):
         self._ck(self.lib.itts_gpt_decode(self.h, nsteps, self._s()), "gpt_decode")
 
@@ -1363,14 +1375,16 @@ def _dvae_code_len(T: int, layers: int) -> int:
 
 def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1234, parts=("gpt", "bigvgan", "dvae"),
                  state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False,
-                 kv_fp8: bool = False, engine_kv_fp8: bool = False, retire_beams: bool = False) -> Engine:
+                 kv_fp8: bool = False, engine_kv_fp8: bool = False, retire_beams: bool = False,
+                 group_attn: bool = False) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
     "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
     engine_fp8: Engine.set_engine_fp8(True) - the fp8 model's small-batch decode steps on the persistent decode engine.
     kv_fp8: Engine.set_kv_fp8(True) - the decode steps' K/V cache as fp8-e4m3 bytes (16-bit engines).
     engine_kv_fp8: Engine.set_engine_kv_fp8(True) - with an fp8 cache the small-batch decode steps stay on the persistent engine.
-    retire_beams: Engine.set_retire_beams(True) - retire_rows() also retires the finished groups of a beam generation."""
+    retire_beams: Engine.set_retire_beams(True) - retire_rows() also retires the finished groups of a beam generation.
+    group_attn: Engine.set_group_attn(True) - beam steps at more than 6 rows run the grouped cache attention."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -1393,4 +1407,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
         eng.set_engine_kv_fp8(True)
     if retire_beams:
         eng.set_retire_beams(True)
+    if group_attn:
+        eng.set_group_attn(True)
     return eng
