@@ -291,6 +291,15 @@ int itts_decode_attn_group(void* ctx, int to, const float* qkv, void* kc, void* 
                            const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
                            itts_stream stream);
 
+/* The grouped step on an e4m3 K/V cache (csrc/decode_attn_group_kv8.hip, what itts_gpt_set_group_attn_kv_fp8 switches to): the
+ * arguments of itts_decode_attn_group with tc = ITTS_FP8 (kc / vc are [B][H][Smax][64] bytes) and `to` = 1.  A workgroup reads
+ * 64-position units of 64-byte rows, decodes them exactly into the 16-bit type for the matrix cores, and appends this step's
+ * k / v as the bytes itts_decode_attn and itts_kv_scatter write.  dh 64, 2 <= nb <= 16, B % nb == 0, anc set; everything else is
+ * refused with an error status and nothing is launched. */
+int itts_decode_attn_group_kv8(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                               const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
+                               itts_stream stream);
+
 /* The prefill's K/V cache write (csrc/decode.hip kv_scatter) on caller memory: the k and v thirds of qkv [B][S][3 * H * dh]
  * (type tq) go to rows 0 .. S - 1 of each [Smax][dh] block of kc / vc [B][H][Smax][dh] (type tc), rounded to the cache type
  * (ITTS_FP8: clamped to [-448, 448], then nearest even); rows S .. Smax - 1 are not touched.  (tq, tc): fp32 -> fp32, 16-bit ->
@@ -921,6 +930,14 @@ int itts_gpt_set_engine_kv_fp8(itts_engine* e, int on);
  * itts_gpt_group_attn_used: 1 if the last decode step ran the grouped kernel, else 0 (-1 for a null engine). */
 int itts_gpt_set_group_attn(itts_engine* e, int on);
 int itts_gpt_group_attn_used(itts_engine* e);
+
+/* Opt-in, on top of itts_gpt_set_group_attn and itts_gpt_set_kv_fp8: the same steps on an e4m3 K/V cache take the grouped kernel
+ * for that cache (itts_decode_attn_group_kv8) instead of decode_attn2's per-row e4m3 form.  Both libraries.  Sticky per engine
+ * object, default 0 = the two switches together run what they ran before, bit for bit.  The environment variable
+ * ITTS_GROUP_ATTN_KV_FP8, read per call, overrides it in both directions (1 / 0).  Without the grouped switch or without an fp8
+ * cache it has no effect.  A change re-captures the step; itts_gpt_group_attn_used then answers 2.  Results agree with the
+ * per-row e4m3 kernel to the 16-bit bounds, not bit for bit (profiles/group_attn_kv8.txt). */
+int itts_gpt_set_group_attn_kv_fp8(itts_engine* e, int on);
 
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);

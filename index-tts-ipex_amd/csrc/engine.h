@@ -129,7 +129,7 @@ struct GraphKey {
   // mixed batch (DecodeState::rows_active): the step launches one sampler kernel per class present (bits ROWCLS_*).  The entries
   // themselves live in device memory behind a pointer that only changes together with dropped graphs
   int rows_active = 0, rows_classes = 0;
-  int group_attn = 0;  // derived: Engine::group_attn_on() - which cache attention kernel a beam step at > 6 rows launches
+  int group_attn = 0;  // derived: Engine::group_attn_on() (+ 1 with group_attn_kv8_on()) - which cache attention kernel a beam step at > 6 rows launches
   bool operator==(const GraphKey& o) const {
     return group_attn == o.group_attn && rows_active == o.rows_active && rows_classes == o.rows_classes && B == o.B &&Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
            host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample && ct == o.ct &&
@@ -236,7 +236,8 @@ struct DecodeState {
   int eng_fp8 = 0;                       // itts_gpt_set_engine_fp8: a model with fp8 GPT weights may use the engine (sticky; default: launch path)
   int eng_kv8 = 0;                       // itts_gpt_set_engine_kv_fp8: a generation with an fp8 K/V cache may use the engine (sticky; default: launch path)
   int group_attn = 0;                    // itts_gpt_set_group_attn: beam steps at > 6 rows run the grouped cache attention (sticky; default: decode_attn2)
-  int last_grp = 0, graph_grp = 0;       // 1: the last launched / the captured decode step ran decode_attn_group (itts_gpt_group_attn_used)
+  int group_attn_kv8 = 0;                // itts_gpt_set_group_attn_kv_fp8: on top of it, an fp8 cache takes decode_attn_group_kv8 (sticky; default: decode_attn2<fp8_t>)
+  int last_grp = 0, graph_grp = 0;       // 1 / 2: the last launched / the captured decode step ran decode_attn_group / _kv8 (itts_gpt_group_attn_used)
   int graph_mode = 0;                    // last_mode of the captured step
   float typical_mass = 0.f;                        // TypicalLogitsWarper pre-pass (0 = off)
   float* scores2 = nullptr;                        // [cap_B][V] its output
@@ -462,6 +463,8 @@ struct Engine {
   int gpt_set_engine_kv_fp8(int on);  // opt-in: the persistent engine reads and appends an fp8 K/V cache (decode_engine_kernel<.., KV8>)
   int gpt_set_group_attn(int on);     // opt-in: beam steps on the launch path at > 6 rows run decode_attn_group (decode_attn_group.hip)
   bool group_attn_on() const;         // the switch as ITTS_GROUP_ATTN (read per call) or the setter says
+  int gpt_set_group_attn_kv_fp8(int on);  // opt-in on top of it: an fp8 cache takes decode_attn_group_kv8 (decode_attn_group_kv8.hip)
+  bool group_attn_kv8_on() const;         // that switch as ITTS_GROUP_ATTN_KV_FP8 (read per call) or the setter says
   bool engine_fp8_model() const;  // every projection of every block and the head carry an fp8 copy + row scales
   int ensure_engine_state(hipStream_t s);
   int engine_check(hipStream_t s);

@@ -273,6 +273,11 @@ int decode_attn2(void* ctx, int to, const float* qkv, void* kc, void* vc, const 
 int decode_attn_group(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
                       const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
                       const uint8_t* anc, int nb);
+// decode_attn_group_kv8.hip (opt-in on top of it): the grouped step on an e4m3 cache - 64-position units of 64-byte rows, decoded
+// exactly into the 16-bit type for the same MFMAs.  tc FP8, 16-bit ctx, head dim 64, 2 <= nb <= 16
+int decode_attn_group_kv8(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                          const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
+                          const uint8_t* anc, int nb);
 // decode_fused.hip: LN + c_attn projection and the cache attention of one layer in one launch (qkv_attn_fused_kernel)
 bool qkv_attn_fused_supported(const GemvArgs& g, int H, int dh);
 int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* kc, void* vc, const int* len,

@@ -270,6 +270,16 @@ bool Engine::group_attn_on() const {
   const char* ev = getenv("ITTS_GROUP_ATTN");  // read per call, like ITTS_ENGINE_KV_FP8
   return ev ? atoi(ev) != 0 : ds.group_attn != 0;
 }
+// Opt-in on top of it (sticky; ITTS_GROUP_ATTN_KV_FP8 overrides it per call, =0 included): those steps on an fp8 K/V cache run
+// decode_attn_group_kv8 (decode_attn_group_kv8.hip) instead of decode_attn2_kernel<fp8_t, .., ANC>.  Part of the graph key too.
+int Engine::gpt_set_group_attn_kv_fp8(int on) {
+  ds.group_attn_kv8 = on != 0;
+  return OK;
+}
+bool Engine::group_attn_kv8_on() const {
+  const char* ev = getenv("ITTS_GROUP_ATTN_KV_FP8");
+  return ev ? atoi(ev) != 0 : ds.group_attn_kv8 != 0;
+}
 
 int Engine::ensure_engine_state(hipStream_t s) {
   DecodeState& d = ds;
@@ -1125,8 +1135,11 @@ int Engine::decode_step_launch(hipStream_t s) {
   const bool bf_ctx = skinny || (fast && gemv_bf16_supported(probe));
   // opt-in: the beam group as the unit of the cache attention (decode_attn_group.hip) - the > 6-row steps of a beam generation on a
   // 16-bit cache; everything else (the engine's row counts, an fp8 cache, fp32 engines, the split and fused forms) keeps decode_attn2
-  const bool grouped = group_attn_on() && ds.nb > 1 && ds.nb <= 16 && ds.anc && ds.ct == BF16 && skinny && B > ENG_MAX_ROWS && B % ds.nb == 0;
-  ds.last_grp = grouped && eng_first < c.layers;
+  const bool grp_shape = group_attn_on() && ds.nb > 1 && ds.nb <= 16 && ds.anc && skinny && B > ENG_MAX_ROWS && B % ds.nb == 0;
+  const bool grouped = grp_shape && ds.ct == BF16;
+  // opt-in on top of it: the same steps on an e4m3 cache (decode_attn_group_kv8.hip); without it they keep decode_attn2<fp8_t>
+  const bool grouped8 = grp_shape && ds.ct == FP8 && group_attn_kv8_on();
+  ds.last_grp = eng_first < c.layers ? (grouped ? 1 : grouped8 ? 2 : 0) : 0;
   for (int l = eng_first; l < c.layers; ++l) {
     const GptLayerW& L = gpt.layers[l];
     GemvArgs g = lin_gemv(L.attn, B);  // qkv = LN1(h) Wqkv + b
@@ -1160,6 +1173,9 @@ int Engine::decode_step_launch(hipStream_t s) {
     } else if (grouped)
       ITTS_TRY(decode_attn_group(ds.ctx, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B, H,
                                  dh, ds.Smax, ds.ct, s, 1, ds.anc, ds.nb));
+    else if (grouped8)
+      ITTS_TRY(decode_attn_group_kv8(ds.ctx, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B,
+                                     H, dh, ds.Smax, ds.ct, s, 1, ds.anc, ds.nb));
     else if (split)
       ITTS_TRY(decode_attn2(nullptr, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B, H,
                             dh, ds.Smax, ds.ct, s, 0, ds.attn_o, ds.attn_ml, ds.nb > 1 ? ds.anc : nullptr, ds.nb));
@@ -1481,7 +1497,7 @@ GraphKey Engine::graph_key() const {
   k.temperature = d.temperature;
   k.rows_active = d.rows_active;
   k.rows_classes = d.rows_classes;
-  k.group_attn = (int)group_attn_on();
+  k.group_attn = group_attn_on() ? 1 + (int)group_attn_kv8_on() : 0;  // 0 / 1 / 2
   return k;
 }
 

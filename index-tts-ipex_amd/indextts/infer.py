@@ -68,7 +68,10 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `group_attn=True` (not in the reference; default off; ITTS_GROUP_ATTN=1 / 0 overrides it in both directions; needs
     `is_fp16=True`) lets the beam decode steps at more than 6 rows - the mode of the default kwargs, `num_beams=3`, from 3 sentences
     on - run the grouped cache attention: one workgroup per (head, sentence) reads the history the beams share once
-    (Engine.set_group_attn).  Not with `kv_fp8`, which keeps its own kernel.
+    (Engine.set_group_attn).  With `kv_fp8` those steps keep the per-row e4m3 kernel unless the next option is on.
+  * `group_attn_kv_fp8=True` (not in the reference; default off; ITTS_GROUP_ATTN_KV_FP8=1 / 0 overrides it in both directions; needs
+    `group_attn=True` and `kv_fp8=True`) lets those steps on the e4m3 K/V cache run the grouped kernel written for that cache
+    (Engine.set_group_attn_kv_fp8).
   * `infer_stream(...)` (not in the reference) is `infer` as a GENERATOR of (24000, int16 [n, 1]) chunks: a sentence's
     audio starts to arrive while its codes are still being decoded.  One beam only.  `stream_chunk_frames=N` holds the default
     chunk size in latent frames (ITTS_STREAM_CHUNK overrides it).  `infer` / `infer_fast` / `infer_batch` are not affected.
@@ -98,7 +101,7 @@ class IndexTTS:
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
                  mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False,
-                 packed_vocoder=False, stream_chunk_frames=None, group_attn=False):
+                 packed_vocoder=False, stream_chunk_frames=None, group_attn=False, group_attn_kv_fp8=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -108,6 +111,10 @@ class IndexTTS:
         if self.group_attn and not is_fp16:
             raise ValueError("group_attn=True needs is_fp16=True: the grouped cache attention reads a 16-bit K/V cache, the fp32 "
                              "engine has none")
+        self.group_attn_kv_fp8 = bool(group_attn_kv_fp8)  # ... on the fp8 K/V cache: its own grouped kernel (ITTS_GROUP_ATTN_KV_FP8 overrides)
+        if self.group_attn_kv_fp8 and not (self.group_attn and kv_fp8):
+            raise ValueError("group_attn_kv_fp8=True needs group_attn=True and kv_fp8=True: it is the grouped cache attention's form "
+                             "for the fp8 K/V cache and has no effect without both")
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -175,6 +182,8 @@ class IndexTTS:
             self.engine.set_engine_kv_fp8(True)
         if self.group_attn:
             self.engine.set_group_attn(True)
+        if self.group_attn_kv_fp8:
+            self.engine.set_group_attn_kv_fp8(True)
         self.gpt =UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])

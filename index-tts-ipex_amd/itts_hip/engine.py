@@ -340,8 +340,15 @@ class Engine:
         self._ck(self.lib.itts_gpt_set_group_attn(self.h, int(bool(on))), "gpt_set_group_attn")
 
     def group_attn_used(self) -> int:
-        """1 if the last decode step ran the grouped cache attention, else 0."""
+        """1 if the last decode step ran the grouped cache attention, 2 if it ran its fp8-cache form, else 0."""
         return int(self.lib.itts_gpt_group_attn_used(self.h))
+
+    def set_group_attn_kv_fp8(self, on: bool = True):
+        """Opt-in, on top of set_group_attn and set_kv_fp8: those steps on an e4m3 K/V cache take the grouped kernel for that cache
+        (decode_attn_group_kv8: 64-position units of 64-byte rows, decoded exactly into the 16-bit type for the matrix cores);
+        off (the default) the two switches together run the per-row e4m3 kernel as before, bit for bit.  No effect without
+        both.  ITTS_GROUP_ATTN_KV_FP8=0 / 1 in the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_group_attn_kv_fp8(self.h, int(bool(on))), "gpt_set_group_attn_kv_fp8")
 
     def decode(self, nsteps: int):
         self._ck(self.lib.itts_gpt_decode(self.h, nsteps, self._s()), "gpt_decode")
@@ -1376,7 +1383,7 @@ def _dvae_code_len(T: int, layers: int) -> int:
 def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1234, parts=("gpt", "bigvgan", "dvae"),
                  state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False,
                  kv_fp8: bool = False, engine_kv_fp8: bool = False, retire_beams: bool = False,
-                 group_attn: bool = False) -> Engine:
+                 group_attn: bool = False, group_attn_kv_fp8: bool = False) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
     "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
@@ -1384,7 +1391,8 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
     kv_fp8: Engine.set_kv_fp8(True) - the decode steps' K/V cache as fp8-e4m3 bytes (16-bit engines).
     engine_kv_fp8: Engine.set_engine_kv_fp8(True) - with an fp8 cache the small-batch decode steps stay on the persistent engine.
     retire_beams: Engine.set_retire_beams(True) - retire_rows() also retires the finished groups of a beam generation.
-    group_attn: Engine.set_group_attn(True) - beam steps at more than 6 rows run the grouped cache attention."""
+    group_attn: Engine.set_group_attn(True) - beam steps at more than 6 rows run the grouped cache attention.
+    group_attn_kv_fp8: Engine.set_group_attn_kv_fp8(True) - with group_attn and kv_fp8, those steps run the grouped fp8-cache kernel."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -1409,4 +1417,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
         eng.set_retire_beams(True)
     if group_attn:
         eng.set_group_attn(True)
+    if group_attn_kv_fp8:
+        eng.set_group_attn_kv_fp8(True)
     return eng

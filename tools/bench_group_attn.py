@@ -2,7 +2,7 @@
 """The grouped cache attention under beams (itts_decode_attn_group, csrc/decode_attn_group.hip) against the per-row ancestry form it
 replaces (itts_decode_attn with `anc`, the 256-thread "many" form), operator alone.
 
-    python tools/bench_group_attn.py [--items 21] [--beams 3] [--heads 20] [--layers 8] [--iters 48] [--rounds 5]
+    python tools/bench_group_attn.py [--items 21] [--beams 3] [--heads 20] [--layers 8] [--iters 48] [--rounds 5] [--kv-fp8]
 
 bf16 library, random caches, `items` x `beams` rows (what one infer_batch generation of the default kwargs carries), S = pos + 1 in
 200, 500, 900 of Smax 1024, kv_start 0.  Two ancestries: "trunk" - every position up to the last 6 lies in ONE (random) physical row
@@ -11,7 +11,9 @@ step's table and the grouped kernel's worst case (beams passes per tile).  Conse
 the layers of a decode step do, so that no launch finds its rows in the caches of the one before (the footprint is printed).  The
 two kernels are alternated `rounds` times in one process after a warm-up of both; per kernel `iters` launches between two device
 events.  Printed: ms per launch (min and median of the rounds), the bytes each algorithm has to fetch and that rate, and the
-largest difference between the two results.  Run it under a time limit; profiles/group_attn.txt holds a record."""
+largest difference between the two results.  --kv-fp8: the same on e4m3 caches (tc = ITTS_FP8) - the per-row e4m3 kernel against
+itts_decode_attn_group_kv8 (csrc/decode_attn_group_kv8.hip), half the bytes per row.  Run it under a time limit;
+profiles/group_attn.txt and profiles/group_attn_kv8.txt hold records."""
 import argparse
 import ctypes as C
 import os
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--layers", type=int, default=8)
     ap.add_argument("--iters", type=int, default=48)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--kv-fp8", action="store_true", help="e4m3 caches: the per-row e4m3 kernel against itts_decode_attn_group_kv8")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_group_attn: needs a GPU")
@@ -46,14 +49,18 @@ def main():
     g = torch.Generator(device=dev).manual_seed(5)
     kc = torch.randn(a.layers, B, H, SMAX, 64, device=dev, dtype=torch.bfloat16, generator=g)
     vc = torch.randn(a.layers, B, H, SMAX, 64, device=dev, dtype=torch.bfloat16, generator=g)
+    tc, row_bytes, grouped = L.BF16, 256, lib.itts_decode_attn_group  # (K + V bytes of one cache row)
+    if a.kv_fp8:
+        kc, vc = kc.to(torch.float8_e4m3fn), vc.to(torch.float8_e4m3fn)
+        tc, row_bytes, grouped = L.FP8, 128, lib.itts_decode_attn_group_kv8
     qkv = torch.randn(B, 3 * H * 64, device=dev, generator=g)
     qkv[:, :H * 64] *= 2.0
     ks = torch.zeros(B, dtype=torch.int32, device=dev)
     pre = torch.zeros(1, dtype=torch.int32, device=dev)
     ctx = [torch.zeros(B, H * 64, device=dev, dtype=torch.bfloat16) for _ in range(2)]
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    print(f"# bench_group_attn: {a.items} items x {nb} beams = {B} rows, H = {H}, bf16, Smax {SMAX}, {a.layers} caches walked "
-          f"({kc[0].numel() * 4 / 2**20:.0f} MiB of K + V each), {a.iters} launches per timing, {a.rounds} alternated rounds")
+    print(f"# bench_group_attn: {a.items} items x {nb} beams = {B} rows, H = {H}, {'e4m3' if a.kv_fp8 else 'bf16'} caches, Smax {SMAX}, {a.layers} caches walked "
+          f"({kc[0].numel() * 2 * kc.element_size() / 2**20:.0f} MiB of K + V each), {a.iters} launches per timing, {a.rounds} alternated rounds")
     rng = np.random.default_rng(3)
     for S in (200, 500, 900):
         pos = S - 1
@@ -67,11 +74,11 @@ def main():
             def launch(which, i):
                 k, v = kc[i % a.layers].data_ptr(), vc[i % a.layers].data_ptr()
                 if which:
-                    st = lib.itts_decode_attn_group(ctx[1].data_ptr(), L.BF16, qkv.data_ptr(), k, v, ln.data_ptr(), ks.data_ptr(),
-                                                    pre.data_ptr(), B, H, 64, SMAX, L.BF16, 0, anc.data_ptr(), nb, s)
+                    st = grouped(ctx[1].data_ptr(), L.BF16, qkv.data_ptr(), k, v, ln.data_ptr(), ks.data_ptr(), pre.data_ptr(), B, H, 64,
+                                 SMAX, tc, 0, anc.data_ptr(), nb, s)
                 else:
                     st = lib.itts_decode_attn(ctx[0].data_ptr(), L.BF16, qkv.data_ptr(), k, v, ln.data_ptr(), ks.data_ptr(), pre.data_ptr(),
-                                              B, H, 64, SMAX, L.BF16, 0, None, None, anc.data_ptr(), nb, s)
+                                              B, H, 64, SMAX, tc, 0, None, None, anc.data_ptr(), nb, s)
                 L.check(st, "bench_group_attn", lib)
 
             for which in (0, 1):  # warm-up, and the two results on the same cache
@@ -89,8 +96,8 @@ def main():
                     e1.record()
                     torch.cuda.synchronize()
                     ms[which].append(e0.elapsed_time(e1) / a.iters)
-            need = (B * pos * H * 256, rows_read * H * 256)  # K + V bytes: per row its whole history / every (position, row) once
-            for which, label in ((0, "decode_attn2 ANC many"), (1, "decode_attn_group")):
+            need = (B * pos * H * row_bytes, rows_read * H * row_bytes)  # K + V bytes: per row its whole history / every (position, row) once
+            for which, label in ((0, "decode_attn2 ANC many"), (1, "decode_attn_group_kv8" if a.kv_fp8 else "decode_attn_group")):
                 t = ms[which]
                 print(f"S={S:4d} {name:<8s} {label:<22s} {min(t) * 1e3:7.1f} us min  {float(np.median(t)) * 1e3:7.1f} us median   "
                       f"fetches {need[which] / 2**20:6.1f} MiB -> {need[which] / min(t) / 1e6:7.1f} GB/s")
