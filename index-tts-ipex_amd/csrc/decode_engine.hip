@@ -7,16 +7,19 @@
 // (decode_gemv / decode_attn / decode_fused / decode_sampler.hip, five graph-captured kernels per layer) is bound by its 120 dependent kernel boundaries per token, not by
 // HBM.  Here every one of the chip's 256 CUs holds ONE 1024-thread workgroup for the whole step:
 //
-//   * each workgroup owns a fixed slice of every projection's output features (16 of c_attn - a head's q / k / v rows are
-//     spread over the 12 workgroups of that head's group -, 5 of c_proj, 20 of c_fc, 5 of mlp.c_proj: 153.6 KB of bf16
-//     weights per layer) and streams it by LDS-DMA (global_load_lds, nontemporal, no VGPR touched) into three LDS slots,
+//   * each workgroup owns a fixed slice of every projection's output features (5 of c_proj, 20 of c_fc, 5 of mlp.c_proj and, of
+//     c_attn, at 1 - 2 rows 16 - 18 consecutive features on every workgroup that runs NO attention, none on the attention
+//     workgroups; at 3 - 6 rows 16 on workgroups 0..239 - a head's q / k / v rows spread over the 12 workgroups of that head's
+//     group -, none on 240..255: about 153.6 KB of bf16 weights per layer) and streams it by
+//     LDS-DMA (global_load_lds, nontemporal, no VGPR touched) into three LDS slots,
 //     one to four phases ahead of its use: ONE loader wave per workgroup issues every request, in a fixed FIFO order, as
 //     soon as the target slot's previous occupant has been read, and waits with counted vmcnt in front of the barriers;
 //   * the five all-to-all phase edges of a layer (residual stream -> LN1, q/k/v -> attention, context -> c_proj,
 //     residual stream -> LN2, gelu(fc) -> mlp.c_proj) are 8-byte {value, tag} granules: written with ONE agent-scope
 //     (sc1, write-through) store by the lane that finished the value, polled with agent-scope loads by the four GATHER
 //     waves of every consuming workgroup - waves that never issue a weight load, so a poll never queues behind the
-//     workgroup's own weight stream (vmcnt is in-order per wave); the eleven COMPUTE waves neither poll nor prefetch;
+//     workgroup's own weight stream (vmcnt is in-order per wave); the eleven COMPUTE waves neither poll nor request weights
+//     (on an attention workgroup they touch its cache rows into L2 at the head of the block, see ITTS_KV_PREFETCH);
 //   * tag = a step counter kept in device memory and advanced by the kernel itself: every (layer, edge) has its own
 //     granule block, so a tag can only match a value of THIS step; nothing is reset between launches (graph replay safe);
 //   * one attention workgroup per (row, head) - workgroup `row` of the head's group - runs the four key splits of
@@ -64,11 +67,21 @@
 // gather, one 16-byte load per candidate, the first weight requests in front of the launch's scalars, the loader's wait for
 // c_attn moved into the first LayerNorm - each slower or inside the run-to-run spread.
 //
+// Per-stage skew between workgroups (profiles/r13_engine_skew.txt, 2 rows): with c_attn on workgroups 0..239, the last eight workgroups
+// of EVERY block at "E1 gathered" and "q / k / v published" were attention workgroups (+ 0.55 / + 0.61 us against the stage median; the
+// per-workgroup means explained 78 / 86 % of the variance there, 8 - 63 % at the later stages) - their E1 pass queues behind their
+// own compute waves' L2 touches of the cache rows.  At 1 - 2 rows they therefore own no c_attn feature now (QFREE below): "q / k / v
+// published" median -> max 1.00 -> 0.32 us, launch 0.4097 -> 0.4018 ms.  No clustering by XCD (workgroup id % 8 is the XCD).
+// Measured there and NOT taken: gather passes that start at a per-workgroup row of the edge (+ 7.6 us per launch, or + 3.1 with
+// the waves' chunks rotated too; VGPR spills at 4 and 6 rows), the L2 touches behind the first barrier (E1 skew 0.98 -> 0.41 us, but
+// c_attn on those workgroups ends 1 us later: + 6.4 us per launch) or behind the first LayerNorm (+ 25 us).
+//
 // Every spin is bounded (wall clock, s_memrealtime) and also ends on a chip-wide abort word; a workgroup that gave up
 // runs on without waiting, so the grid always drains.  The host reads the abort word at status / fetch.
 //
 // Probes (phase stamps, the taps of one block's edges, the gather divisor) are compiled only with -DITTS_PROBES, into
-// libitts_hip_probes.so (`make probes`); the product kernels carry none of their state.
+// libitts_hip_probes.so (`make probes`); the product kernels carry none of their state.  The probes build also records where a
+// workgroup runs (XCC_ID, HW_ID) in two free stamp slots.
 #include <cstdlib>
 #include <type_traits>
 
@@ -314,9 +327,9 @@ __device__ __forceinline__ void dma_row8(const unsigned char* __restrict__ src, 
 // THIN > 0: at most THIN requests in flight (the loader waits in between) - for the one projection that has to be
 // requested while this CU's gather waves are polling (MI355X_MICROARCH "gather-pass": a gather pass queued behind its own
 // CU's unthrottled refill burst takes 2 - 3 x as long)
-template <int ROWS, int K, bool W8, int THIN = 0>
-__device__ __forceinline__ void dma_rows(const bf16_t* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ scale, int n0,
-                                         unsigned slot, int lane) {
+template <int K, bool W8, int THIN = 0>
+__device__ __forceinline__ void dma_rows_n(const bf16_t* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ scale, int n0,
+                                           unsigned slot, int lane, const int ROWS) {  // ROWS: wave-uniform, <= 20 (the slot header)
   if constexpr (W8) {
     for (int r = 0; r < ROWS; ++r)
       dma_row8<K, THIN>(reinterpret_cast<const unsigned char*>(W) + (size_t)(n0 + r) * K + lane * 16, slot + 256 + (unsigned)(r * K), lane);
@@ -340,6 +353,11 @@ __device__ __forceinline__ void dma_rows(const bf16_t* __restrict__ W, const flo
     }
     if (lane < ROWS) dma4(bias + n0 + lane, slot);
   }
+}
+template <int ROWS, int K, bool W8, int THIN = 0>
+__device__ __forceinline__ void dma_rows(const bf16_t* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ scale, int n0,
+                                         unsigned slot, int lane) {
+  dma_rows_n<K, W8, THIN>(W, bias, scale, n0, slot, lane, ROWS);
 }
 // rows [n0, n0 + ROWS) of W [N][K] -> compact rows at LDS address dst, no header (5 - 6 rows: c_attn arrives in two parts)
 template <int ROWS, int K, bool W8>
@@ -726,10 +744,19 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
   const bool cwv = wave > 4;   // compute waves
   const int cw = wave - 5;
   const int gh = cu / GPH, gm = cu % GPH;
-  const bool qcu = cu < H * GPH;        // takes part in c_attn
-  const bool acu = qcu && gm < NB;      // runs the attention of (row gm, head gh)
-  // c_attn rows of this workgroup: q, k or v (gm / 4) of head gh, 16 consecutive features
-  const int an0 = (gm / 4) * D + gh * DH + (gm % 4) * QO;
+  const bool acu = cu < H * GPH && gm < NB;  // runs the attention of (row gm, head gh)
+  // c_attn rows of this workgroup.  3 - 6 rows: q, k or v (gm / 4) of head gh, 16 consecutive features on workgroups 0..239.
+  // 1 - 2 rows (QFREE): the attention workgroups own NONE - their E1 pass ends 0.55 us behind the others' (it queues behind their
+  // own L2 touches of the cache rows) and their q / k / v publish was the last of every block (profiles/r13_engine_skew.txt) - and
+  // the 3 D features are dealt to the other 256 - 20 NB workgroups in order, QB or QB + 1 consecutive ones each (2 rows: 18 on the
+  // first 168, 17 on the rest; two rounds on the eleven compute waves either way).  A feature's value does not depend on its owner.
+  constexpr bool QFREE = NB <= 2;
+  constexpr int QN = NCU - H * NB, QB = 3 * D / QN, QR = 3 * D % QN;  // owners, features each, owners with one more
+  static_assert(!QFREE || (QB + 1 <= 2 * NCW && QB + 1 <= FO), "c_attn share: two rounds, slot A and its header");
+  const bool qcu = QFREE ? !acu : cu < H * GPH;  // takes part in c_attn
+  const int qk = cu - (cu < H * GPH ? gh * NB + min(gm, NB) : H * NB);  // QFREE: index among the owners
+  const int an0 = QFREE ? qk * QB + min(qk, QR) : (gm / 4) * D + gh * DH + (gm % 4) * QO;
+  const int nq = QFREE ? QB + (qk < QR ? 1 : 0) : QO;  // wave-uniform (cu is scalar)
 
   Rt rt;
   rt.t0 = __builtin_amdgcn_s_memrealtime();
@@ -774,7 +801,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
       if constexpr (W8)
         if (lane < QO) dma4(a.S[0].sa + an0 + lane, S0 + ENG_SCALE_OFF);
     } else if (qcu) {
-      dma_rows<QO, D, W8>(a.L[0].wa, a.L[0].ba, a.S[0].sa, an0, S0, lane);
+      dma_rows_n<D, W8>(a.L[0].wa, a.L[0].ba, a.S[0].sa, an0, S0, lane, nq);
     }
   }
   ENG_HSTAMP(1, 256)
@@ -895,7 +922,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const int r = cw + NCW * s;
-        if (r < QO) {
+        if (r < nq) {
           float acc[NB];
 #pragma unroll
           for (int b = 0; b < NB; ++b) acc[b] = 0.f;
@@ -1233,7 +1260,7 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
           if (ll < QO) dma4(a.S[l + 1].sa + an0 + ll, S0 + ENG_SCALE_OFF);
       }
     } else if (lw && qcu && l + 1 < a.NL) {
-      dma_rows<QO, D, W8>(a.L[l + 1].wa, a.L[l + 1].ba, a.S[l + 1].sa, an0, S0, ll);  // next c_attn -> A: all past c_fc
+      dma_rows_n<D, W8>(a.L[l + 1].wa, a.L[l + 1].ba, a.S[l + 1].sa, an0, S0, ll, nq);  // next c_attn -> A: all past c_fc
     }
     if (cwv && cw < HO) {
       float acc[NB];
@@ -1456,6 +1483,10 @@ __global__ __launch_bounds__(1024) void decode_engine_kernel(EngArgs a) {
     if (a.NL >= 3) {  // wall clock at this workgroup's start / end (stamp 15 of blocks 1 / 2)
       a.stamp[((size_t)cu * a.NL + 1) * 16 + 15] = (unsigned)rt.t0;
       a.stamp[((size_t)cu * a.NL + 2) * 16 + 15] = (unsigned)r1;
+    }
+    if (a.NL > 12) {  // where this workgroup runs (stamp 15 of blocks 11 / 12): hardware registers XCC_ID (20) and HW_ID (4), 32 bits each
+      a.stamp[((size_t)cu * a.NL + 11) * 16 + 15] = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+      a.stamp[((size_t)cu * a.NL + 12) * 16 + 15] = __builtin_amdgcn_s_getreg(4 | (31 << 11));
     }
   }
 #endif

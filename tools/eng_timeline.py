@@ -4,6 +4,9 @@ published, 4 E3 gathered, 5 E4 gathered, 6 E5 gathered, 7 after B5; compute side
 10 c_fc published, 11 mlp.c_proj published.  Around the blocks (slot 15 of blocks 3 .. 10): scalars resolved, first weights
 requested, h gathered, ln_f + final_norm done, dots done, candidates published and, on the workgroups that finish a row, candidates
 gathered and token committed - printed as the split of the launch's fixed cost into prologue, head and sampler tail.
+Slot 15 of blocks 11 / 12: the workgroup's XCC_ID / HW_ID registers.  Last section: the per-workgroup skew of every stage over
+blocks 2..NL-2 - how often a workgroup is among the last 8 and its mean lateness against the stage median, by role, by cu % 8,
+by place in the head's group and by XCD - and how much of median -> max the per-workgroup means explain (systematic) or not (noise).
 Needs the probes library (`make -C index-tts-ipex_amd/csrc probes`): the product library compiles the engine's stamps, block taps and
 gather divisor out and ignores their switches.  Select it through the usual override:
 ITTS_HIP_LIB=index-tts-ipex_amd/csrc/libitts_hip_probes.so python tools/eng_timeline.py ..."""
@@ -90,3 +93,63 @@ for i, nm in seq:
         print(f"   {nm:22s} +{d:5.2f} us")
     prev = i
 print(f"   next block E1          +{(mx[3:NL, 0] - mx[2:NL - 1, 11]).mean():5.2f} us")
+
+# ---- per-workgroup skew: which workgroups are late at a stage in EVERY block (systematic) and which only now and then ----
+# lateness = a workgroup's stamp minus the stage's median over workgroups in the same block, over blocks 2..NL-2.  Every edge is
+# an all-to-all, so the consumers of a stage start behind its LAST workgroup: the part of (max - median) that the per-workgroup
+# mean lateness explains is what a change of ownership / order / placement could remove, the rest is arbitration noise.
+LAST = 8
+cus = np.arange(256)
+qcu = cus < 240
+role = np.where(acu, 0, np.where(qcu, 1, 2))
+role_names = ["attention workgroups", "others, cu < 240", "cu >= 240"]
+xcd = None
+if NL > 12:  # probes build: hardware ids of the workgroup (slot 15 of blocks 11 / 12): XCC id, HW_ID
+    x = st[:, 11, 15] & 15
+    if x.max() < 8 and len(np.unique(x)) > 1:
+        xcd = x
+        agree = int((xcd == cus % 8).sum())
+        print(f"-- placement: XCC id recorded; workgroups per XCD {np.bincount(xcd, minlength=8).tolist()}; XCC id == cu % 8 on {agree} of 256 workgroups")
+        hw = st[:, 12, 15]
+        print(f"   HW_ID cu_id (bits 11:8) x se_id (bits 15:13) distinct pairs per XCD: "
+              f"{[len(set(zip(((hw >> 8) & 15)[xcd == k].tolist(), ((hw >> 13) & 7)[xcd == k].tolist()))) for k in range(8)]}")
+if xcd is None:
+    print("-- placement: no XCC id in the stamps (not the probes build of this tree, or fewer than 13 blocks): no grouping by XCD")
+blk = slice(2, NL - 1)
+print(f"-- per-stage skew over blocks 2..{NL - 2} ({NL - 3} blocks): lateness = stamp - stage median of the block; 'last {LAST}' = share of the blocks in which")
+print(f"   the workgroup is among the {LAST} latest (chance: {100.0 * LAST / 256:.1f} % over all 256, {100.0 * LAST / max(1, int(acu.sum())):.1f} % among the attention workgroups)")
+for i in (0, 8, 2, 3, 4, 9, 5, 10, 6, 11):
+    sel = acu if i in (2, 3) else np.ones(256, bool)
+    v = us[sel][:, blk, i]  # [n][blocks]
+    ids = cus[sel]
+    late = v - np.median(v, axis=0, keepdims=True)
+    mean_late = late.mean(axis=1)  # per workgroup
+    resid = late - mean_late[:, None]
+    order = np.argsort(-late, axis=0)[:LAST]  # [LAST][blocks]
+    cnt = np.zeros(len(ids))
+    np.add.at(cnt, order.ravel(), 1)
+    share = cnt / late.shape[1]
+    tot_var = late.var()
+    sys_frac = mean_late.var() / tot_var if tot_var > 0 else 0.0
+    gap = late.max(axis=0).mean()
+    gap_resid = (resid.max(axis=0) - np.median(resid, axis=0)).mean()
+    print(f"   == {names[i]}: median -> max {gap:.2f} us (mean over blocks); with every workgroup's mean lateness taken out {gap_resid:.2f} us; "
+          f"per-workgroup means explain {100 * sys_frac:.0f} % of the variance; workgroup means span {mean_late.min():+.2f} .. {mean_late.max():+.2f} us")
+    top = np.argsort(-share)[:12]
+    print("      most often last: " + ", ".join(f"cu {ids[k]} {100 * share[k]:.0f}% ({mean_late[k]:+.2f})" for k in top))
+
+    def group(label, keys, labels):
+        parts = []
+        for kk, lb in labels:
+            m = keys == kk
+            if m.any():
+                parts.append(f"{lb} n={int(m.sum())} {mean_late[m].mean():+.2f} us / {100 * share[m].mean():.1f}%")
+        print(f"      by {label} (mean lateness / mean 'last {LAST}' share): " + "; ".join(parts))
+
+    group("role", role[sel], list(enumerate(role_names)))
+    if not (i in (2, 3)):
+        group("row finisher", (ids < rows).astype(int), [(1, "cu < rows"), (0, "others")])
+    group("cu % 8", ids % 8, [(k, str(k)) for k in range(8)])
+    group("cu % 12 (place in the head's group)", np.where(ids < 240, ids % 12, 12), [(k, str(k)) for k in range(12)] + [(12, "none")])
+    if xcd is not None:
+        group("XCD", xcd[sel], [(k, str(k)) for k in range(8)])
