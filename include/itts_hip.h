@@ -300,6 +300,16 @@ int itts_decode_attn_group_kv8(void* ctx, int to, const float* qkv, void* kc, vo
                                const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
                                itts_stream stream);
 
+/* The 16-bit grouped step with a key split (csrc/decode_attn_group_split.hip, what itts_gpt_set_group_attn_split switches to): the
+ * arguments and requirements of itts_decode_attn_group, plus nsplit (2 .. 8) workgroups per (head, batch item), each taking a
+ * contiguous chunk of the item's 32-position tiles, and a merge kernel that writes ctx.  The two fp32 workspaces are the caller's:
+ * part_o [nsplit][B][H][64] (un-normalised weighted V per split) and part_ml [nsplit][B][H][2] (maximum, sum); every slot is
+ * written by every call, a split without a visible key writes (-inf, 0) and zeros.  Only split 0 appends this step's k / v.
+ * Everything else is refused with an error status and nothing is launched. */
+int itts_decode_attn_group_split(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                                 const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
+                                 int nsplit, float* part_o, float* part_ml, itts_stream stream);
+
 /* The prefill's K/V cache write (csrc/decode.hip kv_scatter) on caller memory: the k and v thirds of qkv [B][S][3 * H * dh]
  * (type tq) go to rows 0 .. S - 1 of each [Smax][dh] block of kc / vc [B][H][Smax][dh] (type tc), rounded to the cache type
  * (ITTS_FP8: clamped to [-448, 448], then nearest even); rows S .. Smax - 1 are not touched.  (tq, tc): fp32 -> fp32, 16-bit ->
@@ -938,6 +948,18 @@ int itts_gpt_group_attn_used(itts_engine* e);
  * cache it has no effect.  A change re-captures the step; itts_gpt_group_attn_used then answers 2.  Results agree with the
  * per-row e4m3 kernel to the 16-bit bounds, not bit for bit (profiles/group_attn_kv8.txt). */
 int itts_gpt_set_group_attn_kv_fp8(itts_engine* e, int on);
+
+/* Opt-in, on top of itts_gpt_set_group_attn: the grouped steps on a 16-bit cache deal each (head, item)'s keys to several workgroups
+ * (itts_decode_attn_group_split) where few items leave most of the chip idle.  n = 0: off (default; every step as before, bit for
+ * bit), 1: on, the number of splits from itts_group_attn_split_rule(H, items) - where that answers 1 the step keeps the unsplit
+ * kernel -, 2 .. 8: that many splits at every item count (for measurements); anything else is refused.  Both libraries.  Sticky
+ * per engine object; the environment variable ITTS_GROUP_ATTN_SPLIT, read per call, overrides it (0 included).  Without the grouped
+ * switch, on an fp8 cache and on the persistent engine's row counts it has no effect.  A change of the splits in effect
+ * re-captures the step; itts_gpt_group_attn_used answers 3 for a step that ran the split form.  Results agree with the unsplit
+ * grouped kernel to the 16-bit bounds, not bit for bit (profiles/group_attn_split.txt).
+ * itts_group_attn_split_rule: the splits the switch at 1 takes for H heads and `items` batch items (1 = unsplit); a pure function. */
+int itts_gpt_set_group_attn_split(itts_engine* e, int n);
+int itts_group_attn_split_rule(int H, int items);
 
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);

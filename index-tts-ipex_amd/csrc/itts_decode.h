@@ -278,6 +278,16 @@ int decode_attn_group(void* ctx, int to, const float* qkv, void* kc, void* vc, c
 int decode_attn_group_kv8(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
                           const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
                           const uint8_t* anc, int nb);
+// decode_attn_group_split.hip (opt-in on top of decode_attn_group): the 16-bit grouped step with the keys of each (head, item) dealt
+// to nsplit workgroups (grid (H, items, nsplit)) and a merge kernel behind it; the arguments and requirements of decode_attn_group
+// plus 2 <= nsplit <= GROUP_SPLIT_MAX and the two workspaces, fp32, every slot written by every launch:
+//   part_o  [nsplit][B][H][64]  un-normalised weighted V of split z for (row b, head h)
+//   part_ml [nsplit][B][H][2]   its maximum m and sum l; a split without an admitted key holds (-inf, 0) and zeros
+constexpr int GROUP_SPLIT_MAX = 8;
+int decode_attn_group_split(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                            const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
+                            const uint8_t* anc, int nb, int nsplit, float* part_o, float* part_ml);
+int group_split_rule(int H, int items);  // nsplit the decode step takes at H * items unsplit workgroups (1: unsplit).  No GPU work
 // decode_fused.hip: LN + c_attn projection and the cache attention of one layer in one launch (qkv_attn_fused_kernel)
 bool qkv_attn_fused_supported(const GemvArgs& g, int H, int dh);
 int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* kc, void* vc, const int* len,

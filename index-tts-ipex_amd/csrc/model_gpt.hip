@@ -280,6 +280,21 @@ bool Engine::group_attn_kv8_on() const {
   const char* ev = getenv("ITTS_GROUP_ATTN_KV_FP8");
   return ev ? atoi(ev) != 0 : ds.group_attn_kv8 != 0;
 }
+// Opt-in on top of group_attn (sticky; ITTS_GROUP_ATTN_SPLIT overrides it per call, =0 included): the grouped steps on a 16-bit
+// cache deal each (head, item)'s keys to several workgroups (decode_attn_group_split.hip).  0 off, 1 group_split_rule, 2 .. 8 forced.
+// The splits in effect are part of the graph key.
+int Engine::gpt_set_group_attn_split(int n) {
+  ITTS_REQUIRE(n >= 0 && n <= GROUP_SPLIT_MAX, "gpt_set_group_attn_split: 0 (off), 1 (by rule) or 2 .. 8 splits");
+  ds.group_split = n;
+  return OK;
+}
+int Engine::group_split_ns(int B) const {
+  const char* ev = getenv("ITTS_GROUP_ATTN_SPLIT");
+  int n = ev ? atoi(ev) : ds.group_split;
+  if (n <= 0 || n > GROUP_SPLIT_MAX || !group_attn_on() || ds.ct != BF16 || ds.nb < 2 || !ds.grp_o) return 0;
+  if (n == 1) n = group_split_rule(cfg.heads, B / ds.nb);
+  return n >= 2 ? n : 0;
+}
 
 int Engine::ensure_engine_state(hipStream_t s) {
   DecodeState& d = ds;
@@ -404,6 +419,9 @@ int Engine::ensure_beam_state(int rows, int max_gen, int Smax, hipStream_t s) {
   ITTS_TRY(dev_alloc((void**)&d.hyp_worst, (size_t)r * 4));
   ITTS_TRY(dev_alloc((void**)&d.hyp_counter, (size_t)r * 4));
   ITTS_TRY(dev_alloc((void**)&d.beam_done, (size_t)r * 4));
+  // partials of the grouped attention's key split (decode_attn_group_split.hip), sized for GROUP_SPLIT_MAX splits
+  ITTS_TRY(dev_alloc((void**)&d.grp_o, (size_t)GROUP_SPLIT_MAX * r * cfg.heads * 64 * 4));
+  ITTS_TRY(dev_alloc((void**)&d.grp_ml, (size_t)GROUP_SPLIT_MAX * r * cfg.heads * 2 * 4));
   d.beam_rows = r;
   d.beam_gen = g;
   d.beam_smax = sm;
@@ -1139,7 +1157,9 @@ int Engine::decode_step_launch(hipStream_t s) {
   const bool grouped = grp_shape && ds.ct == BF16;
   // opt-in on top of it: the same steps on an e4m3 cache (decode_attn_group_kv8.hip); without it they keep decode_attn2<fp8_t>
   const bool grouped8 = grp_shape && ds.ct == FP8 && group_attn_kv8_on();
-  ds.last_grp = eng_first < c.layers ? (grouped ? 1 : grouped8 ? 2 : 0) : 0;
+  // opt-in on top of it: few items leave most of the chip idle - the keys of each (head, item) go to gsplit workgroups
+  const int gsplit = grouped ? group_split_ns(B) : 0;
+  ds.last_grp = eng_first < c.layers ? (gsplit ? 3 : grouped ? 1 : grouped8 ? 2 : 0) : 0;
   for (int l = eng_first; l < c.layers; ++l) {
     const GptLayerW& L = gpt.layers[l];
     GemvArgs g = lin_gemv(L.attn, B);  // qkv = LN1(h) Wqkv + b
@@ -1170,7 +1190,10 @@ int Engine::decode_step_launch(hipStream_t s) {
 #endif
     if (l == l_tap) ITTS_TRY(tap("lp_qkv", ds.qkv, F32, (int64_t)B * 3 * D, s));
     if (fused) {
-    } else if (grouped)
+    } else if (gsplit)
+      ITTS_TRY(decode_attn_group_split(ds.ctx, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev,
+                                       B, H, dh, ds.Smax, ds.ct, s, 1, ds.anc, ds.nb, gsplit, ds.grp_o, ds.grp_ml));
+    else if (grouped)
       ITTS_TRY(decode_attn_group(ds.ctx, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B, H,
                                  dh, ds.Smax, ds.ct, s, 1, ds.anc, ds.nb));
     else if (grouped8)
@@ -1498,6 +1521,7 @@ GraphKey Engine::graph_key() const {
   k.rows_active = d.rows_active;
   k.rows_classes = d.rows_classes;
   k.group_attn = group_attn_on() ? 1 + (int)group_attn_kv8_on() : 0;  // 0 / 1 / 2
+  k.group_split = group_split_ns(d.B);
   return k;
 }
 

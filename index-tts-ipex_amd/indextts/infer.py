@@ -72,6 +72,9 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `group_attn_kv_fp8=True` (not in the reference; default off; ITTS_GROUP_ATTN_KV_FP8=1 / 0 overrides it in both directions; needs
     `group_attn=True` and `kv_fp8=True`) lets those steps on the e4m3 K/V cache run the grouped kernel written for that cache
     (Engine.set_group_attn_kv_fp8).
+  * `group_attn_split=N` (not in the reference; default 0 = off; ITTS_GROUP_ATTN_SPLIT=0 .. 8 overrides it; needs `group_attn=True`)
+    lets the grouped steps on the 16-bit cache deal each sentence's keys to several workgroups when few sentences leave most of
+    the chip idle: 1 (or True) takes the measured rule, 2 .. 8 force that many splits (Engine.set_group_attn_split).
   * `infer_stream(...)` (not in the reference) is `infer` as a GENERATOR of (24000, int16 [n, 1]) chunks: a sentence's
     audio starts to arrive while its codes are still being decoded.  One beam only.  `stream_chunk_frames=N` holds the default
     chunk size in latent frames (ITTS_STREAM_CHUNK overrides it).  `infer` / `infer_fast` / `infer_batch` are not affected.
@@ -101,7 +104,7 @@ class IndexTTS:
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
                  mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False,
-                 packed_vocoder=False, stream_chunk_frames=None, group_attn=False, group_attn_kv_fp8=False):
+                 packed_vocoder=False, stream_chunk_frames=None, group_attn=False, group_attn_kv_fp8=False, group_attn_split=0):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -115,6 +118,12 @@ class IndexTTS:
         if self.group_attn_kv_fp8 and not (self.group_attn and kv_fp8):
             raise ValueError("group_attn_kv_fp8=True needs group_attn=True and kv_fp8=True: it is the grouped cache attention's form "
                              "for the fp8 K/V cache and has no effect without both")
+        self.group_attn_split = int(group_attn_split)  # ... with each item's keys dealt to several workgroups (ITTS_GROUP_ATTN_SPLIT overrides)
+        if self.group_attn_split and not self.group_attn:
+            raise ValueError("group_attn_split needs group_attn=True: it splits the keys of the grouped cache attention and has no "
+                             "effect without it")
+        if not 0 <= self.group_attn_split <= 8:
+            raise ValueError("group_attn_split is 0 (off), 1 (the measured rule) or 2 .. 8 splits")
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -184,6 +193,8 @@ class IndexTTS:
             self.engine.set_group_attn(True)
         if self.group_attn_kv_fp8:
             self.engine.set_group_attn_kv_fp8(True)
+        if self.group_attn_split:
+            self.engine.set_group_attn_split(self.group_attn_split)
         self.gpt =UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])

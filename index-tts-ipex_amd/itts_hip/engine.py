@@ -340,7 +340,7 @@ class Engine:
         self._ck(self.lib.itts_gpt_set_group_attn(self.h, int(bool(on))), "gpt_set_group_attn")
 
     def group_attn_used(self) -> int:
-        """1 if the last decode step ran the grouped cache attention, 2 if it ran its fp8-cache form, else 0."""
+        """1 if the last decode step ran the grouped cache attention, 2 if it ran its fp8-cache form, 3 its key-split form, else 0."""
         return int(self.lib.itts_gpt_group_attn_used(self.h))
 
     def set_group_attn_kv_fp8(self, on: bool = True):
@@ -349,6 +349,15 @@ class Engine:
         off (the default) the two switches together run the per-row e4m3 kernel as before, bit for bit.  No effect without
         both.  ITTS_GROUP_ATTN_KV_FP8=0 / 1 in the environment overrides this setting."""
         self._ck(self.lib.itts_gpt_set_group_attn_kv_fp8(self.h, int(bool(on))), "gpt_set_group_attn_kv_fp8")
+
+    def set_group_attn_split(self, n: int = 1):
+        """Opt-in, on top of set_group_attn: the grouped steps on a 16-bit K/V cache deal the keys of each (head, batch item) to
+        several workgroups (decode_attn_group_split) and merge the partials in a second small kernel - for the few-item batches
+        at which one workgroup per (head, item) leaves most of the chip idle.  n = 0: off (the default; every step as before, bit
+        for bit); 1 (or True): on, the number of splits by itts_group_attn_split_rule(heads, items), which may keep the unsplit
+        kernel; 2 .. 8: that many splits whatever the item count (measurements).  No effect without set_group_attn, on an fp8
+        cache or on the persistent engine's row counts.  ITTS_GROUP_ATTN_SPLIT=0 .. 8 in the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_group_attn_split(self.h, int(n)), "gpt_set_group_attn_split")
 
     def decode(self, nsteps: int):
         self._ck(self.lib.itts_gpt_decode(self.h, nsteps, self._s()), "gpt_decode")
@@ -1383,7 +1392,7 @@ def _dvae_code_len(T: int, layers: int) -> int:
 def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1234, parts=("gpt", "bigvgan", "dvae"),
                  state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False,
                  kv_fp8: bool = False, engine_kv_fp8: bool = False, retire_beams: bool = False,
-                 group_attn: bool = False, group_attn_kv_fp8: bool = False) -> Engine:
+                 group_attn: bool = False, group_attn_kv_fp8: bool = False, group_attn_split: int = 0) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
     "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
@@ -1392,7 +1401,8 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
     engine_kv_fp8: Engine.set_engine_kv_fp8(True) - with an fp8 cache the small-batch decode steps stay on the persistent engine.
     retire_beams: Engine.set_retire_beams(True) - retire_rows() also retires the finished groups of a beam generation.
     group_attn: Engine.set_group_attn(True) - beam steps at more than 6 rows run the grouped cache attention.
-    group_attn_kv_fp8: Engine.set_group_attn_kv_fp8(True) - with group_attn and kv_fp8, those steps run the grouped fp8-cache kernel."""
+    group_attn_kv_fp8: Engine.set_group_attn_kv_fp8(True) - with group_attn and kv_fp8, those steps run the grouped fp8-cache kernel.
+    group_attn_split: Engine.set_group_attn_split(n) - with group_attn, the grouped 16-bit steps split each item's keys (1: by rule, 2 .. 8: forced)."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -1419,4 +1429,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
         eng.set_group_attn(True)
     if group_attn_kv_fp8:
         eng.set_group_attn_kv_fp8(True)
+    if group_attn_split:
+        eng.set_group_attn_split(int(group_attn_split))
     return eng
