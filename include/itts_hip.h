@@ -310,6 +310,18 @@ int itts_decode_attn_group_split(void* ctx, int to, const float* qkv, void* kc, 
                                  const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
                                  int nsplit, float* part_o, float* part_ml, itts_stream stream);
 
+/* The whole form of itts_decode_attn written for the e4m3 K/V cache (csrc/decode_attn_kv8.hip, what itts_gpt_set_attn_kv8 switches
+ * the batched decode step to): the same attention and the same appended bytes, with a work split of its own - 256 threads per
+ * (row, head), four lanes per 64-byte cache row with one 16-byte load each for K and V, rounds of 64 keys in a register ring,
+ * an online softmax updated once per four rounds.  The arguments of itts_decode_attn_group_kv8: tc = ITTS_FP8 (kc / vc are
+ * [B][H][Smax][64] bytes, 16-byte aligned), dh 64, `to` 0 (fp32, row-major only) or 1 (16-bit, row-major or ctx_tiled = 1); anc
+ * may be null (then nb is ignored), else 1 <= nb <= 16 and B % nb == 0.  Everything else is refused with an error status and
+ * nothing is launched.  The summation order is its own: the result agrees with itts_decode_attn to the bounds of the ctx type,
+ * not bit for bit. */
+int itts_decode_attn_kv8(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                         const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
+                         itts_stream stream);
+
 /* The prefill's K/V cache write (csrc/decode.hip kv_scatter) on caller memory: the k and v thirds of qkv [B][S][3 * H * dh]
  * (type tq) go to rows 0 .. S - 1 of each [Smax][dh] block of kc / vc [B][H][Smax][dh] (type tc), rounded to the cache type
  * (ITTS_FP8: clamped to [-448, 448], then nearest even); rows S .. Smax - 1 are not touched.  (tq, tc): fp32 -> fp32, 16-bit ->
@@ -960,6 +972,17 @@ int itts_gpt_set_group_attn_kv_fp8(itts_engine* e, int on);
  * itts_group_attn_split_rule: the splits the switch at 1 takes for H heads and `items` batch items (1 = unsplit); a pure function. */
 int itts_gpt_set_group_attn_split(itts_engine* e, int n);
 int itts_group_attn_split_rule(int H, int items);
+
+/* Opt-in, on top of itts_gpt_set_kv_fp8: the launch-path decode steps of a generation with an e4m3 K/V cache at B * H >= 512
+ * (row, head) pairs - where itts_decode_attn picks its 256-thread form - take the kernel written for 64-byte cache rows
+ * (itts_decode_attn_kv8), with or without a beam ancestry.  Both libraries.  Sticky per engine object, default 0 = every step as
+ * before, bit for bit.  The environment variable ITTS_ATTN_KV8, read per call, overrides it in both directions (1 / 0).  Without
+ * an fp8 cache and below that row count it has no effect; beam steps that itts_gpt_set_group_attn_kv_fp8 takes keep the grouped
+ * kernel.  A change re-captures the step.  It composes with row retirement and admission.  Results agree with the default path
+ * to the 16-bit bounds, not bit for bit (profiles/attn_kv8.txt).
+ * itts_gpt_attn_kv8_used: 1 if the last decode step ran that kernel, else 0 (-1 for a null engine). */
+int itts_gpt_set_attn_kv8(itts_engine* e, int on);
+int itts_gpt_attn_kv8_used(itts_engine* e);
 
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);

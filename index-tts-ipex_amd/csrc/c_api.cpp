@@ -512,6 +512,17 @@ int itts_decode_attn_group_split(void* ctx, int to, const float* qkv, void* kc, 
 
 int itts_group_attn_split_rule(int H, int items) { return group_split_rule(H, items); }
 
+int itts_decode_attn_kv8(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                         const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
+                         itts_stream stream) {
+  (void)hipGetLastError();
+  if (!ctx || !qkv || !kc || !vc || !len || !kv_start || !prefix || B < 1 || H < 1 || Smax < 1) {
+    set_error("itts_decode_attn_kv8: bad arguments (ctx, qkv, kc, vc, len, kv_start, prefix; B, H, Smax >= 1)");
+    return E_INVALID;
+  }
+  return decode_attn_kv8(ctx, to, qkv, kc, vc, len, kv_start, prefix, B, H, dh, Smax, tc, (hipStream_t)stream, ctx_tiled, anc, nb);
+}
+
 int itts_kv_scatter(void* kc, void* vc, const void* qkv, int B, int S, int H, int dh, int Smax, int tq, int tc, itts_stream stream) {
   (void)hipGetLastError();
   if (!kc || !vc || !qkv || B < 1 || S < 1 || H < 1 || dh < 1 || Smax < 1 || S > Smax) {
@@ -1356,6 +1367,11 @@ int itts_gpt_set_group_attn_split(itts_engine* e, int n) {
   ENG(e);
   return e->e.gpt_set_group_attn_split(n);
 }
+int itts_gpt_set_attn_kv8(itts_engine* e, int on) {
+  ENG(e);
+  return e->e.gpt_set_attn_kv8(on);
+}
+int itts_gpt_attn_kv8_used(itts_engine* e) { return e ? e->e.ds.last_kv8 : -1; }
 
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems) {
   if (!e || !name) return -1;

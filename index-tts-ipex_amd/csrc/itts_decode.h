@@ -288,6 +288,12 @@ int decode_attn_group_split(void* ctx, int to, const float* qkv, void* kc, void*
                             const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
                             const uint8_t* anc, int nb, int nsplit, float* part_o, float* part_ml);
 int group_split_rule(int H, int items);  // nsplit the decode step takes at H * items unsplit workgroups (1: unsplit).  No GPU work
+// decode_attn_kv8.hip (opt-in): decode_attn2's whole form written for the e4m3 cache - 4 lanes per 64-byte key row with one
+// 16-byte load each for K and V, rounds of 64 keys in a register ring, batched online softmax.  tc FP8, ctx 16-bit (row-major or
+// tile_off) or fp32, head dim 64, caches 16-byte aligned, with or without the ancestry `anc` (then 1 <= nb <= 16, B % nb == 0)
+int decode_attn_kv8(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
+                    const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled, const uint8_t* anc,
+                    int nb);
 // decode_fused.hip: LN + c_attn projection and the cache attention of one layer in one launch (qkv_attn_fused_kernel)
 bool qkv_attn_fused_supported(const GemvArgs& g, int H, int dh);
 int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* kc, void* vc, const int* len,

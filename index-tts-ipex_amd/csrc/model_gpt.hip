@@ -295,6 +295,17 @@ int Engine::group_split_ns(int B) const {
   if (n == 1) n = group_split_rule(cfg.heads, B / ds.nb);
   return n >= 2 ? n : 0;
 }
+// Opt-in (sticky; ITTS_ATTN_KV8 overrides it per call, =0 included): the whole-form cache attention of a launch-path step on an
+// fp8 K/V cache at B * H >= 512 runs decode_attn_kv8 (decode_attn_kv8.hip) instead of decode_attn2_kernel<fp8_t, .., 256>.  Part
+// of the graph key.
+int Engine::gpt_set_attn_kv8(int on) {
+  ds.attn_kv8 = on != 0;
+  return OK;
+}
+bool Engine::attn_kv8_on() const {
+  const char* ev = getenv("ITTS_ATTN_KV8");
+  return ev ? atoi(ev) != 0 : ds.attn_kv8 != 0;
+}
 
 int Engine::ensure_engine_state(hipStream_t s) {
   DecodeState& d = ds;
@@ -1079,6 +1090,7 @@ int Engine::decode_step_launch(hipStream_t s) {
   ds.pend_split = 0;
   ds.last_mode = 0;
   ds.last_grp = 0;
+  ds.last_kv8 = 0;
   int eng_first = 0;
   if (engine_usable()) {  // <= 6 rows: the 24 blocks (+ head, + greedy sampler) as ONE persistent launch
     ITTS_REQUIRE(ds.eng_gran && ds.eng_ctr, "decode engine: state not allocated (prefill first)");
@@ -1160,6 +1172,10 @@ int Engine::decode_step_launch(hipStream_t s) {
   // opt-in on top of it: few items leave most of the chip idle - the keys of each (head, item) go to gsplit workgroups
   const int gsplit = grouped ? group_split_ns(B) : 0;
   ds.last_grp = eng_first < c.layers ? (gsplit ? 3 : grouped ? 1 : grouped8 ? 2 : 0) : 0;
+  // opt-in: the whole-form call on an e4m3 cache, with or without ancestry, at the row counts where decode_attn2 picks its
+  // 256-thread form (decode_attn_kv8.hip); the grouped fp8 kernel keeps the beam steps it takes, an fp8 cache has no split form
+  const bool kv8 = attn_kv8_on() && ds.ct == FP8 && (long)B * H >= 512 && dh == 64 && !grouped8;
+  ds.last_kv8 = kv8 && eng_first < c.layers;
   for (int l = eng_first; l < c.layers; ++l) {
     const GptLayerW& L = gpt.layers[l];
     GemvArgs g = lin_gemv(L.attn, B);  // qkv = LN1(h) Wqkv + b
@@ -1202,6 +1218,9 @@ int Engine::decode_step_launch(hipStream_t s) {
     else if (split)
       ITTS_TRY(decode_attn2(nullptr, BF16, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start, ds.prefix_dev, B, H,
                             dh, ds.Smax, ds.ct, s, 0, ds.attn_o, ds.attn_ml, ds.nb > 1 ? ds.anc : nullptr, ds.nb));
+    else if (kv8)
+      ITTS_TRY(decode_attn_kv8(ds.ctx, bf_ctx ? BF16 : F32, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start,
+                               ds.prefix_dev, B, H, dh, ds.Smax, ds.ct, s, skinny ? 1 : 0, ds.nb > 1 ? ds.anc : nullptr, ds.nb));
     else
       ITTS_TRY(decode_attn2(ds.ctx, bf_ctx ? BF16 : F32, ds.qkv, (char*)ds.kc + lo, (char*)ds.vc + lo, ds.len, ds.kv_start,
                             ds.prefix_dev, B, H, dh, ds.Smax, ds.ct, s, skinny ? 1 : 0, nullptr, nullptr,
@@ -1522,6 +1541,7 @@ GraphKey Engine::graph_key() const {
   k.rows_classes = d.rows_classes;
   k.group_attn = group_attn_on() ? 1 + (int)group_attn_kv8_on() : 0;  // 0 / 1 / 2
   k.group_split = group_split_ns(d.B);
+  k.attn_kv8 = (int)attn_kv8_on();
   return k;
 }
 
@@ -1557,10 +1577,12 @@ int Engine::gpt_decode_steps(int nsteps, hipStream_t s) {
       d.graph_key = key;
       d.graph_mode = d.last_mode;  // what the captured step runs on
       d.graph_grp = d.last_grp;
+      d.graph_kv8 = d.last_kv8;
       ++d.graph_captures;
     }
     d.last_mode = d.graph_mode;  // a replayed graph: the mode it was captured with
     d.last_grp = d.graph_grp;
+    d.last_kv8 = d.graph_kv8;
     int left = nsteps;
     if (d.graphK)
       for (; left >= GK; left -= GK) ITTS_HIP_CHECK(hipGraphLaunch(d.graphK, s));

@@ -75,6 +75,9 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `group_attn_split=N` (not in the reference; default 0 = off; ITTS_GROUP_ATTN_SPLIT=0 .. 8 overrides it; needs `group_attn=True`)
     lets the grouped steps on the 16-bit cache deal each sentence's keys to several workgroups when few sentences leave most of
     the chip idle: 1 (or True) takes the measured rule, 2 .. 8 force that many splits (Engine.set_group_attn_split).
+  * `attn_kv8=True` (not in the reference; default off; ITTS_ATTN_KV8=1 / 0 overrides it in both directions; needs `kv_fp8=True`)
+    lets the batched decode steps on the e4m3 K/V cache at rows x heads >= 512 (26 rows of the 20-head model) run the cache
+    attention written for 64-byte cache rows instead of the 16-bit kernel's mapping (Engine.set_attn_kv8).
   * `infer_stream(...)` (not in the reference) is `infer` as a GENERATOR of (24000, int16 [n, 1]) chunks: a sentence's
     audio starts to arrive while its codes are still being decoded.  One beam only.  `stream_chunk_frames=N` holds the default
     chunk size in latent frames (ITTS_STREAM_CHUNK overrides it).  `infer` / `infer_fast` / `infer_batch` are not affected.
@@ -104,7 +107,8 @@ class IndexTTS:
                  use_cuda_kernel=None, state_dicts=None, cfg=None, gpt_fp8=False, wide_sampler=None,
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
                  mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False,
-                 packed_vocoder=False, stream_chunk_frames=None, group_attn=False, group_attn_kv_fp8=False, group_attn_split=0):
+                 packed_vocoder=False, stream_chunk_frames=None, group_attn=False, group_attn_kv_fp8=False, group_attn_split=0,
+                 attn_kv8=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -124,6 +128,10 @@ class IndexTTS:
                              "effect without it")
         if not 0 <= self.group_attn_split <= 8:
             raise ValueError("group_attn_split is 0 (off), 1 (the measured rule) or 2 .. 8 splits")
+        self.attn_kv8 = bool(attn_kv8)  # batched steps on the fp8 K/V cache: the kernel written for e4m3 rows (ITTS_ATTN_KV8 overrides)
+        if self.attn_kv8 and not kv_fp8:
+            raise ValueError("attn_kv8=True needs kv_fp8=True: it is the cache attention written for the fp8 K/V cache and has no "
+                             "effect on the 16-bit cache")
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -195,6 +203,8 @@ class IndexTTS:
             self.engine.set_group_attn_kv_fp8(True)
         if self.group_attn_split:
             self.engine.set_group_attn_split(self.group_attn_split)
+        if self.attn_kv8:
+            self.engine.set_attn_kv8(True)
         self.gpt =UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])

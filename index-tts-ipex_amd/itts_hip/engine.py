@@ -350,6 +350,18 @@ class Engine:
         both.  ITTS_GROUP_ATTN_KV_FP8=0 / 1 in the environment overrides this setting."""
         self._ck(self.lib.itts_gpt_set_group_attn_kv_fp8(self.h, int(bool(on))), "gpt_set_group_attn_kv_fp8")
 
+    def set_attn_kv8(self, on: bool = True):
+        """Opt-in, on top of set_kv_fp8: the launch-path decode steps on an e4m3 K/V cache at rows x heads >= 512 take
+        decode_attn_kv8, the cache attention written for 64-byte rows (four lanes per key row with 16-byte loads, a register ring
+        of four 64-key rounds, a batched online softmax), with or without beams; off (the default) they run decode_attn2's e4m3
+        form as before, bit for bit.  No effect without an fp8 cache or below that row count.  ITTS_ATTN_KV8=0 / 1 in the
+        environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_attn_kv8(self.h, int(bool(on))), "gpt_set_attn_kv8")
+
+    def attn_kv8_used(self) -> int:
+        """1 if the last decode step ran decode_attn_kv8, else 0."""
+        return int(self.lib.itts_gpt_attn_kv8_used(self.h))
+
     def set_group_attn_split(self, n: int = 1):
         """Opt-in, on top of set_group_attn: the grouped steps on a 16-bit K/V cache deal the keys of each (head, batch item) to
         several workgroups (decode_attn_group_split) and merge the partials in a second small kernel - for the few-item batches
@@ -1392,7 +1404,8 @@ def _dvae_code_len(T: int, layers: int) -> int:
 def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1234, parts=("gpt", "bigvgan", "dvae"),
                  state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False,
                  kv_fp8: bool = False, engine_kv_fp8: bool = False, retire_beams: bool = False,
-                 group_attn: bool = False, group_attn_kv_fp8: bool = False, group_attn_split: int = 0) -> Engine:
+                 group_attn: bool = False, group_attn_kv_fp8: bool = False, group_attn_split: int = 0,
+                 attn_kv8: bool = False) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
     "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
@@ -1402,7 +1415,8 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
     retire_beams: Engine.set_retire_beams(True) - retire_rows() also retires the finished groups of a beam generation.
     group_attn: Engine.set_group_attn(True) - beam steps at more than 6 rows run the grouped cache attention.
     group_attn_kv_fp8: Engine.set_group_attn_kv_fp8(True) - with group_attn and kv_fp8, those steps run the grouped fp8-cache kernel.
-    group_attn_split: Engine.set_group_attn_split(n) - with group_attn, the grouped 16-bit steps split each item's keys (1: by rule, 2 .. 8: forced)."""
+    group_attn_split: Engine.set_group_attn_split(n) - with group_attn, the grouped 16-bit steps split each item's keys (1: by rule, 2 .. 8: forced).
+    attn_kv8: Engine.set_attn_kv8(True) - with kv_fp8, the batched steps at rows x heads >= 512 run the cache attention written for e4m3 rows."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -1431,4 +1445,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
         eng.set_group_attn_kv_fp8(True)
     if group_attn_split:
         eng.set_group_attn_split(int(group_attn_split))
+    if attn_kv8:
+        eng.set_attn_kv8(True)
     return eng

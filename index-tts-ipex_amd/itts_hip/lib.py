@@ -155,6 +155,7 @@ _PROTOS = {
     "itts_decode_attn_group_kv8": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "itts_decode_attn_group_split": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "itts_group_attn_split_rule": (i32, [i32, i32]),
+    "itts_decode_attn_kv8": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "itts_kv_scatter": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "itts_sample_rows": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, f32, f32, vp, vp, C.c_size_t, vp]),
     "itts_beam_sample_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, f32, f32, vp,
@@ -196,6 +197,8 @@ _PROTOS = {
     "itts_gpt_group_attn_used": (i32, [vp]),
     "itts_gpt_set_group_attn_kv_fp8": (i32, [vp, i32]),
     "itts_gpt_set_group_attn_split": (i32, [vp, i32]),
+    "itts_gpt_set_attn_kv8": (i32, [vp, i32]),
+    "itts_gpt_attn_kv8_used": (i32, [vp]),
     "itts_gpt_set_host_sampling": (i32, [vp, i32]),
     "itts_gpt_set_cond_per_row": (i32, [vp, i32]),
     "itts_gpt_commit": (i32, [vp, vp, vp]),
