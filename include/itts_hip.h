@@ -291,7 +291,7 @@ int itts_decode_attn_group(void* ctx, int to, const float* qkv, void* kc, void* 
                            const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
                            itts_stream stream);
 
-/* The grouped step on an e4m3 K/V cache (csrc/decode_attn_group_kv8.hip, what itts_gpt_set_group_attn_kv_fp8 switches to): the
+/* The grouped step on an e4m3 K/V cache (decode_attn_group_kv8_kernel in csrc/decode_attn_group.hip, what itts_gpt_set_group_attn_kv_fp8 switches to): the
  * arguments of itts_decode_attn_group with tc = ITTS_FP8 (kc / vc are [B][H][Smax][64] bytes) and `to` = 1.  A workgroup reads
  * 64-position units of 64-byte rows, decodes them exactly into the 16-bit type for the matrix cores, and appends this step's
  * k / v as the bytes itts_decode_attn and itts_kv_scatter write.  dh 64, 2 <= nb <= 16, B % nb == 0, anc set; everything else is
@@ -300,7 +300,7 @@ int itts_decode_attn_group_kv8(void* ctx, int to, const float* qkv, void* kc, vo
                                const int* prefix, int B, int H, int dh, int Smax, int tc, int ctx_tiled, const uint8_t* anc, int nb,
                                itts_stream stream);
 
-/* The 16-bit grouped step with a key split (csrc/decode_attn_group_split.hip, what itts_gpt_set_group_attn_split switches to): the
+/* The 16-bit grouped step with a key split (its split and merge kernels in csrc/decode_attn_group.hip, what itts_gpt_set_group_attn_split switches to): the
  * arguments and requirements of itts_decode_attn_group, plus nsplit (2 .. 8) workgroups per (head, batch item), each taking a
  * contiguous chunk of the item's 32-position tiles, and a merge kernel that writes ctx.  The two fp32 workspaces are the caller's:
  * part_o [nsplit][B][H][64] (un-normalised weighted V per split) and part_ml [nsplit][B][H][2] (maximum, sum); every slot is

@@ -469,9 +469,9 @@ struct Engine {
   int gpt_set_engine_kv_fp8(int on);  // opt-in: the persistent engine reads and appends an fp8 K/V cache (decode_engine_kernel<.., KV8>)
   int gpt_set_group_attn(int on);     // opt-in: beam steps on the launch path at > 6 rows run decode_attn_group (decode_attn_group.hip)
   bool group_attn_on() const;         // the switch as ITTS_GROUP_ATTN (read per call) or the setter says
-  int gpt_set_group_attn_kv_fp8(int on);  // opt-in on top of it: an fp8 cache takes decode_attn_group_kv8 (decode_attn_group_kv8.hip)
+  int gpt_set_group_attn_kv_fp8(int on);  // opt-in on top of it: an fp8 cache takes decode_attn_group_kv8 (decode_attn_group.hip)
   bool group_attn_kv8_on() const;         // that switch as ITTS_GROUP_ATTN_KV_FP8 (read per call) or the setter says
-  int gpt_set_group_attn_split(int n);    // opt-in on top of group_attn: key splits of the 16-bit grouped kernel (decode_attn_group_split.hip)
+  int gpt_set_group_attn_split(int n);    // opt-in on top of group_attn: key splits of the 16-bit grouped kernel (decode_attn_group.hip)
   int group_split_ns(int B) const;        // the splits a grouped 16-bit step at B rows takes, as ITTS_GROUP_ATTN_SPLIT (read per call) or the setter says (0: unsplit)
   int gpt_set_attn_kv8(int on);           // opt-in: batched steps on an fp8 cache run the kernel written for 64-byte rows (decode_attn_kv8.hip)
   bool attn_kv8_on() const;               // that switch as ITTS_ATTN_KV8 (read per call) or the setter says

@@ -273,12 +273,12 @@ int decode_attn2(void* ctx, int to, const float* qkv, void* kc, void* vc, const 
 int decode_attn_group(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
                       const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
                       const uint8_t* anc, int nb);
-// decode_attn_group_kv8.hip (opt-in on top of it): the grouped step on an e4m3 cache - 64-position units of 64-byte rows, decoded
+// decode_attn_group.hip, e4m3 kernel (opt-in on top of it): the grouped step on an e4m3 cache - 64-position units of 64-byte rows, decoded
 // exactly into the 16-bit type for the same MFMAs.  tc FP8, 16-bit ctx, head dim 64, 2 <= nb <= 16
 int decode_attn_group_kv8(void* ctx, int to, const float* qkv, void* kc, void* vc, const int* len, const int* kv_start,
                           const int* prefix_dev, int B, int H, int dh, int Smax, int tc, hipStream_t s, int ctx_tiled,
                           const uint8_t* anc, int nb);
-// decode_attn_group_split.hip (opt-in on top of decode_attn_group): the 16-bit grouped step with the keys of each (head, item) dealt
+// decode_attn_group.hip, split + merge kernels (opt-in on top of decode_attn_group): the 16-bit grouped step with the keys of each (head, item) dealt
 // to nsplit workgroups (grid (H, items, nsplit)) and a merge kernel behind it; the arguments and requirements of decode_attn_group
 // plus 2 <= nsplit <= GROUP_SPLIT_MAX and the two workspaces, fp32, every slot written by every launch:
 //   part_o  [nsplit][B][H][64]  un-normalised weighted V of split z for (row b, head h)

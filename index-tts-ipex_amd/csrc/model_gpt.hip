@@ -271,7 +271,7 @@ bool Engine::group_attn_on() const {
   return ev ? atoi(ev) != 0 : ds.group_attn != 0;
 }
 // Opt-in on top of it (sticky; ITTS_GROUP_ATTN_KV_FP8 overrides it per call, =0 included): those steps on an fp8 K/V cache run
-// decode_attn_group_kv8 (decode_attn_group_kv8.hip) instead of decode_attn2_kernel<fp8_t, .., ANC>.  Part of the graph key too.
+// decode_attn_group_kv8 (decode_attn_group.hip) instead of decode_attn2_kernel<fp8_t, .., ANC>.  Part of the graph key too.
 int Engine::gpt_set_group_attn_kv_fp8(int on) {
   ds.group_attn_kv8 = on != 0;
   return OK;
@@ -281,7 +281,7 @@ bool Engine::group_attn_kv8_on() const {
   return ev ? atoi(ev) != 0 : ds.group_attn_kv8 != 0;
 }
 // Opt-in on top of group_attn (sticky; ITTS_GROUP_ATTN_SPLIT overrides it per call, =0 included): the grouped steps on a 16-bit
-// cache deal each (head, item)'s keys to several workgroups (decode_attn_group_split.hip).  0 off, 1 group_split_rule, 2 .. 8 forced.
+// cache deal each (head, item)'s keys to several workgroups (decode_attn_group_split, decode_attn_group.hip).  0 off, 1 group_split_rule, 2 .. 8 forced.
 // The splits in effect are part of the graph key.
 int Engine::gpt_set_group_attn_split(int n) {
   ITTS_REQUIRE(n >= 0 && n <= GROUP_SPLIT_MAX, "gpt_set_group_attn_split: 0 (off), 1 (by rule) or 2 .. 8 splits");
@@ -430,7 +430,7 @@ int Engine::ensure_beam_state(int rows, int max_gen, int Smax, hipStream_t s) {
   ITTS_TRY(dev_alloc((void**)&d.hyp_worst, (size_t)r * 4));
   ITTS_TRY(dev_alloc((void**)&d.hyp_counter, (size_t)r * 4));
   ITTS_TRY(dev_alloc((void**)&d.beam_done, (size_t)r * 4));
-  // partials of the grouped attention's key split (decode_attn_group_split.hip), sized for GROUP_SPLIT_MAX splits
+  // partials of the grouped attention's key split (decode_attn_group.hip), sized for GROUP_SPLIT_MAX splits
   ITTS_TRY(dev_alloc((void**)&d.grp_o, (size_t)GROUP_SPLIT_MAX * r * cfg.heads * 64 * 4));
   ITTS_TRY(dev_alloc((void**)&d.grp_ml, (size_t)GROUP_SPLIT_MAX * r * cfg.heads * 2 * 4));
   d.beam_rows = r;
@@ -1167,7 +1167,7 @@ int Engine::decode_step_launch(hipStream_t s) {
   // 16-bit cache; everything else (the engine's row counts, an fp8 cache, fp32 engines, the split and fused forms) keeps decode_attn2
   const bool grp_shape = group_attn_on() && ds.nb > 1 && ds.nb <= 16 && ds.anc && skinny && B > ENG_MAX_ROWS && B % ds.nb == 0;
   const bool grouped = grp_shape && ds.ct == BF16;
-  // opt-in on top of it: the same steps on an e4m3 cache (decode_attn_group_kv8.hip); without it they keep decode_attn2<fp8_t>
+  // opt-in on top of it: the same steps on an e4m3 cache (decode_attn_group_kv8, decode_attn_group.hip); without it they keep decode_attn2<fp8_t>
   const bool grouped8 = grp_shape && ds.ct == FP8 && group_attn_kv8_on();
   // opt-in on top of it: few items leave most of the chip idle - the keys of each (head, item) go to gsplit workgroups
   const int gsplit = grouped ? group_split_ns(B) : 0;

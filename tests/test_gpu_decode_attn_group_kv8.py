@@ -1,4 +1,4 @@
-"""The grouped cache attention on the e4m3 K/V cache (csrc/decode_attn_group_kv8.hip) through itts_decode_attn_group_kv8, with the
+"""The grouped cache attention on the e4m3 K/V cache (csrc/decode_attn_group.hip) through itts_decode_attn_group_kv8, with the
 fixture of tests/test_gpu_decode_attn_fp8.py (`launch`: append to the byte, other cache bytes, guards, no NaN byte, finite ctx; finite
 winning poison) behind an adapter.  The Call's caches are the PHYSICAL rows, beam q's history is K[base + anc[q][j], h, j]; reference:
 fp64 softmax over that gathered history from the stored e4m3 values plus the row's rounded k / v.  Unit U = 64 positions; entries at

@@ -1,4 +1,4 @@
-"""The grouped cache attention with a key split (csrc/decode_attn_group_split.hip) through itts_decode_attn_group_split, on the
+"""The grouped cache attention with a key split (csrc/decode_attn_group.hip) through itts_decode_attn_group_split, on the
 fixture of tests/test_gpu_decode_attn_group.py (`problem`: physical rows, poison outside [kv_start, pos), fp64 reference over the
 gathered history) and the `launch` / `judge` of tests/test_gpu_decode_attn.py (append to the bit, every other cache byte, guards,
 NaN / Inf; fp64 agreement at 2^-8 / 2^-10; only the appended key visible -> the rounded v to the bit).  The adapter allocates the

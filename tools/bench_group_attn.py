@@ -12,8 +12,8 @@ the layers of a decode step do, so that no launch finds its rows in the caches o
 two kernels are alternated `rounds` times in one process after a warm-up of both; per kernel `iters` launches between two device
 events.  Printed: ms per launch (min and median of the rounds), the bytes each algorithm has to fetch and that rate, and the
 largest difference between the two results.  --kv-fp8: the same on e4m3 caches (tc = ITTS_FP8) - the per-row e4m3 kernel against
-itts_decode_attn_group_kv8 (csrc/decode_attn_group_kv8.hip), half the bytes per row.  --split N (repeatable, 16-bit caches): the
-key-split form itts_decode_attn_group_split (csrc/decode_attn_group_split.hip, its two kernels) at N splits joins the alternation as
+itts_decode_attn_group_kv8 (csrc/decode_attn_group.hip), half the bytes per row.  --split N (repeatable, 16-bit caches): the
+key-split form itts_decode_attn_group_split (csrc/decode_attn_group.hip, its two kernels) at N splits joins the alternation as
 a further contender, in the same process and the same rounds; its time is also printed over the unsplit grouped kernel's.  --items
 takes several item counts, measured one after another.  Run it under a time limit; profiles/group_attn.txt,
 profiles/group_attn_kv8.txt and profiles/group_attn_split.txt hold records."""
