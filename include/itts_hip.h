@@ -356,6 +356,21 @@ int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_be
                           float top_p, float temperature, const float* uniforms, void* scratch, size_t scratch_bytes,
                           itts_stream stream);
 
+/* The sort-free forms of the two entries above (sampler_select_kernel in csrc/decode_sampler.hip, beam_wide_cand_sel_kernel in
+ * csrc/beam.hip; what itts_gpt_set_wide_select switches to): the same arguments, argument checks, scratch and results.  The TopK
+ * threshold, the TopP cut and the drawn rank are found by radix descents over the score bits with the masses
+ * round(expf(s - max) * 2^40) summed as 64-bit integers, so results repeat bit for bit, and agree with the sorted kernels to
+ * the bounds of their fp32 sums, not bit for bit.  itts_sample_rows_select runs that kernel for ANY top_k, 1 <= top_k
+ * <= 128 included (V <= 16384), and always fills kept; itts_beam_sample_rows_select replaces the first of the two launches. */
+int itts_sample_rows_select(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty,
+                            int stop, int suppress_stop, int preprocessed, int top_k, float top_p, float temperature,
+                            const float* uniforms, void* scratch, size_t scratch_bytes, itts_stream stream);
+int itts_beam_sample_rows_select(float* pick_score, int32_t* pick_tok, int32_t* pick_beam, int32_t* kept, const float* logits,
+                                 const int32_t* ids, int ids_stride, int k, const float* beam_scores, int items, int num_beams, int V,
+                                 float penalty, int stop, int suppress_stop, int start_tok, int fake_id, int preprocessed, int top_k,
+                                 float top_p, float temperature, const float* uniforms, void* scratch, size_t scratch_bytes,
+                                 itts_stream stream);
+
 /* Decode-step projections at batch > 4 (same Conv1D call sites): X bf16 [B, K], W bf16 [N, K], weights streamed once,
  * batch on MFMA; Y fp32 [B, N] (store, or += when accumulate) or bf16 when y_bf16.  K % 32 == 0, B <= 128.
  * ksplit > 1 splits K over workgroups: raw sums go to partial[ksplit][B][N] (no bias / act / Y), to be absorbed by
@@ -983,6 +998,15 @@ int itts_group_attn_split_rule(int H, int items);
  * itts_gpt_attn_kv8_used: 1 if the last decode step ran that kernel, else 0 (-1 for a null engine). */
 int itts_gpt_set_attn_kv8(itts_engine* e, int on);
 int itts_gpt_attn_kv8_used(itts_engine* e);
+
+/* Opt-in: wherever a decode step, the first token of an admitted row or beam group, or a beam step launches a whole-vocabulary
+ * device sampler (top_k < 1 or > 128: sampler_wide_kernel, beam_wide_cand_kernel), it launches the sort-free form
+ * (itts_sample_rows_select / itts_beam_sample_rows_select).  Scalar settings, per-row tables and beams alike.  Sticky per engine
+ * object, default 0 = every launch as before, bit for bit.  The environment variable ITTS_WIDE_SELECT, read per call, overrides it
+ * in both directions (1 / 0); the stateless itts_sampler_step / itts_sampler_step_rows, which have no engine, follow the variable
+ * alone.  No effect where the host chooses the token or a narrow sampler runs.  A change re-captures the step (DESIGN.md 5s,
+ * profiles/wide_select.txt). */
+int itts_gpt_set_wide_select(itts_engine* e, int on);
 
 /* Debug/testing: copy a named intermediate of the LAST call into host memory (fp32), returns element count. */
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems);

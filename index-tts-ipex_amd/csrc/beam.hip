@@ -617,6 +617,103 @@ __global__ __launch_bounds__(1024) void beam_wide_cand_kernel(BeamArgs a, BeamWi
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The same first launch without the sort (opt-in: ITTS_WIDE_SELECT / itts_gpt_set_wide_select, itts_beam_sample_rows_select;
+// DESIGN.md 5s).  The sort above serves two thresholds; here each is a radix descent (itts_sampler_dev.h select_*) over keys
+// that stay in registers - thread t owns the tokens t, t + 1024, ... - and w.sc is written by the token's owner:
+//   1. scores by the expressions of step 1 above, as keys; s0 = the row maximum
+//   3. TopK: T = the key at rank kk - 1 (select_count) when the row has kk finite scores; the n keys >= T stay
+//   4. TopP: masses round(expf(s - s0) * 2^40) as 64-bit integers, Z their sum; the last rank whose tail mass is above
+//      floor((1 - top_p) * Z), the product formed in fp64 (select_mass_from_bottom); R = clamp(that rank + 1, 2, n)
+//   5. the R kept tokens are the keys above the key Kb at rank R - 1 and the members of Kb's group up to the id of the
+//      (R - ranks above Kb)-th (select_group_member); R raised to 2 takes Kb from select_count
+// Integer sums only: the same bits on every run and in every batch.  Nothing is written where the launch above writes nothing.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void beam_wide_cand_sel_kernel(BeamArgs a, BeamWide w) {
+  __shared__ SelectLds L;
+  __shared__ unsigned seenw[512];  // V <= 16384 bits
+  __shared__ float red[16];
+  const int r = blockIdx.x, bi = blockIdx.y, tid = threadIdx.x;
+  const int nb = a.nb, V = a.V, Beff = a.B * nb, mg = a.max_gen;
+  const int k = a.len[bi * nb];
+  if ((k >= mg && !w.one_step) || a.done[bi] || (a.forced && k < a.input_n)) return;  // block-uniform
+  const int* ids_old = w.one_step ? a.ids : a.ids + (size_t)(k & 1) * Beff * mg;
+  const int row = bi * nb + r;
+  const float* __restrict__ lg = a.logits + (size_t)row * V;
+  const float lse = a.preprocessed ? 0.f : row_logsumexp(lg, V, red, tid);
+  beam_seen_bitmap(seenw, V, a.fake_id, a.start_tok, ids_old + (size_t)row * mg, k, tid);
+  unsigned key[SEL_PER];
+  float e[SEL_PER];  // expf(score - s0) of the kept tokens, 0 for the others
+  float mx = -INFINITY;
+  unsigned live = 0;
+#pragma unroll
+  for (int q = 0; q < SEL_PER; ++q) {
+    const int i = tid + 1024 * q;
+    float v = -INFINITY;
+    if (i < V) {
+      v = lg[i] - lse;
+      if (!a.preprocessed) v = processed_score(v, seen_bit(seenw, i), a.penalty, a.suppress_stop, a.stop, i);
+      if (a.temperature != 1.f) v = v / a.temperature;
+    }
+    key[q] = select_key(v);
+    if (key[q]) {
+      mx = fmaxf(mx, v);
+      ++live;
+    }
+  }
+  auto key_of = [&](int q) { return key[q]; };
+  auto mass_of = [&](int q) { return select_mass_of(e[q]); };
+  select_init(L, tid);
+  const float s0 = block_max(mx, red, tid);
+  sel_u64 n = block_add(live, L.red, tid);  // the finite scores
+  unsigned T = 1;
+  const sel_u64 kk = (sel_u64)min(max(a.top_k, 2), V);
+  if (a.top_k >= 1 && kk <= n) {  // block-uniform, as every branch below
+    sel_u64 above;
+    T = select_count(L, kk - 1, key_of, &above, tid);
+    n = above + (select_above_equal(L, T, key_of, tid) & 0xFFFFFFFFull);
+  }
+  sel_u64 R = n, keep_in = n;  // the kept ranks; how many of them lie in the group of Kb, the key at rank R - 1 (R = n: all of key >= T)
+  unsigned Kb = T;
+  bool whole_group = true;
+  if (a.top_p < 1.f && n > 2) {
+    sel_u64 own = 0, rem;
+#pragma unroll
+    for (int q = 0; q < SEL_PER; ++q) {
+      e[q] = key[q] >= T ? expf(select_score(key[q]) - s0) : 0.f;
+      own += select_mass_of(e[q]);
+    }
+    const sel_u64 Z = block_add(own, L.red, tid);
+    if (Z) {  // (an infinite maximum carries no mass: every rank stays)
+      const sel_u64 thr = (sel_u64)((1.0 - (double)a.top_p) * (double)Z);  // rank r stays iff tail_r > thr
+      const unsigned K = select_mass_from_bottom(L, thr + 1 < Z ? thr + 1 : Z, key_of, mass_of, &rem, tid);
+      const sel_u64 mK = max(select_mass(K, s0), 1ull), jb = (rem + mK - 1) / mK;  // the jb-th member from the group's end
+      const sel_u64 ae = select_above_equal(L, K, key_of, tid), eq = ae & 0xFFFFFFFFull;
+      sel_u64 above = ae >> 32;
+      R = above + eq - jb + 1;
+      Kb = K;
+      keep_in = eq - jb + 1;
+      whole_group = jb == 1;
+      if (R < 2) {  // min_tokens_to_keep
+        R = 2;
+        Kb = select_count(L, 1, key_of, &above, tid);
+        keep_in = 2 - above;
+        whole_group = false;
+      }
+    }
+  }
+  // the highest kept id inside Kb's group (its group is kept whole when the cut falls behind its last member)
+  const int id_last = whole_group ? 0x3FFF : select_group_member(L, Kb, keep_in - 1, key_of, tid);
+  const float bs = a.beam_scores[row];
+  float* __restrict__ out = w.sc + (size_t)row * V;
+#pragma unroll
+  for (int q = 0; q < SEL_PER; ++q) {
+    const int i = tid + 1024 * q;
+    if (i < V) out[i] = key[q] >= T && (key[q] > Kb || (key[q] == Kb && i <= id_last)) ? select_score(key[q]) + bs : -INFINITY;
+  }
+  if (tid == 0) w.kept[row] = (int)R;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Second launch: grid (B), one 1024-thread workgroup per batch item, the 2 * nb draws WITHOUT replacement over the item's
 // nb * V scores of w.sc in flat order f = r * V + t (beam-major, token-ascending: next_token_scores.view(batch, beams * vocab),
 // the order of infer_core.host_beam_step).  -inf entries are dead; m = the largest score, e_f = expf(s_f - m).
@@ -827,28 +924,32 @@ int beam_wide_prepare() {
   return allow_dynamic_lds(latch, (const void*)beam_wide_cand_kernel, BEAM_WIDE_MAX_V * 6);
 }
 
-int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s) {
+int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s, bool select) {
   ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB && a.B >= 1, "beam_sample (whole vocabulary): 2 <= num_beams <= 10");
   ITTS_REQUIRE(a.V >= 2 && a.V <= BEAM_WIDE_MAX_V, "beam_sample: top_k outside [1, 128] needs a vocabulary of at most 16384");
   ITTS_REQUIRE(a.top_p > 0.f && a.temperature > 0.f, "beam_sample: top_p > 0, temperature > 0");
   ITTS_REQUIRE(a.stop >= 0 && a.stop < a.V && a.max_gen >= 1, "beam_sample: stop token outside the vocabulary");
   ITTS_REQUIRE(a.logits && a.uniforms && a.ids && a.len && a.done && a.beam_scores, "beam_sample: null state");
   ITTS_REQUIRE(w.sc && w.kept && w.pick_sc && w.pick_tok && w.pick_beam, "beam_sample: whole-vocabulary scratch missing");
-  ITTS_TRY(beam_wide_prepare());
-  int np = 1024;
-  while (np < a.V) np <<= 1;
-  hipLaunchKernelGGL(beam_wide_cand_kernel, dim3(a.nb, a.B), dim3(1024), (size_t)np * 6, s, a, w, np);
+  if (select) {
+    hipLaunchKernelGGL(beam_wide_cand_sel_kernel, dim3(a.nb, a.B), dim3(1024), 0, s, a, w);
+  } else {
+    ITTS_TRY(beam_wide_prepare());
+    int np = 1024;
+    while (np < a.V) np <<= 1;
+    hipLaunchKernelGGL(beam_wide_cand_kernel, dim3(a.nb, a.B), dim3(1024), (size_t)np * 6, s, a, w, np);
+  }
   hipLaunchKernelGGL(beam_wide_pick_kernel, dim3(a.B), dim3(1024), 0, s, a, w);
   ITTS_HIP_CHECK(hipGetLastError());
   return OK;
 }
 
-int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w) {
+int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w, bool select) {
   ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB, "beam_sample: 2 <= num_beams <= 10");
   if (a.do_sample && (a.top_k < 1 || a.top_k > BEAM_MAX_CAND)) {  // TopK off or wider than beam_cand_kernel's candidates
     ITTS_REQUIRE(w, "beam_sample: whole-vocabulary scratch missing");
     ITTS_REQUIRE(a.anc && a.hyp_tok, "beam_sample: null state");
-    ITTS_TRY(beam_wide_pair(a, *w, s));
+    ITTS_TRY(beam_wide_pair(a, *w, s, select));
     BeamArgs sel = a;  // beam_select_kernel takes the picks in draw order where it takes the host's
     sel.host_sc = w->pick_sc;
     sel.host_tok = w->pick_tok;
@@ -872,7 +973,7 @@ int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w) {
 // blockIdx-relative item 0 is that item - while a.B stays the full item count: the kernels use a.B only for the bases of the
 // ping-pong halves (Beff = a.B * nb rows behind ids / anc) and for the stride of the draws ((k * a.B + bi) * 2 nb), and both are
 // relative to pointers that moved by the item's own offset inside a half / a step.  prefix_dev and the embedding tables stay
-int beam_item_step(const BeamArgs& a, int item, hipStream_t s, const BeamWide* w) {
+int beam_item_step(const BeamArgs& a, int item, hipStream_t s, const BeamWide* w, bool select) {
   ITTS_REQUIRE(a.nb >= 2 && a.nb <= MAXB && item >= 0 && item < a.B, "beam_item_step: 2 <= num_beams <= 10, item inside [0, B)");
   ITTS_REQUIRE(!a.preprocessed && !a.host_sc, "beam_item_step: no typical pre-pass and no host picks");
   const size_t r0 = (size_t)item * a.nb, mg = (size_t)a.max_gen, nd = 2 * (size_t)a.nb;
@@ -908,10 +1009,14 @@ int beam_item_step(const BeamArgs& a, int item, hipStream_t s, const BeamWide* w
     v.pick_sc = w->pick_sc + item * nd;
     v.pick_tok = w->pick_tok + item * nd;
     v.pick_beam = w->pick_beam + item * nd;
-    ITTS_TRY(beam_wide_prepare());
-    int np = 1024;
-    while (np < a.V) np <<= 1;
-    hipLaunchKernelGGL(beam_wide_cand_kernel, dim3(a.nb, 1), dim3(1024), (size_t)np * 6, s, b, v, np);
+    if (select) {
+      hipLaunchKernelGGL(beam_wide_cand_sel_kernel, dim3(a.nb, 1), dim3(1024), 0, s, b, v);
+    } else {
+      ITTS_TRY(beam_wide_prepare());
+      int np = 1024;
+      while (np < a.V) np <<= 1;
+      hipLaunchKernelGGL(beam_wide_cand_kernel, dim3(a.nb, 1), dim3(1024), (size_t)np * 6, s, b, v, np);
+    }
     hipLaunchKernelGGL(beam_wide_pick_kernel, dim3(1), dim3(1024), 0, s, b, v);
     b.host_sc = v.pick_sc;
     b.host_tok = v.pick_tok;

@@ -617,13 +617,21 @@ int itts_beam_admit(const itts_beam_admit_args* p, itts_stream stream) {
   return beam_admit(a, p->items_host, (hipStream_t)stream);
 }
 
-int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
-                     int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
-                     void* scratch, size_t scratch_bytes, itts_stream stream) {
+// ITTS_WIDE_SELECT for the stateless token-choice entries (itts_sampler_step, itts_sampler_step_rows), which have no engine to ask:
+// 1 = their whole-vocabulary launches are sampler_select_kernel (csrc/decode_sampler.hip)
+static bool wide_select_env() {
+  const char* ev = getenv("ITTS_WIDE_SELECT");
+  return ev && atoi(ev) != 0;
+}
+
+// itts_sample_rows (select = false) and itts_sample_rows_select: one set of argument checks, one scratch layout
+static int sample_rows(const char* name, bool select, int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B,
+                       int V, float penalty, int stop, int suppress_stop, int preprocessed, int top_k, float top_p, float temperature,
+                       const float* uniforms, void* scratch, size_t scratch_bytes, itts_stream stream) {
   (void)hipGetLastError();
   if (!tok || !kept || !logits || !uniforms || !scratch || B < 1 || V < 1 || stop < 0 || stop >= V || ((uintptr_t)scratch & 3) ||
       scratch_bytes < (size_t)B * ((size_t)V + 16)) {
-    set_error("itts_sample_rows: bad arguments (tok, kept, logits, uniforms, a 4-byte aligned scratch of B * (V + 16) bytes, 0 <= stop < V)");
+    set_error(std::string(name) + ": bad arguments (tok, kept, logits, uniforms, a 4-byte aligned scratch of B * (V + 16) bytes, 0 <= stop < V)");
     return E_INVALID;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -645,28 +653,43 @@ int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uin
   a.V = V; a.max_gen = 1; a.stop = stop; a.suppress_stop = suppress_stop; a.penalty = penalty; a.preprocessed = preprocessed;
   a.do_sample = 1; a.top_k = top_k < 1 ? 0 : top_k; a.B = B; a.top_p = top_p; a.temperature = temperature; a.uniforms = uniforms;
   a.kept = kept;
-  return sampler2_step(a, B, s);
+  return select ? sampler_select_step(a, B, s) : sampler2_step(a, B, s);
 }
 
-int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_beam, int32_t* kept, const float* logits,
-                          const int32_t* ids, int ids_stride, int k, const float* beam_scores, int items, int num_beams, int V,
-                          float penalty, int stop, int suppress_stop, int start_tok, int fake_id, int preprocessed, int top_k,
-                          float top_p, float temperature, const float* uniforms, void* scratch, size_t scratch_bytes,
-                          itts_stream stream) {
+int itts_sample_rows(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty, int stop,
+                     int suppress_stop, int preprocessed, int top_k, float top_p, float temperature, const float* uniforms,
+                     void* scratch, size_t scratch_bytes, itts_stream stream) {
+  return sample_rows("itts_sample_rows", false, tok, kept, logits, seen, B, V, penalty, stop, suppress_stop, preprocessed, top_k, top_p,
+                     temperature, uniforms, scratch, scratch_bytes, stream);
+}
+
+int itts_sample_rows_select(int32_t* tok, int32_t* kept, const float* logits, const uint8_t* seen, int B, int V, float penalty,
+                            int stop, int suppress_stop, int preprocessed, int top_k, float top_p, float temperature,
+                            const float* uniforms, void* scratch, size_t scratch_bytes, itts_stream stream) {
+  return sample_rows("itts_sample_rows_select", true, tok, kept, logits, seen, B, V, penalty, stop, suppress_stop, preprocessed, top_k,
+                     top_p, temperature, uniforms, scratch, scratch_bytes, stream);
+}
+
+// itts_beam_sample_rows (select = false) and itts_beam_sample_rows_select, as above
+static int beam_sample_rows(const char* name, bool select, float* pick_score, int32_t* pick_tok, int32_t* pick_beam, int32_t* kept,
+                            const float* logits, const int32_t* ids, int ids_stride, int k, const float* beam_scores, int items,
+                            int num_beams, int V, float penalty, int stop, int suppress_stop, int start_tok, int fake_id,
+                            int preprocessed, int top_k, float top_p, float temperature, const float* uniforms, void* scratch,
+                            size_t scratch_bytes, itts_stream stream) {
   (void)hipGetLastError();
   if (!pick_score || !pick_tok || !pick_beam || !kept || !logits || !beam_scores || !uniforms || !scratch || items < 1 || k < 0 ||
       (k > 0 && (!ids || ids_stride < k)) || ((uintptr_t)scratch & 3)) {
-    set_error("itts_beam_sample_rows: bad arguments (picks, kept, logits, beam_scores, uniforms, a 4-byte aligned scratch; ids [rows][ids_stride >= k])");
+    set_error(std::string(name) + ": bad arguments (picks, kept, logits, beam_scores, uniforms, a 4-byte aligned scratch; ids [rows][ids_stride >= k])");
     return E_INVALID;
   }
   if (num_beams < 2 || num_beams > 10 || V < 2 || V > BEAM_WIDE_MAX_V || stop < 0 || stop >= V || start_tok < 0 || start_tok >= V ||
       fake_id < 0 || fake_id >= V || !(top_p > 0.f) || !(temperature > 0.f)) {
-    set_error("itts_beam_sample_rows: 2 <= num_beams <= 10, 2 <= V <= 16384, stop / start_tok / fake_id inside the vocabulary, top_p > 0, temperature > 0");
+    set_error(std::string(name) + ": 2 <= num_beams <= 10, 2 <= V <= 16384, stop / start_tok / fake_id inside the vocabulary, top_p > 0, temperature > 0");
     return E_INVALID;
   }
   const int rows = items * num_beams;
   if (scratch_bytes < ((size_t)rows * ((size_t)V + 1) + (size_t)items) * 4) {
-    set_error("itts_beam_sample_rows: scratch shorter than (items * num_beams * (V + 1) + items) * 4 bytes");
+    set_error(std::string(name) + ": scratch shorter than (items * num_beams * (V + 1) + items) * 4 bytes");
     return E_INVALID;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -688,7 +711,27 @@ int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_be
   a.top_p = top_p; a.temperature = temperature; a.uniforms = uniforms; a.len = len; a.ids = (int*)ids; a.beam_scores = (float*)beam_scores;
   a.done = done; a.preprocessed = preprocessed; a.do_sample = 1;
   if (!a.ids) a.ids = len;  // k = 0: never read
-  return beam_wide_pair(a, w, s);
+  return beam_wide_pair(a, w, s, select);
+}
+
+int itts_beam_sample_rows(float* pick_score, int32_t* pick_tok, int32_t* pick_beam, int32_t* kept, const float* logits,
+                          const int32_t* ids, int ids_stride, int k, const float* beam_scores, int items, int num_beams, int V,
+                          float penalty, int stop, int suppress_stop, int start_tok, int fake_id, int preprocessed, int top_k,
+                          float top_p, float temperature, const float* uniforms, void* scratch, size_t scratch_bytes,
+                          itts_stream stream) {
+  return beam_sample_rows("itts_beam_sample_rows", false, pick_score, pick_tok, pick_beam, kept, logits, ids, ids_stride, k, beam_scores,
+                          items, num_beams, V, penalty, stop, suppress_stop, start_tok, fake_id, preprocessed, top_k, top_p, temperature,
+                          uniforms, scratch, scratch_bytes, stream);
+}
+
+int itts_beam_sample_rows_select(float* pick_score, int32_t* pick_tok, int32_t* pick_beam, int32_t* kept, const float* logits,
+                                 const int32_t* ids, int ids_stride, int k, const float* beam_scores, int items, int num_beams, int V,
+                                 float penalty, int stop, int suppress_stop, int start_tok, int fake_id, int preprocessed, int top_k,
+                                 float top_p, float temperature, const float* uniforms, void* scratch, size_t scratch_bytes,
+                                 itts_stream stream) {
+  return beam_sample_rows("itts_beam_sample_rows_select", true, pick_score, pick_tok, pick_beam, kept, logits, ids, ids_stride, k,
+                          beam_scores, items, num_beams, V, penalty, stop, suppress_stop, start_tok, fake_id, preprocessed, top_k, top_p,
+                          temperature, uniforms, scratch, scratch_bytes, stream);
 }
 
 // The argument block of the two skinny entries, without pointers: what itts_skinny_gemm_supported judges and the entries launch.
@@ -993,7 +1036,7 @@ int itts_sampler_step(const itts_sampler_step_args* p, itts_stream stream) {
   (void)hipGetLastError();
   SamplerArgs a = sampler_state_args(p);
   a.penalty = p->penalty; a.do_sample = p->do_sample; a.top_k = p->top_k < 1 ? 0 : p->top_k; a.top_p = p->top_p; a.temperature = p->temperature;
-  return sampler2_step(a, p->B, (hipStream_t)stream);
+  return sampler2_step(a, p->B, (hipStream_t)stream, wide_select_env());
 }
 
 // every entry of a host row table, and the classes it holds (bit ROWCLS_*); 0 with *why set = refused.  No HIP call
@@ -1034,7 +1077,7 @@ int itts_sampler_step_rows(const itts_sampler_step_args* p, const itts_row_sampl
   ITTS_HIP_CHECK(hipStreamSynchronize(s));  // tab is a host buffer of this call
   SamplerArgs a = sampler_state_args(p);
   a.rows = (const RowSampling*)rows_dev_scratch;
-  return sampler_rows_step(a, p->B, classes, s);
+  return sampler_rows_step(a, p->B, classes, s, wide_select_env());
 }
 #undef SAMPLER_STATE_CHECKS
 #undef TOKEN_REQUIRE
@@ -1372,6 +1415,10 @@ int itts_gpt_set_attn_kv8(itts_engine* e, int on) {
   return e->e.gpt_set_attn_kv8(on);
 }
 int itts_gpt_attn_kv8_used(itts_engine* e) { return e ? e->e.ds.last_kv8 : -1; }
+int itts_gpt_set_wide_select(itts_engine* e, int on) {
+  ENG(e);
+  return e->e.gpt_set_wide_select(on);
+}
 
 int64_t itts_debug_fetch(itts_engine* e, const char* name, float* out_host, int64_t max_elems) {
   if (!e || !name) return -1;

@@ -380,6 +380,101 @@ __global__ __launch_bounds__(1024) void sampler_wide_kernel(SamplerArgs a, int N
   sampler_next_embedding(a, b, si, tid);
 }
 
+// ---------------------------------------------------------------------------------------------
+// sampler_select (opt-in: ITTS_WIDE_SELECT / itts_gpt_set_wide_select, itts_sample_rows_select): steps 1 and
+// 3 to 6 of sampler_wide_kernel without its sort.  What the sampler has to produce - the TopK threshold, the TopP cut, the drawn
+// rank - is each a selection over "descending score, lower id first on ties", found by a radix descent over the score bits
+// (itts_sampler_dev.h select_*).  One 1024-thread block per row, V <= 16384, any top_k:
+//   1. thread t: the scores of the tokens t, t + 1024, ... (sampler_score, / temperature) as keys in registers; s0 = the row maximum
+//   3. TopK (top_k >= 1 and at least min(top_k, V) finite scores): T = the key at rank min(top_k, V) - 1 (select_count); the
+//      n keys >= T stay, ties with it too.  Otherwise the n finite scores
+//   4. masses: round(expf(s - s0) * 2^40) of the kept keys as 64-bit integers, Z their sum.  TopP (top_p < 1): rank r >= 1 goes
+//      iff tail_r <= (1 - top_p) * Z; with thr = floor of that product, formed in fp64, the last staying rank is the last one
+//      whose tail reaches thr + 1 (select_mass_from_bottom), R = that rank + 1
+//   5. draw: target = ceil(u * total) formed in fp64, total = the mass of the R kept ranks; the first rank whose prefix reaches
+//      it (select_mass_from_top), which lies among the R; its token is a member of the key's group by id (select_group_member)
+//   6. kept[b] = R, sampler_commit / sampler_next_embedding
+// Every sum is an integer sum: the same bits on every run, at every place in a batch, under graph replay.  No fp32 atomics.
+// ---------------------------------------------------------------------------------------------
+template <bool ROWS>
+__global__ __launch_bounds__(1024) void sampler_select_kernel(SamplerArgs a) {
+  if (!sampler_take_row<ROWS, ROWCLS_WIDE>(a, blockIdx.x)) return;
+  __shared__ SelectLds L;
+  __shared__ float red[16];
+  __shared__ int si[2];
+  const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+  const float* __restrict__ lg = a.logits + (size_t)b * V;
+  const uint8_t* seen = a.seen + (size_t)b * V;
+  const int k_pre = a.step[b], unf_pre = a.unfinished[b];
+  const float u = a.uniforms[(size_t)min(k_pre, a.max_gen - 1) * a.B + b];
+  unsigned key[SEL_PER];
+  float e[SEL_PER];  // expf(score - s0) of the kept tokens, 0 for the others
+  float mx = -INFINITY;
+  unsigned live = 0;
+#pragma unroll
+  for (int q = 0; q < SEL_PER; ++q) {
+    const int i = tid + 1024 * q;
+    float v = -INFINITY;
+    if (i < V) {
+      v = sampler_score(a, seen, lg[i], i);
+      if (a.temperature != 1.f) v = v / a.temperature;  // TemperatureLogitsWarper: scores / temperature
+    }
+    key[q] = select_key(v);
+    if (key[q]) {
+      mx = fmaxf(mx, v);
+      ++live;
+    }
+  }
+  auto key_of = [&](int q) { return key[q]; };
+  auto mass_of = [&](int q) { return select_mass_of(e[q]); };
+  select_init(L, tid);
+  const float s0 = block_max(mx, red, tid);
+  sel_u64 n = block_add(live, L.red, tid);  // the finite scores
+  int pick = 0;                             // (no finite score at all: rank 0, the lowest id, is drawn; one rank is kept)
+  sel_u64 R = 1;
+  if (n) {  // block-uniform, as every branch below
+    unsigned T = 1;
+    if (a.top_k >= 1 && (sel_u64)min(a.top_k, V) <= n) {
+      sel_u64 above;
+      T = select_count(L, (sel_u64)min(a.top_k, V) - 1, key_of, &above, tid);
+      n = above + (select_above_equal(L, T, key_of, tid) & 0xFFFFFFFFull);
+    }
+    sel_u64 own = 0;
+#pragma unroll
+    for (int q = 0; q < SEL_PER; ++q) {
+      e[q] = key[q] >= T ? expf(select_score(key[q]) - s0) : 0.f;
+      own += select_mass_of(e[q]);
+    }
+    const sel_u64 Z = block_add(own, L.red, tid);
+    sel_u64 total = Z, rem;
+    R = n;
+    if (a.top_p < 1.f && Z) {
+      const sel_u64 thr = (sel_u64)((1.0 - (double)a.top_p) * (double)Z);  // rank r stays iff tail_r > thr
+      const sel_u64 reach = thr + 1 < Z ? thr + 1 : Z;
+      const unsigned K = select_mass_from_bottom(L, reach, key_of, mass_of, &rem, tid);
+      const sel_u64 mK = max(select_mass(K, s0), 1ull), jb = (rem + mK - 1) / mK;  // the jb-th member from the group's end
+      const sel_u64 ae = select_above_equal(L, K, key_of, tid);
+      R = (ae >> 32) + (ae & 0xFFFFFFFFull) - jb + 1;
+      total = Z - (reach - rem) - (jb - 1) * mK;  // less the mass behind rank R - 1
+    }
+    if (Z) {
+      sel_u64 target = (sel_u64)ceil((double)u * (double)total);
+      target = target < 1 ? 1 : (target > total ? total : target);
+      const unsigned K = select_mass_from_top(L, target, key_of, mass_of, &rem, tid);
+      const sel_u64 mK = max(select_mass(K, s0), 1ull);
+      pick = select_group_member(L, K, (rem + mK - 1) / mK - 1, key_of, tid);
+    } else {  // (an infinite maximum: no mass at all) rank 0
+      pick = select_group_member(L, select_key(s0), 0, key_of, tid);
+    }
+  }
+  if (tid == 0) {
+    if (a.kept) a.kept[b] = (int)R;
+    sampler_commit(a, b, pick, si, k_pre, unf_pre);
+  }
+  __syncthreads();
+  sampler_next_embedding(a, b, si, tid);
+}
+
 template <typename TW>
 __global__ void decode_embed2_kernel(float* __restrict__ h, const TW* __restrict__ emb, const TW* __restrict__ pos,
                                      const int* __restrict__ tok, const int* __restrict__ len, int D) {
@@ -400,7 +495,8 @@ int sampler_wide_prepare() {
   return allow_dynamic_lds(latch_rows, (const void*)sampler_wide_kernel<true>, WIDE_MAX_V * 6);
 }
 
-int sampler2_step(const SamplerArgs& a, int B, hipStream_t s) {
+// select (every step below): the launches of sampler_wide_kernel become launches of sampler_select_kernel; nothing else changes
+int sampler2_step(const SamplerArgs& a, int B, hipStream_t s, bool select) {
   ITTS_REQUIRE(!a.rows, "sampler: a row table runs through sampler_rows_step");
   if (a.do_sample) {
     ITTS_REQUIRE(a.uniforms && a.temperature > 0.f && a.top_p > 0.f && a.B == B,
@@ -410,10 +506,14 @@ int sampler2_step(const SamplerArgs& a, int B, hipStream_t s) {
       hipLaunchKernelGGL(sampler_sample_kernel<false>, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
     } else {  // TopK off or wider than the narrow kernel's candidates: the whole vocabulary
       ITTS_REQUIRE(a.V >= 1 && a.V <= WIDE_MAX_V, "sampler: top_k outside [1, 128] needs a vocabulary of at most 16384");
-      ITTS_TRY(sampler_wide_prepare());
-      int np = 1024;
-      while (np < a.V) np <<= 1;
-      hipLaunchKernelGGL(sampler_wide_kernel<false>, dim3(B), dim3(1024), (size_t)np * 6, s, a, np);
+      if (select) {
+        hipLaunchKernelGGL(sampler_select_kernel<false>, dim3(B), dim3(1024), 0, s, a);
+      } else {
+        ITTS_TRY(sampler_wide_prepare());
+        int np = 1024;
+        while (np < a.V) np <<= 1;
+        hipLaunchKernelGGL(sampler_wide_kernel<false>, dim3(B), dim3(1024), (size_t)np * 6, s, a, np);
+      }
     }
     ITTS_HIP_CHECK(hipGetLastError());
     return OK;
@@ -423,20 +523,32 @@ int sampler2_step(const SamplerArgs& a, int B, hipStream_t s) {
   return OK;
 }
 
+// The operator form (itts_sample_rows_select): sampler_select_kernel for any top_k, the narrow kernel's [1, 128] included
+int sampler_select_step(const SamplerArgs& a, int B, hipStream_t s) {
+  ITTS_REQUIRE(!a.rows && a.do_sample && a.uniforms && a.temperature > 0.f && a.top_p > 0.f && a.B == B,
+               "sampler: sampling needs uniforms, temperature > 0, top_p > 0");
+  ITTS_REQUIRE(a.V >= 1 && a.V <= WIDE_MAX_V, "sampler: the select kernel needs a vocabulary of at most 16384");
+  hipLaunchKernelGGL(sampler_select_kernel<false>, dim3(B), dim3(1024), 0, s, a);
+  ITTS_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
 // Mixed batch: every class present gets its kernel over the whole grid; row b's block does its work in the kernel of rows[b]'s
 // class and returns at once in the others, so the commit and the next-step embedding of every row run exactly once.  The
 // launches follow one another on the stream and touch disjoint rows.  `classes`: what the caller's host copy of the table holds
 // (bit ROWCLS_*); the entries themselves were checked where the table was built (c_api.cpp, Engine::gpt_set_sampling_rows).
-int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s) {
+int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s, bool select) {
   ITTS_REQUIRE(a.rows && a.B == B && classes > 0 && classes < 8, "sampler: a mixed batch needs its row table and the classes present");
   const bool narrow = classes >> ROWCLS_NARROW & 1, wide = classes >> ROWCLS_WIDE & 1;
   ITTS_REQUIRE(!(narrow || wide) || a.uniforms, "sampler: sampled rows need uniforms");
   ITTS_REQUIRE(!narrow || (size_t)a.V * 4 <= 60 * 1024, "sampler: vocabulary too large for the LDS-resident sampler");
   ITTS_REQUIRE(!wide || (a.V >= 1 && a.V <= WIDE_MAX_V), "sampler: top_k outside [1, 128] needs a vocabulary of at most 16384");
-  if (wide) ITTS_TRY(sampler_wide_prepare());
+  if (wide && !select) ITTS_TRY(sampler_wide_prepare());
   if (classes >> ROWCLS_GREEDY & 1) hipLaunchKernelGGL(sampler2_kernel<true>, dim3(B), dim3(1024), 0, s, a);
   if (narrow) hipLaunchKernelGGL(sampler_sample_kernel<true>, dim3(B), dim3(1024), (size_t)a.V * 4, s, a);
-  if (wide) {
+  if (wide && select) {
+    hipLaunchKernelGGL(sampler_select_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+  } else if (wide) {
     int np = 1024;
     while (np < a.V) np <<= 1;
     hipLaunchKernelGGL(sampler_wide_kernel<true>, dim3(B), dim3(1024), (size_t)np * 6, s, a, np);
@@ -448,7 +560,7 @@ int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s) {
 // One row's token choice (row admission, Engine::gpt_admit_rows): the same kernels with a grid of one block on an argument block
 // whose per-row pointers start at the slot, so block 0 is that row.  uniforms[k * a.B + 0] of the advanced base is
 // uniforms[k * B + slot] of the batch.  a.rows set: the <true> instantiations, which read the slot's own entry.
-int sampler_slot_step(const SamplerArgs& a0, int slot, int cls, hipStream_t s) {
+int sampler_slot_step(const SamplerArgs& a0, int slot, int cls, hipStream_t s, bool select) {
   ITTS_REQUIRE(slot >= 0 && slot < a0.B && cls >= ROWCLS_GREEDY && cls <= ROWCLS_WIDE, "sampler: slot outside the batch, or no such class");
   SamplerArgs a = a0;
   a.logits += (size_t)slot * a.V;
@@ -474,11 +586,16 @@ int sampler_slot_step(const SamplerArgs& a0, int slot, int cls, hipStream_t s) {
       else hipLaunchKernelGGL(sampler_sample_kernel<false>, dim3(1), dim3(1024), (size_t)a.V * 4, s, a);
     } else {
       ITTS_REQUIRE(a.V >= 1 && a.V <= WIDE_MAX_V, "sampler: top_k outside [1, 128] needs a vocabulary of at most 16384");
-      ITTS_TRY(sampler_wide_prepare());
-      int np = 1024;
-      while (np < a.V) np <<= 1;
-      if (rows) hipLaunchKernelGGL(sampler_wide_kernel<true>, dim3(1), dim3(1024), (size_t)np * 6, s, a, np);
-      else hipLaunchKernelGGL(sampler_wide_kernel<false>, dim3(1), dim3(1024), (size_t)np * 6, s, a, np);
+      if (select) {
+        if (rows) hipLaunchKernelGGL(sampler_select_kernel<true>, dim3(1), dim3(1024), 0, s, a);
+        else hipLaunchKernelGGL(sampler_select_kernel<false>, dim3(1), dim3(1024), 0, s, a);
+      } else {
+        ITTS_TRY(sampler_wide_prepare());
+        int np = 1024;
+        while (np < a.V) np <<= 1;
+        if (rows) hipLaunchKernelGGL(sampler_wide_kernel<true>, dim3(1), dim3(1024), (size_t)np * 6, s, a, np);
+        else hipLaunchKernelGGL(sampler_wide_kernel<false>, dim3(1), dim3(1024), (size_t)np * 6, s, a, np);
+      }
     }
   }
   ITTS_HIP_CHECK(hipGetLastError());

@@ -132,8 +132,9 @@ struct GraphKey {
   int group_attn = 0;  // derived: Engine::group_attn_on() (+ 1 with group_attn_kv8_on()) - which cache attention kernel a beam step at > 6 rows launches
   int group_split = 0;  // derived: Engine::group_split_ns() - the key splits of the grouped kernel in effect (0: unsplit)
   int attn_kv8 = 0;  // derived: Engine::attn_kv8_on() - an fp8 cache's whole-form steps at B * H >= 512 launch decode_attn_kv8 (decode_attn_kv8.hip)
+  int wide_select = 0;  // derived: Engine::wide_select_on() - the whole-vocabulary sampler launches of the step are the select kernels (decode_sampler.hip, beam.hip)
   bool operator==(const GraphKey& o) const {
-    return attn_kv8 == o.attn_kv8 && group_attn == o.group_attn && group_split == o.group_split && rows_active == o.rows_active && rows_classes == o.rows_classes && B == o.B &&Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
+    return wide_select == o.wide_select && attn_kv8 == o.attn_kv8 && group_attn == o.group_attn && group_split == o.group_split && rows_active == o.rows_active && rows_classes == o.rows_classes && B == o.B &&Bcache == o.Bcache && Smax == o.Smax && max_gen == o.max_gen && use_forced == o.use_forced && input_n == o.input_n &&
            host_sample == o.host_sample && fuse == o.fuse && eng == o.eng && nb == o.nb && beam_sample == o.beam_sample && ct == o.ct &&
            length_penalty == o.length_penalty && typical_mass == o.typical_mass && penalty == o.penalty &&
            suppress_stop == o.suppress_stop && do_sample == o.do_sample && top_k == o.top_k && top_p == o.top_p &&
@@ -243,6 +244,7 @@ struct DecodeState {
   float *grp_o = nullptr, *grp_ml = nullptr;  // its partials [GROUP_SPLIT_MAX][beam_rows][D] / [..][beam_rows][H][2] (ensure_beam_state)
   int last_grp = 0, graph_grp = 0;       // 1 / 2 / 3: the last launched / the captured decode step ran decode_attn_group / _kv8 / _split (itts_gpt_group_attn_used)
   int attn_kv8 = 0;                      // itts_gpt_set_attn_kv8: an fp8 cache's whole-form steps at B * H >= 512 run decode_attn_kv8 (sticky; default: decode_attn2<fp8_t>)
+  int wide_select = 0;                   // itts_gpt_set_wide_select: the device whole-vocabulary samplers run their sort-free select kernels (sticky; default: the sorted ones)
   int last_kv8 = 0, graph_kv8 = 0;       // 1: the last launched / the captured decode step ran decode_attn_kv8 (itts_gpt_attn_kv8_used)
   int graph_mode = 0;                    // last_mode of the captured step
   float typical_mass = 0.f;                        // TypicalLogitsWarper pre-pass (0 = off)
@@ -475,6 +477,8 @@ struct Engine {
   int group_split_ns(int B) const;        // the splits a grouped 16-bit step at B rows takes, as ITTS_GROUP_ATTN_SPLIT (read per call) or the setter says (0: unsplit)
   int gpt_set_attn_kv8(int on);           // opt-in: batched steps on an fp8 cache run the kernel written for 64-byte rows (decode_attn_kv8.hip)
   bool attn_kv8_on() const;               // that switch as ITTS_ATTN_KV8 (read per call) or the setter says
+  int gpt_set_wide_select(int on);        // opt-in: sampler_select_kernel / beam_wide_cand_sel_kernel where the sorted whole-vocabulary kernels launch
+  bool wide_select_on() const;            // that switch as ITTS_WIDE_SELECT (read per call) or the setter says
   bool engine_fp8_model() const;  // every projection of every block and the head carry an fp8 copy + row scales
   int ensure_engine_state(hipStream_t s);
   int engine_check(hipStream_t s);

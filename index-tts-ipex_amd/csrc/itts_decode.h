@@ -157,13 +157,14 @@ constexpr int BEAM_WIDE_MAX_V = 16384;  // NP * 6 bytes of LDS: 96 KiB
 inline size_t beam_wide_bytes(int rows, int nb, int V) { return ((size_t)rows * V + rows + (size_t)(rows / nb) * 2 * nb * 3) * 4; }
 int beam_wide_prepare();  // once per device ordinal, outside graph capture: beam_wide_cand_kernel's dynamic LDS limit
 // the two wide launches alone (no BeamSearchScorer step): w.sc, w.kept and the picks are written, nothing of `a` is
-int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s);
+// select (here and in the two steps below): beam_wide_cand_sel_kernel in place of beam_wide_cand_kernel (ITTS_WIDE_SELECT)
+int beam_wide_pair(const BeamArgs& a, const BeamWide& w, hipStream_t s, bool select = false);
 // w: needed when a.do_sample and a.top_k < 1 or > BEAM_MAX_CAND (the wide pair + beam_select_kernel on its picks)
-int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w = nullptr);
+int beam_sample_step(const BeamArgs& a, hipStream_t s, const BeamWide* w = nullptr, bool select = false);
 int beam_commit_step(const BeamArgs& a, hipStream_t s);  // host picks -> scorer bookkeeping (beam_select_kernel only)
 // the same step for batch item `item` alone (grid of one item, pointers advanced to it, a.B the full item count): the first token
 // of an admitted beam group.  No typical pre-pass, no host picks
-int beam_item_step(const BeamArgs& a, int item, hipStream_t s, const BeamWide* w = nullptr);
+int beam_item_step(const BeamArgs& a, int item, hipStream_t s, const BeamWide* w = nullptr, bool select = false);
 
 // TypicalLogitsWarper pre-pass (beam.hip): processed scores of every row -> out [rows, V] with the filtered ones at -inf
 struct TypicalArgs {
@@ -300,13 +301,15 @@ int qkv_attn_fused(const GemvArgs& g, unsigned long long* gran, int* err, void* 
                    const int* kv_start, const int* prefix_dev, int H, int dh, int Smax, float* part_o, float* part_ml,
                    const uint8_t* anc, int nb, hipStream_t s);
 // decode_sampler.hip
-int sampler2_step(const SamplerArgs& a, int B, hipStream_t s);
+// select (the three steps): sampler_select_kernel where sampler_wide_kernel would launch (ITTS_WIDE_SELECT)
+int sampler2_step(const SamplerArgs& a, int B, hipStream_t s, bool select = false);
+int sampler_select_step(const SamplerArgs& a, int B, hipStream_t s);  // sampler_select_kernel for any top_k (itts_sample_rows_select)
 int sampler_wide_prepare();  // once per device ordinal, outside graph capture: sampler_wide_kernel's dynamic LDS limit
 // a.rows set: one launch per class in `classes` (bit ROWCLS_*), grid B each; a block whose row another class owns returns at once
-int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s);
+int sampler_rows_step(const SamplerArgs& a, int B, int classes, hipStream_t s, bool select = false);
 // the token choice of ONE row of a batch (row admission): the per-row pointers of `a` are advanced to `slot` - uniforms by slot
 // with the stride a.B kept - and the kernel of class `cls` runs with a grid of one block; no other row is read or written
-int sampler_slot_step(const SamplerArgs& a, int slot, int cls, hipStream_t s);
+int sampler_slot_step(const SamplerArgs& a, int slot, int cls, hipStream_t s, bool select = false);
 int decode_embed2(float* h, const void* emb, const void* pos, const int* tok, const int* len, int B, int D, int tw,
                   hipStream_t s);
 

@@ -6,6 +6,8 @@
 //   - sort_cands_wave, regather_cands_ordered: the two narrow kernels (1 <= top_k <= 128), sampler_sample_kernel and beam_cand_kernel
 //   - wide_sort<DESC>: sampler_wide_kernel, beam_wide_cand_kernel (descending), typical_filter_kernel (ascending); wide_scan_excl:
 //     sampler_wide_kernel, beam_wide_cand_kernel, beam_wide_pick_kernel
+//   - select_key / select_mass / select_descend and the selections built on it (select_count, select_mass_from_top,
+//     select_mass_from_bottom, select_group_member): sampler_select_kernel, beam_wide_cand_sel_kernel (opt-in)
 // Every helper works on the caller's __shared__ arrays: no kernel's LDS layout depends on this file.  Written out per kernel and
 // kept in step by hand, because every shared form measured slower or took a register more (DESIGN.md section 4a,
 // profiles/token_choice_refactor.txt): the radix select, the candidate gather and the narrow top-p of the two narrow kernels; the
@@ -238,6 +240,163 @@ __device__ __forceinline__ void wide_sort(float* keys, unsigned short* idx, int 
       }
     __syncthreads();
   }
+}
+
+// ---- the sort-free whole-vocabulary kernels (opt-in): sampler_select_kernel (decode_sampler.hip),
+//      beam_wide_cand_sel_kernel (beam.hip) - one ownership, one key, one mass, one descent ----
+// Thread t of the row's 1024 owns the tokens t, t + 1024, ... (SEL_PER of them, V <= 16384) in registers for the whole kernel: a
+// key each and, once the row maximum is known, a mass each.  The order of every selection is "descending key, lower id first
+// inside a key".  LDS holds one 256-bucket histogram and a few scalars (SelectLds).
+constexpr int SEL_PER = 16;
+typedef unsigned long long sel_u64;
+struct SelectLds {
+  sel_u64 hist[256];  // zero between the descents: select_init once, then every scan clears what it read
+  sel_u64 red[16];
+  sel_u64 rem;
+  unsigned bin;
+};
+__device__ __forceinline__ void select_init(SelectLds& L, int tid) {  // the caller passes a barrier before the first descent
+  if (tid < 256) L.hist[tid] = 0;
+}
+
+// the key of a score: order_key of a finite one (-0 taken as +0, the sort's comparison does not tell them apart), 0 - below the key
+// of every finite score - for -inf, a NaN and a token beyond V: those never count and carry no mass.  select_score inverts it
+__device__ __forceinline__ unsigned select_key(float v) {
+  if (!(v > -INFINITY)) return 0u;
+  return order_key(v == 0.f ? 0.f : v);
+}
+__device__ __forceinline__ float select_score(unsigned key) {
+  return __uint_as_float((key & 0x80000000u) ? key ^ 0x80000000u : ~key);
+}
+// the mass of a key: expf(score - row maximum) as 2^-40 units, rounded once.  <= 2^40 each, <= 2^54 over a row: every sum of them
+// is an integer sum, the same bits in any order of addition.  A function of the key alone, so a group's mass needs no member
+// (The kernels keep the fp32 exponential per token and convert where they add: half the registers of the 64-bit masses.)
+__device__ __forceinline__ sel_u64 select_mass_of(float e) {
+  return e > 0.f ? __float2ull_rn(e * 1099511627776.f) : 0ull;  // (a NaN - an infinite maximum - is no mass)
+}
+__device__ __forceinline__ sel_u64 select_mass(unsigned key, float s0) { return select_mass_of(expf(select_score(key) - s0)); }
+
+// sum of one value per thread over the block, in integers (red[16])
+__device__ __forceinline__ sel_u64 block_add(sel_u64 v, sel_u64* red, int tid) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  sel_u64 r = 0;
+  for (int i = 0; i < 16; ++i) r += red[i];
+  __syncthreads();
+  return r;
+}
+
+// The one radix descent behind every selection: PASSES digits of BITS bits of digits(q), most significant first.  Over the
+// thread's elements q with weight(q) != 0, walked from the largest digit string down (TOP) or from the smallest up (!TOP), it
+// returns the digit string of the first element whose inclusive running weight reaches target, and in *rem what is left of the
+// target inside that string's group (1 <= *rem <= the group's weight).  1 <= target <= the total weight (block-uniform); a
+// target beyond the total ends in the last group walked.
+// A pass: every thread adds the weights of its elements that still match the prefix into hist - runs of equal digits of one
+// thread go in as one atomic, the top digits of scores crowd into a few buckets - one wave scans the buckets (a lane holds
+// 256 / 64 or 128 / 64 consecutive ones, shuffles give the running sums), the lane whose buckets straddle the target picks
+// the bucket, and the wave clears what it read.  Two barriers per pass.  Integer atomics only.
+template <bool TOP, int BITS, int PASSES, typename DigitsF, typename WeightF>
+__device__ __forceinline__ unsigned select_descend(SelectLds& L, sel_u64 target, DigitsF digits, WeightF weight, sel_u64* rem, int tid) {
+  constexpr int NB = 1 << BITS, PER = NB / 64;
+  static_assert(NB <= 256 && PER >= 1, "one lane of the scanning wave holds PER buckets");
+  const int lane = tid & 63;
+  unsigned prefix = 0;
+#pragma unroll
+  for (int pass = PASSES - 1; pass >= 0; --pass) {
+    const int shift = pass * BITS;
+    unsigned cur = 0;
+    sel_u64 acc = 0;
+#pragma unroll
+    for (int q = 0; q < SEL_PER; ++q) {
+      const sel_u64 wq = weight(q);
+      const unsigned d = digits(q);
+      if (wq && (pass == PASSES - 1 || (d >> (shift + BITS)) == (prefix >> (shift + BITS)))) {
+        const unsigned b = (d >> shift) & (NB - 1);
+        if (b != cur) {
+          if (acc) atomicAdd(&L.hist[cur], acc);
+          cur = b;
+          acc = 0;
+        }
+        acc += wq;
+      }
+    }
+    if (acc) atomicAdd(&L.hist[cur], acc);
+    __syncthreads();
+    if (tid < 64) {
+      sel_u64 h[PER], own = 0;
+#pragma unroll
+      for (int j = 0; j < PER; ++j) {
+        h[j] = L.hist[PER * lane + j];
+        L.hist[PER * lane + j] = 0;
+        own += h[j];
+      }
+      sel_u64 x = own;  // inclusive running sum over the lanes, in walking order
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const sel_u64 t = TOP ? __shfl_down(x, off, 64) : __shfl_up(x, off, 64);
+        if (TOP ? lane + off < 64 : lane >= off) x += t;
+      }
+      const bool last = lane == (TOP ? 0 : 63);  // the lane walked last holds the total
+      if ((x - own < target && target <= x) || (last && x < target)) {  // exactly one lane
+        sel_u64 before = x - own;
+        int bin = -1;
+#pragma unroll
+        for (int jj = 0; jj < PER; ++jj) {
+          const int j = TOP ? PER - 1 - jj : jj;
+          if (bin < 0) {
+            if (before + h[j] >= target) bin = PER * lane + j;
+            else before += h[j];
+          }
+        }
+        L.bin = bin < 0 ? (TOP ? 0 : NB - 1) : bin;
+        L.rem = bin < 0 ? 1 : target - before;
+      }
+    }
+    __syncthreads();
+    prefix |= L.bin << shift;
+    target = L.rem;
+  }
+  *rem = target;
+  return prefix;
+}
+
+// The three selections over the 32 key bits (4 passes of 8).  key(q): the thread's q-th key; mass(q): its mass.
+// select_count: the key at rank k (0-based) among the live keys (k < their count); *above: how many keys lie above it
+template <typename KeyF>
+__device__ __forceinline__ unsigned select_count(SelectLds& L, sel_u64 k, KeyF key, sel_u64* above, int tid) {
+  sel_u64 rem;
+  const unsigned K = select_descend<true, 8, 4>(L, k + 1, key, [&](int q) -> sel_u64 { return key(q) != 0u; }, &rem, tid);
+  *above = k + 1 - rem;
+  return K;
+}
+// select_mass_from_top: the key of the first rank whose inclusive prefix mass reaches target; *rem: the target less the mass above
+// that key's group.  All members of a group have one mass mK: the rank is member (*rem + mK - 1) / mK - 1 of it by ascending id
+template <typename KeyF, typename MassF>
+__device__ __forceinline__ unsigned select_mass_from_top(SelectLds& L, sel_u64 target, KeyF key, MassF mass, sel_u64* rem, int tid) {
+  return select_descend<true, 8, 4>(L, target, key, mass, rem, tid);
+}
+// select_mass_from_bottom: the key of the last rank whose tail mass (its own included) reaches target; *rem: the target less the
+// mass below that key's group - the rank is member (*rem + mK - 1) / mK of it counted from the group's highest id down
+template <typename KeyF, typename MassF>
+__device__ __forceinline__ unsigned select_mass_from_bottom(SelectLds& L, sel_u64 target, KeyF key, MassF mass, sel_u64* rem, int tid) {
+  return select_descend<false, 8, 4>(L, target, key, mass, rem, tid);
+}
+// the j-th lowest id (0-based) of the group key == K: the count descent over the 14 id bits, two passes of 7, lowest id first
+template <typename KeyF>
+__device__ __forceinline__ int select_group_member(SelectLds& L, unsigned K, sel_u64 j, KeyF key, int tid) {
+  sel_u64 rem;
+  const unsigned d = select_descend<true, 7, 2>(L, j + 1, [&](int q) { return 0x3FFFu - (unsigned)(tid + 1024 * q); },
+                                                [&](int q) -> sel_u64 { return key(q) == K; }, &rem, tid);
+  return (int)(0x3FFFu - d);
+}
+// how many keys lie above K (high word) and how many equal it (low word)
+template <typename KeyF>
+__device__ __forceinline__ sel_u64 select_above_equal(SelectLds& L, unsigned K, KeyF key, int tid) {
+  sel_u64 c = 0;
+#pragma unroll
+  for (int q = 0; q < SEL_PER; ++q) c += ((sel_u64)(key(q) > K) << 32) + (key(q) == K);
+  return block_add(c, L.red, tid);
 }
 
 }  // namespace itts

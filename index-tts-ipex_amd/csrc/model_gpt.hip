@@ -306,6 +306,17 @@ bool Engine::attn_kv8_on() const {
   const char* ev = getenv("ITTS_ATTN_KV8");
   return ev ? atoi(ev) != 0 : ds.attn_kv8 != 0;
 }
+// Opt-in (sticky; ITTS_WIDE_SELECT overrides it per call, =0 included): wherever a step, an admitted row's first token or a beam
+// step launches sampler_wide_kernel / beam_wide_cand_kernel, it launches sampler_select_kernel / beam_wide_cand_sel_kernel, the
+// sort-free forms.  No effect where the host chooses the token.  Part of the graph key.
+int Engine::gpt_set_wide_select(int on) {
+  ds.wide_select = on != 0;
+  return OK;
+}
+bool Engine::wide_select_on() const {
+  const char* ev = getenv("ITTS_WIDE_SELECT");
+  return ev ? atoi(ev) != 0 : ds.wide_select != 0;
+}
 
 int Engine::ensure_engine_state(hipStream_t s) {
   DecodeState& d = ds;
@@ -915,14 +926,14 @@ int Engine::sample_from_logits(hipStream_t s, bool sampled) {
   if (ds.nb > 1) {  // beam-sample: one workgroup per batch item over its nb rows
     const BeamArgs ba = beam_args(lg_in, typical);
     const bool wide = ba.do_sample && (ba.top_k < 1 || ba.top_k > BEAM_MAX_CAND);
-    return beam_sample_step(ba, s, wide ? &ds.wide : nullptr);
+    return beam_sample_step(ba, s, wide ? &ds.wide : nullptr, wide_select_on());
   }
   SamplerArgs sa = greedy_sampler_args(lg_in, typical);
   if (ds.rows_active) {  // a mixed batch: one launch per class present, every row in its own class's kernel
     sa.rows = ds.rows;
-    return sampler_rows_step(sa, B, ds.rows_classes, s);
+    return sampler_rows_step(sa, B, ds.rows_classes, s, wide_select_on());
   }
-  return sampler2_step(sa, B, s);
+  return sampler2_step(sa, B, s, wide_select_on());
 }
 
 // arguments of the greedy / sampling kernels (sampler2_step) - also what the persistent engine's in-launch sampler runs on
@@ -1542,6 +1553,7 @@ GraphKey Engine::graph_key() const {
   k.group_attn = group_attn_on() ? 1 + (int)group_attn_kv8_on() : 0;  // 0 / 1 / 2
   k.group_split = group_split_ns(d.B);
   k.attn_kv8 = (int)attn_kv8_on();
+  k.wide_select = (int)wide_select_on();
   return k;
 }
 
@@ -2173,7 +2185,7 @@ int Engine::gpt_admit_rows(const float* cond_dev, int cond_rows, const int32_t* 
     if (d.rows_active) sa.rows = d.rows;
     for (int i = 0; i < n; ++i) {
       ITTS_HIP_CHECK(hipMemcpyAsync(d.logits + (size_t)slots[i] * V, lg + (size_t)i * V, (size_t)V * 4, hipMemcpyDeviceToDevice, s));
-      ITTS_TRY(sampler_slot_step(sa, slots[i], cls[i], s));
+      ITTS_TRY(sampler_slot_step(sa, slots[i], cls[i], s, wide_select_on()));
     }
     return OK;
   };
@@ -2383,7 +2395,7 @@ int Engine::admit_beam_groups(const float* cond_dev, int cond_rows, const int32_
     const BeamArgs ba = beam_args(d.logits, false);
     for (int i = 0; i < n; ++i) {
       ITTS_HIP_CHECK(hipMemcpyAsync(d.logits + (size_t)took[i] * nb * V, lg + (size_t)i * nb * V, (size_t)nb * V * 4, hipMemcpyDeviceToDevice, s));
-      ITTS_TRY(beam_item_step(ba, took[i], s, wide ? &d.wide : nullptr));
+      ITTS_TRY(beam_item_step(ba, took[i], s, wide ? &d.wide : nullptr, wide_select_on()));
     }
     return OK;
   };

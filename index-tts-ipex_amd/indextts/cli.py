@@ -54,6 +54,9 @@ def build_parser():
     p.add_argument("--attn-kv8", action="store_true", default=False,
                    help="with --kv-fp8: batched decode steps at rows x heads >= 512 run the cache attention written for the fp8 K/V "
                         "cache's 64-byte rows; ITTS_ATTN_KV8=0 / 1 overrides")
+    p.add_argument("--wide-select", action="store_true", default=False,
+                   help="device whole-vocabulary samplers (top_k = 0 / > 128 with wide_sampler / wide_beam_sampler \"device\"): the "
+                        "sort-free select kernels instead of the sorted ones; ITTS_WIDE_SELECT=0 / 1 overrides")
     p.add_argument("--packed-latent", action="store_true", default=False,
                    help="batched synthesis (IndexTTS.infer_batch): the latent pass runs on packed rows without padding, one pass per "
                         "decode group under mixed batches; ITTS_PACKED_LATENT=0 / 1 overrides")
@@ -115,7 +118,7 @@ def main():
                    engine_kv_fp8=a.engine_kv_fp8, ragged_vocoder=a.ragged_vocoder, admit_rows=a.admit_rows, retire_beams=a.retire_beams,
                    packed_latent=a.packed_latent, admit_beams=a.admit_beams, packed_vocoder=a.packed_vocoder,
                    group_attn=a.group_attn, group_attn_kv_fp8=a.group_attn_kv_fp8, group_attn_split=a.group_attn_split,
-                   attn_kv8=a.attn_kv8)
+                   attn_kv8=a.attn_kv8, wide_select=a.wide_select)
     if a.stream:
         stream_to_file(tts, a)
         return

@@ -78,6 +78,10 @@ Same constructor and methods (`extract_features`, `infer`, `infer_fast`, `set_gr
   * `attn_kv8=True` (not in the reference; default off; ITTS_ATTN_KV8=1 / 0 overrides it in both directions; needs `kv_fp8=True`)
     lets the batched decode steps on the e4m3 K/V cache at rows x heads >= 512 (26 rows of the 20-head model) run the cache
     attention written for 64-byte cache rows instead of the 16-bit kernel's mapping (Engine.set_attn_kv8).
+  * `wide_select=True` (not in the reference; default off; ITTS_WIDE_SELECT=1 / 0 overrides it in both directions) makes the
+    device whole-vocabulary samplers (`wide_sampler` / `wide_beam_sampler` "device", top_k = 0 or > 128) find the TopK threshold,
+    the TopP cut and the drawn token by radix selection instead of sorting the vocabulary (Engine.set_wide_select).
+    No effect where the host chooses the token.
   * `infer_stream(...)` (not in the reference) is `infer` as a GENERATOR of (24000, int16 [n, 1]) chunks: a sentence's
     audio starts to arrive while its codes are still being decoded.  One beam only.  `stream_chunk_frames=N` holds the default
     chunk size in latent frames (ITTS_STREAM_CHUNK overrides it).  `infer` / `infer_fast` / `infer_batch` are not affected.
@@ -108,7 +112,7 @@ class IndexTTS:
                  wide_beam_sampler=None, kv_fp8=False, retire_rows=None, engine_kv_fp8=False, ragged_vocoder=False,
                  mixed_batch=False, admit_rows=False, retire_beams=None, packed_latent=False, admit_beams=False,
                  packed_vocoder=False, stream_chunk_frames=None, group_attn=False, group_attn_kv_fp8=False, group_attn_split=0,
-                 attn_kv8=False):
+                 attn_kv8=False, wide_select=False):
         # fp8 K/V cache on the persistent decode engine: a mode of the fp8 cache (checked before anything touches the device)
         self.engine_kv_fp8 = bool(engine_kv_fp8)
         if self.engine_kv_fp8 and not kv_fp8:
@@ -132,6 +136,7 @@ class IndexTTS:
         if self.attn_kv8 and not kv_fp8:
             raise ValueError("attn_kv8=True needs kv_fp8=True: it is the cache attention written for the fp8 K/V cache and has no "
                              "effect on the 16-bit cache")
+        self.wide_select = bool(wide_select)  # device whole-vocabulary samplers: the sort-free select kernels (ITTS_WIDE_SELECT overrides)
         if device is None:
             device = "cuda:0"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
@@ -205,6 +210,8 @@ class IndexTTS:
             self.engine.set_group_attn_split(self.group_attn_split)
         if self.attn_kv8:
             self.engine.set_attn_kv8(True)
+        if self.wide_select:
+            self.engine.set_wide_select(True)
         self.gpt =UnifiedVoice(self.engine, self.cfg.gpt)
         self.bigvgan = Generator(self.engine)
         self.bpe_path = os.path.join(model_dir, self.cfg.dataset["bpe_model"])

@@ -358,6 +358,14 @@ class Engine:
         environment overrides this setting."""
         self._ck(self.lib.itts_gpt_set_attn_kv8(self.h, int(bool(on))), "gpt_set_attn_kv8")
 
+    def set_wide_select(self, on: bool = True):
+        """Opt-in: wherever a step launches a device whole-vocabulary sampler (do_sample with top_k = 0 or > 128 - the scalar
+        setting, the wide rows of a mixed batch, an admitted row's first token, beams), it launches the sort-free form:
+        sampler_select_kernel / beam_wide_cand_sel_kernel find the TopK threshold, the TopP cut and the drawn rank by radix
+        descents over the score bits with integer masses.  Off (the default) every launch is as before, bit for bit.  No effect
+        where the host chooses the token.  ITTS_WIDE_SELECT=0 / 1 in the environment overrides this setting."""
+        self._ck(self.lib.itts_gpt_set_wide_select(self.h, int(bool(on))), "gpt_set_wide_select")
+
     def attn_kv8_used(self) -> int:
         """1 if the last decode step ran decode_attn_kv8, else 0."""
         return int(self.lib.itts_gpt_attn_kv8_used(self.h))
@@ -1405,7 +1413,7 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
                  state_dicts: Optional[dict] = None, max_batch: int = 64, gpt_fp8: str = "", engine_fp8: bool = False,
                  kv_fp8: bool = False, engine_kv_fp8: bool = False, retire_beams: bool = False,
                  group_attn: bool = False, group_attn_kv_fp8: bool = False, group_attn_split: int = 0,
-                 attn_kv8: bool = False) -> Engine:
+                 attn_kv8: bool = False, wide_select: bool = False) -> Engine:
     """Engine with synthetic (PRNG) or supplied reference-layout state dicts.  gpt_fp8: "" = plain weights;
     "fp8" = GPT projections quantised to e4m3 (power-of-two row scales) with the fp8 bytes used by the decode GEMV;
     "dequant" = the same quantised model but every kernel reads its bf16 dequantisation (the fp8 path's reference).
@@ -1416,7 +1424,8 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
     group_attn: Engine.set_group_attn(True) - beam steps at more than 6 rows run the grouped cache attention.
     group_attn_kv_fp8: Engine.set_group_attn_kv_fp8(True) - with group_attn and kv_fp8, those steps run the grouped fp8-cache kernel.
     group_attn_split: Engine.set_group_attn_split(n) - with group_attn, the grouped 16-bit steps split each item's keys (1: by rule, 2 .. 8: forced).
-    attn_kv8: Engine.set_attn_kv8(True) - with kv_fp8, the batched steps at rows x heads >= 512 run the cache attention written for e4m3 rows."""
+    attn_kv8: Engine.set_attn_kv8(True) - with kv_fp8, the batched steps at rows x heads >= 512 run the cache attention written for e4m3 rows.
+    wide_select: Engine.set_wide_select(True) - the device whole-vocabulary samplers run their sort-free select kernels."""
     from . import pack, synth
 
     eng = Engine(cfg, dtype, device, max_batch)
@@ -1447,4 +1456,6 @@ def build_engine(cfg, dtype: str = "bf16", device: str = "cuda:0", seed: int = 1
         eng.set_group_attn_split(int(group_attn_split))
     if attn_kv8:
         eng.set_attn_kv8(True)
+    if wide_select:
+        eng.set_wide_select(True)
     return eng

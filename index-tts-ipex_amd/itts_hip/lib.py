@@ -160,6 +160,9 @@ _PROTOS = {
     "itts_sample_rows": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, f32, f32, vp, vp, C.c_size_t, vp]),
     "itts_beam_sample_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, f32, f32, vp,
                                     vp, C.c_size_t, vp]),
+    "itts_sample_rows_select": (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, f32, f32, vp, vp, C.c_size_t, vp]),
+    "itts_beam_sample_rows_select": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, f32, f32,
+                                           vp, vp, C.c_size_t, vp]),
     "itts_skinny_gemm": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "itts_skinny_gemm_fp8": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "itts_skinny_gemm_supported": (i32, [i32] * 9),
@@ -199,6 +202,7 @@ _PROTOS = {
     "itts_gpt_set_group_attn_split": (i32, [vp, i32]),
     "itts_gpt_set_attn_kv8": (i32, [vp, i32]),
     "itts_gpt_attn_kv8_used": (i32, [vp]),
+    "itts_gpt_set_wide_select": (i32, [vp, i32]),
     "itts_gpt_set_host_sampling": (i32, [vp, i32]),
     "itts_gpt_set_cond_per_row": (i32, [vp, i32]),
     "itts_gpt_commit": (i32, [vp, vp, vp]),
